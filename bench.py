@@ -8,6 +8,10 @@
 One step = SegmentationNet.training_step on one batch (segmentation.py:58-65): fwd + DiceLoss + bwd, one RCCL
 all-reduce of the flat gradient buffer, Adam -- BASELINE config 2 (ResidualUNet3D f_maps=[32,64,128,256], 4 classes,
 128^3 patches, batch 4 per GPU, bf16 storage / fp32 accumulate), weak scaling.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the headline.  --full adds everything else the line can carry:
+the roofline records of the dominant kernels, the RCCL exchange timing, the fp32 / fp16 / fp16x2 storage modes, the CPU
+baseline and config 1.  --dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -320,6 +324,24 @@ def self_launch(n: int) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
+GRAD_SAMPLE = 1 << 22  # gradient elements in the dump: params (33.5 MB at config 2) + this sample (16 MB) stay under 64 MB
+
+
+def dump_outputs(out_dir: str, step, loss) -> None:
+    """What the last timed step handed its caller, as float32 .npy files: `loss` (the returned loss), `params` (every
+    parameter after the Adam update, in model.parameters() order, unpadded) and `grads` (the step's gradients in the same
+    order -- summed over ranks, times the loss scale in the fp16 modes -- at GRAD_SAMPLE positions drawn with a fixed seed)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = torch.cat([p.detach().reshape(-1) for p in step.flat.params])
+    grads = torch.cat([p._mednet_grad.reshape(-1) for p in step.flat.params])
+    if grads.numel() > GRAD_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(grads.numel(), GRAD_SAMPLE, replace=False))
+        grads = grads[torch.from_numpy(idx).to(grads.device)]
+    for name, t in (("loss", loss.detach().reshape(())), ("params", params), ("grads", grads)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -328,16 +350,26 @@ def main():
     ap.add_argument("--batch", type=int, default=4, help="patches per GPU per step (config 2: 4)")
     ap.add_argument("--patch", type=int, default=128)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp16", "fp16x2"])
-    ap.add_argument("--cpu-steps", type=int, default=3, help="timed oracle steps for cpu_baseline (0 = skip)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the records beyond the headline: roofline, RCCL exchange timing, the other storage modes, "
+                         "cpu_baseline and cfg1_plumbing (each behind the options below)")
+    ap.add_argument("--cpu-steps", type=int, default=3, help="with --full: timed oracle steps for cpu_baseline (0 = skip)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline records")
     ap.add_argument("--fp32-steps", type=int, default=10,
-                    help="timed steps of the fp32 (1e-3 parity) mode for the fp32_parity_mode sub-record (0 = skip)")
+                    help="with --full: timed steps of the fp32 (1e-3 parity) mode for the fp32_parity_mode sub-record, and of "
+                         "the fp16 / fp16x2 sub-records (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's loss, updated parameters and (a fixed sample of) its "
+                         "gradients as DIR/<name>.npy, float32 (rank 0)")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("MEDNET_GRAPH", "0")),
                     help="1: replay forward+loss+backward as one captured hipGraph per step (train._GraphedStep)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="every rank prints its RANK/LOCAL_RANK/WORLD_SIZE as one JSON line and exits (no GPU call): "
                          "checks the launcher on a box without GPUs")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    roofline = a.full and not a.no_roofline
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Bare `python bench.py --gpus N`: this process becomes the launcher.  It has made no GPU call (importing torch
@@ -400,12 +432,12 @@ def main():
     for _ in range(a.warmup):
         loss = step(batch)
     sync()
-    if not a.no_roofline:
+    if roofline:
         # dominant kernel: the 3x3x3 conv at full resolution with f0 -> f0 channels (forward launches; the data
         # gradient runs the same kernel).  HIP events on the launch stream (= torch's current stream).
         ops.PROFILE.update(enabled=True, events=[], wgrad_events=[], dgrad_events=[],
                            match=lambda k, ci, co, d, h, w: k == 3 and ci == F_MAPS[0] and co == F_MAPS[0] and d == P)
-    if use_dist:
+    if use_dist and a.full:
         from mednet_hip.train import BucketedExchange
         BucketedExchange.TIMING = []
     t0 = time.perf_counter()
@@ -422,6 +454,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     final_loss = float(loss)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step, loss)
 
     if rank == 0:
         patches = a.batch * world * a.steps
@@ -441,7 +475,7 @@ def main():
                                        "wgrad_workgroups": ops.SIDE["wgrad_wgs"] or "one per CU"}},
             "host_enqueue_ms_per_step": round(1e3 * t_issue / n_issue, 3),
         }
-        if use_dist:
+        if use_dist and a.full:
             from mednet_hip.train import BucketedExchange
             ev = BucketedExchange.TIMING or []
             xms = [e0.elapsed_time(e1) for e0, e1 in ev]
@@ -464,7 +498,7 @@ def main():
             out["rehearsal"] = f"{world} ranks on ONE GPU over gloo: exercises the multi-rank code path, not a throughput"
         if P == 128 and a.precision == "bf16":
             out["model_flops_utilization"] = round(patches / dt * FLOP_PER_PATCH / (world * MFMA_PEAK_TFLOPS["bf16"] * 1e12), 4)
-        if not a.no_roofline and ops.PROFILE["events"]:
+        if roofline and ops.PROFILE["events"]:
             ev = ops.PROFILE["events"]
             ms = [e0.elapsed_time(e1) for e0, e1, _ in ev]
             flops = ev[0][2]
@@ -502,7 +536,7 @@ def main():
                                                      "FLOP-weighted", "launches": tot_n, "avg_ms": round(tot_ms / tot_n, 4),
                                              "achieved": round(fam, 2), "frac": round(fam / peak, 4)}
                 out["roofline_dgrad"] = {"bound": "mfma", "peak": peak, "unit": "TFLOP/s", "flop_per_launch": flops, "variants": var}
-        if not a.no_roofline and ops.PROFILE.get("wgrad_events"):
+        if roofline and ops.PROFILE.get("wgrad_events"):
             # the kernel with the largest share of the step's kernel time: the weight gradient of the same layers.  In the step it
             # runs on the second stream, on all CUs, BESIDE the main stream's bandwidth-bound GroupNorm-backward passes (which is
             # what it was rebuilt for in round 5), so its in-step duration includes that sharing; `alone` is the same launch by
@@ -520,13 +554,13 @@ def main():
                                          "launches": alone_launches, "flop_per_launch": flops,
                                          "in_step_beside_the_main_stream": {"avg_ms": round(avg, 4), "launches": len(ms),
                                                                             "achieved": round(flops / (avg * 1e-3) / 1e12, 2)}}
-        if a.fp32_steps > 0 and world == 1 and a.precision == "bf16":
+        if a.full and a.fp32_steps > 0 and world == 1 and a.precision == "bf16":
             del step, model
             torch.cuda.empty_cache()
             out["fp32_parity_mode"] = fp32_parity_mode(dev, a.batch, P, a.fp32_steps)
             out["fp16_mode"] = fp16_storage_mode(dev, a.batch, P, a.fp32_steps)
             out["fp16x2_mode"] = fp16_storage_mode(dev, a.batch, P, a.fp32_steps, "fp16x2")
-        if a.cpu_steps > 0 and world == 1:
+        if a.full and a.cpu_steps > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(a.cpu_steps)
             out["cfg1_plumbing"] = cfg1_plumbing(dev)
         print(json.dumps(out), flush=True)

@@ -258,6 +258,11 @@ def test_bench_world_size_mismatch_is_an_error():
     assert r.returncode != 0 and "--gpus 1 but WORLD_SIZE=2" in r.stderr
 
 
+def test_bench_needs_at_least_one_timed_step():
+    r = _run_bench(["--steps", "0", "--dry-launch"])
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the loud failure on a box WITHOUT GPUs")
 def test_bench_gpus2_without_gpus_fails_inside_the_ranks():
     r = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0"])

@@ -4,7 +4,7 @@
 # usage: ROUND=r04 tools/collect_profiles.sh
 set -e
 R=${ROUND:?set ROUND=rNN}
-tail -1 gpurun_out/bench_line_final.log > profiles/${R}_bench_line.json
+tail -1 "${BENCH_LOG:-bench_line_final.log}" > profiles/${R}_bench_line.json
 python3 -c "import json,sys; json.load(open('profiles/${R}_bench_line.json'))"
 cp gpurun_out/bench_full.log profiles/${R}_bench_full.log
 python3 -c "

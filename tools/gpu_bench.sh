@@ -3,7 +3,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 export PYTHONPATH="$PWD:$PWD/torch-mednet_amd:$PYTHONPATH"
-ARGS="${BENCH_ARGS:---steps 3 --warmup 1 --cpu-steps 0}"
+ARGS="${BENCH_ARGS:---full --steps 3 --warmup 1 --cpu-steps 0}"
 timeout -k 10 900 python bench.py $ARGS > gpurun_out/bench.log 2>&1 || { tail -30 gpurun_out/bench.log; exit 1; }
 tail -3 gpurun_out/bench.log
 if [ -n "$PROFILE" ]; then

@@ -7,6 +7,7 @@ set -o pipefail
 mkdir -p gpurun_out
 export PYTHONPATH="$PWD:$PWD/torch-mednet_amd:$PYTHONPATH"
 R=$PWD
+BENCH_FULL_ARGS="--full ${BENCH_FULL_ARGS:-}"
 timeout -k 10 900 python bench.py ${BENCH_FULL_ARGS:-} > gpurun_out/bench_full.log 2>&1 || { tail -30 gpurun_out/bench_full.log; exit 1; }
 tail -2 gpurun_out/bench_full.log
 cd /tmp && export TMPDIR=/tmp

@@ -4,7 +4,8 @@
 set -o pipefail
 export PYTHONPATH="$PWD:$PWD/torch-mednet_amd:$PYTHONPATH"
 R=$PWD
-python bench.py > gpurun_out/bench_line_final.log 2>&1 && tail -1 gpurun_out/bench_line_final.log | cut -c1-200
+LOG=${BENCH_LOG:-bench_line_final.log}  # the full bench record; tools/collect_profiles.sh reads it from the same BENCH_LOG
+python bench.py --full > "$LOG" 2>&1 && tail -1 "$LOG" | cut -c1-200
 python tools/run_configs.py > gpurun_out/configs_final.log 2>&1; grep -c . gpurun_out/configs_final.log
 bash tools/single_stream_trace.sh > /dev/null 2>&1
 export TMPDIR=/tmp
