@@ -62,6 +62,7 @@ enum { MEDNET_PACK_LOW = 0x100,
         * multiples of 32) it must re-pack that layer in full (mednet_conv3d_pack_elt).  mednet_hip.nn does (`_packed(x)`). */
        MEDNET_PACK_HIGH_ONLY = 0x200 };
 enum { MEDNET_REG_L2 = 0, MEDNET_REG_L1 = 1 };
+enum { MEDNET_CLASS_DICE = 0, MEDNET_CLASS_CE = 1 };  /* class-loss kind of mednet_head_landmark_cls_fwd / _bwd */
 enum {
   MEDNET_OK = 0, MEDNET_E_SHAPE = -1, MEDNET_E_DTYPE = -2, MEDNET_E_WORKSPACE = -3, MEDNET_E_HIP = -4,
   MEDNET_E_UNSUPPORTED = -5
@@ -383,6 +384,41 @@ int mednet_head_landmark_bwd(const void* z, const void* packed, const float* bia
                              int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int nh, int ncls,
                              int kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
                              mednet_stream stream);
+/* The same two heads with nn.CrossEntropyLoss(weight, ignore_index) as the class loss (segmentation.py:49, landmarks.py:49: the
+ * callers' `loss='CE'` / `loss_class='CE'`).  Additive to ABI 3: the Dice entry points above are unchanged.
+ * mednet_head_ce_*: the segmentation head of mednet_head_dice_* with CE -- same layouts, label forms, workspace, GroupNorm rows
+ * and fold rule.  _fwd writes the logits, loss = sum w_y nll / sum w_y over the voxels whose label is not ignore_index, and
+ * saved[0] = sum w_y (saved holds 2 floats); a label outside [0, cout) that is not ignore_index makes the loss NaN.  _bwd forms
+ * the logit gradient (dloss / saved[0]) w_y (p_k - [k == y]) (0 for ignored voxels) in registers.  Logits, loss, dz and the
+ * GroupNorm sums are bit-identical to mednet_conv3d_fwd + mednet_ce_fwd / mednet_ce_bwd (int64 labels) + mednet_head_dgrad_gn;
+ * dW / dbias are summed in another fixed order.  _supported: as mednet_head_dice_supported.
+ * mednet_head_landmark_cls_*: mednet_head_landmark_* with the class-loss kind as an argument.  MEDNET_CLASS_DICE runs exactly
+ * mednet_head_landmark_fwd / _bwd.  MEDNET_CLASS_CE (softmax only: sigmoid must be 0): _fwd writes class_loss = the CE of the
+ * class channels (ignore_index honoured, out-of-range labels -> NaN) and saved[0] = sum w_y; _bwd reads saved[0].  dice_metric
+ * (nullable, [ncls]): dice_metric(outputs[:, nh:], labels) (loss.py:51-55: softmax, no weight, no mask) from the same pass; with
+ * MEDNET_CLASS_DICE it requires sigmoid == 0 and ignore_index == MEDNET_NO_IGNORE.  Workspace: mednet_head_landmark_ws_bytes.
+ * Results equal the unfused launches (mednet_ce_* for the class term) up to fp32 summation order. */
+int mednet_head_ce_supported(int cin, int cout, int dtype, int label_dtype);
+size_t mednet_head_ce_ws_bytes(int n, size_t spatial, int cin, int cout);
+int mednet_head_ce_gn_rows(int n, size_t spatial, int cin);
+int mednet_head_ce_fwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                       int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n, size_t spatial,
+                       int cin, int cout, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+int mednet_head_ce_bwd(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const void* packed,
+                       const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
+                       int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
+                       int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+int mednet_head_landmark_cls_fwd(const void* z, const void* packed, const float* bias, const void* heatmaps, int64_t heatmap_stride_n,
+                                 const void* labels, int64_t label_stride_n, const float* class_weight, const float* reg_weight,
+                                 float* logits, float* class_loss, float* reg_loss, float* saved, float* dice_metric, int n,
+                                 size_t spatial, int cin, int nh, int ncls, int kind, int class_kind, float eps, int sigmoid,
+                                 int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+int mednet_head_landmark_cls_bwd(const void* z, const void* packed, const float* bias, const void* heatmaps, int64_t heatmap_stride_n,
+                                 const void* labels, int64_t label_stride_n, const float* class_weight, const float* reg_weight,
+                                 const float* saved, const float* dclass_loss, const float* dreg_loss, void* dz, const void* gn_y,
+                                 int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int nh,
+                                 int ncls, int kind, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
+                                 size_t ws_bytes, mednet_stream stream);
 /* nn.CrossEntropyLoss(weight)  segmentation.py:49: sum w_y * -log softmax_y / sum w_y.  saved[0] = sum w_y. */
 int mednet_ce_fwd(const float* logits, const int64_t* labels, const float* weight, float* loss, float* saved,
                   int n, int c, size_t spatial, int64_t stride_n, int64_t stride_c, int ignore_index, void* ws,

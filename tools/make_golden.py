@@ -416,6 +416,106 @@ def caller_cases(out):
     print(f"[make_golden] callers: seg loss={float(res['loss']):.8f} ldmk loss={float(res2['loss']):.6f} ok")
 
 
+# callers_ce.npz: the class-loss choices of the callers (segmentation.py:43-49 `loss`, landmarks.py:43-56 `loss_class`), f_maps [32, 64]
+# so that the fused heads of the HIP path (32 features) meet these numbers.  Inputs are O.synthetic_batch / O.keyed_init_ with these
+# seeds; tests/test_callers_ce_golden.py and tests/test_gpu_ce_heads.py rebuild them.
+CE_SEG = dict(ctor=(1, 2, [32, 64]), shape=(16, 16, 16), weight=[0.05, 1.0], seed=1240, val_seeds=(640, 641))
+CE_LDMK = dict(ctor=(1, 5, [32, 64]), shape=(16, 16, 16), weight=[0.05, 1.0], regw=[0.015, 0.02, 0.001], seed=4330,
+               val_seeds=(740, 741))
+
+
+def ldmk_validation_step(model, loss_class, regw, batch):
+    """LandmarkNet.validation_step (landmarks.py:136-162) composed from the oracle: O.landmark_loss + O.dice_metric."""
+    x = batch["data"].float()
+    hm = batch["label"][:, :-1, ...].float()
+    nh = hm.shape[1]
+    y = batch["label"][:, -1, ...].long()
+    with torch.no_grad():
+        out = model(x)
+        tot, cl, rg = O.landmark_loss(out[:, nh:], out[:, :nh], y, hm, loss_class, nn.MSELoss(), regw)
+        dm = O.dice_metric(out[:, nh:], y)
+    res = {"val_loss": tot, "val_class_loss": cl, "val_regression_loss": rg}
+    for c in range(out.shape[1] - nh):
+        res[f"val_dice{c}"] = dm[c]
+    return res
+
+
+def caller_ce_cases(out):
+    """SegmentationNet(loss='CE') and LandmarkNet(loss_class='CE' / 'DICE') on the reference: training_step, validation_step,
+    validation_epoch_end -- asserted equal to the oracle composition before anything is written."""
+    rseg, rldm = import_reference_callers()
+    rec = {}
+    cin, cout, fm = CE_SEG["ctor"]
+    w = torch.tensor(CE_SEG["weight"])
+    hp = types.SimpleNamespace(in_channels=cin, out_channels=cout, fmaps=fm, learning_rate=1e-3, num_workers=0, batch_size=2,
+                               loss="CE", loss_weight=CE_SEG["weight"], log_interval=10 ** 9)
+    net = O.keyed_init_(rseg.SegmentationNet(hp))
+    assert isinstance(net.loss, nn.CrossEntropyLoss)
+    ora = O.keyed_init_(O.ResidualUNet3D(cin, cout, False, f_maps=fm))
+    batch = O.synthetic_batch(2, 1, CE_SEG["shape"], cout, 0, seed=CE_SEG["seed"])
+    res = net.training_step(batch, 0)
+    assert_same("ce_seg_step", res["loss"].detach(), O.seg_training_step(ora, nn.CrossEntropyLoss(weight=w), batch).detach())
+    rec["seg.loss"] = res["loss"].detach().numpy()
+    net.eval()
+    ora.eval()
+    vb = [O.synthetic_batch(2, 1, CE_SEG["shape"], cout, 0, seed=s) for s in CE_SEG["val_seeds"]]
+    with torch.no_grad():
+        vres = [net.validation_step(b, 1 + i) for i, b in enumerate(vb)]
+    vora = [O.seg_validation_step(ora, nn.CrossEntropyLoss(weight=w), b) for b in vb]
+    for i, (a, b) in enumerate(zip(vres, vora)):
+        assert list(a.keys()) == list(b.keys()) == ["val_loss", "val_dice0", "val_dice1"]
+        for k in a:
+            assert_same(f"ce_seg_val{i}.{k}", a[k].detach(), b[k].detach())
+            rec[f"seg.val{i}.{k}"] = b[k].numpy()
+    vend, oend = net.validation_epoch_end(vres), O.validation_epoch_end(vora)
+    assert sorted(vend.keys()) == ["log", "progress_bar", "val_loss"]
+    for k in oend:
+        assert_same("ce_seg_val_end." + k, vend["log"][k], oend[k])
+        rec["seg.val_end." + k] = oend[k].numpy()
+
+    cin, cout, fm = CE_LDMK["ctor"]
+    w = torch.tensor(CE_LDMK["weight"])
+    regw = CE_LDMK["regw"]
+    nh = len(regw)
+    batch = O.synthetic_batch(2, 1, CE_LDMK["shape"], cout - nh, nh, seed=CE_LDMK["seed"])
+    for kind, crit in (("L2", nn.MSELoss()), ("L1", nn.L1Loss())):
+        hp = types.SimpleNamespace(in_channels=cin, out_channels=cout, fmaps=fm, learning_rate=1e-3, num_workers=0, batch_size=2,
+                                   loss_class="CE", loss_class_weight=CE_LDMK["weight"], loss_regression=kind,
+                                   loss_regression_weight=regw, log_interval=10 ** 9)
+        net = O.keyed_init_(rldm.LandmarkNet(hp))
+        res = net.training_step(batch, 0)
+        ora = O.keyed_init_(O.ResidualUNet3D(cin, cout, False, f_maps=fm))
+        tot, cl, rg = O.ldmk_training_step(ora, nn.CrossEntropyLoss(weight=w), crit, regw, batch)
+        assert_same(f"ce_ldmk_step.{kind}", res["loss"].detach(), tot.detach())
+        assert res["log"]["class_loss"] == cl.item() and res["log"]["regression_loss"] == rg.item()
+        rec[f"ldmk.{kind}.loss"] = tot.detach().numpy()
+        rec[f"ldmk.{kind}.class_loss"] = cl.detach().numpy()
+        rec[f"ldmk.{kind}.regression_loss"] = rg.detach().numpy()
+    vb = [O.synthetic_batch(2, 1, CE_LDMK["shape"], cout - nh, nh, seed=s) for s in CE_LDMK["val_seeds"]]
+    for lc in ("DICE", "CE"):
+        hp = types.SimpleNamespace(in_channels=cin, out_channels=cout, fmaps=fm, learning_rate=1e-3, num_workers=0, batch_size=2,
+                                   loss_class=lc, loss_class_weight=CE_LDMK["weight"], loss_regression="L2",
+                                   loss_regression_weight=regw, log_interval=10 ** 9)
+        net = O.keyed_init_(rldm.LandmarkNet(hp)).eval()
+        ora = O.keyed_init_(O.ResidualUNet3D(cin, cout, False, f_maps=fm)).eval()
+        crit = O.DiceLoss(weight=w) if lc == "DICE" else nn.CrossEntropyLoss(weight=w)
+        with torch.no_grad():
+            vres = [net.validation_step(b, 1 + i) for i, b in enumerate(vb)]
+        vora = [ldmk_validation_step(ora, crit, regw, b) for b in vb]
+        for i, (a, b) in enumerate(zip(vres, vora)):
+            assert list(a.keys()) == list(b.keys()) == ["val_loss", "val_class_loss", "val_regression_loss", "val_dice0", "val_dice1"]
+            for k in a:
+                assert_same(f"ldmk_val.{lc}{i}.{k}", a[k].detach(), b[k].detach())
+                rec[f"ldmk_val.{lc}.{i}.{k}"] = b[k].numpy()
+        vend, oend = net.validation_epoch_end(vres), O.validation_epoch_end(vora)
+        assert sorted(vend.keys()) == ["log", "progress_bar", "val_loss"] and list(vend["log"]) == list(oend)
+        for k in oend:
+            assert_same(f"ldmk_val_end.{lc}.{k}", vend["log"][k], oend[k])
+            rec[f"ldmk_val_end.{lc}.{k}"] = oend[k].numpy()
+    np.savez_compressed(os.path.join(out, "callers_ce.npz"), **rec)
+    print(f"[make_golden] callers_ce: {len(rec)} values, seg CE loss {float(rec['seg.loss']):.7f} ok")
+
+
 def predict_cases(out):
     """Row N2: the reference's grid_patch_generator / GridPatchSampler.add_processed_batch (dataset.py) and
     the post-processing lines of examples/predict.py, run on deterministic inputs; oracle/ref_predict.py must agree
@@ -555,6 +655,8 @@ def main():
         loss_cases(a.out, rloss)
     if want("callers"):
         caller_cases(a.out)
+    if want("callers_ce"):
+        caller_ce_cases(a.out)
     if want("predict"):
         predict_cases(a.out)
     if want("sampler"):

@@ -468,6 +468,75 @@ extern "C" int mednet_head_landmark_bwd(const void* z, const void* packed, const
                   sigmoid, ignore_index, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ... with the class-loss kind as an argument (MEDNET_CLASS_DICE: the calls above; MEDNET_CLASS_CE: nn.CrossEntropyLoss) and, from the
+// forward, dice_metric of the class channels
+extern "C" int mednet_head_landmark_cls_fwd(const void* z, const void* packed, const float* bias, const void* heatmaps,
+                                            int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n,
+                                            const float* class_weight, const float* reg_weight, float* logits, float* class_loss,
+                                            float* reg_loss, float* saved, float* dice_metric, int n, size_t spatial, int cin, int nh,
+                                            int ncls, int kind, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype,
+                                            void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED,
+                 "head_landmark_cls_fwd: class-loss kind %d", class_kind);
+  MEDNET_REQUIRE(!(class_kind == MEDNET_CLASS_CE || dice_metric) || sigmoid == 0, MEDNET_E_UNSUPPORTED,
+                 "head_landmark_cls_fwd: cross-entropy and dice_metric are softmax forms");
+  MEDNET_REQUIRE(!(class_kind == MEDNET_CLASS_DICE && dice_metric) || ignore_index == MEDNET_NO_IGNORE, MEDNET_E_UNSUPPORTED,
+                 "head_landmark_cls_fwd: dice_metric of a Dice forward needs ignore_index == MEDNET_NO_IGNORE");
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = head_lm_chunks(spatial);
+  float* hm_partial = (float*)ws;
+  float* dice_partial = hm_partial + (size_t)n * nh * chunks;
+  float* ce_partial = dice_partial + (size_t)n * chunks * ncls * 2;
+  float* metric_saved = ce_partial + (size_t)n * chunks * 2;  // [ncls][2]: (the forward's fp64 combine writes its sums somewhere)
+  int rc;
+  if (class_kind == MEDNET_CLASS_DICE) {
+    rc = mednet_head_landmark_fwd(z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight, reg_weight, logits,
+                                  class_loss, reg_loss, saved, n, spatial, cin, nh, ncls, kind, eps, sigmoid, ignore_index, z_dtype, ws,
+                                  ws_bytes, stream);
+    if (rc || !dice_metric) return rc;
+  } else {
+    MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && heatmaps && labels && class_loss && reg_loss && saved && ws, MEDNET_E_SHAPE,
+                   "head_landmark_cls_fwd: bad arguments");
+    MEDNET_REQUIRE(mednet_head_landmark_supported(cin, nh, ncls, z_dtype, spatial), MEDNET_E_UNSUPPORTED,
+                   "head_landmark_cls_fwd: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", cin, nh, ncls, z_dtype, spatial);
+    MEDNET_REQUIRE(kind == MEDNET_REG_L2 || kind == MEDNET_REG_L1, MEDNET_E_UNSUPPORTED, "head_landmark_cls_fwd: regression kind %d", kind);
+    MEDNET_REQUIRE(ws_bytes >= head_lm_ws_bytes(n, spatial, nh, ncls), MEDNET_E_WORKSPACE, "head_landmark_cls_fwd: workspace too small");
+    const PackLayout L = pack_layout(cin, nh + ncls, 1);
+    const float* W = (const float*)((const char*)packed + L.f32_bwd);
+    rc = ELT_CALL(z_dtype, launch_head_lm_ce_fwd, z, W, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight, logits,
+                  hm_partial, dice_partial, ce_partial, n, spatial, nh, ncls, kind, ignore_index, s);
+    if (rc) return rc;
+    rc = launch_hm_finalize(hm_partial, reg_weight, reg_loss, n, nh, chunks, spatial, s);
+    if (rc) return rc;
+    rc = launch_ce_finalize(ce_partial, class_loss, saved, n * chunks, s);
+    if (rc || !dice_metric) return rc;
+  }
+  return launch_dice_finalize(dice_partial, nullptr, nullptr, metric_saved, ncls, n * chunks, 1e-5f, s, dice_metric);
+}
+extern "C" int mednet_head_landmark_cls_bwd(const void* z, const void* packed, const float* bias, const void* heatmaps,
+                                            int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n,
+                                            const float* class_weight, const float* reg_weight, const float* saved,
+                                            const float* dclass_loss, const float* dreg_loss, void* dz, const void* gn_y, int gn_act,
+                                            float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int nh, int ncls,
+                                            int kind, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
+                                            size_t ws_bytes, mednet_stream stream) {
+  if (class_kind == MEDNET_CLASS_DICE)
+    return mednet_head_landmark_bwd(z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight, reg_weight, saved,
+                                    dclass_loss, dreg_loss, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, cin, nh, ncls, kind, eps,
+                                    sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
+  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED, "head_landmark_cls_bwd: class-loss kind %d", class_kind);
+  MEDNET_REQUIRE(sigmoid == 0, MEDNET_E_UNSUPPORTED, "head_landmark_cls_bwd: cross-entropy is a softmax form");
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && heatmaps && labels && saved && dclass_loss && dreg_loss && dz && dw && ws,
+                 MEDNET_E_SHAPE, "head_landmark_cls_bwd: bad arguments");
+  MEDNET_REQUIRE(mednet_head_landmark_supported(cin, nh, ncls, z_dtype, spatial), MEDNET_E_UNSUPPORTED,
+                 "head_landmark_cls_bwd: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", cin, nh, ncls, z_dtype, spatial);
+  const PackLayout L = pack_layout(cin, nh + ncls, 1);
+  const float* W = (const float*)((const char*)packed + L.f32_bwd);
+  return ELT_CALL(z_dtype, launch_head_lm_ce_bwd, z, W, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, saved, class_weight,
+                  reg_weight, dclass_loss, dreg_loss, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, nh, ncls, kind, ignore_index,
+                  ws, ws_bytes, (hipStream_t)stream);
+}
+
 extern "C" int mednet_conv3d_dgrad_gn_rows(int n, int d, int h, int w, int cin, int cout, int algo) {
   if (!tuning_option("conv_fuse_gnb", 1) || !mednet_conv3d_act_supported(n, d, h, w, cout, cin, algo)) return 0;
   // (the kernel reads the layer's Cout channels, writes its Cin; 16-bit storage only, so the split-weight request counts as given)

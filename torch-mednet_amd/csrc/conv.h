@@ -58,7 +58,9 @@ int launch_pack_f32(const float* w, float* Pf, float* Pb, int cin, int cout, int
 int launch_hm_finalize(const float* partial, const float* cweight, float* loss, int n, int c, int nblocks, size_t spatial,
                        hipStream_t s);
 int launch_dice_finalize(const float* partial, const float* weight, float* loss, float* saved, int c, int nblocks, float eps,
-                         hipStream_t s);
+                         hipStream_t s, float* dice_out = nullptr);
+// partial[nblocks][2] = {sum w_y nll, sum w_y} -> *loss = num / den, saved[0] = den (ce_finalize_kernel)
+int launch_ce_finalize(const float* partial, float* loss, float* saved, int nblocks, hipStream_t s);
 
 // 16-bit matrix-core kernels, conv_mfma.hip (namespace mednet: bf16; api.hip declares the same set in namespace mednet_f16
 // for the fp16 build of that file)

@@ -77,3 +77,12 @@ int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const v
                        const float* dreg, float eps, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db,
                        int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, void* ws, size_t ws_bytes,
                        hipStream_t s);
+// ... with nn.CrossEntropyLoss(weight, ignore_index) as the class term (softmax): ce_partial [n][chunk][2] for ce_finalize, and
+// dice_partial takes dice_metric's unweighted, unmasked sums.  The backward reads saved[0] = sum w_y of the CE forward.
+int launch_head_lm_ce_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                          int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial, float* ce_partial,
+                          int n, size_t spatial, int nh, int ncls, int kind, int ignore, hipStream_t s);
+int launch_head_lm_ce_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                          int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
+                          const float* dreg, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db, int n,
+                          size_t spatial, int nh, int ncls, int kind, int ignore, void* ws, size_t ws_bytes, hipStream_t s);

@@ -81,14 +81,18 @@ __device__ __forceinline__ void probs_reg(const float* lg, int c, int sigmoid, f
 
 // ---- forward: one voxel per lane, weights wave-uniform (SGPR operands), 8 voxels per thread ------------------------------
 // logits[n][i][v] = bias[i] + sum_k z[n][v][k] W[i][k];  partial[n][block][c][2] = {sum p t mask, sum (p + t) mask}
-template <typename TI, int K, typename TL>
+// CE (head_ce): partial[n][block][2] = {sum w_y nll, sum w_y} instead (loss.hip ce_fwd_kernel's rows, for ce_finalize_kernel);
+// cw = the class weights (nullable; read by this form only), `sigmoid` unused
+template <typename TI, int K, typename TL, bool CE = false>
 __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict__ z, const float* __restrict__ Pb /*[m][K]*/,
                                                             const float* __restrict__ bias, const TL* __restrict__ lab,
                                                             int64_t lab_sn, float* __restrict__ y, float* __restrict__ partial,
-                                                            size_t spatial, int m, int sigmoid, int ignore) {
+                                                            size_t spatial, int m, int sigmoid, int ignore,
+                                                            const float* __restrict__ cw = nullptr) {
   __shared__ float scratch[4];
   const int n = blockIdx.y;
   float I[HL_MAXC], D[HL_MAXC];
+  float num = 0.f, den = 0.f;  // (CE)
   bool bad = false;
 #pragma unroll
   for (int k = 0; k < HL_MAXC; ++k) I[k] = D[k] = 0.f;
@@ -119,6 +123,27 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
           y[((size_t)n * m + i) * spatial + v] = lg[i];
         }
       }
+      if constexpr (CE) {
+        // loss.hip ce_fwd_kernel on registers: an out-of-range label that is not ignore_index poisons the loss
+        if (yl != ignore && (unsigned)yl >= (unsigned)m) num = __builtin_nanf("");
+        if (yl != ignore && yl >= 0 && yl < m) {
+          float mx = -INFINITY, zy = 0.f;
+#pragma unroll
+          for (int k = 0; k < HL_MAXC; ++k)
+            if (k < m) {
+              mx = fmaxf(mx, lg[k]);
+              if (k == yl) zy = lg[k];
+            }
+          float s = 0.f;
+#pragma unroll
+          for (int k = 0; k < HL_MAXC; ++k)
+            if (k < m) s += expf(lg[k] - mx);
+          const float w = cw ? cw[yl] : 1.f;
+          num = fmaf(w, (mx + logf(s)) - zy, num);
+          den += w;
+        }
+        continue;
+      }
       probs_reg(lg, m, sigmoid, p);
       bad |= (unsigned)yl >= (unsigned)m;  // (loss.hip dice_fwd_kernel: an out-of-range label poisons the loss)
 #pragma unroll
@@ -130,6 +155,16 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
           D[k] += (p[k] + t) * mk;
         }
     }
+  }
+  if constexpr (CE) {
+    num = block_sum<4>(num, scratch);
+    den = block_sum<4>(den, scratch);
+    if (threadIdx.x == 0) {
+      float* o = partial + ((size_t)n * gridDim.x + blockIdx.x) * 2;
+      o[0] = num;
+      o[1] = den;
+    }
+    return;
   }
   if (bad) I[0] = D[0] = __builtin_nanf("");
   float* out = partial + ((size_t)n * gridDim.x + blockIdx.x) * m * 2;
@@ -149,7 +184,9 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
 // wpart[n][block][wave][m * K + m]: this wave's partial of dW (row-major [class][channel]) and, behind it, of db
 // FOLD: z is the output of a fused conv -> activation layer and there are no GroupNorm sums to take (UNet3D's last block): the
 // stored gradient carries act'(z).  Its own instantiation: as a runtime branch it cost the main form its third wave per SIMD.
-template <typename TO, int K, typename TL, bool FOLD = false>
+// CE (head_ce): the logit gradient is loss.hip ce_bwd_kernel's closed form (dloss / saved[0]) w_y (p_k - [k == y]), 0 for an
+// ignored or out-of-range label; saved = {sum w_y} of the CE forward, `eps` and `sigmoid` unused.  Everything after it is shared.
+template <typename TO, int K, typename TL, bool FOLD = false, bool CE = false>
 __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_dice_bwd_kernel(const float* __restrict__ lgs, const TL* __restrict__ lab, int64_t lab_sn,
                                                             const float* __restrict__ Pb /*[m][K]*/, const float* __restrict__ weight,
                                                             const float* __restrict__ saved, const float* __restrict__ dloss,
@@ -165,13 +202,15 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
   for (int i = 0; i < HL_MAXC; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) wreg[i][j] = i < m ? Pb[(size_t)i * K + cgi * 8 + j] : 0.f;
-  // per-class coefficients of the closed form (loss.hip dice_bwd_kernel)
+  // per-class coefficients of the closed form (loss.hip dice_bwd_kernel; CE: gI[k] = w_k dloss / saved[0], ce_bwd_kernel's `w`)
   const float go = *dloss;
   float gI[HL_MAXC], gD[HL_MAXC];
 #pragma unroll
   for (int k = 0; k < HL_MAXC; ++k) {
     gI[k] = gD[k] = 0.f;
-    if (k < m) {
+    if (CE && k < m) {
+      gI[k] = (weight ? weight[k] : 1.f) * (go / saved[0]);
+    } else if (k < m) {
       const float w = weight ? weight[k] : 1.f;
       const float I = saved[2 * k], D = saved[2 * k + 1];
       const float Dc = fmaxf(D, eps);
@@ -180,6 +219,18 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
     }
   }
   auto dlogits_of = [&](const float* lg, int yl, float* dl) {  // the logit gradient of one voxel
+    if constexpr (CE) {
+      float p[HL_MAXC];
+      probs_reg(lg, m, 0, p);
+      float w = 0.f;
+#pragma unroll
+      for (int k = 0; k < HL_MAXC; ++k)
+        if (k < m && k == yl) w = gI[k];
+      w = (yl != ignore && yl >= 0 && yl < m) ? w : 0.f;
+#pragma unroll
+      for (int k = 0; k < HL_MAXC; ++k) dl[k] = k < m ? w * (p[k] - (k == yl ? 1.f : 0.f)) : 0.f;
+      return;
+    }
     float p[HL_MAXC], g[HL_MAXC];
     probs_reg(lg, m, sigmoid, p);
     float dot = 0.f;
@@ -392,21 +443,23 @@ extern "C" int mednet_head_dice_gn_rows(int n, size_t spatial, int cin) {
   return 4 * (int)hl_bwd_blocks(spatial, cin);
 }
 
-extern "C" int mednet_head_dice_fwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
-                                    int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
-                                    size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
-                                    void* ws, size_t ws_bytes, mednet_stream stream) {
+// the forward / backward launches of both loss forms (CE: head_dice_*_kernel<..., CE = true>, ce_finalize instead of dice_finalize)
+template <bool CE>
+static int head_loss_fwd(const char* what, const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                         int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n, size_t spatial,
+                         int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
+                         mednet_stream stream) {
   MEDNET_REQUIRE(mednet_head_dice_supported(cin, cout, z_dtype, label_dtype), MEDNET_E_UNSUPPORTED,
-                 "head_dice_fwd: %d -> %d classes, dtype %d, labels %d", cin, cout, z_dtype, label_dtype);
-  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && logits && loss && saved, MEDNET_E_SHAPE, "head_dice_fwd: bad arguments");
-  MEDNET_REQUIRE(ws_bytes >= mednet_head_dice_ws_bytes(n, spatial, cin, cout), MEDNET_E_WORKSPACE, "head_dice_fwd: workspace too small");
+                 "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && logits && loss && saved, MEDNET_E_SHAPE, "%s: bad arguments", what);
+  MEDNET_REQUIRE(ws_bytes >= mednet_head_dice_ws_bytes(n, spatial, cin, cout), MEDNET_E_WORKSPACE, "%s: workspace too small", what);
   const PackLayout L = pack_layout(cin, cout, 1);
   const float* Pb = (const float*)((const char*)packed + L.f32_bwd);  // Pb[t = 0][co][ci] = W[co][ci]
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = hl_fwd_blocks(spatial);
   float* partial = (float*)ws;
   const dim3 grid(nb, n);
-#define HF(TI_, K_, TL_) hipLaunchKernelGGL((head_dice_fwd_kernel<TI_, K_, TL_>), grid, dim3(256), 0, s, (const TI_*)z, Pb, bias, (const TL_*)labels, label_stride_n, logits, partial, spatial, cout, sigmoid, ignore_index)
+#define HF(TI_, K_, TL_) hipLaunchKernelGGL((head_dice_fwd_kernel<TI_, K_, TL_, CE>), grid, dim3(256), 0, s, (const TI_*)z, Pb, bias, (const TL_*)labels, label_stride_n, logits, partial, spatial, cout, sigmoid, ignore_index, CE ? weight : nullptr)
 #define HF_L(TI_, K_) do { if (label_dtype == MEDNET_U8) HF(TI_, K_, uint8_t); else HF(TI_, K_, int64_t); } while (0)
 #define HF_K(TI_) do { if (cin == 16) HF_L(TI_, 16); else if (cin == 32) HF_L(TI_, 32); else HF_L(TI_, 64); } while (0)
   if (z_dtype == MEDNET_F32) HF_K(float);
@@ -415,22 +468,23 @@ extern "C" int mednet_head_dice_fwd(const void* z, const void* packed, const flo
 #undef HF_K
 #undef HF_L
 #undef HF
-  int rc = check_launch("head_dice_fwd");
+  int rc = check_launch(what);
   if (rc) return rc;
+  if (CE) return launch_ce_finalize(partial, loss, saved, (int)(nb * n), s);
   hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, s, partial, weight, loss, saved, (float*)nullptr, cout, (int)(nb * n), eps);
   return check_launch("dice_finalize");
 }
 
-extern "C" int mednet_head_dice_bwd(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
-                                    const void* packed, const float* weight, const float* saved, const float* dloss, void* dz,
-                                    const void* gn_y, const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n,
-                                    size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
-                                    void* ws, size_t ws_bytes, mednet_stream stream) {
+template <bool CE>
+static int head_loss_bwd(const char* what, const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
+                         const void* packed, const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y,
+                         const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
+                         float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
   MEDNET_REQUIRE(mednet_head_dice_supported(cin, cout, z_dtype, label_dtype), MEDNET_E_UNSUPPORTED,
-                 "head_dice_bwd: %d -> %d classes, dtype %d, labels %d", cin, cout, z_dtype, label_dtype);
-  MEDNET_REQUIRE(n > 0 && spatial > 0 && logits && labels && packed && saved && dloss && dz && z && dw, MEDNET_E_SHAPE, "head_dice_bwd: bad arguments");
-  MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "head_dice_bwd: gn_y and gn_partial go together");
-  MEDNET_REQUIRE(ws_bytes >= mednet_head_dice_ws_bytes(n, spatial, cin, cout), MEDNET_E_WORKSPACE, "head_dice_bwd: workspace too small");
+                 "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && logits && labels && packed && saved && dloss && dz && z && dw, MEDNET_E_SHAPE, "%s: bad arguments", what);
+  MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "%s: gn_y and gn_partial go together", what);
+  MEDNET_REQUIRE(ws_bytes >= mednet_head_dice_ws_bytes(n, spatial, cin, cout), MEDNET_E_WORKSPACE, "%s: workspace too small", what);
   const PackLayout L = pack_layout(cin, cout, 1);
   const float* Pb = (const float*)((const char*)packed + L.f32_bwd);
   hipStream_t s = (hipStream_t)stream;
@@ -438,7 +492,7 @@ extern "C" int mednet_head_dice_bwd(const float* logits, const void* labels, int
   float* wpart = (float*)ws;
   const dim3 grid(nb, n);
   const bool fold = gn_y == nullptr && gn_act != MEDNET_ACT_NONE;
-#define HB_(TO_, K_, TL_, F_) hipLaunchKernelGGL((head_dice_bwd_kernel<TO_, K_, TL_, F_>), grid, dim3(256), 0, s, logits, (const TL_*)labels, label_stride_n, Pb, weight, saved, dloss, eps, sigmoid, ignore_index, (TO_*)dz, (const TO_*)gn_y, (const TO_*)z, gn_act, gn_partial, wpart, spatial, cout)
+#define HB_(TO_, K_, TL_, F_) hipLaunchKernelGGL((head_dice_bwd_kernel<TO_, K_, TL_, F_, CE>), grid, dim3(256), 0, s, logits, (const TL_*)labels, label_stride_n, Pb, weight, saved, dloss, eps, sigmoid, ignore_index, (TO_*)dz, (const TO_*)gn_y, (const TO_*)z, gn_act, gn_partial, wpart, spatial, cout)
 #define HB(TO_, K_, TL_) do { if (fold) HB_(TO_, K_, TL_, true); else HB_(TO_, K_, TL_, false); } while (0)
 #define HB_L(TO_, K_) do { if (label_dtype == MEDNET_U8) HB(TO_, K_, uint8_t); else HB(TO_, K_, int64_t); } while (0)
 #define HB_K(TO_) do { if (cin == 16) HB_L(TO_, 16); else if (cin == 32) HB_L(TO_, 32); else HB_L(TO_, 64); } while (0)
@@ -449,11 +503,53 @@ extern "C" int mednet_head_dice_bwd(const float* logits, const void* labels, int
 #undef HB_L
 #undef HB_
 #undef HB
-  int rc = check_launch("head_dice_bwd");
+  int rc = check_launch(what);
   if (rc) return rc;
   const int width = cout * cin + cout, rows = (int)(n * nb * 4);
   double* part2 = (double*)((char*)ws + (((size_t)rows * width + 64) * sizeof(float) + 7) / 8 * 8);
   hipLaunchKernelGGL(head_dice_wfinal1_kernel, dim3(HL_WF_GROUPS), dim3(192), 0, s, wpart, part2, rows, width);
   hipLaunchKernelGGL(head_dice_wfinal2_kernel, dim3(1), dim3(192), 0, s, part2, dw, dbias, width, cout * cin);
   return check_launch("head_dice_wfinal");
+}
+
+extern "C" int mednet_head_dice_fwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                                    int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
+                                    size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
+                                    void* ws, size_t ws_bytes, mednet_stream stream) {
+  return head_loss_fwd<false>("head_dice_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
+                              cin, cout, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
+}
+
+extern "C" int mednet_head_dice_bwd(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
+                                    const void* packed, const float* weight, const float* saved, const float* dloss, void* dz,
+                                    const void* gn_y, const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n,
+                                    size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
+                                    void* ws, size_t ws_bytes, mednet_stream stream) {
+  return head_loss_bwd<false>("head_dice_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
+                              gn_partial, dw, dbias, n, spatial, cin, cout, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
+}
+
+// ---- the same head fused with nn.CrossEntropyLoss(weight, ignore_index) (segmentation.py:49): the CE instantiations -------------
+extern "C" int mednet_head_ce_supported(int cin, int cout, int dtype, int label_dtype) {
+  return mednet_head_dice_supported(cin, cout, dtype, label_dtype);
+}
+extern "C" size_t mednet_head_ce_ws_bytes(int n, size_t spatial, int cin, int cout) {
+  return mednet_head_dice_ws_bytes(n, spatial, cin, cout);  // (the CE rows, 2 floats per workgroup, fit in the Dice form's 2 * cout)
+}
+extern "C" int mednet_head_ce_gn_rows(int n, size_t spatial, int cin) { return mednet_head_dice_gn_rows(n, spatial, cin); }
+
+extern "C" int mednet_head_ce_fwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                                  int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
+                                  size_t spatial, int cin, int cout, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
+                                  mednet_stream stream) {
+  return head_loss_fwd<true>("head_ce_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
+                             cin, cout, 0.f, 0, ignore_index, z_dtype, ws, ws_bytes, stream);
+}
+
+extern "C" int mednet_head_ce_bwd(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const void* packed,
+                                  const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
+                                  int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
+                                  int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  return head_loss_bwd<true>("head_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
+                             gn_partial, dw, dbias, n, spatial, cin, cout, 0.f, 0, ignore_index, z_dtype, ws, ws_bytes, stream);
 }

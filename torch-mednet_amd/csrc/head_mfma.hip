@@ -57,9 +57,13 @@ struct HlmArgs {
   int gn_act;
   float* gn_partial;     // [n][chunks][32][2] = {sum du, sum du * gn_y}, du = dz * act'(z)
   float* wpart;          // [n * chunks][HLM_WIDTH]
+  float* ce_partial;     // CE forward: [n][chunk][2] = {sum w_y nll, sum w_y}  (ce_finalize_kernel's layout)
 };
 
-template <bool BWD>
+// CE: the class term is nn.CrossEntropyLoss(weight, ignore_index) (landmarks.py:49) instead of Dice: the forward accumulates
+// ce_fwd_kernel's {sum w_y nll, sum w_y} and, for dice_metric (loss.py:51-55), the unweighted, unmasked softmax sums {I, D} into
+// dice_partial; the backward's class gradient is ce_bwd_kernel's closed form (dcls / sum w) w_y (p_k - [k == y]).  Softmax only.
+template <bool BWD, bool CE = false>
 __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
   typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
   __shared__ __attribute__((aligned(16))) char smem[256 * HLM_SCR * 4];
@@ -114,17 +118,21 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
   }
   // ---- constants of a lane half, in LDS (they would hold 36 registers for the whole kernel): per h the biases of its 8 heat maps
   // [0..7] and of the classes [8..11], the heat maps' gradient scales [12..19] and the Dice gradient terms gI [20..23], gD [24..27]
+  // (CE: the class weights [12..15] in the forward; w_k dcls / sum w [20..23] in the backward)
   if (wv == 2) {
     const int hh = lane >> 5, i = lane & 31;
     float v = 0.f;
     if (i < 8) v = (a.bias && 8 * hh + i < a.nh) ? a.bias[8 * hh + i] : 0.f;
     else if (i < 12) v = (a.bias && i - 8 < a.ncls) ? a.bias[a.nh + i - 8] : 0.f;
+    else if (CE && !BWD && i < 16) v = i - 12 < a.ncls ? (a.cls_weight ? a.cls_weight[i - 12] : 1.f) : 0.f;
     else if (BWD && i < 20) {
       const int c = 8 * hh + i - 12;
       v = c < a.nh ? *a.dreg * (a.reg_weight ? a.reg_weight[c] : 1.f) * a.inv_count : 0.f;
     } else if (BWD && i < 28) {  // loss.hip dice_bwd_kernel
       const int k = (i - 20) & 3;
-      if (k < a.ncls) {
+      if (CE && k < a.ncls) {
+        v = i < 24 ? (a.cls_weight ? a.cls_weight[k] : 1.f) * (*a.dcls / a.saved[0]) : 0.f;  // (ce_bwd_kernel's `w`)
+      } else if (k < a.ncls) {
         const float gc = *a.dcls, w = a.cls_weight ? a.cls_weight[k] : 1.f;
         const float I = a.saved[2 * k], D = a.saved[2 * k + 1];
         const float Dc = fmaxf(D, a.eps);
@@ -156,6 +164,10 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
   char* zt = smem + wv * 6144;
   char* dlh = zt + 2048;
   char* dll = zt + 4096;
+  // CE forward: {sum w_y nll, sum w_y} of this thread in its own slot of the end-of-kernel scratch (idle until then): as two more
+  // loop-carried registers they took the form past its Dice twin's 148 VGPRs
+  float* const ce_acc = reinterpret_cast<float*>(smem) + tid * HLM_SCR + 16;
+  if constexpr (CE && !BWD) ce_acc[0] = ce_acc[1] = 0.f;
   const int tq = (lane & 15) >> 2, tp = lane & 3, tg = lane >> 4;
   const int troff = (8 * h + tq) * 64 + (16 * (tg & 1) + 4 * tp) * 2;  // tr_operand: voxel rows 8h + tq (+ 4), 4 columns
   if constexpr (BWD) {  // columns 20 .. 31 of the dl tiles are never written: zero once (rows of dW that nobody reads, but no NaNs)
@@ -232,6 +244,7 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
       }
       const bool cls_lane = live && h == 0;
       const int yl = (int)((lb >> (8 * j)) & 0xFFu);
+      float lse = 0.f;  // (CE: max + log of the softmax's denominator)
       {
         // softmax / sigmoid of the class logits (loss.hip probs_of on registers)
         if (a.sigmoid) {
@@ -251,6 +264,7 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
           const float inv = 1.f / den;
 #pragma unroll
           for (int k = 0; k < HLM_MAXC; ++k) p[k] *= inv;
+          if (CE) lse = mx + logf(den);
         }
       }
       if constexpr (!BWD) {
@@ -261,7 +275,30 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
           const float t = a.kind == MEDNET_REG_L2 ? d * d : fabsf(d);
           hm_acc[e] += (live && 8 * h + e < a.nh) ? t : 0.f;
         }
-        if (cls_lane) {
+        if (CE && cls_lane) {
+          // ce_fwd_kernel: w_y ((max + log sum exp) - z_y); an out-of-range label that is not ignore_index poisons the loss
+          if (yl != a.ignore && (unsigned)yl >= (unsigned)a.ncls) ce_acc[0] = __builtin_nanf("");
+          if (yl != a.ignore && yl < a.ncls) {
+            float zy = 0.f, w = 0.f;
+#pragma unroll
+            for (int k = 0; k < HLM_MAXC; ++k)
+              if (k == yl) {
+                zy = lc[k];
+                w = cbase[12 + k];
+              }
+            ce_acc[0] = fmaf(w, lse - zy, ce_acc[0]);
+            ce_acc[1] += w;
+          }
+          // dice_metric's sums (dice_fwd_kernel without weight or mask)
+          bad |= (unsigned)yl >= (unsigned)a.ncls;
+#pragma unroll
+          for (int k = 0; k < HLM_MAXC; ++k)
+            if (k < a.ncls) {
+              const float t = (k == yl) ? 1.f : 0.f;
+              dI[k] = fmaf(p[k], t, dI[k]);
+              dD[k] += p[k] + t;
+            }
+        } else if (cls_lane) {
           bad |= (unsigned)yl >= (unsigned)a.ncls;
 #pragma unroll
           for (int k = 0; k < HLM_MAXC; ++k)
@@ -282,7 +319,18 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
           dh[e] = a.kind == MEDNET_REG_L2 ? 2.f * d * sc : (d > 0.f ? sc : (d < 0.f ? -sc : 0.f));
           dbh[e] += dh[e];
         }
-        {
+        if constexpr (CE) {
+          float wy = 0.f;
+#pragma unroll
+          for (int k = 0; k < HLM_MAXC; ++k)
+            if (k == yl) wy = cbase[20 + k];  // (0 for k >= ncls)
+          wy = (yl != a.ignore && yl < a.ncls) ? wy : 0.f;
+#pragma unroll
+          for (int k = 0; k < HLM_MAXC; ++k) {
+            dc[k] = (cls_lane && k < a.ncls) ? wy * (p[k] - (k == yl ? 1.f : 0.f)) : 0.f;
+            dbc[k] += dc[k];
+          }
+        } else {
           float gg[HLM_MAXC], dot = 0.f;
 #pragma unroll
           for (int k = 0; k < HLM_MAXC; ++k) {
@@ -386,7 +434,14 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
       mine[8 + k] = dI[k];
       mine[12 + k] = dD[k];
     }
-    __syncthreads();
+    __syncthreads();  // (CE: values 16 / 17 are the thread's ce_acc)
+    if (CE && tid >= 16 + 2 * HLM_MAXC && tid < 18 + 2 * HLM_MAXC) {  // CE sums: lanes of half 0, values 16 / 17
+      const int which = tid - (16 + 2 * HLM_MAXC);
+      float s = 0.f;
+      for (int w = 0; w < 4; ++w)
+        for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + gg) * HLM_SCR + 16 + which];
+      a.ce_partial[((size_t)n * a.chunks + chunk) * 2 + which] = s;
+    }
     if (tid < 16 + 2 * HLM_MAXC) {
       // heat map c = 8hh + e: lanes of half hh, value e; class sums: lanes of half 0
       const int hh = tid < 16 ? tid >> 3 : 0, idx = tid < 16 ? tid & 7 : tid - 8;
@@ -497,31 +552,47 @@ int head_lm_chunks(size_t spatial) {
 }
 size_t head_lm_ws_bytes(int n, size_t spatial, int nh, int ncls) {
   const size_t chunks = head_lm_chunks(spatial);
-  const size_t fwd = (size_t)n * chunks * (nh + 2 * ncls);
+  // forward: heat-map rows, Dice rows, CE rows [n][chunk][2] and dice_metric's scratch [ncls][2] (mednet_head_landmark_cls_fwd)
+  const size_t fwd = (size_t)n * chunks * (nh + 2 * ncls + 2) + 2 * (size_t)ncls;
   const size_t bwd = (size_t)n * chunks * HLM_WIDTH;
   return ((fwd > bwd ? fwd : bwd) + 64) * sizeof(float);
 }
 
-int launch_head_lm_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                       int64_t lab_sn, float* logits, float* hm_partial, float* dice_partial, int n, size_t spatial, int nh, int ncls,
-                       int kind, int sigmoid, int ignore, hipStream_t s) {
+template <bool CE>
+static int head_lm_fwd_launch(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                              int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial,
+                              float* ce_partial, int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, hipStream_t s) {
   HlmArgs a = {};
   a.z = (const elt*)z; a.W = W; a.bias = bias; a.tgt = (const uint8_t*)tgt; a.lab = (const uint8_t*)lab;
   a.tgt_sn = tgt_sn; a.lab_sn = lab_sn; a.spatial = spatial; a.nh = nh; a.ncls = ncls;
   head_lm_plan(spatial, a.runs, a.chunk_runs, a.chunks);
   a.kind = kind; a.sigmoid = sigmoid; a.ignore = ignore;
   a.hm_partial = hm_partial; a.dice_partial = dice_partial; a.logits = logits;
+  a.cls_weight = cls_weight; a.ce_partial = ce_partial;
   MEDNET_REQUIRE(tgt_sn % 4 == 0 && lab_sn % 4 == 0 && ((uintptr_t)tgt & 3) == 0 && ((uintptr_t)lab & 3) == 0, MEDNET_E_SHAPE,
                  "head_lm: targets and labels must be 4-byte aligned per sample");
-  hipLaunchKernelGGL(head_lm_kernel<false>, dim3(a.chunks, n), dim3(256), 0, s, a);
-  return check_launch("head_lm_fwd");
+  hipLaunchKernelGGL((head_lm_kernel<false, CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  return check_launch(CE ? "head_lm_ce_fwd" : "head_lm_fwd");
+}
+int launch_head_lm_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                       int64_t lab_sn, float* logits, float* hm_partial, float* dice_partial, int n, size_t spatial, int nh, int ncls,
+                       int kind, int sigmoid, int ignore, hipStream_t s) {
+  return head_lm_fwd_launch<false>(z, W, bias, tgt, tgt_sn, lab, lab_sn, nullptr, logits, hm_partial, dice_partial, nullptr, n, spatial,
+                                   nh, ncls, kind, sigmoid, ignore, s);
+}
+int launch_head_lm_ce_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                          int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial, float* ce_partial,
+                          int n, size_t spatial, int nh, int ncls, int kind, int ignore, hipStream_t s) {
+  return head_lm_fwd_launch<true>(z, W, bias, tgt, tgt_sn, lab, lab_sn, cls_weight, logits, hm_partial, dice_partial, ce_partial, n,
+                                  spatial, nh, ncls, kind, 0, ignore, s);
 }
 
-int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                       int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
-                       const float* dreg, float eps, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db,
-                       int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, void* ws, size_t ws_bytes,
-                       hipStream_t s) {
+template <bool CE>
+static int head_lm_bwd_launch(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                              int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
+                              const float* dreg, float eps, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db,
+                              int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, void* ws, size_t ws_bytes,
+                              hipStream_t s) {
   HlmArgs a = {};
   a.z = (const elt*)z; a.W = W; a.bias = bias; a.tgt = (const uint8_t*)tgt; a.lab = (const uint8_t*)lab;
   a.tgt_sn = tgt_sn; a.lab_sn = lab_sn; a.spatial = spatial; a.nh = nh; a.ncls = ncls;
@@ -535,12 +606,27 @@ int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const v
   MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "head_lm_bwd: gn_y and gn_partial go together");
   MEDNET_REQUIRE(ws_bytes >= head_lm_ws_bytes(n, spatial, nh, ncls), MEDNET_E_WORKSPACE, "head_lm_bwd: workspace too small");
   a.wpart = (float*)ws;
-  hipLaunchKernelGGL(head_lm_kernel<true>, dim3(a.chunks, n), dim3(256), 0, s, a);
-  int rc = check_launch("head_lm_bwd");
+  hipLaunchKernelGGL((head_lm_kernel<true, CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  int rc = check_launch(CE ? "head_lm_ce_bwd" : "head_lm_bwd");
   if (rc) return rc;
   const int total = (nh + ncls) * 33;
   hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((total + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, nh, ncls, dw, db);
   return check_launch("head_lm_wfinal");
+}
+int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                       int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
+                       const float* dreg, float eps, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db,
+                       int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, void* ws, size_t ws_bytes,
+                       hipStream_t s) {
+  return head_lm_bwd_launch<false>(z, W, bias, tgt, tgt_sn, lab, lab_sn, saved, cls_weight, reg_weight, dcls, dreg, eps, dz, gn_y, gn_act,
+                                   gn_partial, dw, db, n, spatial, nh, ncls, kind, sigmoid, ignore, ws, ws_bytes, s);
+}
+int launch_head_lm_ce_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                          int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
+                          const float* dreg, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db, int n,
+                          size_t spatial, int nh, int ncls, int kind, int ignore, void* ws, size_t ws_bytes, hipStream_t s) {
+  return head_lm_bwd_launch<true>(z, W, bias, tgt, tgt_sn, lab, lab_sn, saved, cls_weight, reg_weight, dcls, dreg, 0.f, dz, gn_y, gn_act,
+                                  gn_partial, dw, db, n, spatial, nh, ncls, kind, 0, ignore, ws, ws_bytes, s);
 }
 
 }  // namespace mednet

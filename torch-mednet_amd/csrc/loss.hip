@@ -343,9 +343,14 @@ int launch_hm_finalize(const float* partial, const float* cweight, float* loss, 
   return check_launch("heatmap_loss_finalize");
 }
 int launch_dice_finalize(const float* partial, const float* weight, float* loss, float* saved, int c, int nblocks, float eps,
-                         hipStream_t s) {
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, s, partial, weight, loss, saved, (float*)nullptr, c, nblocks, eps);
+                         hipStream_t s, float* dice_out) {
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, s, partial, weight, loss, saved, dice_out, c, nblocks, eps);
   return check_launch("dice_finalize");
+}
+// (for the fused CE heads, head_loss.hip / head_mfma.hip, whose partial rows have ce_fwd_kernel's layout)
+int launch_ce_finalize(const float* partial, float* loss, float* saved, int nblocks, hipStream_t s) {
+  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, loss, saved, nblocks);
+  return check_launch("ce_finalize");
 }
 
 }  // namespace mednet

@@ -1132,6 +1132,84 @@ def head_dice(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5, sigmo
     return HeadDiceFn.apply(x, weight, bias, packed, labels, loss_weight, eps, sigmoid, ignore_index)
 
 
+def head_ce_supported(x: torch.Tensor, cin: int, cout: int, labels: torch.Tensor) -> bool:
+    if not (FUSE_HEAD_LOSS and x.is_cuda and x.dim() == 5 and labels.is_cuda):
+        return False
+    if x.dtype != config.act_dtype() or not x.is_contiguous(memory_format=CL):
+        return False
+    ld = L.U8 if labels.dtype == torch.uint8 else L.I64
+    return bool(L.lib().mednet_head_ce_supported(cin, cout, L.dt(x), ld))
+
+
+class HeadCEFn(Function):
+    """logits = final_conv(x) and loss = nn.CrossEntropyLoss(weight, ignore_index)(logits, labels) (segmentation.py:49, 61-62) as
+    ONE autograd node -- HeadDiceFn with the cross-entropy closed form (mednet_head_ce_fwd / _bwd): no int64 label copy, no
+    logit-gradient tensor.  Returns (logits, loss); the logits are not a differentiable output of this node."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, packed, labels, loss_weight, ignore_index):
+        L.require_gpu(x, "head_ce")
+        n, cin, d, h, w = x.shape
+        cout = weight.shape[0]
+        spatial = d * h * w
+        lab, lab_sn, lab_dt = _label_view(labels, n, (d, h, w))
+        wt = None if loss_weight is None else loss_weight.to(device=x.device, dtype=torch.float32).contiguous()
+        logits = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        saved = torch.empty((2,), dtype=torch.float32, device=x.device)
+        lib = L.lib()
+        ws = L.workspace(lib.mednet_head_ce_ws_bytes(n, spatial, cin, cout), x.device)
+        ii = int(ignore_index)
+        L.check(lib.mednet_head_ce_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt),
+                                       logits.data_ptr(), loss.data_ptr(), saved.data_ptr(), n, spatial, cin, cout, ii, L.dt(x),
+                                       ws.data_ptr(), ws.numel(), L.stream()), "head_ce_fwd")
+        ctx.save_for_backward(x, packed, logits, lab, wt, saved)
+        ctx.meta = (ii, lab_sn, lab_dt, cin, cout)
+        ctx.params = (weight, bias)
+        ctx.gn3 = _gn3_hook_of(x, x.dtype)
+        ctx.inmask = getattr(x, "_mednet_actmask", None) if (ctx.gn3 is None and FUSE_GN3 and POOL_ACT_MASK) else None
+        ctx.mark_non_differentiable(logits)
+        if debug.TRACE is not None:
+            debug.trace("head_ce.fwd", logits, loss, saved)
+        return logits, loss
+
+    @staticmethod
+    def backward(ctx, _dlogits, dloss):
+        x, packed, logits, lab, wt, saved = ctx.saved_tensors
+        ii, lab_sn, lab_dt, cin, cout = ctx.meta
+        weight, bias = ctx.params
+        n, _, d, h, w = x.shape
+        spatial = d * h * w
+        lib = L.lib()
+        dl = dloss.to(torch.float32).contiguous()
+        dx = torch.empty_like(x, memory_format=CL)
+        dw, direct_w = _grad_target(weight, (cout, cin, 1, 1, 1))
+        db, direct_b = (None, True) if bias is None else _grad_target(bias, (cout,))
+        hook = ctx.gn3
+        partial = None
+        if hook is not None:
+            partial = torch.empty((n, lib.mednet_head_ce_gn_rows(n, spatial, cin), cin, 2), dtype=torch.float32, device=x.device)
+        ws = L.workspace(lib.mednet_head_ce_ws_bytes(n, spatial, cin, cout), x.device)
+        L.check(lib.mednet_head_ce_bwd(logits.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, packed.data_ptr(), L.ptr(wt),
+                                       saved.data_ptr(), dl.data_ptr(), dx.data_ptr(),
+                                       None if hook is None else hook.gn_in.data_ptr(), x.data_ptr(),
+                                       hook.act if hook is not None else (ctx.inmask.act if ctx.inmask is not None else 0),
+                                       L.ptr(partial), dw.data_ptr(), L.ptr(db), n, spatial, cin, cout, ii, L.dt(x),
+                                       ws.data_ptr(), ws.numel(), L.stream()), "head_ce_bwd")
+        if hook is not None:
+            hook.offer(dx, partial)
+        elif ctx.inmask is not None:
+            ctx.inmask.offer(dx)
+        if debug.TRACE is not None:
+            debug.trace("head_ce.bwd", dx, partial, dw, db)
+        return dx, (None if direct_w else dw), (None if (bias is None or direct_b) else db), None, None, None, None
+
+
+def head_ce(x, weight, bias, packed, labels, loss_weight=None, ignore_index=-100):
+    """-> (logits N x C x D x H x W fp32, cross-entropy loss)."""
+    return HeadCEFn.apply(x, weight, bias, packed, labels, loss_weight, ignore_index)
+
+
 def _heatmap_view(heatmaps: torch.Tensor, n: int, nh: int, spatial_shape):
     """uint8 heat-map targets as the fused landmark head takes them: N x nh x spatial, channels dense, any stride between samples
     (the first channels of a uint8 label volume are consumed where they lie, landmarks.py:69)."""
@@ -1165,39 +1243,21 @@ class HeadLandmarkFn(Function):
     mean f(outputs[:, c] - heatmaps[:, c]).  Forward: one matrix-core pass over the features that writes nothing but loss partials
     (mednet_head_landmark_fwd); backward: one pass that rebuilds the logits the same way and produces the feature gradient, the
     head's weight / bias gradients and the first pass of the producing block's GroupNorm-3 backward
-    (mednet_head_landmark_bwd).  No logit or logit-gradient tensor exists.  Returns (class_loss, regression_loss)."""
+    (mednet_head_landmark_bwd).  No logit or logit-gradient tensor exists.  Returns (class_loss, regression_loss).
+    class_kind CLASS_CE: the class term is nn.CrossEntropyLoss(class_weight, ignore_index) (landmarks.py:49; the _cls_ entry points)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, packed, heatmaps, labels, class_weight, reg_weight, kind, eps, sigmoid, ignore_index):
+    def forward(ctx, x, weight, bias, packed, heatmaps, labels, class_weight, reg_weight, kind, eps, sigmoid, ignore_index,
+                class_kind=L.CLASS_DICE):
         L.require_gpu(x, "head_landmark")
-        n, cin, d, h, w = x.shape
+        n, cin = x.shape[:2]
         nh = heatmaps.shape[1]
         ncls = weight.shape[0] - nh
-        spatial = d * h * w
-        hm, hm_sn = _heatmap_view(heatmaps, n, nh, (d, h, w))
-        lab, lab_sn, _ = _label_view(labels, n, (d, h, w))
-        # launch_head_lm_* reads targets and labels four voxels at a time: base pointers and sample strides must be multiples of 4
-        # bytes.  A view with an odd storage offset / stride (e.g. a label volume sliced at an odd channel offset) is copied once.
-        if hm.data_ptr() % 4 or (n > 1 and hm_sn % 4):
-            hm = hm.contiguous().clone() if hm.is_contiguous() else hm.contiguous()
-            hm_sn = nh * spatial
-        if lab.data_ptr() % 4 or (n > 1 and lab_sn % 4):
-            lab = lab.contiguous().clone() if lab.is_contiguous() else lab.contiguous()
-            lab_sn = spatial
-        cw = None if class_weight is None else class_weight.to(device=x.device, dtype=torch.float32).contiguous()
-        rw = None if reg_weight is None else torch.as_tensor(reg_weight, dtype=torch.float32, device=x.device).contiguous()
-        closs = torch.empty((), dtype=torch.float32, device=x.device)
-        rloss = torch.empty((), dtype=torch.float32, device=x.device)
-        saved = torch.empty((ncls, 2), dtype=torch.float32, device=x.device)
-        lib = L.lib()
-        ws = L.workspace(lib.mednet_head_landmark_ws_bytes(n, spatial, nh, ncls), x.device)
-        ii = L.NO_IGNORE if ignore_index is None else int(ignore_index)
-        L.check(lib.mednet_head_landmark_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(), lab_sn,
-                                             L.ptr(cw), L.ptr(rw), None, closs.data_ptr(), rloss.data_ptr(), saved.data_ptr(), n,
-                                             spatial, cin, nh, ncls, kind, eps, int(sigmoid), ii, L.dt(x), ws.data_ptr(), ws.numel(),
-                                             L.stream()), "head_landmark_fwd")
+        hm, hm_sn, lab, lab_sn, cw, rw, ii = _landmark_operands(x, heatmaps, labels, class_weight, reg_weight, ignore_index)
+        closs, rloss, saved, _ = _landmark_fwd(x, packed, bias, hm, hm_sn, lab, lab_sn, cw, rw, nh, ncls, kind, eps, sigmoid, ii,
+                                               class_kind, False)
         ctx.save_for_backward(x, packed, hm, lab, cw, rw, saved)
-        ctx.meta = (kind, eps, int(sigmoid), ii, hm_sn, lab_sn, cin, nh, ncls)
+        ctx.meta = (kind, eps, int(sigmoid), ii, hm_sn, lab_sn, cin, nh, ncls, class_kind)
         ctx.params = (weight, bias)
         ctx.gn3 = _gn3_hook_of(x, x.dtype)
         if debug.TRACE is not None:
@@ -1207,7 +1267,7 @@ class HeadLandmarkFn(Function):
     @staticmethod
     def backward(ctx, dclass, dreg):
         x, packed, hm, lab, cw, rw, saved = ctx.saved_tensors
-        kind, eps, sigmoid, ii, hm_sn, lab_sn, cin, nh, ncls = ctx.meta
+        kind, eps, sigmoid, ii, hm_sn, lab_sn, cin, nh, ncls, class_kind = ctx.meta
         weight, bias = ctx.params
         n, _, d, h, w = x.shape
         spatial = d * h * w
@@ -1225,23 +1285,93 @@ class HeadLandmarkFn(Function):
         if hook is not None:
             partial = torch.empty((n, lib.mednet_head_landmark_gn_rows(spatial), cin, 2), dtype=torch.float32, device=x.device)
         ws = L.workspace(lib.mednet_head_landmark_ws_bytes(n, spatial, nh, ncls), x.device)
-        L.check(lib.mednet_head_landmark_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(), lab_sn,
-                                             L.ptr(cw), L.ptr(rw), saved.data_ptr(), dc.data_ptr(), dr.data_ptr(), dx.data_ptr(),
-                                             None if hook is None else hook.gn_in.data_ptr(), hook.act if hook is not None else 0,
-                                             L.ptr(partial), dw.data_ptr(), L.ptr(db), n, spatial, cin, nh, ncls, kind, eps, sigmoid,
-                                             ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_landmark_bwd")
+        if class_kind == L.CLASS_DICE:
+            L.check(lib.mednet_head_landmark_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(), lab_sn,
+                                                 L.ptr(cw), L.ptr(rw), saved.data_ptr(), dc.data_ptr(), dr.data_ptr(), dx.data_ptr(),
+                                                 None if hook is None else hook.gn_in.data_ptr(), hook.act if hook is not None else 0,
+                                                 L.ptr(partial), dw.data_ptr(), L.ptr(db), n, spatial, cin, nh, ncls, kind, eps, sigmoid,
+                                                 ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_landmark_bwd")
+        else:
+            L.check(lib.mednet_head_landmark_cls_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(),
+                                                     lab_sn, L.ptr(cw), L.ptr(rw), saved.data_ptr(), dc.data_ptr(), dr.data_ptr(),
+                                                     dx.data_ptr(), None if hook is None else hook.gn_in.data_ptr(),
+                                                     hook.act if hook is not None else 0, L.ptr(partial), dw.data_ptr(), L.ptr(db), n,
+                                                     spatial, cin, nh, ncls, kind, class_kind, eps, sigmoid, ii, L.dt(x), ws.data_ptr(),
+                                                     ws.numel(), L.stream()), "head_landmark_cls_bwd")
         if hook is not None:
             hook.offer(dx, partial)
         if debug.TRACE is not None:
             debug.trace("head_landmark.bwd", dx, partial, dw, db)
-        return (dx, (None if direct_w else dw), (None if (bias is None or direct_b) else db)) + (None,) * 9
+        return (dx, (None if direct_w else dw), (None if (bias is None or direct_b) else db)) + (None,) * 10
 
 
 def head_landmark(x, weight, bias, packed, heatmaps, labels, class_weight=None, reg_weight=None, kind="L2", eps=1e-5, sigmoid=False,
-                  ignore_index=None):
-    """-> (class_loss, regression_loss) of LandmarkNet.loss on final_conv(x)."""
+                  ignore_index=None, class_loss="DICE"):
+    """-> (class_loss, regression_loss) of LandmarkNet.loss on final_conv(x); class_loss "DICE" (DiceLoss) or "CE"
+    (nn.CrossEntropyLoss: softmax, `ignore_index` as that module's, -100 by default there)."""
     return HeadLandmarkFn.apply(x, weight, bias, packed, heatmaps, labels, class_weight, reg_weight,
-                                L.REG_L2 if kind == "L2" else L.REG_L1, eps, sigmoid, ignore_index)
+                                L.REG_L2 if kind == "L2" else L.REG_L1, eps, sigmoid, ignore_index, _class_kind(class_loss))
+
+
+def head_landmark_eval(x, weight, bias, packed, heatmaps, labels, class_weight=None, reg_weight=None, kind="L2", eps=1e-5,
+                       ignore_index=None, class_loss="DICE"):
+    """Forward only (LandmarkNet.validation_step, landmarks.py:136-162): -> (class_loss, regression_loss, dice_metric [ncls]) of
+    final_conv(x) from ONE pass over the features, no autograd node, no logit tensor (mednet_head_landmark_cls_fwd)."""
+    L.require_gpu(x, "head_landmark")
+    nh = heatmaps.shape[1]
+    ncls = weight.shape[0] - nh
+    hm, hm_sn, lab, lab_sn, cw, rw, ii = _landmark_operands(x, heatmaps, labels, class_weight, reg_weight, ignore_index)
+    closs, rloss, _, dice = _landmark_fwd(x, packed, bias, hm, hm_sn, lab, lab_sn, cw, rw, nh, ncls, L.REG_L2 if kind == "L2" else L.REG_L1,
+                                          eps, False, ii, _class_kind(class_loss), True)
+    return closs, rloss, dice
+
+
+def _class_kind(class_loss):
+    if class_loss not in ("DICE", "CE"):
+        raise ValueError(f"class_loss must be 'DICE' or 'CE', not {class_loss!r}")
+    return L.CLASS_DICE if class_loss == "DICE" else L.CLASS_CE
+
+
+def _landmark_operands(x, heatmaps, labels, class_weight, reg_weight, ignore_index):
+    n, _, d, h, w = x.shape
+    nh = heatmaps.shape[1]
+    spatial = d * h * w
+    hm, hm_sn = _heatmap_view(heatmaps, n, nh, (d, h, w))
+    lab, lab_sn, _ = _label_view(labels, n, (d, h, w))
+    # launch_head_lm_* reads targets and labels four voxels at a time: base pointers and sample strides must be multiples of 4
+    # bytes.  A view with an odd storage offset / stride (e.g. a label volume sliced at an odd channel offset) is copied once.
+    if hm.data_ptr() % 4 or (n > 1 and hm_sn % 4):
+        hm = hm.contiguous().clone() if hm.is_contiguous() else hm.contiguous()
+        hm_sn = nh * spatial
+    if lab.data_ptr() % 4 or (n > 1 and lab_sn % 4):
+        lab = lab.contiguous().clone() if lab.is_contiguous() else lab.contiguous()
+        lab_sn = spatial
+    cw = None if class_weight is None else class_weight.to(device=x.device, dtype=torch.float32).contiguous()
+    rw = None if reg_weight is None else torch.as_tensor(reg_weight, dtype=torch.float32, device=x.device).contiguous()
+    ii = L.NO_IGNORE if ignore_index is None else int(ignore_index)
+    return hm, hm_sn, lab, lab_sn, cw, rw, ii
+
+
+def _landmark_fwd(x, packed, bias, hm, hm_sn, lab, lab_sn, cw, rw, nh, ncls, kind, eps, sigmoid, ii, class_kind, metric):
+    n, cin, d, h, w = x.shape
+    spatial = d * h * w
+    closs = torch.empty((), dtype=torch.float32, device=x.device)
+    rloss = torch.empty((), dtype=torch.float32, device=x.device)
+    saved = torch.empty((ncls, 2), dtype=torch.float32, device=x.device)
+    dice = torch.empty((ncls,), dtype=torch.float32, device=x.device) if metric else None
+    lib = L.lib()
+    ws = L.workspace(lib.mednet_head_landmark_ws_bytes(n, spatial, nh, ncls), x.device)
+    if class_kind == L.CLASS_DICE and not metric:
+        L.check(lib.mednet_head_landmark_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(), lab_sn,
+                                             L.ptr(cw), L.ptr(rw), None, closs.data_ptr(), rloss.data_ptr(), saved.data_ptr(), n,
+                                             spatial, cin, nh, ncls, kind, eps, int(sigmoid), ii, L.dt(x), ws.data_ptr(), ws.numel(),
+                                             L.stream()), "head_landmark_fwd")
+    else:
+        L.check(lib.mednet_head_landmark_cls_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(),
+                                                 lab_sn, L.ptr(cw), L.ptr(rw), None, closs.data_ptr(), rloss.data_ptr(), saved.data_ptr(),
+                                                 L.ptr(dice), n, spatial, cin, nh, ncls, kind, class_kind, eps, int(sigmoid), ii, L.dt(x),
+                                                 ws.data_ptr(), ws.numel(), L.stream()), "head_landmark_cls_fwd")
+    return closs, rloss, saved, dice
 
 
 def per_channel_dice(logits, labels, weight=None, eps=1e-5, sigmoid=False, ignore_index=None):

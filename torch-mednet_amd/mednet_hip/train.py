@@ -414,18 +414,21 @@ class SegmentationStep(_GraphedStep):
 
     def _head_loss(self, inputs, label_u8):
         """`outputs = self(inputs); loss = self.loss(outputs, labels)` (segmentation.py:61-62).  When the model is this package's
-        U-Net with a 1x1x1 head of at most 4 classes and the loss is DiceLoss, the head and the loss run as one fused node
-        (ops.head_dice: logits written once, no logit-gradient tensor, the label volume's uint8 channel consumed where it
-        lies); anything else takes the two calls as they stand."""
+        U-Net with a 1x1x1 head of at most 4 classes and the loss is DiceLoss or CrossEntropyLoss, the head and the loss run as one
+        fused node (ops.head_dice / ops.head_ce: logits written once, no logit-gradient tensor, the label volume's uint8 channel
+        consumed where it lies); anything else takes the two calls as they stand."""
         from .unet.model import _UNetCore
         m, fc = self.model, getattr(self.model, "final_conv", None)
-        if (isinstance(m, _UNetCore) and not m.testing and isinstance(self.loss, HL.DiceLoss) and not self.loss.skip_last_target
+        dice = isinstance(self.loss, HL.DiceLoss)
+        if (isinstance(m, _UNetCore) and not m.testing and (isinstance(self.loss, HL.CrossEntropyLoss) or (dice and not self.loss.skip_last_target))
                 and fc is not None and getattr(fc, "planar_output", False) and fc.kernel_size[0] == 1 and inputs.is_cuda
                 and not _call_is_hooked(m, fc)):
             feats = m.forward_features(inputs)
-            if ops.head_dice_supported(feats, fc.in_channels, fc.out_channels, label_u8):
+            if dice and ops.head_dice_supported(feats, fc.in_channels, fc.out_channels, label_u8):
                 return ops.head_dice(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon,
                                      self.loss.sigmoid_normalization, self.loss.ignore_index)
+            if not dice and ops.head_ce_supported(feats, fc.in_channels, fc.out_channels, label_u8):
+                return ops.head_ce(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.ignore_index)
             outputs = fc(feats)
         else:
             outputs = m(inputs)
@@ -485,14 +488,36 @@ class SegmentationValidation:
         return {"val_loss": logs["val_loss"], "log": logs, "progress_bar": logs}
 
 
-class LandmarkStep(_GraphedStep):
-    """LandmarkNet.training_step (landmarks.py:66-83, loss :125-134) with the per-channel regression loop fused."""
+def _landmark_losses(class_weight, regression_weight, class_loss, regression, dev):
+    """LandmarkNet's two criteria (landmarks.py:43-56): DiceLoss or nn.CrossEntropyLoss(weight) for the class channels, the fused
+    per-channel heat-map regression for the others."""
+    if class_loss not in ("DICE", "CE"):
+        raise ValueError(f"class_loss must be 'DICE' or 'CE', not {class_loss!r}")
+    w = torch.tensor(class_weight, dtype=torch.float32, device=dev)
+    loss_class = (HL.DiceLoss(weight=w) if class_loss == "DICE" else HL.CrossEntropyLoss(weight=w)).to(dev)
+    return loss_class, HL.HeatmapRegressionLoss(regression_weight, regression).to(dev)
 
-    def __init__(self, model, class_weight, regression_weight, regression="L2", lr=1e-3, world_size=1, graph=None):
+
+def _landmark_head_fusable(model, loss_class, loss_reg, inputs) -> bool:
+    """The fused landmark head serves this package's U-Net with a planar 1x1x1 head and L1 / L2 regression, without hooks: its node
+    bypasses model.__call__ and final_conv.__call__ and never forms `outputs`, so with a forward (pre-)hook on the model, on one of
+    its children or a global module hook the stock m(inputs) path runs and the hook sees its tensor."""
+    from .unet.model import _UNetCore
+    fc = getattr(model, "final_conv", None)
+    return (isinstance(model, _UNetCore) and not model.testing and fc is not None and getattr(fc, "planar_output", False)
+            and fc.kernel_size[0] == 1 and inputs.is_cuda and not getattr(loss_class, "skip_last_target", False)
+            and loss_reg.kind in ("L1", "L2") and not _call_is_hooked(model, fc))
+
+
+class LandmarkStep(_GraphedStep):
+    """LandmarkNet.training_step (landmarks.py:66-83, loss :125-134) with the per-channel regression loop fused.  class_loss:
+    the hparams' `loss_class`, "DICE" (DiceLoss) or "CE" (nn.CrossEntropyLoss(weight=class_weight))."""
+
+    def __init__(self, model, class_weight, regression_weight, regression="L2", lr=1e-3, world_size=1, graph=None, class_loss="DICE"):
         self.model = model
         dev = next(model.parameters()).device
-        self.loss_class = HL.DiceLoss(weight=torch.tensor(class_weight, dtype=torch.float32, device=dev)).to(dev)
-        self.loss_reg = HL.HeatmapRegressionLoss(regression_weight, regression).to(dev)
+        self.class_loss = class_loss
+        self.loss_class, self.loss_reg = _landmark_losses(class_weight, regression_weight, class_loss, regression, dev)
         self.flat = FlatParams(model)
         self.opt = FlatAdam(self.flat, lr=lr)
         self.repack = BatchedRepack(model)
@@ -506,15 +531,14 @@ class LandmarkStep(_GraphedStep):
         """`outputs = self(inputs)` and the two terms of LandmarkNet.loss (landmarks.py:71-75, 125-134).  In the 16-bit storage
         modes, with this package's U-Net, a 32-feature 1x1x1 head and uint8 targets, head and losses run as one fused node on the
         matrix cores (ops.head_landmark: no logit tensor); anything else takes the calls as they stand."""
-        from .unet.model import _UNetCore
         m, fc = self.model, getattr(self.model, "final_conv", None)
-        # (the fused branch bypasses model.__call__ and final_conv.__call__ and never forms `outputs`: with a forward (pre-)hook on
-        #  the model, on one of its children or a global module hook, the stock m(inputs) path runs so that the hook sees its tensor)
-        if (isinstance(m, _UNetCore) and not m.testing and fc is not None and getattr(fc, "planar_output", False)
-                and fc.kernel_size[0] == 1 and inputs.is_cuda and not self.loss_class.skip_last_target and self.loss_reg.kind in ("L1", "L2")
-                and not _call_is_hooked(m, fc)):
+        if _landmark_head_fusable(m, self.loss_class, self.loss_reg, inputs):
             feats = m.forward_features(inputs)
             if ops.head_landmark_supported(feats, fc.in_channels, nh, fc.out_channels - nh, heatmaps, labels):
+                if self.class_loss == "CE":
+                    return ops.head_landmark(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, self.loss_class.weight,
+                                             self.loss_reg.channel_weights, self.loss_reg.kind, ignore_index=self.loss_class.ignore_index,
+                                             class_loss="CE")
                 return ops.head_landmark(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, self.loss_class.weight,
                                          self.loss_reg.channel_weights, self.loss_reg.kind, self.loss_class.epsilon,
                                          self.loss_class.sigmoid_normalization, self.loss_class.ignore_index)
@@ -546,3 +570,58 @@ class LandmarkStep(_GraphedStep):
             self.opt.step_scaled(self.scaler, inv_world=scale)
         self.repack.run()
         return out
+
+
+class LandmarkValidation:
+    """LandmarkNet.validation_step / validation_epoch_end (landmarks.py:136-174) on the MI355X path: forward kernels only, results
+    as device scalars (no host synchronisation per batch; the reference's sample plotting is not part of it).  With this package's
+    U-Net and a head the fused landmark kernel serves (16-bit storage, 32 features), the head, both loss terms and dice_metric
+    come from ONE pass over the features (ops.head_landmark_eval: no autograd node, no logit tensor); otherwise
+    `outputs = model(inputs)` and the two losses and dice_metric as fused passes over its channel slices."""
+
+    def __init__(self, model, class_weight, regression_weight, class_loss="DICE", regression="L2"):
+        self.model = model
+        dev = next(model.parameters()).device
+        self.class_loss = class_loss
+        self.loss_class, self.loss_reg = _landmark_losses(class_weight, regression_weight, class_loss, regression, dev)
+
+    def _forward(self, inputs, heatmaps, labels, nh):
+        m, fc = self.model, getattr(self.model, "final_conv", None)
+        lc = self.loss_class
+        # (the Dice forward's sums serve dice_metric only when they are its sums: softmax, no ignore mask)
+        metric_ok = self.class_loss == "CE" or (not lc.sigmoid_normalization and lc.ignore_index is None)
+        if metric_ok and _landmark_head_fusable(m, lc, self.loss_reg, inputs):
+            feats = m.forward_features(inputs)
+            if ops.head_landmark_supported(feats, fc.in_channels, nh, fc.out_channels - nh, heatmaps, labels):
+                return ops.head_landmark_eval(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, lc.weight,
+                                              self.loss_reg.channel_weights, self.loss_reg.kind, getattr(lc, "epsilon", 1e-5),
+                                              lc.ignore_index, self.class_loss)
+            outputs = fc(feats)
+        else:
+            outputs = m(inputs)
+        out_hm, out_cls = outputs[:, :nh], outputs[:, nh:]
+        return lc(out_cls, labels), self.loss_reg(out_hm, heatmaps), HL.dice_metric(out_cls, labels)
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_nb=0):
+        inputs = batch["data"].float()
+        heatmaps = batch["label"][:, :-1, ...]  # uint8, consumed where it lies
+        nh = heatmaps.shape[1]
+        labels = batch["label"][:, -1, ...]
+        if not labels.is_cuda:
+            labels = labels.long()
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            class_loss, regression_loss, per_channel_dice = self._forward(inputs, heatmaps, labels, nh)
+        finally:
+            self.model.train(was_training)
+        results = {"val_loss": regression_loss + class_loss, "val_class_loss": class_loss, "val_regression_loss": regression_loss}
+        for c in range(per_channel_dice.shape[0]):
+            results[f"val_dice{c}"] = per_channel_dice[c]
+        return results
+
+    @staticmethod
+    def validation_epoch_end(outputs):
+        logs = {k: torch.stack([o[k] for o in outputs]).mean() for k in outputs[0]}
+        return {"val_loss": logs["val_loss"], "log": logs, "progress_bar": logs}
