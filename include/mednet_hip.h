@@ -272,6 +272,32 @@ int mednet_gn_act_bwd_fused_res_pool(const void* dy_pool, const void* skip_grad,
                                      const float* gamma, const float* fused_partial, int rows, void* dx, void* dres, float* dgamma,
                                      float* dbeta, int n, int d, int h, int w, int c, int groups, int act, int pool_mode, int dtype,
                                      void* ws, size_t ws_bytes, mednet_stream stream);
+/* ---- nn.BatchNorm3d(C, eps, momentum) fused with the following activation and the residual add
+ *      components.py:58-63 (order char 'b').  Channels-last storage: the batch is one [N * S][C] array.  stats[n][c] =
+ *      {mean, rstd} and coef[n][c] = {gamma*rstd, beta - mean*gamma*rstd} are written REPLICATED per sample (all n rows equal), so
+ *      mednet_gn_act_fwd, mednet_gn_act_pool_fwd and the data-gradient forms that take a GroupNorm's coef (mednet_conv3d_dgrad_gn
+ *      and relatives) apply / consume them unchanged.  Workspace of every call: mednet_gn_ws_bytes(n, c, spatial). */
+/* Training mode: batch statistics over all N * S voxels (biased variance) and, when running_mean / running_var are given (both
+ * or neither, fp32 [c]), running = (1 - momentum) * running + momentum * {mean, unbiased variance}; num_batches_tracked (nullable,
+ * one int64) += 1.  Everything happens on the device in stream order (the call can be captured in a graph). */
+int mednet_bn_stats(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                    long long* num_batches_tracked, float momentum, float* stats, float* coef, int n, size_t spatial, int c,
+                    float eps, int dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+/* Evaluation mode: the same stats / coef rows from the running statistics; apply with mednet_gn_act_fwd. */
+int mednet_bn_eval_coef(const float* running_mean, const float* running_var, const float* gamma, const float* beta, float* stats,
+                        float* coef, int n, int c, float eps, mednet_stream stream);
+/* du = dz * act' (from z when given, else recomputed from x and coef);  dbeta = sum du, dgamma = sum du * xhat over all samples;
+ * dx = k1 * du + k2 * x + k3 (BatchNorm backward; frozen != 0: the statistics were constants -- evaluation mode --, dx = k1 * du);
+ * dres (nullable) := du.  in_act as for mednet_gn_act_bwd.  Sums in a fixed order: two runs give the same bits. */
+int mednet_bn_act_bwd(const void* dz, const void* x, const void* z, const float* coef, const float* stats, const float* gamma,
+                      void* dx, void* dres, float* dgamma, float* dbeta, int n, size_t spatial, int c, int act, int in_act,
+                      int frozen, int dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+/* ... without its first pass: `partial` [n][rows][c][2] = per-channel {sum du, sum du * x} from the kernel that produced dz
+ * (mednet_conv3d_dgrad_gn and relatives), summed here over rows AND samples. */
+int mednet_bn_act_bwd_fused(const void* dz, const void* x, const float* coef, const float* stats, const float* gamma,
+                            const float* partial, int rows, void* dx, float* dgamma, float* dbeta, int n, size_t spatial, int c,
+                            int act, int in_act, int frozen, int dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+
 /* stand-alone activation (orders such as 'cr', 'crg'); in-place allowed (x == z). */
 int mednet_act_fwd(const void* x, void* z, size_t count, int act, int dtype, mednet_stream stream);
 int mednet_act_bwd(const void* dz, const void* z, void* dx, size_t count, int act, int dtype,

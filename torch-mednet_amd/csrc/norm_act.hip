@@ -1538,6 +1538,253 @@ extern "C" int mednet_gn_act_bwd_fused_res_pool(const void* dy_pool, const void*
   return check_launch("gn_bwd_apply_pool");
 }
 
+// ---------------------------------------------------------------------------------------------- BatchNorm3d
+// nn.BatchNorm3d(C) (components.py:58-63).  In channels-last storage the batch is ONE [N * S][C] array, so the statistics are
+// per-channel sums over all samples: the first passes are GroupNorm's (gn_partial_kernel, gn_bwd_partial_kernel with
+// groups = C, or the rows a data-gradient epilogue wrote), the apply passes are GroupNorm's too (they read coef[n][c] /
+// bcoef[n][c], which the kernels below write REPLICATED per sample, as they do stats[n][c] = {mean, rstd}: every row equal).
+// New here: the reduction across samples, the running statistics, the evaluation coefficients.
+
+namespace mednet {
+// Workgroup-wide column sums of `rows` rows of partial[rows][c][2] (the rows of ALL samples: [n][rows_per_sample] is contiguous)
+// for the cw channels c0 .. c0 + cw - 1: thread t walks channel c0 + t % cw over rows t / cw, t / cw + 1024 / cw, ..., eight loads
+// in flight, fp64, then the 1024 / cw row classes in order => bitwise reproducible.  Result in (ra, rb) of threads t < cw; cw divides 1024.
+constexpr int BN_NT = 1024;
+__device__ __forceinline__ void bn_column_sums(const float* __restrict__ partial, int rows, int c, int c0, int cw, double* sha,
+                                               double* shb, double& ra, double& rb) {
+  const int t = threadIdx.x, i = t % cw, r0 = t / cw, rstep = BN_NT / cw;
+  const float* base = partial + (size_t)(c0 + i) * 2;
+  const size_t rs = (size_t)c * 2;
+  constexpr int U = 8;
+  double a[U], b[U];
+#pragma unroll
+  for (int k = 0; k < U; ++k) a[k] = b[k] = 0.0;
+  int r = r0;
+  for (; r + (U - 1) * rstep < rows; r += U * rstep) {
+    float2 p[U];
+#pragma unroll
+    for (int k = 0; k < U; ++k) p[k] = *reinterpret_cast<const float2*>(base + (size_t)(r + k * rstep) * rs);
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      a[k] += (double)p[k].x;
+      b[k] += (double)p[k].y;
+    }
+  }
+  for (; r < rows; r += rstep) {
+    const float2 p0 = *reinterpret_cast<const float2*>(base + (size_t)r * rs);
+    a[0] += (double)p0.x;
+    b[0] += (double)p0.y;
+  }
+#pragma unroll
+  for (int w = 1; w < U; w *= 2) {  // fixed pairwise order
+#pragma unroll
+    for (int k = 0; k < U; k += 2 * w) {
+      a[k] += a[k + w];
+      b[k] += b[k + w];
+    }
+  }
+  sha[t] = a[0];
+  shb[t] = b[0];
+  __syncthreads();
+  ra = rb = 0.0;
+  if (t < cw) {
+    for (int k = 0; k < rstep; ++k) {
+      ra += sha[k * cw + t];
+      rb += shb[k * cw + t];
+    }
+  }
+}
+// channels per workgroup of the two kernels below: 4 (32 contiguous bytes of a row per row class) when C allows
+static inline int bn_cw(int c) { return c % 4 == 0 ? 4 : 1; }
+
+// training statistics: partial rows {sum x, sum x^2} of all samples -> stats, coef (replicated per sample), running statistics
+// (momentum blend, unbiased variance) and the batch counter.  All on the device: nothing here is read by the host.
+__global__ __launch_bounds__(BN_NT) void bn_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float* __restrict__ running_mean,
+                                                            float* __restrict__ running_var, long long* __restrict__ num_batches,
+                                                            float* __restrict__ stats, float* __restrict__ coef, int n, int c,
+                                                            int cw, int rows, double count, float eps, float momentum) {
+  __shared__ double sha[BN_NT], shb[BN_NT];
+  const int c0 = blockIdx.x * cw, t = threadIdx.x;
+  double s, q;
+  bn_column_sums(partial, rows, c, c0, cw, sha, shb, s, q);
+  if (t < cw) {
+    const int cc = c0 + t;
+    const double mean = s / count;
+    double var = q / count - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    const float ga = gamma ? gamma[cc] : 1.f, be = beta ? beta[cc] : 0.f;
+    const float a = ga * rstd, b = be - (float)mean * a;
+    for (int i = 0; i < n; ++i) {
+      stats[((size_t)i * c + cc) * 2] = (float)mean;
+      stats[((size_t)i * c + cc) * 2 + 1] = rstd;
+      coef[((size_t)i * c + cc) * 2] = a;
+      coef[((size_t)i * c + cc) * 2 + 1] = b;
+    }
+    if (running_mean) {
+      const double m = (double)momentum;
+      const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
+      running_mean[cc] = (float)((1.0 - m) * (double)running_mean[cc] + m * mean);
+      running_var[cc] = (float)((1.0 - m) * (double)running_var[cc] + m * unbiased);
+    }
+  }
+  if (num_batches && blockIdx.x == 0 && t == 0) *num_batches += 1;
+}
+
+// evaluation: the same stats / coef rows from the running statistics
+__global__ __launch_bounds__(256) void bn_eval_coef_kernel(const float* __restrict__ running_mean, const float* __restrict__ running_var,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ stats, float* __restrict__ coef, int n, int c, float eps) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n * c) return;
+  const int cc = idx % c;
+  const float mean = running_mean[cc];
+  const float rstd = (float)(1.0 / sqrt((double)running_var[cc] + (double)eps));
+  const float a = (gamma ? gamma[cc] : 1.f) * rstd;
+  stats[(size_t)idx * 2] = mean;
+  stats[(size_t)idx * 2 + 1] = rstd;
+  coef[(size_t)idx * 2] = a;
+  coef[(size_t)idx * 2 + 1] = (beta ? beta[cc] : 0.f) - mean * a;
+}
+
+// backward coefficients: rows {sum du, sum du * xhat} (gn_bwd_partial_kernel) or, DUX, {sum du, sum du * x} (data-gradient
+// epilogues) of all samples -> dbeta, dgamma and bcoef[n][c] = {k1, k2, k3}, dx = k1 * du + k2 * x + k3 (gn_bwd_finalize_kernel's
+// formulas with one channel per group and count = N * S).  frozen: the statistics were constants (evaluation mode): k2 = k3 = 0.
+template <bool DUX>
+__global__ __launch_bounds__(BN_NT) void bn_bwd_coef_kernel(const float* __restrict__ partial, const float* __restrict__ stats,
+                                                            const float* __restrict__ gamma, float* __restrict__ bcoef,
+                                                            float* __restrict__ dgamma, float* __restrict__ dbeta, int n, int c,
+                                                            int cw, int rows, double count, int frozen) {
+  __shared__ double sha[BN_NT], shb[BN_NT];
+  const int c0 = blockIdx.x * cw, t = threadIdx.x;
+  double a, b;
+  bn_column_sums(partial, rows, c, c0, cw, sha, shb, a, b);
+  if (t >= cw) return;
+  const int cc = c0 + t;
+  const double mean = stats[(size_t)cc * 2], rstd = stats[(size_t)cc * 2 + 1];
+  if (DUX) b = rstd * (b - mean * a);
+  const float af = (float)a, bf = (float)b;
+  if (dbeta) dbeta[cc] = af;
+  if (dgamma) dgamma[cc] = bf;
+  const double ga = gamma ? (double)gamma[cc] : 1.0;
+  const double s1 = ga * (double)af, s2 = ga * (double)bf;
+  const float k1 = (float)rstd * (gamma ? gamma[cc] : 1.f);
+  const float k2 = frozen ? 0.f : (float)(-rstd * rstd * s2 / count);
+  const float k3 = frozen ? 0.f : (float)((rstd * rstd * s2 * mean - rstd * s1) / count);
+  for (int i = 0; i < n; ++i) {
+    float* o = bcoef + ((size_t)i * c + cc) * 3;
+    o[0] = k1;
+    o[1] = k2;
+    o[2] = k3;
+  }
+}
+
+}  // namespace mednet
+
+extern "C" int mednet_bn_stats(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                               long long* num_batches_tracked, float momentum, float* stats, float* coef, int n, size_t spatial,
+                               int c, float eps, int dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "bn_stats: bad dtype %d", dtype);
+  MEDNET_REQUIRE(n > 0 && c > 0 && spatial > 0 && x && stats && coef, MEDNET_E_SHAPE, "bn_stats: bad shape n=%d c=%d", n, c);
+  MEDNET_REQUIRE((running_mean == nullptr) == (running_var == nullptr), MEDNET_E_SHAPE,
+                 "bn_stats: running_mean and running_var come together");
+  const int vec = pick_vec(c, dtype);
+  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "bn_stats: C=%d unsupported (need C%%8==0 or C<=256)", c);
+  MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "bn_stats: workspace too small");
+  size_t cv;
+  unsigned chunks;
+  chunk_plan(spatial, c, vec, cv, chunks);
+  float* partial = (float*)ws;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(chunks, n);
+#define GO(T, V) hipLaunchKernelGGL((gn_partial_kernel<T, V>), grid, dim3(256), 0, s, (const T*)x, partial, spatial, c, cv)
+  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
+  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
+  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
+#undef GO
+  int rc = check_launch("gn_partial");
+  if (rc) return rc;
+  const int cw = bn_cw(c);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(c / cw), dim3(BN_NT), 0, s, partial, gamma, beta, running_mean, running_var,
+                     num_batches_tracked, stats, coef, n, c, cw, (int)chunks * n, (double)spatial * n, eps, momentum);
+  return check_launch("bn_finalize");
+}
+
+extern "C" int mednet_bn_eval_coef(const float* running_mean, const float* running_var, const float* gamma, const float* beta,
+                                   float* stats, float* coef, int n, int c, float eps, mednet_stream stream) {
+  MEDNET_REQUIRE(n > 0 && c > 0 && running_mean && running_var && stats && coef, MEDNET_E_SHAPE, "bn_eval_coef: bad arguments");
+  hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((n * c + 255) / 256), dim3(256), 0, (hipStream_t)stream, running_mean, running_var,
+                     gamma, beta, stats, coef, n, c, eps);
+  return check_launch("bn_eval_coef");
+}
+
+static int bn_bwd_apply(const void* dz, const void* x, const void* z, const float* coef, const float* bcoef, void* dx, void* dres,
+                        int n, size_t spatial, int c, int act, int in_act, int dtype, int vec, hipStream_t s) {
+  size_t cv;
+  unsigned chunks;
+  chunk_plan(spatial, c, vec, cv, chunks);
+  const dim3 grid(chunks, n);
+  const GnParamGrad pg;  // (dgamma / dbeta were written by bn_bwd_coef_kernel)
+#define GO(T, V) hipLaunchKernelGGL((gn_bwd_apply_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dz, (const T*)nullptr, (const T*)x, (const T*)z, coef, bcoef, (T*)dx, (T*)dres, spatial, c, act, cv, in_act, pg)
+  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
+  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
+  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
+#undef GO
+  return check_launch("gn_bwd_apply");
+}
+
+extern "C" int mednet_bn_act_bwd(const void* dz, const void* x, const void* z, const float* coef, const float* stats,
+                                 const float* gamma, void* dx, void* dres, float* dgamma, float* dbeta, int n, size_t spatial, int c,
+                                 int act, int in_act, int frozen, int dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "bn_act_bwd: bad dtype");
+  MEDNET_REQUIRE(n > 0 && c > 0 && spatial > 0 && dz && x && coef && stats && dx, MEDNET_E_SHAPE, "bn_act_bwd: bad arguments");
+  const int vec = pick_vec(c, dtype);
+  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "bn_act_bwd: C=%d unsupported", c);
+  MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "bn_act_bwd: workspace too small");
+  size_t cv;
+  unsigned chunks;
+  chunk_plan(spatial, c, vec, cv, chunks);
+  float* partial = (float*)ws;
+  float* bcoef = partial + (size_t)n * gn_partial_rows_max(c) * c * 2;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(chunks, n);
+  const int rpw = tuning_option("gn_lds_free", 1) ? lds_free_rows_per_wg(c / vec) : 0;
+#define GO(T, V) hipLaunchKernelGGL((gn_bwd_partial_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dz, (const T*)nullptr, (const T*)x, (const T*)z, coef, stats, partial, spatial, c, c, act, cv, rpw)
+  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
+  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
+  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
+#undef GO
+  int rc = check_launch("gn_bwd_partial");
+  if (rc) return rc;
+  const int cw = bn_cw(c);
+  hipLaunchKernelGGL(bn_bwd_coef_kernel<false>, dim3(c / cw), dim3(BN_NT), 0, s, partial, stats, gamma, bcoef, dgamma, dbeta, n, c, cw,
+                     (int)chunks * (rpw > 0 ? rpw : 1) * n, (double)spatial * n, frozen);
+  rc = check_launch("bn_bwd_coef");
+  if (rc) return rc;
+  return bn_bwd_apply(dz, x, z, coef, bcoef, dx, dres, n, spatial, c, act, in_act, dtype, vec, s);
+}
+
+extern "C" int mednet_bn_act_bwd_fused(const void* dz, const void* x, const float* coef, const float* stats, const float* gamma,
+                                       const float* fused_partial, int rows, void* dx, float* dgamma, float* dbeta, int n,
+                                       size_t spatial, int c, int act, int in_act, int frozen, int dtype, void* ws, size_t ws_bytes,
+                                       mednet_stream stream) {
+  MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "bn_act_bwd_fused: bad dtype");
+  MEDNET_REQUIRE(n > 0 && c > 0 && spatial > 0 && rows > 0 && fused_partial && dz && x && coef && stats && dx, MEDNET_E_SHAPE,
+                 "bn_act_bwd_fused: bad arguments");
+  const int vec = pick_vec(c, dtype);
+  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "bn_act_bwd_fused: C=%d unsupported", c);
+  MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "bn_act_bwd_fused: workspace too small");
+  float* bcoef = (float*)ws + (size_t)n * gn_partial_rows_max(c) * c * 2;
+  hipStream_t s = (hipStream_t)stream;
+  const int cw = bn_cw(c);
+  hipLaunchKernelGGL(bn_bwd_coef_kernel<true>, dim3(c / cw), dim3(BN_NT), 0, s, fused_partial, stats, gamma, bcoef, dgamma, dbeta, n, c,
+                     cw, rows * n, (double)spatial * n, frozen);
+  int rc = check_launch("bn_bwd_coef");
+  if (rc) return rc;
+  return bn_bwd_apply(dz, x, nullptr, coef, bcoef, dx, nullptr, n, spatial, c, act, in_act, dtype, vec, s);
+}
+
 extern "C" int mednet_act_fwd(const void* x, void* z, size_t count, int act, int dtype, mednet_stream stream) {
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "act_fwd: bad dtype");
   hipStream_t s = (hipStream_t)stream;

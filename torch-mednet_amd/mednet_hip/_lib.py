@@ -83,6 +83,10 @@ SIGNATURES = {
     "mednet_act_bwd": (_i, [_vp, _vp, _vp, _sz, _i, _i, _vp]),
     "mednet_add": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
     "mednet_pool2_fwd": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
+    "mednet_bn_stats": (_i, [_vp] * 6 + [_f, _vp, _vp, _i, _sz, _i, _f, _i, _vp, _sz, _vp]),
+    "mednet_bn_eval_coef": (_i, [_vp] * 6 + [_i, _i, _f, _vp]),
+    "mednet_bn_act_bwd": (_i, [_vp] * 10 + [_i, _sz, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_bn_act_bwd_fused": (_i, [_vp] * 6 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mednet_gn_act_pool_supported": (_i, [_i] * 5),
     "mednet_gn_act_pool_fwd": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
     "mednet_pool2_bwd": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp]),

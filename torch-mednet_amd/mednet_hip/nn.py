@@ -147,6 +147,52 @@ class GroupNorm(nn.Module):
         return f"{self.num_groups}, {self.num_channels}, eps={self.eps}"
 
 
+class BatchNorm3d(nn.Module):
+    """nn.BatchNorm3d(num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True) with its parameter and
+    buffer names, shapes and dtypes (state dicts interchange); `forward(x, act=..., residual=...)` fuses the following
+    activation and residual add.  train(): batch statistics, running statistics updated on the device; eval(): the running
+    statistics (batch statistics when they are not tracked)."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True):
+        super().__init__()
+        if momentum is None:
+            raise NotImplementedError("mednet_hip.BatchNorm3d: momentum=None (cumulative moving average) is not implemented")
+        self.num_features, self.eps, self.momentum = num_features, eps, momentum
+        self.affine, self.track_running_stats = affine, track_running_stats
+        if affine:
+            self.weight = nn.Parameter(torch.ones(num_features))
+            self.bias = nn.Parameter(torch.zeros(num_features))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+        if track_running_stats:
+            self.register_buffer("running_mean", torch.zeros(num_features))
+            self.register_buffer("running_var", torch.ones(num_features))
+            self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+        else:
+            self.register_buffer("running_mean", None)
+            self.register_buffer("running_var", None)
+            self.register_buffer("num_batches_tracked", None)
+
+    def reset_running_stats(self):
+        if self.track_running_stats:
+            self.running_mean.zero_()
+            self.running_var.fill_(1)
+            self.num_batches_tracked.zero_()
+
+    def forward(self, x, act=L.ACT_NONE, residual=None):
+        if x.dim() != 5:
+            raise ValueError(f"expected 5D input (got {x.dim()}D input)")
+        if x.shape[1] != self.num_features:
+            raise RuntimeError(f"batch_norm: input has {x.shape[1]} channels, the module {self.num_features}")
+        return ops.batch_norm_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.num_batches_tracked,
+                                  self.training, self.momentum, self.eps, act, residual)
+
+    def extra_repr(self):
+        return (f"{self.num_features}, eps={self.eps}, momentum={self.momentum}, affine={self.affine}, "
+                f"track_running_stats={self.track_running_stats}")
+
+
 class _Act(nn.Module):
     code = L.ACT_NONE
 

@@ -291,6 +291,13 @@ class GNBHook(GN3Hook):
         self.coef = None
 
 
+class BNBHook(GNBHook):
+    """GNBHook of a BatchNorm (ops.batch_norm_act): `coef` rows are equal for all samples, and the consumer's per-sample rows are
+    summed over samples as well (mednet_bn_act_bwd_fused).  A type of its own because the plain convolution (Conv3dFn) takes the
+    first backward pass for these only -- the 'c b .' orders; a GroupNorm's hook is honoured where it always was."""
+    __slots__ = ()
+
+
 class ActMaskHook:
     """Carried by the output z of a fused conv -> activation layer: if z goes straight into a GroupNorm, that GroupNorm's
     backward multiplies the gradient it produces by act'(z) (z is its own input, in registers anyway) and says so here; the
@@ -358,6 +365,12 @@ class Conv3dFn(Function):
         ctx.meta = (ksize, out_planar, cin, cout, bias is not None, x.dtype)
         ctx.params = (weight, bias)
         ctx.gn3 = _gn3_hook_of(x, xin.dtype) if (ksize == 1 and out_planar and xin is x) else None
+        # 'c b .' orders: x is act(BatchNorm(y_prev)) of the layer before, this conv is followed by its own BatchNorm (no fused
+        # activation, so it runs here and not in ConvActFn): its data gradient takes that BatchNorm's first backward pass
+        ctx.gnb = None
+        if ksize == 3 and not out_planar and xin is x:
+            hook = _gnb_hook_of(x, xin.dtype)
+            ctx.gnb = hook if isinstance(hook, BNBHook) else None
         if debug.TRACE is not None:
             debug.trace(f"conv3d.fwd k{ksize} {cin}->{cout}", y, partial)
         if not want_stats:
@@ -382,12 +395,22 @@ class Conv3dFn(Function):
             rows = 0
             if hook is not None and dy.dtype == torch.float32 and dx.dtype == xin.dtype and config.conv_algo() != L.ALGO_DIRECT:
                 rows = lib.mednet_head_dgrad_gn_rows(n, d, h, w, cin, L.dt(dx))
+            bnb = ctx.gnb
+            bn_rows = 0
+            if bnb is not None and dx.dtype == dy.dtype:
+                bn_rows = lib.mednet_conv3d_dgrad_gn_rows_dt(n, d, h, w, cin, cout, config.conv_algo(), L.dt(dy))
             if rows > 0:  # + the first pass of the producing block's GroupNorm-3 backward (xin IS that block's output)
                 partial = torch.empty((n, rows, cin, 2), dtype=torch.float32, device=dy.device)
                 L.check(lib.mednet_head_dgrad_gn(dy.data_ptr(), packed.data_ptr(), dx.data_ptr(), hook.gn_in.data_ptr(),
                                                  xin.data_ptr(), hook.act, partial.data_ptr(), n, d, h, w, cin, cout, L.dt(dx),
                                                  L.stream()), "head_dgrad_gn")
                 hook.offer(dx, partial)
+            elif bn_rows > 0:  # + the first pass of the backward of the BatchNorm (+ activation) that produced xin
+                partial = torch.empty((n, bn_rows, cin, 2), dtype=torch.float32, device=dy.device)
+                L.check(lib.mednet_conv3d_dgrad_gn(dy.data_ptr(), packed.data_ptr(), None, dx.data_ptr(), bnb.gn_in.data_ptr(),
+                                                   bnb.coef.data_ptr(), bnb.act, partial.data_ptr(), n, d, h, w, cin, cout,
+                                                   config.conv_algo(), L.dt(dy), L.stream()), "conv3d_dgrad_gn")
+                bnb.offer(dx, partial)
             else:
                 L.check(lib.mednet_conv3d_fwd(dy.data_ptr(), packed.data_ptr(), None, dx.data_ptr(), n, d, h, w, cout, cin,
                                               ksize, L.dt(dy), L.NCDHW if out_planar else L.NDHWC, L.dt(dx), L.NDHWC, 1,
@@ -651,6 +674,110 @@ def group_norm_act(x, gamma, beta, groups, eps=1e-5, act=L.ACT_NONE, residual=No
     if FUSE_GN3 and residual is None and config.is_half_mode() and torch.is_grad_enabled() and gamma is not None:
         hook = GNBHook()  # the conv that consumes z may take this GroupNorm's first backward pass (see GNBHook)
     z = GroupNormActFn.apply(x, gamma, beta, residual, groups, eps, act, partial, hook)
+    if hook is not None:
+        z._mednet_gnb = hook
+    return z
+
+
+# ------------------------------------------------------------------------------------------------- BatchNorm3d (+act, +residual)
+class BatchNormActFn(Function):
+    """z = act(BatchNorm3d(x) [+ residual])  -- components.py:58-63, :36-40, :177-178.  The statistics pass and both backward
+    first passes are GroupNorm's kernels over the channels-last batch; the reduction across samples, the running statistics and
+    the evaluation coefficients are mednet_bn_* (csrc/norm_act.hip).  `running` = (running_mean, running_var,
+    num_batches_tracked) or None: updated on the device when `training`, read when not."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, running, training, momentum, eps, act, hook=None):
+        L.require_gpu(x, "batch_norm_act")
+        x0 = x
+        x = to_cl(_as_act(x))
+        ctx.inmask = getattr(x0, "_mednet_actmask", None) if (x is x0 and FUSE_GN3) else None
+        if ctx.inmask is not None and ctx.inmask.act != L.ACT_RELU:  # (only ReLU layers are folded: GroupNormActFn.forward says why)
+            ctx.inmask = None
+        n, c, d, h, w = x.shape
+        spatial = d * h * w
+        lib = L.lib()
+        batch_stats = training or running is None
+        stats = torch.empty((n, c, 2), dtype=torch.float32, device=x.device)
+        coef = torch.empty((n, c, 2), dtype=torch.float32, device=x.device)
+        if batch_stats:
+            if n * spatial <= 1:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+            rm, rv, nbt = running if (training and running is not None) else (None, None, None)
+            ws = L.workspace(lib.mednet_gn_ws_bytes(n, c, spatial), x.device)
+            L.check(lib.mednet_bn_stats(x.data_ptr(), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), momentum,
+                                        stats.data_ptr(), coef.data_ptr(), n, spatial, c, eps, L.dt(x), ws.data_ptr(), ws.numel(),
+                                        L.stream()), "bn_stats")
+        else:
+            rm, rv, _ = running
+            L.check(lib.mednet_bn_eval_coef(rm.data_ptr(), rv.data_ptr(), L.ptr(gamma), L.ptr(beta), stats.data_ptr(),
+                                            coef.data_ptr(), n, c, eps, L.stream()), "bn_eval_coef")
+        res = None
+        if residual is not None:
+            res = to_cl(residual.to(x.dtype))
+        z = torch.empty_like(x, memory_format=CL)
+        L.check(lib.mednet_gn_act_fwd(x.data_ptr(), coef.data_ptr(), L.ptr(res), z.data_ptr(), n, spatial, c, act,
+                                      L.dt(x), L.dt(z), L.stream()), "gn_act_fwd")
+        keep_z = act != L.ACT_NONE and residual is not None  # (as GroupNormActFn: else act' is recomputed from x and coef)
+        ctx.save_for_backward(x, z if keep_z else None, stats, gamma, coef)
+        ctx.meta = (act, residual is not None, gamma is not None, beta is not None, not batch_stats)
+        ctx.params = (gamma, beta)
+        ctx.gnb = hook
+        if hook is not None:
+            hook.gn_in, hook.coef, hook.act = x, coef, act
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, z, stats, gamma, coef = ctx.saved_tensors
+        act, has_res, has_gamma, has_beta, frozen = ctx.meta
+        n, c, d, h, w = x.shape
+        spatial = d * h * w
+        fused = ctx.gnb.take(dz) if ctx.gnb is not None else None  # (before any conversion: identity matters)
+        dz = to_cl(dz.to(x.dtype))
+        lib = L.lib()
+        dx = torch.empty_like(x, memory_format=CL)
+        dres = torch.empty_like(x, memory_format=CL) if has_res else None
+        pg, pb = ctx.params
+        dgamma, direct_g = _grad_target(pg, (c,)) if has_gamma else (None, False)
+        dbeta, direct_b = _grad_target(pb, (c,)) if has_beta else (None, False)
+        ws = L.workspace(lib.mednet_gn_ws_bytes(n, c, spatial), x.device)
+        inmask = ctx.inmask  # x is the output of a fused conv -> activation layer: fold act'(x) into dx (ActMaskHook)
+        in_act = inmask.act if inmask is not None else L.ACT_NONE
+        if inmask is not None:
+            inmask.offer(dx)
+        if fused is not None and not has_res:  # first pass taken by the conv data gradient that produced dz
+            L.check(lib.mednet_bn_act_bwd_fused(dz.data_ptr(), x.data_ptr(), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
+                                                fused.data_ptr(), fused.shape[1], dx.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), n,
+                                                spatial, c, act, in_act, int(frozen), L.dt(x), ws.data_ptr(), ws.numel(),
+                                                L.stream()), "bn_act_bwd_fused")
+        else:
+            L.check(lib.mednet_bn_act_bwd(dz.data_ptr(), x.data_ptr(), L.ptr(z), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
+                                          dx.data_ptr(), L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta), n, spatial, c, act, in_act,
+                                          int(frozen), L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "bn_act_bwd")
+        return dx, (None if direct_g else dgamma), (None if direct_b else dbeta), dres, None, None, None, None, None, None
+
+
+def batch_norm_act(x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, training=True, momentum=0.1,
+                   eps=1e-5, act=L.ACT_NONE, residual=None):
+    """act(F.batch_norm(x, running_mean, running_var, gamma, beta, training, momentum, eps) [+ residual]) on a 5-D tensor.  The
+    running buffers (fp32 [C] on x's device; num_batches_tracked one int64, optional) are updated in place by the statistics
+    kernel when `training`; without them batch statistics are used in both modes."""
+    if momentum is None:
+        raise NotImplementedError("mednet_hip batch_norm: momentum=None (cumulative moving average) is not implemented; pass a float")
+    running = None
+    if running_mean is not None:
+        for name, t, dt in (("running_mean", running_mean, torch.float32), ("running_var", running_var, torch.float32),
+                            ("num_batches_tracked", num_batches_tracked, torch.int64)):
+            if t is None and name == "num_batches_tracked":
+                continue
+            if t is None or t.dtype != dt or t.device != x.device or not t.is_contiguous():
+                raise RuntimeError(f"batch_norm: {name} must be a contiguous {dt} tensor on {x.device}")
+        running = (running_mean, running_var, num_batches_tracked)
+    hook = None
+    if FUSE_GN3 and residual is None and config.is_half_mode() and torch.is_grad_enabled() and gamma is not None:
+        hook = BNBHook()  # the conv that consumes z may take this BatchNorm's first backward pass (see GNBHook)
+    z = BatchNormActFn.apply(x, gamma, beta, residual, running, bool(training), float(momentum), float(eps), act, hook)
     if hook is not None:
         z._mednet_gnb = hook
     return z

@@ -3,6 +3,7 @@
 
 Fusions applied inside SingleConv / ExtResNetBlock / Decoder (the reference runs each as a separate ATen op):
   conv -> [GroupNorm -> activation]           one GN-stats + one apply pass      (components.py:44,57,36-40)
+  conv -> [BatchNorm3d -> activation]         one statistics + one apply pass    (components.py:44,58-63,36-40)
   GroupNorm(conv3) + residual -> activation   folded into that same apply pass   (components.py:175-178)
   ConvTranspose3d + `x += encoder_features`   skip added in the conv epilogue    (components.py:283-284)
 """
@@ -47,9 +48,8 @@ def create_conv(in_channels, out_channels, kernel_size, order, num_groups, paddi
                                        f"num_channels={nch}, num_groups={groups}")
             modules.append(("groupnorm", hnn.GroupNorm(num_groups=groups, num_channels=nch)))
         elif ch == "b":
-            # BatchNorm is reachable through the grammar but used by no caller of the reference; it stays a stock
-            # torch module (off the hot path, components.py:58-63).
-            modules.append(("batchnorm", nn.BatchNorm3d(in_channels if i < conv_pos else out_channels)))
+            # (components.py:58-63; used by no caller of the reference, reachable through the grammar: 'cbr', 'cbe', 'bcr')
+            modules.append(("batchnorm", hnn.BatchNorm3d(in_channels if i < conv_pos else out_channels)))
         else:
             raise ValueError(f"Unsupported layer type '{ch}'. MUST be one of ['b', 'g', 'r', 'l', 'e', 'c']")
     return modules
@@ -57,8 +57,11 @@ def create_conv(in_channels, out_channels, kernel_size, order, num_groups, paddi
 
 def _kinked(order: str) -> bool:
     """ReLU / LeakyReLU in the layer: the network is piecewise linear and asks for exact fp32 products in the fp32 storage
-    mode (config.exact_products says why)."""
-    return "r" in order or "l" in order
+    mode (config.exact_products says why).  BatchNorm asks for them too: its backward subtracts from the gradient its mean and
+    its projection on the normalised input over the WHOLE batch, and what reaches the first level is the small remainder -- the
+    2^-16 error of the split products came out as 3.6e-3 on the gradients of the first block of ResidualUNet3D 'cbe' at 32^3
+    (GroupNorm 'cge', same input: 1e-4), against 4e-6 with exact products."""
+    return "r" in order or "l" in order or "b" in order
 
 
 class SingleConv(nn.Sequential):
@@ -84,6 +87,20 @@ class SingleConv(nn.Sequential):
         out_partial = None
         while i < len(mods):
             m = mods[i]
+            if isinstance(m, hnn.BatchNorm3d):  # the same fusions, batch statistics (no partial sums from a conv epilogue)
+                nxt = mods[i + 1] if i + 1 < len(mods) else None
+                if isinstance(nxt, hnn._Act):
+                    x = m(x, act=nxt.code)
+                    i += 2
+                elif nxt is None and residual is not None:
+                    x = m(x, act=final_act, residual=residual)
+                    fused_res = True
+                    i += 1
+                else:
+                    x = m(x)
+                    i += 1
+                partial = None
+                continue
             if isinstance(m, hnn.GroupNorm):
                 nxt = mods[i + 1] if i + 1 < len(mods) else None
                 if isinstance(nxt, hnn._Act):
@@ -114,8 +131,6 @@ class SingleConv(nn.Sequential):
                     out_partial = p
                 i += 2
                 continue
-            elif isinstance(m, nn.BatchNorm3d):
-                x = m(x.float().contiguous()).to(memory_format=ops.CL)
             else:
                 x = m(x)
             i += 1
@@ -160,7 +175,7 @@ class ExtResNetBlock(nn.Module):
                                 num_groups=num_groups)
         key = "l" if "l" in order else ("e" if "e" in order else "r")
         self.non_linearity = _ACT_MODULES[key][1](inplace=True)
-        self._kinked = key != "e"
+        self._kinked = key != "e" or "b" in order
 
     def _plain(self):
         """(convs, norms) when the block is 3 x [3^3 conv without bias -> GroupNorm (-> activation)] with one group count:
