@@ -518,6 +518,31 @@ size_t mednet_augment_ws_bytes(int batch, int channels, size_t spatial);
 int mednet_augment_patches(float* data, const float* params, int batch, int channels, size_t spatial, void* ws,
                            size_t ws_bytes, mednet_stream stream);
 
+/* ---- validation sample logging: the arrays `log_samples` (segmentation.py:67-92, landmarks.py:85-123) hands
+ * to imshow through vis_loglabels / vis_logheatmaps (utils/plots.py:45-127), from ONE sample where its tensors lie.  Additive to
+ * ABI 3.  All pointers address that sample: logits = channel 0 of its network output (planar fp32, plane k at + k * stride_c
+ * elements: the num_heatmaps raw heat-map outputs, then num_classes class planes), labels = its class map (MEDNET_U8 or
+ * MEDNET_I64, d*h*w dense -- the last channel of a label volume is read in place), heatmaps = its num_heatmaps target planes
+ * (MEDNET_U8 or MEDNET_F32, dense), input = its first input channel.  `axis` (0, 1, 2) counts within d x h x w and is reduced
+ * away; a panel is the remaining two extents, row-major:
+ *   pred_mip            uint8          max over the axis of the arg-max over the class planes (first maximum on ties, like
+ *                                      torch.argmax; the reference's soft-max does not change it), 1 <= num_classes <= 256
+ *   label_mip           uint8          max over the axis of the class map (values above 255 are a caller error: they wrap)
+ *   input_mip           fp32           MEDNET_MIP_MEAN: mean, MEDNET_MIP_MAX: max over the axis of the input
+ *   heatmap_mip         fp32 [nh][..]  max over the axis of the target heat maps
+ *   output_heatmap_mip  fp32 [nh][..]  max over the axis of the raw heat-map outputs (landmarks.py:94 does not clip them)
+ * A NULL output pointer switches its panel off (its source is then not read and may be NULL); num_heatmaps == 0 switches both
+ * heat-map panels off.  Each source is read once -- the class planes once for arg-max and projection together -- and nothing
+ * intermediate is stored.  Axes 0 and 1 cut the reduced extent into segments (partials in `ws`, combined in index order by a
+ * second launch); axis 2 reduces inside a wave and needs no workspace (_ws_bytes returns 0).  No atomics: the same inputs give the
+ * same bits.  max ignores NaN (fmaxf). */
+enum { MEDNET_MIP_MEAN = 0, MEDNET_MIP_MAX = 1 };
+size_t mednet_sample_panels_ws_bytes(int d, int h, int w, int num_heatmaps, int axis);
+int mednet_sample_panels(const float* logits, int64_t stride_c, int num_heatmaps, int num_classes, const void* labels,
+                         int label_dtype, const void* heatmaps, int heatmap_dtype, const float* input, uint8_t* pred_mip,
+                         uint8_t* label_mip, float* input_mip, float* heatmap_mip, float* output_heatmap_mip, int d, int h, int w,
+                         int axis, int image_mode, void* ws, size_t ws_bytes, mednet_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ PACK_HIGH_ONLY = 0x200  # mednet_conv3d_pack_many: only the images the 16-bit ma
 REG_L2, REG_L1 = 0, 1
 CLASS_DICE, CLASS_CE = 0, 1
 PAD_CONSTANT, PAD_SYMMETRIC = 0, 1
+MIP_MEAN, MIP_MAX = 0, 1
 F16, U8, I64 = 2, 3, 4  # F16: fp16 storage / resident volumes; U8, I64: label types
 NO_IGNORE = -(2 ** 31)
 
@@ -134,6 +135,8 @@ SIGNATURES = {
     "mednet_crop_patches": (_i, [_vp, _i, _vp, _vp, _i, _vp] + [_i] * 10 + [_vp]),
     "mednet_augment_ws_bytes": (_sz, [_i, _i, _sz]),
     "mednet_augment_patches": (_i, [_vp, _vp, _i, _i, _sz, _vp, _sz, _vp]),
+    "mednet_sample_panels_ws_bytes": (_sz, [_i] * 5),
+    "mednet_sample_panels": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _i, _vp] + [_vp] * 5 + [_i] * 5 + [_vp, _sz, _vp]),
 }
 
 _lib = None

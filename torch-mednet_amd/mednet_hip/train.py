@@ -14,7 +14,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import ops, vis
 from .unet import loss as HL
 
 
@@ -458,13 +458,18 @@ class SegmentationStep(_GraphedStep):
 class SegmentationValidation:
     """SegmentationNet.validation_step / validation_epoch_end (segmentation.py:94-118) on the MI355X
     path: forward kernels only, the configured loss and `dice_metric` each as ONE fused pass over the logits, results as
-    device scalars (no host synchronisation per batch; the reference's sample plotting is not part of it)."""
+    device scalars (no host synchronisation per batch).  Sample logging (`log_samples`, segmentation.py:67-92,100-101): with
+    log_interval set, every batch with batch_nb % log_interval == 0 hands on_samples(panels, batch_nb) the vis.SamplePanels of
+    sample 0 -- what the reference draws, computed on the device from `outputs` and the batch where they lie, still without a
+    synchronisation; drawing and the one host copy (panels.to_host()) are the callback's.  log_vis_mip: the hparams' "mean" | "max".
+    log_interval=None (the default) logs nothing; the results are the same either way."""
 
-    def __init__(self, model, loss_weight=None, loss="DICE"):
+    def __init__(self, model, loss_weight=None, loss="DICE", log_interval=None, log_vis_mip="mean", on_samples=None):
         self.model = model
         dev = next(model.parameters()).device
         w = None if loss_weight is None else torch.tensor(loss_weight, dtype=torch.float32, device=dev)
         self.loss = (HL.DiceLoss(weight=w) if loss == "DICE" else HL.CrossEntropyLoss(weight=w)).to(dev)
+        self.log_interval, self.log_vis_mip, self.on_samples = log_interval, log_vis_mip, on_samples
 
     @torch.no_grad()
     def validation_step(self, batch, batch_nb=0):
@@ -476,6 +481,9 @@ class SegmentationValidation:
             outputs = self.model(inputs)
         finally:
             self.model.train(was_training)
+        if _logs_samples(self, batch_nb):
+            self.on_samples(vis.sample_panels(outputs, _class_map(batch["label"], labels), inputs, 0,
+                                              projection_type=self.log_vis_mip), batch_nb)
         results = {"val_loss": self.loss(outputs, labels)}
         per_channel_dice = HL.dice_metric(outputs, labels)
         for c in range(outputs.shape[1]):
@@ -486,6 +494,17 @@ class SegmentationValidation:
     def validation_epoch_end(outputs):
         logs = {k: torch.stack([o[k] for o in outputs]).mean() for k in outputs[0]}
         return {"val_loss": logs["val_loss"], "log": logs, "progress_bar": logs}
+
+
+def _logs_samples(validation, batch_nb) -> bool:
+    """`if batch_nb % self.log_interval == 0` of the reference's validation_step, off without an interval or a callback."""
+    return bool(validation.log_interval) and validation.on_samples is not None and batch_nb % validation.log_interval == 0
+
+
+def _class_map(label, labels_long):
+    """The class map for the sample panels: the last channel of the batch's label volume where it lies when the kernel reads its
+    type (uint8 / int64), else the int64 copy the loss takes anyway."""
+    return label[:, -1, ...] if label.dtype in (torch.uint8, torch.int64) else labels_long
 
 
 def _landmark_losses(class_weight, regression_weight, class_loss, regression, dev):
@@ -574,18 +593,34 @@ class LandmarkStep(_GraphedStep):
 
 class LandmarkValidation:
     """LandmarkNet.validation_step / validation_epoch_end (landmarks.py:136-174) on the MI355X path: forward kernels only, results
-    as device scalars (no host synchronisation per batch; the reference's sample plotting is not part of it).  With this package's
+    as device scalars (no host synchronisation per batch).  With this package's
     U-Net and a head the fused landmark kernel serves (16-bit storage, 32 features), the head, both loss terms and dice_metric
     come from ONE pass over the features (ops.head_landmark_eval: no autograd node, no logit tensor); otherwise
-    `outputs = model(inputs)` and the two losses and dice_metric as fused passes over its channel slices."""
+    `outputs = model(inputs)` and the two losses and dice_metric as fused passes over its channel slices.
+    Sample logging (`log_samples`, landmarks.py:85-123,148-149): log_interval, log_vis_mip and on_samples as for
+    SegmentationValidation; the panels include the heat-map projections.  Where the step forms `outputs` the panels come from that
+    tensor; on the fused path, which has no logit tensor, from final_conv(feats[0:1]) -- the head on the one sample that is drawn
+    -- while the metric path stays as it is."""
 
-    def __init__(self, model, class_weight, regression_weight, class_loss="DICE", regression="L2"):
+    def __init__(self, model, class_weight, regression_weight, class_loss="DICE", regression="L2", log_interval=None,
+                 log_vis_mip="mean", on_samples=None):
         self.model = model
         dev = next(model.parameters()).device
         self.class_loss = class_loss
         self.loss_class, self.loss_reg = _landmark_losses(class_weight, regression_weight, class_loss, regression, dev)
+        self.log_interval, self.log_vis_mip, self.on_samples = log_interval, log_vis_mip, on_samples
 
-    def _forward(self, inputs, heatmaps, labels, nh):
+    def _log_samples(self, outputs, batch, inputs, nh, batch_nb, first=slice(None)):
+        """`outputs`: the logits of the whole batch, or (first = slice(0, 1)) of its first sample alone."""
+        label = batch["label"]
+        if label.dtype != torch.uint8:  # (heat maps and class map of another type: the float / int64 forms the reference takes)
+            panels = vis.sample_panels(outputs, label[first, -1].long(), inputs[first], nh, projection_type=self.log_vis_mip,
+                                       heatmaps=label[first, :-1].float())
+        else:
+            panels = vis.sample_panels(outputs, label[first], inputs[first], nh, projection_type=self.log_vis_mip)
+        self.on_samples(panels, batch_nb)
+
+    def _forward(self, inputs, heatmaps, labels, nh, batch=None, batch_nb=None):
         m, fc = self.model, getattr(self.model, "final_conv", None)
         lc = self.loss_class
         # (the Dice forward's sums serve dice_metric only when they are its sums: softmax, no ignore mask)
@@ -593,12 +628,16 @@ class LandmarkValidation:
         if metric_ok and _landmark_head_fusable(m, lc, self.loss_reg, inputs):
             feats = m.forward_features(inputs)
             if ops.head_landmark_supported(feats, fc.in_channels, nh, fc.out_channels - nh, heatmaps, labels):
+                if batch is not None:
+                    self._log_samples(fc(feats[0:1]), batch, inputs, nh, batch_nb, first=slice(0, 1))
                 return ops.head_landmark_eval(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, lc.weight,
                                               self.loss_reg.channel_weights, self.loss_reg.kind, getattr(lc, "epsilon", 1e-5),
                                               lc.ignore_index, self.class_loss)
             outputs = fc(feats)
         else:
             outputs = m(inputs)
+        if batch is not None:
+            self._log_samples(outputs, batch, inputs, nh, batch_nb)
         out_hm, out_cls = outputs[:, :nh], outputs[:, nh:]
         return lc(out_cls, labels), self.loss_reg(out_hm, heatmaps), HL.dice_metric(out_cls, labels)
 
@@ -613,7 +652,8 @@ class LandmarkValidation:
         was_training = self.model.training
         self.model.eval()
         try:
-            class_loss, regression_loss, per_channel_dice = self._forward(inputs, heatmaps, labels, nh)
+            class_loss, regression_loss, per_channel_dice = self._forward(inputs, heatmaps, labels, nh,
+                                                                          batch if _logs_samples(self, batch_nb) else None, batch_nb)
         finally:
             self.model.train(was_training)
         results = {"val_loss": regression_loss + class_loss, "val_class_loss": class_loss, "val_regression_loss": regression_loss}
