@@ -1,10 +1,14 @@
 """Helpers for the -m gpu parity tests (HIP path vs the CPU oracle on identical seeded inputs)."""
+import types
+
 import numpy as np
 import torch
 
 from oracle import ref_cpu as O
 
 DEV = "cuda:0"
+CL = torch.channels_last_3d
+DT = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}   # storage type of a mode
 # tolerance of the parity metric ||a-b||2/||b||2: fp32 mode must meet the north-star 1e-3 with margin;
 # bf16 mode stores activations/gradients in bf16 (8 significant bits): the reference's own bf16 drift is 8e-3/2e-2.
 TOL = {"fp32": 1e-4, "bf16": 2.5e-2, "fp16": 4e-3}  # fp16 storage: 11 significant bits
@@ -44,6 +48,11 @@ def copy_params(dst, src):
 # representable in the kernel's output type and every fp32 partial sum is exact in ANY summation order: accumulation order,
 # MFMA blocking, split products and output rounding drop out, and a correct kernel equals ATen's fp64 result in every element.
 FP32_EXACT = float(2 ** 24)   # every integer of magnitude <= 2^24 is an fp32 number
+
+
+def report(item, what, kernel, elements):
+    """One line per comparison group of the exact-arithmetic suites (pytest -s / -rP shows them)."""
+    print(f"[exact] item={item} {what} kernel={kernel} elements={elements}")
 
 
 def lattice(tag, *shape, values=(-2, -1, 1, 2), density=0.25, scale=1.0):
@@ -98,3 +107,93 @@ def assert_exact(a, ref, what, first=10):
     nan = int(torch.isnan(a).sum())
     raise AssertionError(f"{what}: {nbad} of {a.numel()} elements differ ({nan} NaN); first at " + " | ".join(lines)
                          + (f"; residues: {where}" if where else ""))
+
+
+# ------------------------------------------------------------------------------- exact arithmetic: normalisation
+# Inputs for GroupNorm / BatchNorm whose statistics, coefficients and gradients are dyadic numbers of the storage types.
+def snap(ref, step=2.0 ** -12, moved=1e-9):
+    """An fp64 ATen reference rounded to the grid of the exact result.  ATen's fp64 rstd is 1 / sqrt(var + eps) and not
+    exactly 1 / sigma: the snapped tensor is the reference, and NO element may have moved by more than `moved`, so that
+    snapping cannot hide a real difference (the grid step is 2.4e-4)."""
+    ref = ref.detach().double()
+    out = torch.round(ref / step) * step
+    d = float((out - ref).abs().max()) if ref.numel() else 0.0
+    assert d <= moved, f"snap: an element moved by {d:.3e} > {moved:.1e}: the reference is not on the 2^{int(np.log2(step))} grid"
+    return out
+
+
+def norm_lattice(tag, n, c, groups, shape, eps, batch=False, nonneg=False):
+    """Seeded like `lattice`.  Per (sample, group): x = m + sigma * s and du = e + p + q * s with s in {-1, +1} balanced so
+    that the group mean is exactly m and the variance exactly sigma^2 (eps 0: sigma in {1, 2, 4}, rstd = 1 / sigma; eps 3:
+    sigma = 1, rstd = 1 / 2); e in {+-1, +-2} (0 for an odd leftover) comes in +t / -t pairs among the voxels of equal s of a channel, so every sum
+    the backward divides by `count` is an exact multiple of it -- also when an activation masks du by the sign of s.  Even
+    spatial size: s is balanced inside every channel; odd: channel 2j + 1 carries -s of channel 2j and shares its gamma (odd
+    size with an odd channel count per group raises).  gamma in {1, 2} with a dyadic group mean (uniform from {1/2, 1, 2}
+    when a group has fewer than four channels), beta a small integer; beta_act, for the variants that recompute an
+    activation mask from the forward coefficients, is uniform per group: +-3 (all pass / all blocked) or +-1/8 (the mask
+    is the sign of s), never giving a pre-activation of 0.
+    batch=True (BatchNorm, groups == c): one (m, sigma, p, q) row per channel for all samples; the balance of s and the pairs
+    of e run over the n * S voxels of a channel (n * S even).  nonneg=True: m = sigma, so x is 0 or 2 * sigma (the output of
+    a ReLU).  Returns x, du [n, c, *shape], gamma, beta, beta_act [c] (fp32) and m, sigma, p, q [n, groups] (fp64)."""
+    if float(eps) not in (0.0, 3.0):
+        raise ValueError("norm_lattice: eps must be 0 or 3")
+    if c % groups:
+        raise ValueError("norm_lattice: c % groups != 0")
+    g = O._rng("in:" + tag)
+    cg, S = c // groups, int(np.prod(shape))
+    if batch:
+        if groups != c or (n * S) % 2:
+            raise ValueError("norm_lattice: BatchNorm wants groups == c and an even n * S")
+    ns, ln = (1, n * S) if batch else (n, S)
+    if ln % 2 and cg % 2:
+        raise ValueError(f"norm_lattice: odd spatial size {ln} with an odd channel count per group {cg}")
+    sigma = g.choice(np.asarray([1.0, 2.0, 4.0]), size=(ns, groups)) if float(eps) == 0.0 else np.ones((ns, groups))
+    m = sigma.copy() if nonneg else g.integers(-3, 4, size=(ns, groups)).astype(np.float64)
+    p = g.choice(np.asarray([-2.0, -1.0, 1.0, 2.0]), size=(ns, groups))
+    q = g.choice(np.asarray([-2.0, -1.0, 1.0, 2.0]), size=(ns, groups))
+    s = np.empty((ns, c, ln))
+    e = np.zeros((ns, c, ln))
+    for i in range(ns):
+        for ch in range(c):
+            if ln % 2 and ch % 2:
+                s[i, ch] = -s[i, ch - 1]
+            else:
+                k = ln // 2 + (int(g.integers(0, 2)) if ln % 2 else 0)
+                row = -np.ones(ln)
+                row[g.permutation(ln)[:k]] = 1.0
+                s[i, ch] = row
+            for sign in (1.0, -1.0):
+                idx = g.permutation(np.flatnonzero(s[i, ch] == sign))
+                h = len(idx) // 2
+                t = g.choice(np.asarray([-2.0, -1.0, 1.0, 2.0]), size=h)
+                e[i, ch, idx[:h]] = t
+                e[i, ch, idx[h:2 * h]] = -t
+    per_ch = lambda a: np.repeat(a, cg, axis=1)[:, :, None]
+    x = per_ch(m) + per_ch(sigma) * s
+    du = e + per_ch(p) + per_ch(q) * s
+    gamma = np.empty(c)
+    for gi in range(groups):
+        if cg >= 4 and cg % 4 == 0:
+            unit = 2 if ln % 2 else 1                                  # odd size: the 2s come in channel pairs
+            ks = [k for k in range(0, cg + 1, cg // 4) if k % unit == 0]
+            k = int(g.choice(np.asarray(ks)))
+            row = np.ones(cg)
+            chosen = g.permutation(cg // unit)[:k // unit]
+            for j in chosen:
+                row[j * unit:(j + 1) * unit] = 2.0
+            gamma[gi * cg:(gi + 1) * cg] = row
+        else:
+            gamma[gi * cg:(gi + 1) * cg] = float(g.choice(np.asarray([0.5, 1.0, 2.0])))
+    beta = g.integers(-3, 4, size=c).astype(np.float64)
+    beta_act = np.repeat(g.choice(np.asarray([3.0, -3.0, 0.125, -0.125]), size=groups, p=[0.3, 0.15, 0.3, 0.25]), cg)
+
+    def vol(a):
+        if batch:
+            a = a.reshape(c, n, S).transpose(1, 0, 2)
+        return torch.from_numpy(np.ascontiguousarray(a.reshape(n, c, *shape)).astype(np.float32))
+
+    rows = lambda a: torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, (n, groups))).astype(np.float64))
+    f32 = lambda a: torch.from_numpy(a.astype(np.float32))
+    return types.SimpleNamespace(x=vol(x), du=vol(du), gamma=f32(gamma), beta=f32(beta), beta_act=f32(beta_act), m=rows(m),
+                                 sigma=rows(sigma), p=rows(p), q=rows(q), n=n, c=c, groups=groups, shape=tuple(shape), eps=float(eps),
+                                 spatial=S, cg=cg, batch=batch)
