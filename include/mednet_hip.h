@@ -131,6 +131,14 @@ int mednet_conv3d_fused_stats_chunks(int n, int d, int h, int w, int cin, int co
 int mednet_conv3d_fwd(const void* x, const void* packed, const float* bias, void* y, int n, int d, int h, int w,
                       int cin, int cout, int ksize, int x_dtype, int x_layout, int y_dtype, int y_layout,
                       int dgrad, int algo, float* gn_partial, mednet_stream stream);
+/* Multi-channel network input (Cin = 2, 3, 4: PET/CT, multi-sequence MRI) in the 16-bit storage modes: 1 exactly for the calls
+ * that mednet_conv3d_fwd gives to the matrix-core first-layer kernel -- 3x3x3, no bias, fp32 x, 16-bit channels-last y,
+ * Cout % 16 == 0, algo AUTO or MFMA (with or without MEDNET_ALGO_SPLITW_BIT), tuning option conv_cm = 1 (the default; 0 restores
+ * the dispatch without this kernel).  For such a call x may be passed in EITHER layout -- planar N x C x D x H x W as a batch
+ * holds it (x_layout = MEDNET_NCDHW, no layout copy) or channels-last --, with identical results; gn_partial is accepted and
+ * mednet_conv3d_fused_stats_chunks gives its row count.  mednet_conv3d_wgrad takes the same two layouts for this layer when
+ * Cout <= 64 (matrix-core kernel, obeys option wgrad_c1_mfma). */
+int mednet_conv3d_cm_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int algo);
 /* conv 3x3x3 without bias + activation (MEDNET_ACT_*) in the epilogue, bf16 NDHWC in and out, matrix-core path only:
  * the conv -> ReLU / LeakyReLU / ELU step of the 'gcr'-style orders (components.py:12-67; UNet3D's default).  gn_partial as
  * in mednet_conv3d_fwd; the statistics are those of the ACTIVATED output (the next GroupNorm's input).  Ask
@@ -205,6 +213,18 @@ int mednet_conv3d_wgrad_c1_gn_supported(int cout, int x_dtype, int dtype);
 int mednet_conv3d_wgrad_c1_gn(const void* x, const void* dz, const void* y, const float* coef, const float* bcoef, float* dw,
                               int n, int d, int h, int w, int cout, int act, int x_dtype, int dtype, void* ws, size_t ws_bytes,
                               mednet_stream stream);
+/* The same for the multi-channel first layer (Cin = 2, 3, 4): x is fp32 in `x_layout` (planar or channels-last), dw is
+ * (cout, cin, 3, 3, 3); dz and y are read from memory once, all Cin channels of x are contracted against the one staged brick.
+ * Workspace: mednet_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout, 3, 0).  _supported: Cin in {2, 3, 4}, Cout in {16, 32, 48, 64},
+ * fp32 x, 16-bit dtype, options conv_cm and wgrad_c1_mfma on.
+ * mednet_conv3d_wgrad_cm_plan: the launcher's own plan of this weight gradient (no device needed), out4 = {workgroups,
+ * 32-channel blocks per workgroup, workgroups per CU the kernel is compiled for, dynamic LDS bytes}; gn = 1: the GroupNorm form,
+ * gn = 0: the plain form mednet_conv3d_wgrad runs. */
+int mednet_conv3d_wgrad_cm_gn_supported(int cin, int cout, int x_dtype, int dtype);
+int mednet_conv3d_wgrad_cm_plan(int n, int d, int h, int w, int cin, int cout, int dtype, int gn, int* out4);
+int mednet_conv3d_wgrad_cm_gn(const void* x, int x_layout, const void* dz, const void* y, const float* coef, const float* bcoef,
+                              float* dw, int n, int d, int h, int w, int cin, int cout, int act, int x_dtype, int dtype, void* ws,
+                              size_t ws_bytes, mednet_stream stream);
 int mednet_conv3d_wgrad(const void* x, const void* dy, float* dw, float* dbias, int n, int d, int h, int w,
                         int cin, int cout, int ksize, int x_dtype, int x_layout, int dy_dtype, int dy_layout,
                         int algo, int workgroups, void* ws, size_t ws_bytes, mednet_stream stream);

@@ -178,6 +178,13 @@ static int conv_common_checks(const char* who, int n, int d, int h, int w, int c
   return MEDNET_OK;
 }
 
+// Multi-channel first layer (Cin = 2, 3, 4; conv_cm_mfma.inc): 1 exactly for the calls mednet_conv3d_fwd gives to that kernel --
+// 3x3x3, no bias, fp32 x in EITHER layout, 16-bit channels-last y, Cout % 16 == 0, any algo but DIRECT, option conv_cm on.
+extern "C" int mednet_conv3d_cm_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int algo) {
+  if (algo_base(algo) == MEDNET_ALGO_DIRECT || !is16(y_dtype) || !tuning_option("conv_cm", 1)) return 0;
+  return ELT_CALL(y_dtype, conv_cm_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, MEDNET_NDHWC, false) ? 1 : 0;
+}
+
 extern "C" int mednet_conv3d_fused_stats_chunks(int n, int d, int h, int w, int cin, int cout, int ksize, int x_dtype,
                                                 int y_dtype, int algo) {
   if (algo_base(algo) == MEDNET_ALGO_DIRECT || !tuning_option("conv_fuse_stats", 1)) return 0;
@@ -187,6 +194,7 @@ extern "C" int mednet_conv3d_fused_stats_chunks(int n, int d, int h, int w, int 
     return conv_x3_supported(cin, cout, ksize) && conv_x3_fits(d, h, w, cin) ? conv_x3_stats_rows(n, d, h, w, cout) : 0;
   }
   if (ELT_CALL(y_dtype, conv_c1_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, MEDNET_NDHWC, false)) return ELT_CALL(y_dtype, conv_c1_stats_chunks, n, d, h, w, cout);
+  if (mednet_conv3d_cm_supported(cin, cout, ksize, x_dtype, y_dtype, algo)) return ELT_CALL(y_dtype, conv_cm_stats_chunks, n, d, h, w, cout);
   if (!ELT_CALL(y_dtype, conv_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, MEDNET_NDHWC, MEDNET_NDHWC, false)) return 0;
   return conv_mfma_stats_chunks(n, d, h, w, cin, cout, false, algo_split(algo, y_dtype));
 }
@@ -218,6 +226,11 @@ extern "C" int mednet_conv3d_fwd(const void* x, const void* packed, const float*
   // take and under ALGO_EXACT, the fp32 matrix instruction.  Both satisfy MEDNET_ALGO_MFMA ("a matrix-core path is required").
   const bool f32_mode = algo_base(algo) != MEDNET_ALGO_DIRECT && conv_f32_mfma_enabled() && ksize == 3 && x_dtype == MEDNET_F32 &&
                         y_dtype == MEDNET_F32 && (x_layout == MEDNET_NDHWC || cin == 1) && y_layout == MEDNET_NDHWC;
+  // multi-channel first layer (2-4 input channels, read planar or channels-last where they lie): contraction over Cin x 27 taps
+  if (!dgrad && !bias && y_layout == MEDNET_NDHWC && (x_layout == MEDNET_NDHWC || x_layout == MEDNET_NCDHW) &&
+      mednet_conv3d_cm_supported(cin, cout, ksize, x_dtype, y_dtype, algo))
+    return ELT_CALL(y_dtype, launch_conv_cm_mfma, x, x_layout, (const float*)(base + L.f32_fwd), y, n, d, h, w, cin, cout, gn_partial, s,
+                    algo_split(algo, y_dtype) ? 1 : 0);
   if (algo_base(algo) == MEDNET_ALGO_MFMA && !mfma_ok && !f32_mode)
     return fail(MEDNET_E_UNSUPPORTED, "conv3d_fwd: MFMA path does not take cin=%d cout=%d k=%d dtypes %d->%d", cin, cout,
                 ksize, x_dtype, y_dtype);
@@ -258,7 +271,8 @@ extern "C" size_t mednet_conv3d_wgrad_ws_bytes(int n, int d, int h, int w, int c
   const size_t a = wgrad_direct_ws_bytes((size_t)n * d * h * w, cout, cin, ksize);
   // (the 16-bit element types share one plan; `workgroups`: see mednet_conv3d_wgrad)
   const size_t b = wgrad_mfma_ws_bytes(n, d, h, w, cin, cout, ksize, workgroups);
-  const size_t c1 = cin == 1 ? wgrad_c1_ws_bytes(n, d, h, w, cout) : 0;
+  size_t c1 = cin == 1 ? wgrad_c1_ws_bytes(n, d, h, w, cout) : 0;
+  if (ksize == 3 && cin >= 2 && cin <= 4) c1 = wgrad_cm_ws_bytes(n, d, h, w, cin, cout);  // multi-channel first layer
   const size_t c2 = ksize == 1 ? wgrad_1x1_ws_bytes(n, (size_t)d * h * w, cin, cout) : 0;
   const size_t f = ksize == 3 ? wgrad_f32_mfma_ws_bytes(n, d, h, w, cout, cin, 0) : 0;
   const size_t f3 = conv_x3_supported(cin, cout, ksize) ? wgrad_x3_ws_bytes(n, d, h, w, cin, cout, workgroups) : 0;
@@ -306,6 +320,28 @@ extern "C" int mednet_conv3d_wgrad_c1_gn(const void* x, const void* dz, const vo
   return launch_wgrad_c1_gn(x, dz, y, coef, bcoef, act, dw, n, d, h, w, cout, x_dtype, dtype, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// The same for the multi-channel first layer (Cin = 2, 3, 4): x is fp32 in `x_layout` (planar N x C x D x H x W or channels-last),
+// dw is (cout, cin, 3, 3, 3); workspace as mednet_conv3d_wgrad_ws_bytes(.., cin, ..).  mednet_conv3d_wgrad_cm_plan: the launcher's
+// own plan, out4 = {workgroups, 32-channel blocks per workgroup (NB), workgroups per CU the kernel is built for, LDS bytes};
+// gn = 0 is the plain form mednet_conv3d_wgrad runs.
+extern "C" int mednet_conv3d_wgrad_cm_gn_supported(int cin, int cout, int x_dtype, int dtype) {
+  return is16(dtype) && wgrad_cm_gn_supported(cin, cout, x_dtype, dtype) ? 1 : 0;
+}
+extern "C" int mednet_conv3d_wgrad_cm_plan(int n, int d, int h, int w, int cin, int cout, int dtype, int gn, int* out4) {
+  MEDNET_REQUIRE(out4 && n > 0 && d > 0 && h > 0 && w > 0, MEDNET_E_SHAPE, "conv3d_wgrad_cm_plan: bad arguments");
+  return wgrad_cm_plan(n, d, h, w, cin, cout, dtype, gn != 0, out4);
+}
+extern "C" int mednet_conv3d_wgrad_cm_gn(const void* x, int x_layout, const void* dz, const void* y, const float* coef,
+                                         const float* bcoef, float* dw, int n, int d, int h, int w, int cin, int cout, int act,
+                                         int x_dtype, int dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(x && dz && y && coef && bcoef && dw && ws, MEDNET_E_SHAPE, "conv3d_wgrad_cm_gn: null argument");
+  MEDNET_REQUIRE(is16(dtype) && x_dtype == MEDNET_F32, MEDNET_E_DTYPE, "conv3d_wgrad_cm_gn: x must be fp32, dz / y 16-bit (dtypes %d, %d)", x_dtype, dtype);
+  MEDNET_REQUIRE(x_layout == MEDNET_NDHWC || x_layout == MEDNET_NCDHW, MEDNET_E_SHAPE, "conv3d_wgrad_cm_gn: bad x_layout %d", x_layout);
+  const int rc = conv_common_checks("conv3d_wgrad_cm_gn", n, d, h, w, cin, cout, 3, x_dtype, dtype);
+  if (rc) return rc;
+  return launch_wgrad_cm(x, x_layout, dz, y, coef, bcoef, act, dw, n, d, h, w, cin, cout, dtype, ws, ws_bytes, (hipStream_t)stream);
+}
+
 extern "C" int mednet_conv3d_wgrad(const void* x, const void* dy, float* dw, float* dbias, int n, int d, int h, int w,
                                    int cin, int cout, int ksize, int x_dtype, int x_layout, int dy_dtype, int dy_layout,
                                    int algo, int workgroups, void* ws, size_t ws_bytes, mednet_stream stream) {
@@ -323,6 +359,9 @@ extern "C" int mednet_conv3d_wgrad(const void* x, const void* dy, float* dw, flo
   }
   if (algo_base(algo) != MEDNET_ALGO_DIRECT && wgrad_c1_supported(cin, cout, ksize, x_layout, dy_layout))
     return launch_wgrad_c1(x, dy, dw, n, d, h, w, cout, x_dtype, dy_dtype, ws, ws_bytes, s, !algo_exact(algo) && conv_x3_enabled());
+  if (algo_base(algo) != MEDNET_ALGO_DIRECT && (x_layout == MEDNET_NDHWC || x_layout == MEDNET_NCDHW) &&
+      wgrad_cm_supported(cin, cout, ksize, x_dtype, dy_dtype, dy_layout))  // multi-channel first layer, plain form
+    return launch_wgrad_cm(x, x_layout, dy, nullptr, nullptr, nullptr, 0, dw, n, d, h, w, cin, cout, dy_dtype, ws, ws_bytes, s);
   if (algo_base(algo) != MEDNET_ALGO_DIRECT && wgrad_1x1_supported(cin, cout, ksize, x_layout, dy_layout, dy_dtype))
     return launch_wgrad_1x1(x, dy, dw, n, (size_t)d * h * w, cin, cout, x_dtype, ws, ws_bytes, s);
   if (algo_base(algo) != MEDNET_ALGO_DIRECT && conv_f32_mfma_enabled() && ksize == 3 && x_dtype == MEDNET_F32 && dy_dtype == MEDNET_F32 &&

@@ -1049,6 +1049,41 @@ int launch_wgrad_c1_gn(const void* x, const void* dz, const void* y, const float
   hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, part, dw, count, blocks);
   return check_launch("wgrad_c1_reduce");
 }
+// ---- multi-channel first layer (Cin = 2, 3, 4; conv_cm_mfma.inc): fp32 x in either layout, 16-bit channels-last dy.  Options
+// conv_cm (the whole path) and wgrad_c1_mfma (the matrix-core first-layer weight gradients) both have to be on.
+static bool is16_dt(int dt) { return dt == MEDNET_BF16 || dt == MEDNET_F16; }
+bool wgrad_cm_supported(int cin, int cout, int ksize, int x_dtype, int dy_dtype, int dy_layout) {
+  if (!tuning_option("conv_cm", 1) || !tuning_option("wgrad_c1_mfma", 1) || ksize != 3 || dy_layout != MEDNET_NDHWC || !is16_dt(dy_dtype)) return false;
+  return dy_dtype == MEDNET_F16 ? mednet_f16::wgrad_cm_mfma_supported(cin, cout, x_dtype, dy_dtype) : wgrad_cm_mfma_supported(cin, cout, x_dtype, dy_dtype);
+}
+bool wgrad_cm_gn_supported(int cin, int cout, int x_dtype, int dtype) { return wgrad_cm_supported(cin, cout, 3, x_dtype, dtype, MEDNET_NDHWC); }
+size_t wgrad_cm_ws_bytes(int n, int d, int h, int w, int cin, int cout) {  // (one plan for both element types; the plain form has the most workgroups)
+  if (cin < 2 || cin > 4 || cout % 16 || cout > 64) return 0;
+  return (size_t)wgrad_cm_mfma_blocks(n, d, h, w, cin, cout, false) * 27 * cin * cout * sizeof(float);
+}
+int wgrad_cm_plan(int n, int d, int h, int w, int cin, int cout, int dtype, bool gn, int* out4) {
+  MEDNET_REQUIRE(is16_dt(dtype) && wgrad_cm_mfma_supported(cin, cout, MEDNET_F32, MEDNET_BF16), MEDNET_E_UNSUPPORTED,
+                 "wgrad_cm_plan: Cin in {2, 3, 4}, Cout in {16, 32, 48, 64}, 16-bit dy (cin=%d cout=%d dtype=%d)", cin, cout, dtype);
+  if (dtype == MEDNET_F16) mednet_f16::wgrad_cm_mfma_plan(n, d, h, w, cin, cout, gn, out4);
+  else wgrad_cm_mfma_plan(n, d, h, w, cin, cout, gn, out4);
+  return MEDNET_OK;
+}
+// y != NULL: the GroupNorm form (dz, y, coef, bcoef as launch_wgrad_c1_gn), else the plain form with dz = dy
+int launch_wgrad_cm(const void* x, int x_layout, const void* dz, const void* y, const float* coef, const float* bcoef, int act,
+                    float* dw, int n, int d, int h, int w, int cin, int cout, int dtype, void* ws, size_t ws_bytes, hipStream_t s) {
+  MEDNET_REQUIRE(wgrad_cm_supported(cin, cout, 3, MEDNET_F32, dtype, MEDNET_NDHWC), MEDNET_E_UNSUPPORTED,
+                 "wgrad_cm: Cin in {2, 3, 4}, Cout in {16, 32, 48, 64}, fp32 x, 16-bit dy (cin=%d cout=%d)", cin, cout);
+  const bool gn = y != nullptr;
+  const int blocks = dtype == MEDNET_F16 ? mednet_f16::wgrad_cm_mfma_blocks(n, d, h, w, cin, cout, gn) : wgrad_cm_mfma_blocks(n, d, h, w, cin, cout, gn);
+  const size_t count = (size_t)27 * cin * cout;
+  MEDNET_REQUIRE(ws_bytes >= (size_t)blocks * count * sizeof(float), MEDNET_E_WORKSPACE, "wgrad_cm: workspace too small");
+  float* part = (float*)ws;
+  const int rc = dtype == MEDNET_F16 ? mednet_f16::launch_wgrad_cm_mfma(x, x_layout, dz, part, n, d, h, w, cin, cout, s, y, coef, bcoef, act)
+                                     : launch_wgrad_cm_mfma(x, x_layout, dz, part, n, d, h, w, cin, cout, s, y, coef, bcoef, act);
+  if (rc) return rc;
+  hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, part, dw, count, blocks);
+  return check_launch("wgrad_cm_reduce");
+}
 int launch_wgrad_c1(const void* x, const void* dy, float* dw, int n, int d, int h, int w, int cout, int x_dtype,
                     int dy_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool split_bf16) {
   const int tz = (d + W1_TZ - 1) / W1_TZ, ty = (h + W1_TY - 1) / W1_TY, tx = (w + W1_TX - 1) / W1_TX;

@@ -3019,6 +3019,8 @@ int launch_wgrad_c1_mfma(const void* x, const void* dy, float* part, int n, int 
   return check_launch("wgrad_c1_mfma");
 }
 
+#include "conv_cm_mfma.inc"  // the same two kernels for Cin = 2, 3, 4 (multi-channel network input)
+
 // ---- ConvTranspose3d weight gradient, second generation: output-parity classes ------------------------------------
 //   dW[k][ci][co] = sum_i x[i][ci] * dy[2i - 1 + k][co]          (per dimension: k=1 -> dy[2i], k=2 -> dy[2i+1], k=0 -> dy[2i-1])
 // With E[j] = dy[2j], O[j] = dy[2j+1] per dimension:  k=1: x[j] E[j],  k=2: x[j] O[j],  k=0: x[j+1] O[j].  So a workgroup

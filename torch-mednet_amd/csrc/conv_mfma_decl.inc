@@ -64,6 +64,18 @@ int wgrad_c1_mfma_blocks(int n, int d, int h, int w);
 int launch_wgrad_c1_mfma(const void* x, const void* dy, float* part, int n, int d, int h, int w, int cout, hipStream_t s,
                          int x_dtype = MEDNET_F32, const void* gn_y = nullptr, const float* gn_coef = nullptr,
                          const float* gn_bcoef = nullptr, int gn_act = 0);
+// conv_cm_mfma.inc: the multi-channel first layer (Cin = 2, 3, 4; fp32 x, planar or channels-last by `x_layout`)
+bool conv_cm_mfma_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int y_layout, bool bias);
+int conv_cm_grid(int n, int d, int h, int w, int cout);
+int conv_cm_stats_chunks(int n, int d, int h, int w, int cout);
+int launch_conv_cm_mfma(const void* x, int x_layout, const float* w_pf, void* y, int n, int d, int h, int w, int cin, int cout,
+                        float* gn_partial, hipStream_t s, int split = 0);
+bool wgrad_cm_mfma_supported(int cin, int cout, int x_dtype, int dy_dtype);
+void wgrad_cm_mfma_plan(int n, int d, int h, int w, int cin, int cout, bool gn, int* out4);  // {workgroups, NB, workgroups per CU, LDS bytes}
+int wgrad_cm_mfma_blocks(int n, int d, int h, int w, int cin, int cout, bool gn);  // (the plain form never has fewer)
+int launch_wgrad_cm_mfma(const void* x, int x_layout, const void* dy, float* part, int n, int d, int h, int w, int cin, int cout,
+                         hipStream_t s, const void* gn_y = nullptr, const float* gn_coef = nullptr, const float* gn_bcoef = nullptr,
+                         int gn_act = 0);
 
 // head_mfma.hip: the landmark head (1x1x1 conv 32 -> nh heat maps + ncls classes) fused with its two losses, matrix-core form
 bool head_lm_supported(int cin, int nh, int ncls, int dtype, size_t spatial);

@@ -71,6 +71,10 @@ SIGNATURES = {
     "mednet_conv3d_wgrad_plan": (_i, [_i] * 8 + [_vp]),
     "mednet_conv3d_wgrad_c1_gn_supported": (_i, [_i] * 3),
     "mednet_conv3d_wgrad_c1_gn": (_i, [_vp] * 6 + [_i] * 8 + [_vp, _sz, _vp]),
+    "mednet_conv3d_cm_supported": (_i, [_i] * 6),
+    "mednet_conv3d_wgrad_cm_gn_supported": (_i, [_i] * 4),
+    "mednet_conv3d_wgrad_cm_plan": (_i, [_i] * 8 + [_vp]),
+    "mednet_conv3d_wgrad_cm_gn": (_i, [_vp, _i] + [_vp] * 5 + [_i] * 9 + [_vp, _sz, _vp]),
     "mednet_conv3d_wgrad": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp, _sz, _vp]),
     "mednet_convt3d_fwd": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
     "mednet_convt3d_dgrad": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp]),

@@ -22,7 +22,7 @@ ENABLED = os.environ.get("MEDNET_BLOCK_NODE", "1") == "1"
 WGRAD_FIRST = os.environ.get("MEDNET_WGRAD_FIRST", "1") == "1"  # A/B knob: launch order of the two gradients
 
 
-def _conv_fwd(x, packed, cout, want_stats):
+def _conv_fwd(x, packed, cout, want_stats, x_layout=L.NDHWC):
     n, cin, d, h, w = x.shape
     lib = L.lib()
     y = ops.empty_cl(n, cout, d, h, w, config.act_dtype(), x.device)
@@ -33,7 +33,7 @@ def _conv_fwd(x, packed, cout, want_stats):
             partial = torch.empty((n, chunks, cout, 2), dtype=torch.float32, device=x.device)
     with ops.profiled_conv(3, cin, cout, n, d, h, w):
         L.check(lib.mednet_conv3d_fwd(x.data_ptr(), packed.data_ptr(), None, y.data_ptr(), n, d, h, w, cin, cout, 3, L.dt(x),
-                                      L.NDHWC, L.dt(y), L.NDHWC, 0, config.conv_algo(), L.ptr(partial), L.stream()), "conv3d_fwd")
+                                      x_layout, L.dt(y), L.NDHWC, 0, config.conv_algo(), L.ptr(partial), L.stream()), "conv3d_fwd")
     return y, partial
 
 
@@ -115,31 +115,41 @@ C1GN_COUNT = {"fused": 0}  # (tests check that the fused form really ran, like o
 
 
 def _c1_gn_applies(xin, y, partial, need_dx):
-    """The network's first SingleConv (Cin = 1, no gradient of the input wanted): its GroupNorm backward feeds nothing but the
-    weight gradient, so the apply pass can happen inside that kernel's staging (mednet_conv3d_wgrad_c1_gn)."""
-    return (FUSE_C1GN and partial is not None and not need_dx and xin.shape[1] == 1 and y.dtype != torch.float32
-            and config.conv_algo() != L.ALGO_DIRECT
-            and bool(L.lib().mednet_conv3d_wgrad_c1_gn_supported(y.shape[1], L.dt(xin), L.dt(y))))
+    """The network's first SingleConv (Cin = 1, or 2-4 fp32 channels; no gradient of the input wanted): its GroupNorm backward
+    feeds nothing but the weight gradient, so the apply pass can happen inside that kernel's staging (mednet_conv3d_wgrad_c1_gn /
+    mednet_conv3d_wgrad_cm_gn)."""
+    if not (FUSE_C1GN and partial is not None and not need_dx and y.dtype != torch.float32 and config.conv_algo() != L.ALGO_DIRECT):
+        return False
+    cin = xin.shape[1]
+    if cin == 1:
+        return bool(L.lib().mednet_conv3d_wgrad_c1_gn_supported(y.shape[1], L.dt(xin), L.dt(y)))
+    return bool(L.lib().mednet_conv3d_wgrad_cm_gn_supported(cin, y.shape[1], L.dt(xin), L.dt(y)))
 
 
-def _c1_gn_bwd(xin, dz, y, coef, stats, gamma_p, beta_p, weight_p, groups, act, partial):
+def _c1_gn_bwd(xin, dz, y, coef, stats, gamma_p, beta_p, weight_p, groups, act, partial, x_layout=L.NDHWC):
     """GroupNorm(+activation) backward and 3x3x3 weight gradient of the first layer without the gradient tensor between them.
     Returns (dw-or-None, dgamma-or-None, dbeta-or-None) like _gn_bwd / _conv_bwd.  On the caller's stream: the side stream is
     busy with the second layer's weight gradient at this point, and this kernel is HBM-bound like the pass it replaces."""
     n, c, d, h, w = y.shape
+    cin = xin.shape[1]
     lib = L.lib()
     C1GN_COUNT["fused"] += 1
     dgamma, dg_direct = ops._grad_target(gamma_p, (c,))
     dbeta, db_direct = ops._grad_target(beta_p, (c,))
-    dw, dw_direct = ops._grad_target(weight_p, (c, 1, 3, 3, 3))
+    dw, dw_direct = ops._grad_target(weight_p, (c, cin, 3, 3, 3))
     bcoef = torch.empty((n, c, 3), dtype=torch.float32, device=y.device)
-    ws = L.workspace(max(lib.mednet_gn_ws_bytes(n, c, d * h * w), lib.mednet_conv3d_wgrad_ws_bytes(n, d, h, w, 1, c, 3, 0)), y.device)
+    ws = L.workspace(max(lib.mednet_gn_ws_bytes(n, c, d * h * w), lib.mednet_conv3d_wgrad_ws_bytes(n, d, h, w, cin, c, 3, 0)), y.device)
     L.check(lib.mednet_gn_bwd_coefficients(stats.data_ptr(), gamma_p.data_ptr(), partial.data_ptr(), partial.shape[1],
                                            bcoef.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), n, d * h * w, c, groups,
                                            ws.data_ptr(), ws.numel(), L.stream()), "gn_bwd_coefficients")
-    L.check(lib.mednet_conv3d_wgrad_c1_gn(xin.data_ptr(), dz.data_ptr(), y.data_ptr(), coef.data_ptr(), bcoef.data_ptr(),
-                                          dw.data_ptr(), n, d, h, w, c, act, L.dt(xin), L.dt(y), ws.data_ptr(), ws.numel(),
-                                          L.stream()), "conv3d_wgrad_c1_gn")
+    if cin == 1:
+        L.check(lib.mednet_conv3d_wgrad_c1_gn(xin.data_ptr(), dz.data_ptr(), y.data_ptr(), coef.data_ptr(), bcoef.data_ptr(),
+                                              dw.data_ptr(), n, d, h, w, c, act, L.dt(xin), L.dt(y), ws.data_ptr(), ws.numel(),
+                                              L.stream()), "conv3d_wgrad_c1_gn")
+    else:  # 2-4 input channels, read in the layout the forward read them in
+        L.check(lib.mednet_conv3d_wgrad_cm_gn(xin.data_ptr(), x_layout, dz.data_ptr(), y.data_ptr(), coef.data_ptr(), bcoef.data_ptr(),
+                                              dw.data_ptr(), n, d, h, w, cin, c, act, L.dt(xin), L.dt(y), ws.data_ptr(), ws.numel(),
+                                              L.stream()), "conv3d_wgrad_cm_gn")
     return (None if dw_direct else dw), (None if dg_direct else dgamma), (None if db_direct else dbeta)
 
 
@@ -149,7 +159,7 @@ FUSE_DRES = os.environ.get("MEDNET_FUSE_DRES", "1") == "1"  # A/B knob: residual
 FUSE_GNB = os.environ.get("MEDNET_FUSE_GNB", "1") == "1"  # A/B knob: GroupNorm-backward sums in the data-gradient epilogue
 
 
-def _conv_bwd(x, dy, packed, weight_p, need_dx, add=None, gnb=None):
+def _conv_bwd(x, dy, packed, weight_p, need_dx, add=None, gnb=None, x_layout=L.NDHWC):
     """Weight gradient (side stream in trainer mode) + data gradient (+ `add`, a second gradient of x, summed in the
     data-gradient kernel's epilogue when given).  `gnb` = (y_prev, coef_prev, act): x is act(GroupNorm(y_prev)); when the
     kernel can, it also takes the first pass of that GroupNorm's backward over the dx it stores.
@@ -194,7 +204,7 @@ def _conv_bwd(x, dy, packed, weight_p, need_dx, add=None, gnb=None):
         ws = L.workspace(lib.mednet_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout, 3, side.workgroups), dy.device)
         with ops.profiled_wgrad(3, cin, cout, n, d, h, w):
             L.check(lib.mednet_conv3d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), None, n, d, h, w, cin, cout, 3, L.dt(x),
-                                            L.NDHWC, L.dt(dy), L.NDHWC, config.conv_algo(), side.workgroups, ws.data_ptr(),
+                                            x_layout, L.dt(dy), L.NDHWC, config.conv_algo(), side.workgroups, ws.data_ptr(),
                                             ws.numel(), L.stream()), "conv3d_wgrad")
     if WGRAD_FIRST:
         dgrad()
@@ -207,10 +217,12 @@ class ResBlockFn(Function):
         L.require_gpu(x, "ExtResNetBlock")
         ctx.algo = config.conv_algo()
         x = ops._as_act(x)
-        xin = x.contiguous() if x.shape[1] == 1 else ops.to_cl(x)  # Cin == 1: NCDHW and NDHWC coincide
         cout = w1.shape[0]
+        # Cin == 1: NCDHW and NDHWC coincide; 2-4 fp32 channels (16-bit storage) are read where they lie
+        xin, x_layout = ops.first_layer_input(x, cout, 3, config.act_dtype())
+        ctx.x_layout = x_layout
         fuse = (cout // groups) % 2 == 0  # fused partials are per channel pair (include/mednet_hip.h)
-        y1, p1 = _conv_fwd(xin, pk1, cout, fuse)
+        y1, p1 = _conv_fwd(xin, pk1, cout, fuse, x_layout)
         z1, s1, c1 = _gn_fwd(y1, p1, g1, b1, groups, eps, act, None)
         y2, p2 = _conv_fwd(z1, pk2, cout, fuse)
         z2, s2, c2 = _gn_fwd(y2, p2, g2, b2, groups, eps, act, None)
@@ -256,10 +268,10 @@ class ResBlockFn(Function):
         dz1, dw2, part1 = _conv_bwd(z1, dy2, pk2, w2, True, add=dres if fuse else None, gnb=(y1, c1, act) if fuse else None)
         if fuse and _c1_gn_applies(xin, y1, part1, ctx.needs_input_grad[0]):
             dy1 = dx = None  # (never materialised)
-            dw1, dg1, db1 = _c1_gn_bwd(xin, dz1, y1, c1, s1, g1, b1, w1, groups, act, part1)
+            dw1, dg1, db1 = _c1_gn_bwd(xin, dz1, y1, c1, s1, g1, b1, w1, groups, act, part1, ctx.x_layout)
         else:
             dy1, _, dg1, db1 = _gn_bwd(dz1, None if fuse else dres, y1, None, c1, s1, g1, b1, groups, act, False, partial=part1)
-            dx, dw1, _ = _conv_bwd(xin, dy1, pk1, w1, ctx.needs_input_grad[0])
+            dx, dw1, _ = _conv_bwd(xin, dy1, pk1, w1, ctx.needs_input_grad[0], x_layout=ctx.x_layout)
         if debug.TRACE is not None:
             debug.trace("resblock.bwd", None if lazy is not None else dout, part3, dy3, dres, dz2, part2, dy2, dz1, part1, dy1, dx)
         return (dx, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3) + (None,) * 8

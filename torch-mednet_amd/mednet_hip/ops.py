@@ -223,6 +223,22 @@ def _as_act(x: torch.Tensor) -> torch.Tensor:
     return x.to(config.act_dtype())
 
 
+def first_layer_input(x, cout, ksize, out_dtype, plain=True):
+    """-> (tensor, layout) a 3x3x3 convolution reads its input from.  One channel: planar and channels-last coincide.  2-4 fp32
+    channels into a 16-bit channels-last output (the multi-channel network input, mednet_conv3d_cm_supported; `plain`: no bias,
+    output not planar): the kernels read the batch where it lies, planar or channels-last -- no layout copy.  Everything else is
+    brought to channels-last."""
+    cin = x.shape[1]
+    if cin == 1:
+        return x.contiguous(), L.NDHWC
+    if (plain and 2 <= cin <= 4 and x.dtype == torch.float32 and out_dtype in config.HALF_TYPES
+            and L.lib().mednet_conv3d_cm_supported(cin, cout, ksize, L.F32, L.dt_of(out_dtype), config.conv_algo())):
+        if x.is_contiguous(memory_format=CL) and not x.is_contiguous():
+            return x, L.NDHWC
+        return x.contiguous(), L.NCDHW
+    return to_cl(x), L.NDHWC
+
+
 # ------------------------------------------------------------------------------------------------- weights
 def pack_conv_weight(weight: torch.Tensor, ksize: int, transposed: bool, out: torch.Tensor = None) -> torch.Tensor:
     """PyTorch-layout fp32 weight -> opaque packed buffer read by the forward / data-gradient kernels (`out`: rewrite that buffer)."""
@@ -345,8 +361,8 @@ class Conv3dFn(Function):
         x = _as_act(x)
         n, cin, d, h, w = x.shape
         cout = weight.shape[0]
-        # Cin == 1: NCDHW and NDHWC coincide, so the network input is consumed as it arrives.
-        xin = x.contiguous() if cin == 1 else to_cl(x)
+        # Cin == 1: NCDHW and NDHWC coincide, so the network input is consumed as it arrives; so are 2-4 fp32 channels
+        xin, x_layout = first_layer_input(x, cout, ksize, out_dtype, plain=bias is None and not out_planar)
         if out_planar:
             y = torch.empty((n, cout, d, h, w), dtype=out_dtype, device=x.device)
         else:
@@ -359,9 +375,10 @@ class Conv3dFn(Function):
                 partial = torch.empty((n, chunks, cout, 2), dtype=torch.float32, device=x.device)
         with profiled_conv(ksize, cin, cout, n, d, h, w):
             L.check(L.lib().mednet_conv3d_fwd(xin.data_ptr(), packed.data_ptr(), L.ptr(bias), y.data_ptr(), n, d, h, w, cin,
-                                              cout, ksize, L.dt(xin), L.NDHWC, L.dt(y), L.NCDHW if out_planar else L.NDHWC,
+                                              cout, ksize, L.dt(xin), x_layout, L.dt(y), L.NCDHW if out_planar else L.NDHWC,
                                               0, config.conv_algo(), L.ptr(partial), L.stream()), "conv3d_fwd")
         ctx.save_for_backward(xin, packed)
+        ctx.x_layout = x_layout
         ctx.meta = (ksize, out_planar, cin, cout, bias is not None, x.dtype)
         ctx.params = (weight, bias)
         ctx.gn3 = _gn3_hook_of(x, xin.dtype) if (ksize == 1 and out_planar and xin is x) else None
@@ -427,7 +444,7 @@ class Conv3dFn(Function):
                 nbytes = lib.mednet_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout, ksize, side.workgroups)
                 ws = L.workspace(nbytes, dy.device)
                 L.check(lib.mednet_conv3d_wgrad(xin.data_ptr(), dy.data_ptr(), dw.data_ptr(), L.ptr(db), n, d, h, w, cin,
-                                                cout, ksize, L.dt(xin), L.NDHWC, L.dt(dy),
+                                                cout, ksize, L.dt(xin), ctx.x_layout, L.dt(dy),
                                                 L.NCDHW if out_planar else L.NDHWC, config.conv_algo(), side.workgroups,
                                                 ws.data_ptr(), ws.numel(), L.stream()), "conv3d_wgrad")
         return dx, (None if direct_w else dw), (None if direct_b else db), None, None, None, None, None
