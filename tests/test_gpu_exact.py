@@ -326,8 +326,8 @@ def test_weight_gradient_kernels(mode, v4, n, cin, cout, shape, wgs):
 @pytest.mark.parametrize("mode", ["bf16", "fp16", "fp16x2"])
 @pytest.mark.parametrize("n,cout,shape", FIRST_CASES)
 def test_first_layer_kernels(mode, n, cout, shape):
-    """Cin = 1: conv_c1_mfma_kernel (persistent walk for the big volume) with its fused GroupNorm sums, and the weight gradient
-    in its matrix-core form (wgrad_c1_mfma = 1) and its VALU form."""
+    """Cin = 1: conv_first_mfma_kernel<1, .> (persistent walk for the big volume) with its fused GroupNorm sums, and the weight
+    gradient in its matrix-core form (wgrad_first_mfma_kernel<1, ., .>, wgrad_c1_mfma = 1) and its VALU form."""
     c = case("conv", n, 1, cout, shape)
     c.check_conditions(mode)
     ref = c.ref()[0]
@@ -349,7 +349,38 @@ def test_first_layer_kernels(mode, n, cout, shape):
             torch.cuda.synchronize()
             total += assert_exact(y, ref["y"], f"first layer {mode} {c}: y") + assert_exact(conv.weight.grad, ref["dw"], f"wgrad_c1 mfma={c1}: dw")
             total += compare_pair_sums(partial, ref["y"], f"first layer {mode} {c}")
-    report("a", f"{c} {mode}", "conv_c1_mfma_kernel+wgrad_c1(mfma,valu)", total)
+    report("a", f"{c} {mode}", "conv_first_mfma_kernel<1>+wgrad_c1(mfma,valu)", total)
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp16", "fp16x2"])
+@pytest.mark.parametrize("n,cout,shape", FIRST_CASES[:4])
+def test_first_layer_kernels_16bit_input(mode, n, cout, shape):
+    """Cin = 1 with the input already in the 16-bit storage type (the one-channel output of a GroupNorm in the 'gcr' orders): the
+    16-bit-load form of conv_first_mfma_kernel<1, .> with its fused GroupNorm sums, and of the weight gradient in its matrix-core
+    and its VALU form.  The lattice input converts exactly, so the fp64 reference is the one of the fp32-input test."""
+    c = case("conv", n, 1, cout, shape)
+    c.check_conditions(mode)
+    ref = c.ref()[0]
+    lib, dt = L.lib(), DT[mode]
+    x16 = c.x.to(dt)
+    assert bool((x16.double() == c.x.double()).all()), "the lattice input is not a number of the storage type"
+    rows = lib.mednet_conv3d_fused_stats_chunks(n, *shape, 1, cout, 3, L.dt_of(dt), L.dt_of(dt), L.ALGO_AUTO | (L.ALGO_SPLITW_BIT if mode == "fp16x2" else 0))
+    assert rows > 0, "the first-layer matrix-core kernel does not take 16-bit input"
+    check_sum_conditions(ref["y"], f"{c}")
+    total = 0
+    for c1 in (1, 0):
+        with options(wgrad_c1_mfma=c1), mednet_hip.precision(mode):
+            conv = hnn.Conv3d(1, cout, 3, bias=False).to(DEV)
+            with torch.no_grad():
+                conv.weight.copy_(c.w)
+            y, partial = conv.forward_with_stats(x16.to(DEV))
+            assert partial is not None and tuple(partial.shape) == (n, rows, cout, 2)
+            y.backward(c.g.to(DEV).to(dt))
+            torch.cuda.synchronize()
+            total += assert_exact(y, ref["y"], f"first layer, 16-bit x, {mode} {c}: y")
+            total += assert_exact(conv.weight.grad, ref["dw"], f"wgrad_c1 mfma={c1}, 16-bit x: dw")
+            total += compare_pair_sums(partial, ref["y"], f"first layer, 16-bit x, {mode} {c}")
+    report("a", f"{c} {mode} x16", "conv_first_mfma_kernel<1>+wgrad_c1(mfma,valu)", total)
 
 
 def x3_family_takes(n, cin, cout, shape):

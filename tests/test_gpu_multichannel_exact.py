@@ -1,5 +1,5 @@
-"""Exact-arithmetic tests of the multi-channel first layer (2-4 fp32 input channels, 16-bit storage): conv_cm_mfma_kernel with
-its fused GroupNorm pair sums and wgrad_cm_mfma_kernel, against ATen (fp64, CPU) with EQUALITY in every element.
+"""Exact-arithmetic tests of the multi-channel first layer (2-4 fp32 input channels, 16-bit storage): conv_first_mfma_kernel<2..4, .>
+with its fused GroupNorm pair sums and wgrad_first_mfma_kernel<2..4, ., .>, against ATen (fp64, CPU) with EQUALITY in every element.
 
 Same method as tests/test_gpu_exact.py (lattice inputs: the exact result is a number of the output type and every fp32 partial
 sum is exact in any order), same first-layer shapes -- the brick is still 4 x 8 x 16.  Because two correct kernels give the same
@@ -101,7 +101,7 @@ def test_multichannel_first_layer_kernels(mode, cin, n, cout, shape):
                 got[layout] = (y, partial, dw)
             for a, b, name in zip(got["planar"], got["channels_last"], ("y", "partial", "dw")):
                 assert torch.equal(a, b), f"{c} {mode}: {name} differs between the two input layouts"
-    report("a", f"{c} {mode}", "conv_cm_mfma_kernel+wgrad_cm(mfma,direct)", total)
+    report("a", f"{c} {mode}", "conv_first_mfma_kernel+wgrad_cm(mfma,direct)", total)
 
 
 # ------------------------------------------------------------------------------------------------ persistent walk
@@ -132,7 +132,7 @@ def test_multichannel_persistent_walk(mode, cin):
     b = jumps[0]
     mid = b // per_sample + 1
     assert float(partial[mid, 4 * (b // ncb):4 * (b // ncb) + 4].abs().max()) == 0.0, "rows of a skipped sample are not zero"
-    report("a", f"{c} {mode}", f"conv_cm_mfma_kernel walk {items} items / {grid} workgroups", total)
+    report("a", f"{c} {mode}", f"conv_first_mfma_kernel walk {items} items / {grid} workgroups", total)
 
 
 # ------------------------------------------------------------------------------------------------ low parts of the input
@@ -193,7 +193,7 @@ def test_low_part_of_the_input_in_the_weight_gradient(mode, cin):
     rows = L.lib().mednet_conv3d_fused_stats_chunks(n, *shape, cin, cout, 3, L.F32, L.dt_of(DT[mode]), algo_of(mode))
     assert rows > 0 and L.lib().mednet_conv3d_wgrad_cm_gn_supported(cin, cout, L.F32, L.dt_of(DT[mode])) == 1
     _, _, dw = run_first_layer(c.x.to(DEV), c.w, c.g, mode, cout, rows)
-    report("b", f"{c} {mode}", "wgrad_cm_mfma_kernel low part of x", assert_exact(dw, ref["dw"], f"low part {mode} {c}: dw"))
+    report("b", f"{c} {mode}", "wgrad_first_mfma_kernel low part of x", assert_exact(dw, ref["dw"], f"low part {mode} {c}: dw"))
     hi_only = F.conv3d(c.x.to(DT[mode]).double(), c.w.double(), padding=1)   # (the case depends on the low part)
     assert not torch.equal(hi_only, ref["y"])
 
@@ -215,7 +215,7 @@ def test_low_part_of_the_input_in_the_forward(mode, cin):
     y, partial, dw = run_first_layer(c.x.to(DEV), c.w, c.g, mode, cout, rows)
     total = assert_exact(y, ref["y"], f"low part {mode} {c}: y") + assert_exact(dw, ref["dw"], f"low part {mode} {c}: dw")
     total += compare_pair_sums(partial, ref["y"], f"low part {mode} {c}")
-    report("b", f"{c} {mode}", "conv_cm_mfma_kernel low part of x", total)
+    report("b", f"{c} {mode}", "conv_first_mfma_kernel low part of x", total)
 
 
 # ------------------------------------------------------------------------------------------------ the dispatch

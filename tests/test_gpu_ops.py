@@ -1273,7 +1273,7 @@ def test_first_layer_mfma_keeps_fp32_input_precision(n, cout, shape):
     (1, 32, (9, 11, 21)),     # fewer items than workgroups: one brick per workgroup
 ])
 def test_first_layer_persistent_walk_and_fused_statistics(mode, n, cout, shape):
-    """conv_c1_mfma_kernel (model.py:171-174's first convolution, one input channel) as a persistent kernel (round 6): at most four
+    """conv_first_mfma_kernel<1, .> (model.py:171-174's first convolution, one input channel) as a persistent kernel (round 6): at most four
     workgroups per CU walk the (brick, channel block) items and a wave keeps its GroupNorm sums over its bricks of a sample.  The
     output must be BIT-identical to the one-workgroup-per-item launch (option conv_c1_persist=0), every partial row must be written
     (NaN-filled buffer), and the rows must add up to the sums of the STORED output per channel pair."""

@@ -123,3 +123,33 @@ def test_weight_gradient_workspace_and_plan():
     assert lib.mednet_conv3d_wgrad_ws_bytes(n, *shape, 1, 32, 3, 0) == 57147904
     assert lib.mednet_conv3d_wgrad_ws_bytes(n, *shape, 32, 32, 3, 0) == 113771008
     assert lib.mednet_conv3d_wgrad_ws_bytes(n, *shape, 4, 32, 3, 0) == 57147904
+
+
+# (n, shape, cout, mednet_conv3d_wgrad_ws_bytes as the library answered before the one- and multi-channel kernels became one)
+C1_CASES = [(4, (128, 128, 128), 32, 57147904), (2, (160, 160, 96), 64, 57852416), (3, (40, 72, 80), 32, 56667008),
+            (2, (9, 11, 21), 16, 6636160), (1, (5, 6, 7), 64, 1327872)]
+
+
+@pytest.mark.parametrize("n,shape,cout,ws_bytes", C1_CASES)
+def test_one_channel_plans_are_what_they_were(n, shape, cout, ws_bytes):
+    """Cin = 1 through the merged first-layer host code: the weight gradient launches min(bricks, 1024) workgroups of 27 * cout
+    partial sums -- the workspace query, a maximum over every weight-gradient path of the layer plus the bias partials, covers them
+    and has not moved -- and the forward writes 4 partial rows per workgroup of a channel block, for fp32 and 16-bit input."""
+    lib = L.lib()
+    d, h, w = shape
+    bricks = n * ((d + 3) // 4) * ((h + 7) // 8) * ((w + 15) // 16)
+    got = lib.mednet_conv3d_wgrad_ws_bytes(n, d, h, w, 1, cout, 3, 0)
+    assert got >= min(bricks, 1024) * 27 * cout * 4
+    assert got == ws_bytes
+    grid, ncb = c1_grid_rule(n, d, h, w, cout)
+    for x_dtype, y_dtype in ((F32, BF16), (F32, F16), (BF16, BF16), (F16, F16)):
+        for algo in (L.ALGO_AUTO, L.ALGO_AUTO | L.ALGO_SPLITW_BIT):
+            rows = with_option(b"assume_cus", 256, 0, lambda: lib.mednet_conv3d_fused_stats_chunks(n, d, h, w, 1, cout, 3, x_dtype, y_dtype, algo))
+            assert rows == 4 * grid // ncb
+    # the conv_cm option gates 2 to 4 channels only; 16-bit input of the other 16-bit type is not taken
+    assert with_option(b"conv_cm", 0, 1, lambda: lib.mednet_conv3d_fused_stats_chunks(n, d, h, w, 1, cout, 3, F32, BF16, L.ALGO_AUTO)) > 0
+    assert lib.mednet_conv3d_fused_stats_chunks(n, d, h, w, 1, cout, 3, F16, BF16, L.ALGO_AUTO) == 0
+    g = lib.mednet_conv3d_wgrad_c1_gn_supported
+    assert g(cout, F32, BF16) == 1 and g(cout, F16, F16) == 1 and g(cout, BF16, F16) == 0 and g(48, F32, BF16) == 0
+    assert with_option(b"wgrad_c1_mfma", 0, 1, lambda: g(cout, F32, BF16)) == 0
+    assert with_option(b"conv_cm", 0, 1, lambda: g(cout, F32, BF16)) == 1

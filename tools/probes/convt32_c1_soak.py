@@ -1,5 +1,5 @@
 """Race screen of round 6's last two kernels.  convt_dgrad32_mfma_kernel commits the next brick's 24 staging registers per thread into a
-single-buffered LDS image between two barriers while its GroupNorm rows and the brick after are in flight; conv_c1_mfma_kernel (now
+single-buffered LDS image between two barriers while its GroupNorm rows and the brick after are in flight; conv_first_mfma_kernel<1, .> (now
 persistent) does the same with its halo values.  A protocol error would show as an occasional wrong output, most likely when the
 waves of a workgroup drift apart.  SOAK_RUNS launches of every form -- alone, beside a 256 MB copy and beside a 32 -> 32 convolution
 on a second stream (what the training step puts next to them) -- must equal the first launch bit for bit, partial rows included."""

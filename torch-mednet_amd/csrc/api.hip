@@ -178,11 +178,11 @@ static int conv_common_checks(const char* who, int n, int d, int h, int w, int c
   return MEDNET_OK;
 }
 
-// Multi-channel first layer (Cin = 2, 3, 4; conv_cm_mfma.inc): 1 exactly for the calls mednet_conv3d_fwd gives to that kernel --
+// Multi-channel first layer (Cin = 2, 3, 4; conv_first_mfma.inc): 1 exactly for the calls mednet_conv3d_fwd gives to that kernel --
 // 3x3x3, no bias, fp32 x in EITHER layout, 16-bit channels-last y, Cout % 16 == 0, any algo but DIRECT, option conv_cm on.
 extern "C" int mednet_conv3d_cm_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int algo) {
   if (algo_base(algo) == MEDNET_ALGO_DIRECT || !is16(y_dtype) || !tuning_option("conv_cm", 1)) return 0;
-  return ELT_CALL(y_dtype, conv_cm_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, MEDNET_NDHWC, false) ? 1 : 0;
+  return cin >= 2 && ELT_CALL(y_dtype, conv_first_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, MEDNET_NDHWC, false) ? 1 : 0;
 }
 
 extern "C" int mednet_conv3d_fused_stats_chunks(int n, int d, int h, int w, int cin, int cout, int ksize, int x_dtype,
@@ -193,8 +193,9 @@ extern "C" int mednet_conv3d_fused_stats_chunks(int n, int d, int h, int w, int 
     if (conv_c1_x3_supported(cin, cout, ksize)) return tuning_option("x3_stats", 1) ? conv_c1_x3_stats_rows(d, h, w) : 0;
     return conv_x3_supported(cin, cout, ksize) && conv_x3_fits(d, h, w, cin) ? conv_x3_stats_rows(n, d, h, w, cout) : 0;
   }
-  if (ELT_CALL(y_dtype, conv_c1_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, MEDNET_NDHWC, false)) return ELT_CALL(y_dtype, conv_c1_stats_chunks, n, d, h, w, cout);
-  if (mednet_conv3d_cm_supported(cin, cout, ksize, x_dtype, y_dtype, algo)) return ELT_CALL(y_dtype, conv_cm_stats_chunks, n, d, h, w, cout);
+  if (cin == 1 ? ELT_CALL(y_dtype, conv_first_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, MEDNET_NDHWC, false)
+               : mednet_conv3d_cm_supported(cin, cout, ksize, x_dtype, y_dtype, algo))  // first layer: one channel, or 2 to 4
+    return ELT_CALL(y_dtype, conv_first_stats_chunks, n, d, h, w, cout);
   if (!ELT_CALL(y_dtype, conv_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, MEDNET_NDHWC, MEDNET_NDHWC, false)) return 0;
   return conv_mfma_stats_chunks(n, d, h, w, cin, cout, false, algo_split(algo, y_dtype));
 }
@@ -229,8 +230,8 @@ extern "C" int mednet_conv3d_fwd(const void* x, const void* packed, const float*
   // multi-channel first layer (2-4 input channels, read planar or channels-last where they lie): contraction over Cin x 27 taps
   if (!dgrad && !bias && y_layout == MEDNET_NDHWC && (x_layout == MEDNET_NDHWC || x_layout == MEDNET_NCDHW) &&
       mednet_conv3d_cm_supported(cin, cout, ksize, x_dtype, y_dtype, algo))
-    return ELT_CALL(y_dtype, launch_conv_cm_mfma, x, x_layout, (const float*)(base + L.f32_fwd), y, n, d, h, w, cin, cout, gn_partial, s,
-                    algo_split(algo, y_dtype) ? 1 : 0);
+    return ELT_CALL(y_dtype, launch_conv_first_mfma, x, x_layout, x_dtype, (const float*)(base + L.f32_fwd), y, n, d, h, w, cin, cout,
+                    gn_partial, s, algo_split(algo, y_dtype) ? 1 : 0);
   if (algo_base(algo) == MEDNET_ALGO_MFMA && !mfma_ok && !f32_mode)
     return fail(MEDNET_E_UNSUPPORTED, "conv3d_fwd: MFMA path does not take cin=%d cout=%d k=%d dtypes %d->%d", cin, cout,
                 ksize, x_dtype, y_dtype);
@@ -238,10 +239,10 @@ extern "C" int mednet_conv3d_fwd(const void* x, const void* packed, const float*
     return ELT_CALL(y_dtype, launch_conv_mfma, x, base + (dgrad ? L.mfma_bwd : L.mfma_fwd), y, n, d, h, w, cin, cout, x_dtype,
                     y_dtype, gn_partial, s, MEDNET_ACT_NONE, nullptr, algo_lo_delta(algo, y_dtype, L));
   // first layer (one input channel): contraction over the 27 taps on the matrix cores
-  if (!dgrad && algo_base(algo) != MEDNET_ALGO_DIRECT && x_layout == MEDNET_NDHWC &&
-      ELT_CALL(y_dtype, conv_c1_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, y_layout, bias != nullptr))
-    return ELT_CALL(y_dtype, launch_conv_c1_mfma, x, (const float*)(base + L.f32_fwd), y, n, d, h, w, cout, gn_partial, s, x_dtype,
-                    algo_split(algo, y_dtype) ? 1 : 0);
+  if (!dgrad && algo_base(algo) != MEDNET_ALGO_DIRECT && x_layout == MEDNET_NDHWC && cin == 1 &&
+      ELT_CALL(y_dtype, conv_first_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, y_layout, bias != nullptr))
+    return ELT_CALL(y_dtype, launch_conv_first_mfma, x, x_layout, x_dtype, (const float*)(base + L.f32_fwd), y, n, d, h, w, cin, cout,
+                    gn_partial, s, algo_split(algo, y_dtype) ? 1 : 0);
   // fp32 storage: the split-bf16 contraction ...
   if (f32_mode && (!algo_exact(algo) && conv_x3_enabled()) && L.mfma_bytes && conv_x3_supported(cin, cout, ksize) && conv_x3_fits(d, h, w, cin))
     return launch_conv_x3(x, base + (dgrad ? L.mfma_bwd : L.mfma_fwd), L.lo_delta, bias, y, n, d, h, w, cin, cout, gn_partial, s);

@@ -52,7 +52,7 @@ int launch_wgrad_c1_gn(const void* x, const void* dz, const void* y, const float
                        int n, int d, int h, int w, int cout, int x_dtype, int dtype, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_wgrad_c1(const void* x, const void* dy, float* dw, int n, int d, int h, int w, int cout, int x_dtype,
                     int dy_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool split_bf16 = false);
-// multi-channel first layer (Cin = 2, 3, 4): the matrix-core weight gradient of conv_cm_mfma.inc, plain and GroupNorm form
+// multi-channel first layer (Cin = 2, 3, 4): the matrix-core weight gradient of conv_first_mfma.inc, plain and GroupNorm form
 bool wgrad_cm_supported(int cin, int cout, int ksize, int x_dtype, int dy_dtype, int dy_layout);
 bool wgrad_cm_gn_supported(int cin, int cout, int x_dtype, int dtype);
 size_t wgrad_cm_ws_bytes(int n, int d, int h, int w, int cin, int cout);

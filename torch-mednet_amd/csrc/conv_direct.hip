@@ -1026,63 +1026,63 @@ bool wgrad_c1_supported(int cin, int cout, int ksize, int x_layout, int dy_layou
 static int wgrad_c1_blocks(int ntiles) { return ntiles < 1024 ? ntiles : 1024; }
 size_t wgrad_c1_ws_bytes(int n, int d, int h, int w, int cout) {
   const int nt = n * ((d + W1_TZ - 1) / W1_TZ) * ((h + W1_TY - 1) / W1_TY) * ((w + W1_TX - 1) / W1_TX);
-  const int b1 = wgrad_c1_blocks(nt), b2 = wgrad_c1_mfma_blocks(n, d, h, w);  // VALU and matrix-core forms
+  const int b1 = wgrad_c1_blocks(nt), b2 = wgrad_first_mfma_blocks(n, d, h, w, 1, cout, false);  // VALU and matrix-core forms
   return (size_t)(b1 > b2 ? b1 : b2) * 27 * cout * sizeof(float);
 }
-// The first layer's weight gradient with GroupNorm's backward applied while dz is staged (16-bit storage, matrix-core
-// kernel only): dy is never materialised.  See Wc1Args in conv_mfma.hip.
+// ---- the first layer's weight gradient on the matrix cores (Cin = 1 .. 4; conv_first_mfma.inc), 16-bit channels-last dy: the
+// kernel's partial blocks, then their reduction.  y != NULL: the GroupNorm form -- `dz` is the gradient of the layer's activated,
+// normalised output and GroupNorm's backward is applied while it is staged (WfirstArgs), so dy is never materialised -- else the
+// plain form with dz = dy.  `who` names the caller in the error texts.
+static bool is16_dt(int dt) { return dt == MEDNET_BF16 || dt == MEDNET_F16; }
+static bool wgrad_first_mfma_takes(int cin, int cout, int x_dtype, int dtype) {
+  return dtype == MEDNET_F16 ? mednet_f16::wgrad_first_mfma_supported(cin, cout, x_dtype, dtype) : wgrad_first_mfma_supported(cin, cout, x_dtype, dtype);
+}
+static int launch_wgrad_first(const char* who, const void* x, int x_layout, int x_dtype, const void* dz, const void* y, const float* coef,
+                              const float* bcoef, int act, float* dw, int n, int d, int h, int w, int cin, int cout, int dtype, void* ws,
+                              size_t ws_bytes, hipStream_t s) {
+  const int blocks = wgrad_first_mfma_blocks(n, d, h, w, cin, cout, y != nullptr);  // (one plan for both element types)
+  const size_t count = (size_t)27 * cin * cout;
+  MEDNET_REQUIRE(ws_bytes >= (size_t)blocks * count * sizeof(float), MEDNET_E_WORKSPACE, "%s: workspace too small", who);
+  float* part = (float*)ws;
+  const int rc = dtype == MEDNET_F16 ? mednet_f16::launch_wgrad_first_mfma(x, x_layout, x_dtype, dz, part, n, d, h, w, cin, cout, s, y, coef, bcoef, act)
+                                     : launch_wgrad_first_mfma(x, x_layout, x_dtype, dz, part, n, d, h, w, cin, cout, s, y, coef, bcoef, act);
+  if (rc) return rc;
+  hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, part, dw, count, blocks);
+  return check_launch(cin == 1 ? "wgrad_c1_reduce" : "wgrad_cm_reduce");
+}
+// one input channel, GroupNorm form (obeys option wgrad_c1_mfma)
 bool wgrad_c1_gn_supported(int cout, int x_dtype, int dtype) {
-  return tuning_option("wgrad_c1_mfma", 1) && (dtype == MEDNET_F16 ? mednet_f16::wgrad_c1_mfma_supported(cout, x_dtype, dtype)
-                                                                  : wgrad_c1_mfma_supported(cout, x_dtype, dtype));
+  return tuning_option("wgrad_c1_mfma", 1) && wgrad_first_mfma_takes(1, cout, x_dtype, dtype);
 }
 int launch_wgrad_c1_gn(const void* x, const void* dz, const void* y, const float* coef, const float* bcoef, int act, float* dw,
                        int n, int d, int h, int w, int cout, int x_dtype, int dtype, void* ws, size_t ws_bytes, hipStream_t s) {
   MEDNET_REQUIRE(wgrad_c1_gn_supported(cout, x_dtype, dtype), MEDNET_E_UNSUPPORTED,
                  "wgrad_c1_gn: Cout in {16, 32, 64}, 16-bit dz / y, x fp32 or the same 16-bit type (Cout=%d)", cout);
-  const int blocks = wgrad_c1_mfma_blocks(n, d, h, w);
-  MEDNET_REQUIRE(ws_bytes >= (size_t)blocks * 27 * cout * sizeof(float), MEDNET_E_WORKSPACE, "wgrad_c1_gn: workspace too small");
-  float* part = (float*)ws;
-  const int rc = dtype == MEDNET_F16 ? mednet_f16::launch_wgrad_c1_mfma(x, dz, part, n, d, h, w, cout, s, x_dtype, y, coef, bcoef, act)
-                                     : launch_wgrad_c1_mfma(x, dz, part, n, d, h, w, cout, s, x_dtype, y, coef, bcoef, act);
-  if (rc) return rc;
-  const size_t count = (size_t)27 * cout;
-  hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, part, dw, count, blocks);
-  return check_launch("wgrad_c1_reduce");
+  return launch_wgrad_first("wgrad_c1_gn", x, MEDNET_NDHWC, x_dtype, dz, y, coef, bcoef, act, dw, n, d, h, w, 1, cout, dtype, ws, ws_bytes, s);
 }
-// ---- multi-channel first layer (Cin = 2, 3, 4; conv_cm_mfma.inc): fp32 x in either layout, 16-bit channels-last dy.  Options
-// conv_cm (the whole path) and wgrad_c1_mfma (the matrix-core first-layer weight gradients) both have to be on.
-static bool is16_dt(int dt) { return dt == MEDNET_BF16 || dt == MEDNET_F16; }
+// 2 to 4 input channels: fp32 x in either layout.  Options conv_cm (the whole multi-channel path) and wgrad_c1_mfma (the
+// matrix-core first-layer weight gradients) both have to be on.
 bool wgrad_cm_supported(int cin, int cout, int ksize, int x_dtype, int dy_dtype, int dy_layout) {
   if (!tuning_option("conv_cm", 1) || !tuning_option("wgrad_c1_mfma", 1) || ksize != 3 || dy_layout != MEDNET_NDHWC || !is16_dt(dy_dtype)) return false;
-  return dy_dtype == MEDNET_F16 ? mednet_f16::wgrad_cm_mfma_supported(cin, cout, x_dtype, dy_dtype) : wgrad_cm_mfma_supported(cin, cout, x_dtype, dy_dtype);
+  return cin >= 2 && wgrad_first_mfma_takes(cin, cout, x_dtype, dy_dtype);
 }
 bool wgrad_cm_gn_supported(int cin, int cout, int x_dtype, int dtype) { return wgrad_cm_supported(cin, cout, 3, x_dtype, dtype, MEDNET_NDHWC); }
-size_t wgrad_cm_ws_bytes(int n, int d, int h, int w, int cin, int cout) {  // (one plan for both element types; the plain form has the most workgroups)
+size_t wgrad_cm_ws_bytes(int n, int d, int h, int w, int cin, int cout) {  // (the plain form has the most workgroups)
   if (cin < 2 || cin > 4 || cout % 16 || cout > 64) return 0;
-  return (size_t)wgrad_cm_mfma_blocks(n, d, h, w, cin, cout, false) * 27 * cin * cout * sizeof(float);
+  return (size_t)wgrad_first_mfma_blocks(n, d, h, w, cin, cout, false) * 27 * cin * cout * sizeof(float);
 }
 int wgrad_cm_plan(int n, int d, int h, int w, int cin, int cout, int dtype, bool gn, int* out4) {
-  MEDNET_REQUIRE(is16_dt(dtype) && wgrad_cm_mfma_supported(cin, cout, MEDNET_F32, MEDNET_BF16), MEDNET_E_UNSUPPORTED,
+  MEDNET_REQUIRE(is16_dt(dtype) && cin >= 2 && wgrad_first_mfma_supported(cin, cout, MEDNET_F32, MEDNET_BF16), MEDNET_E_UNSUPPORTED,
                  "wgrad_cm_plan: Cin in {2, 3, 4}, Cout in {16, 32, 48, 64}, 16-bit dy (cin=%d cout=%d dtype=%d)", cin, cout, dtype);
-  if (dtype == MEDNET_F16) mednet_f16::wgrad_cm_mfma_plan(n, d, h, w, cin, cout, gn, out4);
-  else wgrad_cm_mfma_plan(n, d, h, w, cin, cout, gn, out4);
+  wgrad_first_mfma_plan(n, d, h, w, cin, cout, gn, out4);  // (one plan for both element types)
   return MEDNET_OK;
 }
-// y != NULL: the GroupNorm form (dz, y, coef, bcoef as launch_wgrad_c1_gn), else the plain form with dz = dy
+// y != NULL: the GroupNorm form, else the plain form with dz = dy
 int launch_wgrad_cm(const void* x, int x_layout, const void* dz, const void* y, const float* coef, const float* bcoef, int act,
                     float* dw, int n, int d, int h, int w, int cin, int cout, int dtype, void* ws, size_t ws_bytes, hipStream_t s) {
   MEDNET_REQUIRE(wgrad_cm_supported(cin, cout, 3, MEDNET_F32, dtype, MEDNET_NDHWC), MEDNET_E_UNSUPPORTED,
                  "wgrad_cm: Cin in {2, 3, 4}, Cout in {16, 32, 48, 64}, fp32 x, 16-bit dy (cin=%d cout=%d)", cin, cout);
-  const bool gn = y != nullptr;
-  const int blocks = dtype == MEDNET_F16 ? mednet_f16::wgrad_cm_mfma_blocks(n, d, h, w, cin, cout, gn) : wgrad_cm_mfma_blocks(n, d, h, w, cin, cout, gn);
-  const size_t count = (size_t)27 * cin * cout;
-  MEDNET_REQUIRE(ws_bytes >= (size_t)blocks * count * sizeof(float), MEDNET_E_WORKSPACE, "wgrad_cm: workspace too small");
-  float* part = (float*)ws;
-  const int rc = dtype == MEDNET_F16 ? mednet_f16::launch_wgrad_cm_mfma(x, x_layout, dz, part, n, d, h, w, cin, cout, s, y, coef, bcoef, act)
-                                     : launch_wgrad_cm_mfma(x, x_layout, dz, part, n, d, h, w, cin, cout, s, y, coef, bcoef, act);
-  if (rc) return rc;
-  hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, part, dw, count, blocks);
-  return check_launch("wgrad_cm_reduce");
+  return launch_wgrad_first("wgrad_cm", x, x_layout, MEDNET_F32, dz, y, coef, bcoef, act, dw, n, d, h, w, cin, cout, dtype, ws, ws_bytes, s);
 }
 int launch_wgrad_c1(const void* x, const void* dy, float* dw, int n, int d, int h, int w, int cout, int x_dtype,
                     int dy_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool split_bf16) {
@@ -1091,8 +1091,6 @@ int launch_wgrad_c1(const void* x, const void* dy, float* dw, int n, int d, int 
   int blocks = wgrad_c1_blocks(nt);
   MEDNET_REQUIRE(ws_bytes >= (size_t)blocks * 27 * cout * sizeof(float), MEDNET_E_WORKSPACE, "wgrad_c1: workspace too small");
   float* part = (float*)ws;
-  const bool c1_mfma = dy_dtype == MEDNET_F16 ? mednet_f16::wgrad_c1_mfma_supported(cout, x_dtype, dy_dtype)
-                                              : wgrad_c1_mfma_supported(cout, x_dtype, dy_dtype);
   if (split_bf16 && tuning_option("wgrad_c1_x3", 1) && wgrad_c1_x3_supported(cout, x_dtype, dy_dtype)) {  // fp32 storage mode
     blocks = wgrad_c1_x3_blocks(n, d, h, w);
     MEDNET_REQUIRE(ws_bytes >= (size_t)blocks * 27 * cout * sizeof(float), MEDNET_E_WORKSPACE, "wgrad_c1: workspace too small");
@@ -1102,15 +1100,8 @@ int launch_wgrad_c1(const void* x, const void* dy, float* dw, int n, int d, int 
     hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, part, dw, count, blocks);
     return check_launch("wgrad_c1_reduce");
   }
-  if (tuning_option("wgrad_c1_mfma", 1) && c1_mfma) {  // matrix-core form (16-bit modes)
-    blocks = wgrad_c1_mfma_blocks(n, d, h, w);
-    int rc = dy_dtype == MEDNET_F16 ? mednet_f16::launch_wgrad_c1_mfma(x, dy, part, n, d, h, w, cout, s, x_dtype)
-                                    : launch_wgrad_c1_mfma(x, dy, part, n, d, h, w, cout, s, x_dtype);
-    if (rc) return rc;
-    const size_t count = (size_t)27 * cout;
-    hipLaunchKernelGGL(reduce_chunks_kernel, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, part, dw, count, blocks);
-    return check_launch("wgrad_c1_reduce");
-  }
+  if (tuning_option("wgrad_c1_mfma", 1) && wgrad_first_mfma_takes(1, cout, x_dtype, dy_dtype))  // matrix-core form (16-bit modes)
+    return launch_wgrad_first("wgrad_c1", x, MEDNET_NDHWC, x_dtype, dy, nullptr, nullptr, nullptr, 0, dw, n, d, h, w, 1, cout, dy_dtype, ws, ws_bytes, s);
 #define W1_GO(TX__, TDY__, CO__)                                                                                       \
   hipLaunchKernelGGL((wgrad_c1_kernel<TX__, TDY__, CO__>), dim3(blocks), dim3(256), 0, s, (const TX__*)x, (const TDY__*)dy, \
                      part, n, d, h, w, tz, ty, tx, nt)

@@ -1,40 +1,67 @@
-// Multi-channel first layer (Cin = 2, 3, 4): the Cin = 1 kernels of conv_mfma.hip with the contraction running over
-// Cin x (27 taps padded to 32).  Included by conv_mfma.hip inside namespace mednet, after the Cin = 1 weight gradient (so once
-// per element type).  DESIGN.md section 16.
+// The first layer (Cin = 1, 2, 3, 4) of the 16-bit modes on the matrix cores: forward with its fused GroupNorm pair sums, and the
+// weight gradient in its plain and GroupNorm form.  Included by conv_mfma.hip inside namespace mednet (so once per element type).
+// DESIGN.md sections 4 and 16.
 //
-// Forward:  y[v][co] = sum_ci sum_tap W[co][ci][tap] * x_ci[v + tap - 1]: 2 * Cin k-steps of MFMA_32x32x16, each with the elt
-// high and low part of the fp32 input (x = hi + lo to ~2^-17) and, under SPLIT, the weights' low part.  One halo brick per channel
-// in LDS, split into hi / lo where it is committed; the tap-offset table is the same for every channel.  The input is read where it
-// lies: element (v, ci) of a sample sits at v * sv + ci * sc -- planar N x C x D x H x W (sv = 1, sc = D H W) or channels-last
-// (sv = Cin, sc = 1) -- through a per-sample buffer resource; positions outside the volume get an out-of-range offset and come
-// back as zeros.  Epilogue, persistent walk, grid rule (conv_c1_grid) and the fused GroupNorm pair sums are those of
-// conv_c1_mfma_kernel: the partial rows are [n][rows][cout][2].  No atomics.
-struct CmArgs {
-  const float* x;     // N samples of Cin x D x H x W (planar) or D x H x W x Cin (channels-last), fp32
+// Forward:  y[v][co] = sum_ci sum_tap W[co][ci][tap] * x_ci[v + tap - 1].  With so few input channels the contraction index is
+// the TAP (27, padded to 32 = two MFMA k-steps) per channel: 2 * Cin k-steps of MFMA_32x32x16.  The B operand (k = tap, n = voxel)
+// is gathered from a halo brick of x in LDS -- 8 scalar LDS reads per fragment -- in its elt high and low parts (x = hi + lo to
+// ~2^-17), so the network input keeps fp32-level precision at 4 MFMAs per 32 voxels and channel; under SPLIT the weights' low part
+// is multiplied too.  The weights (Cin x 32 x 32 elt) live in registers for the kernel's lifetime.  The kernel is bound by writing
+// its output (32 channels per input voxel); the VALU formulation it replaced was 4x slower.
+// The input is read where it lies: element (v, ci) of a sample sits at v * sv + ci * sc -- planar N x C x D x H x W (sv = 1,
+// sc = D H W) or channels-last (sv = Cin, sc = 1) -- through a per-sample buffer resource; positions outside the volume get an
+// out-of-range offset and come back as zeros.  One channel may also arrive in the storage type (x16).
+// PERSISTENT (round 6).  With one short-lived workgroup per brick, 63 % of the instruction stream was per-brick fixed cost -- the
+// weight fragments and tap offsets (21 %) and the reduction of the 32 statistics sums over the wave (42 %) -- in a kernel that
+// is instruction-bound (252 us for 537 MB of output).  Now at most 4 workgroups per CU walk the (brick, channel block) items:
+// weights and offsets are made once, the next brick's halo values are in flight (registers) while the current brick is on the
+// matrix cores, and a wave keeps its sums over all its bricks of a sample: one partial row per wave, workgroup and sample.
+// The output is bit-identical to the one-brick-per-workgroup form (same MFMA sequence per voxel); option conv_c1_persist=0
+// launches a workgroup per item.  No atomics.
+struct FirstArgs {
+  const void* x;      // N samples of Cin x D x H x W (planar) or D x H x W x Cin (channels-last): fp32, or elt when x16
   const float* w;     // packed forward image Pf[tap][ci][co] (fp32)
   elt* y;             // NDHWC
-  float* gn_partial;  // nullable: [n][4 * gridDim.x / ncb][cout][2]
+  float* gn_partial;  // nullable: [n][4 * gridDim.x / ncb][cout][2] per-wave {sum y, sum y^2} of the stored values
   int n, d, h, w_, cout;
   int tiles_z, tiles_y, tiles_x, ntiles, ncb;
   unsigned rcp_tiles_x, rcp_tiles_y, rcp_tiles_z, rcp_ncb;
   unsigned sv4, sc4;  // byte strides of a voxel and of a channel inside one sample
   unsigned bytes_x;   // one sample of x, all channels
+  int x16;            // Cin = 1 only: x holds elt values (the 1-channel output of a GroupNorm in the 'gcr' orders), else fp32
 };
 
-// waves per SIMD (= workgroups of 256 per CU) the registers leave room for: the weights take 8 per channel, twice that under
-// SPLIT, and the halo values in flight 5 per channel -- 147 to 161 registers without SPLIT (three workgroups, 168 each; Cin = 2 spilled at the 128 of four), 183 and
-// 191 for SPLIT with Cin = 3, 4 (two).  DESIGN.md section 16 has the counts the compiler reports.
-constexpr int cm_fwd_waves(int cin, bool split) { return split && cin >= 3 ? 2 : 3; }
+// one element of x at byte `off` of a sample; the 16-bit form exists in the one-channel kernels only
+template <int CIN, typename Rsrc>
+__device__ __forceinline__ float first_load_x(Rsrc rsrc, unsigned off, int x16) {
+  if constexpr (CIN == 1) {
+    if (x16) {  // (workgroup-uniform) a 16-bit buffer load of the element, widened
+      const unsigned short raw = __builtin_amdgcn_raw_buffer_load_b16(rsrc, off, 0, 0);
+      return (float)__builtin_bit_cast(elt, raw);
+    }
+  }
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
+}
+
+// waves per SIMD (= workgroups of 256 per CU) the registers leave room for.  One channel: four (128 registers per lane; SPLIT is
+// compiled apart so that the default form keeps no registers for the weights' low parts).  More: the weights take 8 per channel,
+// twice that under SPLIT, and the halo values in flight 5 per channel -- 147 to 161 registers without SPLIT (three workgroups, 168
+// each; Cin = 2 spilled at the 128 of four), 183 and 191 for SPLIT with Cin = 3, 4 (two).  DESIGN.md section 16 has the counts the
+// compiler reports.
+constexpr int first_fwd_waves(int cin, bool split) { return cin == 1 ? 4 : split && cin >= 3 ? 2 : 3; }
 
 template <int CIN, bool SPLIT>
-__global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_kernel(CmArgs a) {
+__global__ __launch_bounds__(256, first_fwd_waves(CIN, SPLIT)) void conv_first_mfma_kernel(FirstArgs a) {
   constexpr int TZ = 4, TY = 8, TX = 16, HZ = TZ + 2, HY = TY + 2, HX = TX + 2, NV = HZ * HY * HX, NTW = 4;
   static_assert(NTW == TY / 2 && TZ == 4, "a wave owns one z-plane of the brick");
   constexpr int IN_ROUNDS = (NV + 255) / 256;
   constexpr unsigned OOB = 0xFFFFFF00u;
-  __shared__ elt xs_hi[CIN * NV], xs_lo[CIN * NV];              // one halo brick per channel, already split
+  // one halo brick per channel, ALREADY split into its elt high and low parts: every halo value feeds up to 27 taps, and split
+  // where it is gathered (round 1-5) the two conversions and the subtraction ran once per tap, tile and k-step
+  __shared__ elt xs_hi[CIN * NV], xs_lo[CIN * NV];
   __shared__ __attribute__((aligned(16))) elt epi[4 * 1024];  // per wave: one tile of 32 voxels x 32 channels on its way out
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
+  // items (brick, channel block) = item / ncb, item % ncb; gridDim.x is a multiple of ncb: a workgroup keeps its channel block
   const int cb = (int)(blockIdx.x % a.ncb);
   const int nitems = a.ntiles * a.ncb;
   // weights: A operand of k-step (ci, ks): lane (co = r, h) holds taps 16 ks + 8h .. + 7 of channel ci; taps >= 27 are 0
@@ -46,11 +73,13 @@ __global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_ke
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int tap = ks * 16 + 8 * h + j;
+        // (a 16-channel layer fills half a block)
         const float wf = tap < 27 && cb * 32 + r < a.cout ? a.w[((size_t)tap * CIN + ci) * a.cout + cb * 32 + r] : 0.f;
         wa[ci][ks][j] = (elt)wf;
         if constexpr (SPLIT) wl[ci][ks][j] = (elt)(wf - (float)wa[ci][ks][j]);
       }
-  int toff[2][8];  // LDS offsets of this lane's 8 taps per k-step (every channel's brick has the same shape)
+  // LDS offsets of this lane's 8 taps per k-step (every channel's brick has the same shape)
+  int toff[2][8];  // (both k-halves' offsets are compile-time constants: one select per entry instead of the divisions by 9 and 3)
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -59,7 +88,8 @@ __global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_ke
       const int o0 = t0 < 27 ? ((t0 / 9) * HY + (t0 / 3) % 3) * HX + t0 % 3 : 0, o1 = t1 < 27 ? ((t1 / 9) * HY + (t1 / 3) % 3) * HX + t1 % 3 : 0;
       toff[ks][j] = h ? o1 : o0;
     }
-  int hpos[IN_ROUNDS];  // this thread's halo positions: hz << 16 | hy << 8 | hx; slots past the halo fail every range check
+  // this thread's halo positions (the same for every brick): hz << 16 | hy << 8 | hx; slots past the halo fail every range check
+  int hpos[IN_ROUNDS];
 #pragma unroll
   for (int k = 0; k < IN_ROUNDS; ++k) {
     const int i = tid + 256 * k;
@@ -77,6 +107,7 @@ __global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_ke
     tz0 = (tt - qd * a.tiles_z) * TZ;
     n = qd;
   };
+  // halo values of a brick: buffer loads through a per-sample resource (no bytes at all for a brick that does not exist)
   float xin[CIN][IN_ROUNDS];
   auto fetch = [&](int item, bool valid) {
     int n, tz0, ty0, tx0;
@@ -89,8 +120,7 @@ __global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_ke
       const bool in_vol = ((unsigned)gz < (unsigned)a.d) & ((unsigned)gy < (unsigned)a.h) & ((unsigned)gx < (unsigned)a.w_);
       const unsigned off = (unsigned)((gz * a.h + gy) * a.w_ + gx) * a.sv4;
 #pragma unroll
-      for (int ci = 0; ci < CIN; ++ci)
-        xin[ci][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, in_vol ? off + ci * a.sc4 : OOB, 0, 0));
+      for (int ci = 0; ci < CIN; ++ci) xin[ci][k] = first_load_x<CIN>(rsrc, in_vol ? off + ci * a.sc4 : OOB, a.x16);
     }
   };
   auto commit = [&]() {
@@ -108,15 +138,18 @@ __global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_ke
     }
   };
   const size_t vol = (size_t)a.d * a.h * a.w_;
-  // fused GroupNorm statistics per channel PAIR from the stored rows, one partial row per wave, workgroup and sample (as in
-  // conv_c1_mfma_kernel)
+  // fused GroupNorm statistics, as in conv_mfma_kernel: per channel PAIR (v_dot2c_f32: two exact products + fp32 add per
+  // instruction), taken from the stored 64-byte rows -- lane = (voxel, 16-byte piece lane & 3) -- over the wave's tiles of a sample;
+  // entry 2j of the partial row gets the sums of channels 2j and 2j + 1, entry 2j + 1 is zero (GroupNorm only adds the channels of a
+  // group; the host asks for fused partials only when the channels per group are even).  Until round 6: 32 per-channel sums per
+  // lane from the accumulators, reduced over the wave once per BRICK -- 42 % of the kernel's instructions.
   typedef __attribute__((ext_vector_type(2))) elt eltx2;
   const eltx2 ones = {(elt)1.0f, (elt)1.0f};
   float gs[4], gq[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) gs[k] = gq[k] = 0.f;
   int acc_n = 0;
-  auto flush = [&](int nn) {
+  auto flush = [&](int nn) {  // one row per wave: sum over the 16 lanes that share a piece (DPP / v_permlane steps: plain VALU)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       gs[k] = lane_class_sum<4>(gs[k]);
@@ -153,10 +186,12 @@ __global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_ke
     commit();
     __syncthreads();
     fetch(has_next ? nitem : item, has_next);  // in flight while this brick is on the matrix cores
+    // (a rolled loop: unrolled inside the item loop, the compiler hoists the 4 x 16 gather addresses, which are the same for every
+    //  brick, out of it and spills 181 registers at the 128 that four workgroups per CU leave)
 #pragma unroll 1
     for (int t = 0; t < NTW; ++t) {
       const int g = wv * NTW + t;
-      const int lz = wv, ly = t * 2 + (r >> 4), lx = r & 15;
+      const int lz = wv, ly = t * 2 + (r >> 4), lx = r & 15;  // (N-tile g = wv * 4 + t: z-plane g / 4, rows 2 (g % 4), + 1)
       const int oz_t = tz0 + lz;
       const int base = (lz * HY + ly) * HX + lx;
       f32x16 acc;
@@ -176,9 +211,13 @@ __global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_ke
           acc = MEDNET_MFMA_32x32x16(wa[ci][ks], lo, acc, 0, 0, 0);
           if constexpr (SPLIT) acc = MEDNET_MFMA_32x32x16(wl[ci][ks], hi, acc, 0, 0, 0);
         }
-      // the tile leaves as whole 64-byte rows through 2 KB of LDS private to the wave (conv_c1_mfma_kernel's epilogue)
+      // The accumulator layout gives a lane four 8-byte pieces (channels 8q + 4h ..) of ITS voxel's 64-byte row: stored as they
+      // stand, one instruction touches 64 rows with 8 bytes each, and this kernel does little else than store.
+      // The tile goes through 2 KB of LDS private to the wave (8-byte pieces XOR-swizzled by voxel: conflict-free both ways, no
+      // barrier -- a wave's LDS operations execute in order, the fence keeps the compiler from reordering them) and leaves as whole
+      // rows: 4 lanes per voxel, 16 voxels = one x-row of the brick = 1 KB contiguous per instruction when Cout = 32.
       elt* tile_lds = epi + wv * 1024;
-      wave_lds_fence();
+      wave_lds_fence();  // (the previous tile's row reads stay above these writes)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         eltx4 o;
@@ -223,19 +262,44 @@ __global__ __launch_bounds__(256, cm_fwd_waves(CIN, SPLIT)) void conv_cm_mfma_ke
   }
 }
 
-bool conv_cm_mfma_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int y_layout, bool bias) {
-  return cin >= 2 && cin <= 4 && ksize == 3 && cout % 16 == 0 && x_dtype == MEDNET_F32 && y_dtype == ELT_DTYPE &&
-         y_layout == MEDNET_NDHWC && !bias;
+// One channel arrives as fp32 (the network input) or in the storage type, in either layout (they coincide); 2 to 4 as fp32.
+bool conv_first_mfma_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int y_layout, bool bias) {
+  return cin >= 1 && cin <= 4 && ksize == 3 && cout % 16 == 0 && (x_dtype == MEDNET_F32 || (cin == 1 && x_dtype == ELT_DTYPE)) &&
+         y_dtype == ELT_DTYPE && y_layout == MEDNET_NDHWC && !bias;
 }
-// the grid rule is the Cin = 1 kernel's (its brick and its items): 4 rows per workgroup of a channel block
-int conv_cm_grid(int n, int d, int h, int w, int cout) { return conv_c1_grid(n, d, h, w, cout); }
-int conv_cm_stats_chunks(int n, int d, int h, int w, int cout) { return 4 * (conv_c1_grid(n, d, h, w, cout) / ((cout + 31) / 32)); }
-int launch_conv_cm_mfma(const void* x, int x_layout, const float* w_pf, void* y, int n, int d, int h, int w, int cin, int cout,
-                        float* gn_partial, hipStream_t s, int split) {
-  MEDNET_REQUIRE(cin >= 2 && cin <= 4, MEDNET_E_UNSUPPORTED, "conv_cm_mfma: cin=%d (2, 3 or 4)", cin);
-  CmArgs a;
+// workgroups of a launch: 4, 3 or 2 per CU -- whichever leaves the last round of the walk fullest (the item count of config 5's
+// first layer, 14 400, is 14.06 rounds of 1024 workgroups: 15 rounds with the last one 6 % full, measured 6 % slower than 18.75
+// rounds of 768) -- rounded down to a multiple of the channel-block count so that a workgroup keeps its block; one per (brick,
+// channel block) item when there are no more items than that, or with option conv_c1_persist=0
+static int conv_c1_grid(int n, int d, int h, int w, int cout) {
+  const int ncb = (cout + 31) / 32;
+  const int nitems = n * ((d + 3) / 4) * ((h + 7) / 8) * ((w + 15) / 16) * ncb;
+  const int cus = ::mednet_internal_cu_count() > 0 ? ::mednet_internal_cu_count() : 256;
+  if (!tuning_option("conv_c1_persist", 1) || nitems <= 4 * cus) return nitems;
+  int best = 0;
+  double best_fill = 0.0;
+  for (int per_cu = 4; per_cu >= 2; --per_cu) {
+    const int g = per_cu * cus / ncb * ncb;
+    if (g <= 0) continue;
+    const double fill = (double)nitems / ((double)((nitems + g - 1) / g) * g);
+    if (fill > best_fill + 0.01) {  // (more workgroups per CU hide more latency: fewer only for a clearly fuller last round)
+      best = g;
+      best_fill = fill;
+    }
+  }
+  return best > 0 ? best : nitems;
+}
+// partial rows per sample: 4 (one per wave) per workgroup of a channel block
+int conv_first_stats_chunks(int n, int d, int h, int w, int cout) { return 4 * (conv_c1_grid(n, d, h, w, cout) / ((cout + 31) / 32)); }
+int launch_conv_first_mfma(const void* x, int x_layout, int x_dtype, const float* w_pf, void* y, int n, int d, int h, int w, int cin,
+                           int cout, float* gn_partial, hipStream_t s, int split) {
+  const char* who = cin == 1 ? "conv_c1_mfma" : "conv_cm_mfma";
+  MEDNET_REQUIRE(cin >= 1 && cin <= 4 && (cin == 1 || x_dtype == MEDNET_F32), MEDNET_E_UNSUPPORTED,
+                 "conv_first_mfma: cin=%d (1 to 4; 16-bit x with one channel only)", cin);
+  FirstArgs a;
   a.gn_partial = gn_partial;
-  a.x = (const float*)x;
+  a.x = x;
+  a.x16 = x_dtype != MEDNET_F32;
   a.w = w_pf;
   a.y = (elt*)y;
   a.n = n; a.d = d; a.h = h; a.w_ = w; a.cout = cout;
@@ -244,53 +308,61 @@ int launch_conv_cm_mfma(const void* x, int x_layout, const float* w_pf, void* y,
   a.tiles_x = (w + 15) / 16;
   a.ntiles = n * a.tiles_z * a.tiles_y * a.tiles_x;
   a.ncb = (cout + 31) / 32;
-  auto rcp = [](int dd) { return dd == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)dd - 1) / (unsigned)dd); };
-  a.rcp_tiles_x = rcp(a.tiles_x); a.rcp_tiles_y = rcp(a.tiles_y); a.rcp_tiles_z = rcp(a.tiles_z); a.rcp_ncb = rcp(a.ncb);
-  MEDNET_REQUIRE((double)a.ntiles * a.ncb * 1024.0 < 4294967296.0, MEDNET_E_UNSUPPORTED, "conv_cm_mfma: grid too large");
-  MEDNET_REQUIRE((double)d * h * w * cin * 4.0 < 4294960000.0, MEDNET_E_UNSUPPORTED, "conv_cm_mfma: one input sample must stay below 4 GB");
+  a.rcp_tiles_x = fastdiv_rcp(a.tiles_x); a.rcp_tiles_y = fastdiv_rcp(a.tiles_y); a.rcp_tiles_z = fastdiv_rcp(a.tiles_z); a.rcp_ncb = fastdiv_rcp(a.ncb);
+  MEDNET_REQUIRE((double)a.ntiles * a.ncb * 1024.0 < 4294967296.0, MEDNET_E_UNSUPPORTED, "%s: grid too large", who);
+  MEDNET_REQUIRE((double)d * h * w * cin * 4.0 < 4294960000.0, MEDNET_E_UNSUPPORTED, "%s: one input sample must stay below 4 GB", who);
   const size_t vol = (size_t)d * h * w;
-  a.bytes_x = (unsigned)(vol * cin * 4);
-  a.sv4 = x_layout == MEDNET_NCDHW ? 4u : 4u * (unsigned)cin;
-  a.sc4 = x_layout == MEDNET_NCDHW ? (unsigned)(vol * 4) : 4u;
+  const unsigned esz = a.x16 ? 2u : 4u;
+  a.bytes_x = (unsigned)(vol * cin * esz);
+  a.sv4 = x_layout == MEDNET_NCDHW ? esz : esz * (unsigned)cin;
+  a.sc4 = x_layout == MEDNET_NCDHW ? (unsigned)(vol * esz) : esz;
   const dim3 grid((unsigned)conv_c1_grid(n, d, h, w, cout));
-#define CM_GO(CIN_)                                                                           \
-  do {                                                                                        \
-    if (split) hipLaunchKernelGGL((conv_cm_mfma_kernel<CIN_, true>), grid, dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((conv_cm_mfma_kernel<CIN_, false>), grid, dim3(256), 0, s, a);      \
+#define FIRST_GO(CIN_)                                                                             \
+  do {                                                                                             \
+    if (split) hipLaunchKernelGGL((conv_first_mfma_kernel<CIN_, true>), grid, dim3(256), 0, s, a); \
+    else hipLaunchKernelGGL((conv_first_mfma_kernel<CIN_, false>), grid, dim3(256), 0, s, a);      \
   } while (0)
-  if (cin == 2) CM_GO(2);
-  else if (cin == 3) CM_GO(3);
-  else CM_GO(4);
-#undef CM_GO
-  return check_launch("conv_cm_mfma");
+  if (cin == 1) FIRST_GO(1);
+  else if (cin == 2) FIRST_GO(2);
+  else if (cin == 3) FIRST_GO(3);
+  else FIRST_GO(4);
+#undef FIRST_GO
+  return check_launch(who);
 }
 
 // ---- weight gradient: dW[co][ci][tap] = sum_v x_ci[v + tap - 1] * dy[v][co] ------------------------------------------------------
-// wgrad_c1_mfma_kernel with Cin accumulator tiles D_ci[tap (27 of 32 rows)][co]: the dy brick (in the GN form: dz and y, with
-// GroupNorm's backward applied while they are staged, expression for expression as there) is read from HBM once per launch and
-// staged once per brick; all Cin halo bricks of x (fp32 in LDS, split into elt hi + lo where they are gathered) are contracted
-// against the one B operand read from it.  One partial block [co][ci][27] per workgroup, then reduce_chunks_kernel.
-struct WcmArgs {
-  const float* x;  // as CmArgs::x
+//   D_ci[tap (27 of 32 rows)][co] += A_ci[tap][k = voxel] * B[k = voxel][co], one accumulator tile per input channel.
+// B comes from the dy brick in LDS through the transposing read (as in wgrad_mfma2); A is gathered from an fp32 halo brick of x_ci
+// (lane = tap row: 8 consecutive x-values of its shifted row) and split into elt hi + lo parts (two MFMAs), so the network input
+// keeps fp32-level precision.  The dy brick is read from HBM once per launch and staged once per brick; all Cin halo bricks of x
+// are contracted against the one B operand read from it.  The kernel is bound by reading dy (537 MB at config 2); the VALU kernel
+// it replaced (27 FMAs per voxel and channel) took 0.65 ms.  One partial block [co][ci][27] per workgroup, then reduce_chunks_kernel.
+struct WfirstArgs {
+  const void* x;   // as FirstArgs::x
   const elt* dy;   // N x D x H x W x cout
   float* part;     // [workgroup][cout][cin][27]
   int n, d, h, w, cout;
   int tiles_z, tiles_y, tiles_x, ntiles;
   unsigned rcp_tiles_x, rcp_tiles_y, rcp_tiles_z;
   unsigned sv4, sc4, bytes_x, bytes_dy;  // byte strides inside a sample of x; bytes per sample
-  const elt* y;        // GN form (see Wc1Args)
+  int x16;                               // as FirstArgs::x16
+  // GN form: `dy` holds dz (the gradient of the layer's activated, normalised output) and the kernel applies GroupNorm's
+  // backward while it stages:  dy = k1 * dz * act'(ca * y + cb) + k2 * y + k3, rounded to elt -- the value
+  // norm_act.hip's gn_bwd_apply_kernel would have stored, expression for expression -- so dy is never written or re-read
+  const elt* y;        // N x D x H x W x cout: the convolution's output
   const float* coef;   // [n][cout][2] = {ca, cb}
   const float* bcoef;  // [n][cout][3] = {k1, k2, k3}
   int act;
 };
 
-// Cin * NB accumulator tiles of 16 registers: up to 4 of them beside the staging registers at two workgroups per CU, more only
-// at one (512 registers per lane; the LDS of Cin = 4, NB = 2 -- 81 KB -- allows one anyway)
-// (the GN form stages dz and y: 64 NB registers in flight instead of 32 NB, so its Cin = 2, NB = 2 form needs the 512 too)
-constexpr int wcm_waves(int cin, int nb, bool gn) { return cin * nb > 4 || (gn && nb == 2) ? 1 : 2; }
+// workgroups per CU.  One channel: two in every form.  More: Cin * NB accumulator tiles of 16 registers, up to 4 of them beside
+// the staging registers at two workgroups per CU, more only at one (512 registers per lane; the LDS of Cin = 4, NB = 2 -- 81 KB --
+// allows one anyway); the GN form stages dz and y, 64 NB registers in flight instead of 32 NB, so its Cin = 2, NB = 2 form needs
+// the 512 too.  (At two, <1, 2, GN> spills 17 registers: DESIGN.md section 16.)
+constexpr int wfirst_waves(int cin, int nb, bool gn) { return cin == 1 ? 2 : cin * nb > 4 || (gn && nb == 2) ? 1 : 2; }
 
-template <int CIN, int NB, bool GN>
-__global__ __launch_bounds__(256, wcm_waves(CIN, NB, GN)) void wgrad_cm_mfma_kernel(WcmArgs a) {
+template <int CIN, int NB, bool GN>  // NB: 32-channel blocks of dy
+__global__ __launch_bounds__(256, wfirst_waves(CIN, NB, GN)) void wgrad_first_mfma_kernel(WfirstArgs a) {
   constexpr int TZ = 4, TY = 8, TX = 16, HZ = TZ + 2, HY = TY + 2, HX = TX + 2;
   constexpr int NJ = TZ * TY * TX, NH = HZ * HY * HX;
   constexpr int ROWB = 64 * NB;                         // bytes of one voxel row of dy in LDS
@@ -314,6 +386,7 @@ __global__ __launch_bounds__(256, wcm_waves(CIN, NB, GN)) void wgrad_cm_mfma_ker
   u32x4 rdy[DY_ROUNDS];
   u32x4 ryy[GN ? DY_ROUNDS : 1];
   float rx[CIN][X_ROUNDS];
+  // GN form: this thread's 8 channels are the same in every round (256 % (4 * NB) == 0)
   float gca[GN ? 8 : 1], gcb[GN ? 8 : 1], gk1[GN ? 8 : 1], gk2[GN ? 8 : 1], gk3[GN ? 8 : 1];
   unsigned in_mask = 0;  // bit `it`: round `it` of the fetched brick lies inside the volume
   int coef_n = -1;       // sample the coefficients in registers belong to
@@ -370,8 +443,7 @@ __global__ __launch_bounds__(256, wcm_waves(CIN, NB, GN)) void wgrad_cm_mfma_ker
       const bool in_vol = (v < NH) & ((unsigned)gz < (unsigned)a.d) & ((unsigned)gy < (unsigned)a.h) & ((unsigned)gx < (unsigned)a.w);
       const unsigned off = (unsigned)((gz * a.h + gy) * a.w + gx) * a.sv4;
 #pragma unroll
-      for (int ci = 0; ci < CIN; ++ci)
-        rx[ci][it] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX, in_vol ? off + ci * a.sc4 : OOB, 0, 0));
+      for (int ci = 0; ci < CIN; ++ci) rx[ci][it] = first_load_x<CIN>(rX, in_vol ? off + ci * a.sc4 : OOB, a.x16);
     }
   };
   auto commit = [&]() {
@@ -470,74 +542,81 @@ __global__ __launch_bounds__(256, wcm_waves(CIN, NB, GN)) void wgrad_cm_mfma_ker
   }
 }
 
-bool wgrad_cm_mfma_supported(int cin, int cout, int x_dtype, int dy_dtype) {
-  return cin >= 2 && cin <= 4 && cout % 16 == 0 && cout <= 64 && x_dtype == MEDNET_F32 && dy_dtype == ELT_DTYPE;
+// One channel: Cout in {16, 32, 64}, x fp32 or in the storage type.  2 to 4: Cout a multiple of 16 up to 64, fp32 x.
+bool wgrad_first_mfma_supported(int cin, int cout, int x_dtype, int dy_dtype) {
+  if (dy_dtype != ELT_DTYPE) return false;
+  if (cin == 1) return (cout == 16 || cout == 32 || cout == 64) && (x_dtype == MEDNET_F32 || x_dtype == ELT_DTYPE);
+  return cin >= 2 && cin <= 4 && cout % 16 == 0 && cout <= 64 && x_dtype == MEDNET_F32;
 }
 // out4 = {workgroups, NB (32-channel blocks per workgroup), workgroups per CU the kernel is built for, dynamic LDS bytes}
-void wgrad_cm_mfma_plan(int n, int d, int h, int w, int cin, int cout, bool gn, int* out4) {
+void wgrad_first_mfma_plan(int n, int d, int h, int w, int cin, int cout, bool gn, int* out4) {
   const int nt = n * ((d + 3) / 4) * ((h + 7) / 8) * ((w + 15) / 16);
   const int nb = (cout + 31) / 32;
-  const int per_cu = wcm_waves(cin, nb, gn);
-  const int cap = 512 * per_cu;  // two rounds of resident workgroups on 256 CUs, as the Cin = 1 kernel's 1024
+  const int per_cu = wfirst_waves(cin, nb, gn);
+  const int cap = 512 * per_cu;  // two rounds of resident workgroups on 256 CUs
   const size_t stage = (size_t)cin * 4352 + (size_t)512 * 64 * nb, red = (size_t)4 * nb * 16 * 64 * 4;
   out4[0] = nt < cap ? nt : cap;
   out4[1] = nb;
   out4[2] = per_cu;
   out4[3] = (int)(stage > red ? stage : red);
 }
-int wgrad_cm_mfma_blocks(int n, int d, int h, int w, int cin, int cout, bool gn) {
+int wgrad_first_mfma_blocks(int n, int d, int h, int w, int cin, int cout, bool gn) {
   int p[4];
-  wgrad_cm_mfma_plan(n, d, h, w, cin, cout, gn, p);
+  wgrad_first_mfma_plan(n, d, h, w, cin, cout, gn, p);
   return p[0];
 }
-int launch_wgrad_cm_mfma(const void* x, int x_layout, const void* dy, float* part, int n, int d, int h, int w, int cin, int cout,
-                         hipStream_t s, const void* gn_y, const float* gn_coef, const float* gn_bcoef, int gn_act) {
-  WcmArgs a;
-  const bool gn = gn_y != nullptr;
-  MEDNET_REQUIRE(cin >= 2 && cin <= 4 && cout % 16 == 0 && cout <= 64, MEDNET_E_UNSUPPORTED, "wgrad_cm_mfma: cin=%d cout=%d", cin, cout);
-  MEDNET_REQUIRE(!gn || (gn_coef && gn_bcoef), MEDNET_E_SHAPE, "wgrad_cm_mfma: the GroupNorm form needs both coefficient tables");
+int launch_wgrad_first_mfma(const void* x, int x_layout, int x_dtype, const void* dy, float* part, int n, int d, int h, int w, int cin,
+                            int cout, hipStream_t s, const void* gn_y, const float* gn_coef, const float* gn_bcoef, int gn_act) {
+  const char* who = cin == 1 ? "wgrad_c1_mfma" : "wgrad_cm_mfma";
+  WfirstArgs a;
+  const bool gn = gn_y != nullptr;  // dy is dz: GroupNorm's backward applied while staging (WfirstArgs)
+  MEDNET_REQUIRE(cin >= 1 && cin <= 4 && cout % 16 == 0 && cout <= 64 && (cin == 1 || x_dtype == MEDNET_F32), MEDNET_E_UNSUPPORTED,
+                 "%s: cin=%d cout=%d", who, cin, cout);
+  MEDNET_REQUIRE(!gn || (gn_coef && gn_bcoef), MEDNET_E_SHAPE, "%s: the GroupNorm form needs both coefficient tables", who);
   a.y = (const elt*)gn_y; a.coef = gn_coef; a.bcoef = gn_bcoef; a.act = gn_act;
-  a.x = (const float*)x;
+  a.x = x;
+  a.x16 = x_dtype != MEDNET_F32;
   a.dy = (const elt*)dy;
   a.part = part;
   a.n = n; a.d = d; a.h = h; a.w = w; a.cout = cout;
   a.tiles_z = (d + 3) / 4; a.tiles_y = (h + 7) / 8; a.tiles_x = (w + 15) / 16;
   a.ntiles = n * a.tiles_z * a.tiles_y * a.tiles_x;
-  auto rcp = [](int dd) { return dd == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)dd - 1) / (unsigned)dd); };
-  a.rcp_tiles_x = rcp(a.tiles_x); a.rcp_tiles_y = rcp(a.tiles_y); a.rcp_tiles_z = rcp(a.tiles_z);
+  a.rcp_tiles_x = fastdiv_rcp(a.tiles_x); a.rcp_tiles_y = fastdiv_rcp(a.tiles_y); a.rcp_tiles_z = fastdiv_rcp(a.tiles_z);
   MEDNET_REQUIRE((double)d * h * w * cout * 2.0 < 4294960000.0 && (double)d * h * w * cin * 4.0 < 4294960000.0, MEDNET_E_UNSUPPORTED,
-                 "wgrad_cm_mfma: one sample must stay below 4 GB");
+                 "%s: one sample must stay below 4 GB", who);
   const size_t vol = (size_t)d * h * w;
-  a.bytes_x = (unsigned)(vol * cin * 4);
+  const unsigned esz = a.x16 ? 2u : 4u;
+  a.bytes_x = (unsigned)(vol * cin * esz);
   a.bytes_dy = (unsigned)(vol * cout * 2);
-  a.sv4 = x_layout == MEDNET_NCDHW ? 4u : 4u * (unsigned)cin;
-  a.sc4 = x_layout == MEDNET_NCDHW ? (unsigned)(vol * 4) : 4u;
+  a.sv4 = x_layout == MEDNET_NCDHW ? esz : esz * (unsigned)cin;
+  a.sc4 = x_layout == MEDNET_NCDHW ? (unsigned)(vol * esz) : esz;
   int plan[4];
-  wgrad_cm_mfma_plan(n, d, h, w, cin, cout, gn, plan);
+  wgrad_first_mfma_plan(n, d, h, w, cin, cout, gn, plan);
   const int blocks = plan[0], nb = plan[1];
   const size_t lds = (size_t)plan[3];
-  static bool attr_set[3][2][2] = {};
-#define WCM_GO(CIN_, NB_, GN_)                                                                                                  \
-  do {                                                                                                                          \
-    if (lds > 48 * 1024 && !attr_set[CIN_ - 2][NB_ - 1][GN_]) {                                                                 \
-      if (hipFuncSetAttribute((const void*)wgrad_cm_mfma_kernel<CIN_, NB_, GN_>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                              (int)lds) != hipSuccess)                                                                          \
-        return fail(MEDNET_E_HIP, "wgrad_cm_mfma: cannot raise dynamic LDS to %zu", lds);                                       \
-      attr_set[CIN_ - 2][NB_ - 1][GN_] = true;                                                                                  \
-    }                                                                                                                           \
-    hipLaunchKernelGGL((wgrad_cm_mfma_kernel<CIN_, NB_, GN_>), dim3(blocks), dim3(256), lds, s, a);                             \
+  static bool attr_set[4][2][2] = {};  // (once per process and instantiation)
+#define WFIRST_GO(CIN_, NB_, GN_)                                                                                                 \
+  do {                                                                                                                            \
+    if (lds > 48 * 1024 && !attr_set[CIN_ - 1][NB_ - 1][GN_]) {                                                                   \
+      if (hipFuncSetAttribute((const void*)wgrad_first_mfma_kernel<CIN_, NB_, GN_>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                              (int)lds) != hipSuccess)                                                                            \
+        return fail(MEDNET_E_HIP, "%s: cannot raise dynamic LDS to %zu", who, lds);                                               \
+      attr_set[CIN_ - 1][NB_ - 1][GN_] = true;                                                                                    \
+    }                                                                                                                             \
+    hipLaunchKernelGGL((wgrad_first_mfma_kernel<CIN_, NB_, GN_>), dim3(blocks), dim3(256), lds, s, a);                            \
   } while (0)
-#define WCM_NB(CIN_)                        \
-  do {                                      \
-    if (nb == 1 && gn) WCM_GO(CIN_, 1, true);       \
-    else if (nb == 1) WCM_GO(CIN_, 1, false);       \
-    else if (gn) WCM_GO(CIN_, 2, true);             \
-    else WCM_GO(CIN_, 2, false);                    \
+#define WFIRST_NB(CIN_)                          \
+  do {                                           \
+    if (nb == 1 && gn) WFIRST_GO(CIN_, 1, true); \
+    else if (nb == 1) WFIRST_GO(CIN_, 1, false); \
+    else if (gn) WFIRST_GO(CIN_, 2, true);       \
+    else WFIRST_GO(CIN_, 2, false);              \
   } while (0)
-  if (cin == 2) WCM_NB(2);
-  else if (cin == 3) WCM_NB(3);
-  else WCM_NB(4);
-#undef WCM_NB
-#undef WCM_GO
-  return check_launch("wgrad_cm_mfma");
+  if (cin == 1) WFIRST_NB(1);
+  else if (cin == 2) WFIRST_NB(2);
+  else if (cin == 3) WFIRST_NB(3);
+  else WFIRST_NB(4);
+#undef WFIRST_NB
+#undef WFIRST_GO
+  return check_launch(who);
 }

@@ -43,10 +43,6 @@ int wgrad_mfma_plan(int n, int d, int h, int w, int cin, int cout, int workgroup
 size_t wgrad_mfma_ws_bytes(int n, int d, int h, int w, int cin, int cout, int ksize, int workgroups);
 int launch_wgrad_mfma(const void* x, const void* dy, float* dw, int n, int d, int h, int w, int cin, int cout, int dtype,
                       void* ws, size_t ws_bytes, hipStream_t s, int workgroups);
-bool conv_c1_mfma_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int y_layout, bool bias);
-int conv_c1_stats_chunks(int n, int d, int h, int w, int cout);
-int launch_conv_c1_mfma(const void* x, const float* w_pt, void* y, int n, int d, int h, int w, int cout, float* gn_partial,
-                        hipStream_t s, int x_dtype = MEDNET_F32, int split = 0);
 int launch_convt_fwd_mfma(const void* x, const void* sec, const float* bias, const void* skip, void* y, int n, int d,
                           int h, int w, int cin, int cout, hipStream_t s, size_t lo_delta = 0);
 int launch_convt_dgrad_mfma(const void* dy, const void* packed_section, void* dx, int n, int d, int h, int w, int cin,
@@ -58,24 +54,19 @@ size_t convt_wgrad_mfma_ws_bytes(int n, int d, int h, int w, int cin, int cout, 
 int launch_convt_wgrad_mfma(const void* x, const void* dy, float* dw, int n, int d, int h, int w, int cin, int cout,
                             void* ws, size_t ws_bytes, hipStream_t s, int workgroups);
 
-bool wgrad_c1_mfma_supported(int cout, int x_dtype, int dy_dtype);
-int wgrad_c1_mfma_blocks(int n, int d, int h, int w);
+// conv_first_mfma.inc: the first layer (Cin = 1 .. 4; x fp32, planar or channels-last by `x_layout`, or with one channel in the
+// storage type)
+bool conv_first_mfma_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int y_layout, bool bias);
+int conv_first_stats_chunks(int n, int d, int h, int w, int cout);
+int launch_conv_first_mfma(const void* x, int x_layout, int x_dtype, const float* w_pf, void* y, int n, int d, int h, int w, int cin,
+                           int cout, float* gn_partial, hipStream_t s, int split = 0);
+bool wgrad_first_mfma_supported(int cin, int cout, int x_dtype, int dy_dtype);
+void wgrad_first_mfma_plan(int n, int d, int h, int w, int cin, int cout, bool gn, int* out4);  // {workgroups, NB, workgroups per CU, LDS bytes}
+int wgrad_first_mfma_blocks(int n, int d, int h, int w, int cin, int cout, bool gn);  // (the plain form never has fewer)
 // gn_y != NULL: `dy` is dz and GroupNorm's backward (coefficient tables [n][cout][2] and [n][cout][3]) is applied on the way in
-int launch_wgrad_c1_mfma(const void* x, const void* dy, float* part, int n, int d, int h, int w, int cout, hipStream_t s,
-                         int x_dtype = MEDNET_F32, const void* gn_y = nullptr, const float* gn_coef = nullptr,
-                         const float* gn_bcoef = nullptr, int gn_act = 0);
-// conv_cm_mfma.inc: the multi-channel first layer (Cin = 2, 3, 4; fp32 x, planar or channels-last by `x_layout`)
-bool conv_cm_mfma_supported(int cin, int cout, int ksize, int x_dtype, int y_dtype, int y_layout, bool bias);
-int conv_cm_grid(int n, int d, int h, int w, int cout);
-int conv_cm_stats_chunks(int n, int d, int h, int w, int cout);
-int launch_conv_cm_mfma(const void* x, int x_layout, const float* w_pf, void* y, int n, int d, int h, int w, int cin, int cout,
-                        float* gn_partial, hipStream_t s, int split = 0);
-bool wgrad_cm_mfma_supported(int cin, int cout, int x_dtype, int dy_dtype);
-void wgrad_cm_mfma_plan(int n, int d, int h, int w, int cin, int cout, bool gn, int* out4);  // {workgroups, NB, workgroups per CU, LDS bytes}
-int wgrad_cm_mfma_blocks(int n, int d, int h, int w, int cin, int cout, bool gn);  // (the plain form never has fewer)
-int launch_wgrad_cm_mfma(const void* x, int x_layout, const void* dy, float* part, int n, int d, int h, int w, int cin, int cout,
-                         hipStream_t s, const void* gn_y = nullptr, const float* gn_coef = nullptr, const float* gn_bcoef = nullptr,
-                         int gn_act = 0);
+int launch_wgrad_first_mfma(const void* x, int x_layout, int x_dtype, const void* dy, float* part, int n, int d, int h, int w, int cin,
+                            int cout, hipStream_t s, const void* gn_y = nullptr, const float* gn_coef = nullptr,
+                            const float* gn_bcoef = nullptr, int gn_act = 0);
 
 // head_mfma.hip: the landmark head (1x1x1 conv 32 -> nh heat maps + ncls classes) fused with its two losses, matrix-core form
 bool head_lm_supported(int cin, int nh, int ncls, int dtype, size_t spatial);

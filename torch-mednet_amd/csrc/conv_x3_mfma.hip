@@ -1101,7 +1101,7 @@ size_t wgrad_x3_ws_bytes(int n, int d, int h, int w, int cin, int cout, int work
 
 // ---- first-layer weight gradient (Cin = 1) of the fp32 storage mode ------------------------------------------------------
 //   dW[co][tap] = sum_v x[v + tap - 1] * dy[v][co]:  D[tap (27 of 32 rows)][co] += A[tap][k = voxel] * B[k = voxel][co],
-// as wgrad_c1_mfma_kernel (conv_mfma.hip) with both operands split: A gathered from the fp32 halo brick of x (lane = tap row: 8
+// as wgrad_first_mfma_kernel (conv_first_mfma.inc) with both operands split: A gathered from the fp32 halo brick of x (lane = tap row: 8
 // x-consecutive values of its shifted row), B = the fp32 dy brick committed to a high and a low bf16 plane and read through the
 // transposing LDS read.  Bound by reading dy once (1.07 GB at config 2); the VALU kernel it replaces took 0.49 ms.
 struct Wc1X3Args {
