@@ -465,6 +465,34 @@ int mednet_head_landmark_cls_bwd(const void* z, const void* packed, const float*
                                  int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int nh,
                                  int ncls, int kind, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
                                  size_t ws_bytes, mednet_stream stream);
+/* The segmentation head for 5 .. 16 classes (SegmentationNet, segmentation.py:30-31, 58-62: final_conv 32 -> ncls) fused with its
+ * loss on the matrix cores, 16-bit storage only.  Additive to ABI 3; mednet_head_dice_* / mednet_head_ce_* (<= 4 classes) are
+ * unchanged.  class_kind MEDNET_CLASS_DICE: DiceLoss (loss.py:114-130: class weight in the numerator, eps, sigmoid | softmax,
+ * ignore_index on the one-hot target); MEDNET_CLASS_CE: nn.CrossEntropyLoss(weight, ignore_index) (softmax: sigmoid must be 0).
+ * z: N x spatial x cin (NDHWC); labels: MEDNET_U8, N x spatial, sample stride label_stride_n, base pointer and stride multiples
+ * of 4 bytes; `packed` = the head's mednet_conv3d_pack image (its fp32 [co][ci] block, split hi + lo for the MFMAs).
+ * _fwd writes loss and saved (Dice: [ncls][2] = {I, D}; CE: saved[0] = sum w_y, saved holds 2 floats), both required, and the
+ * logits (N x ncls x spatial fp32, planar) only if `logits` != NULL.
+ * A label >= ncls that is not ignore_index makes the loss NaN.
+ * _bwd rebuilds the logits with the same instructions, forms their gradient in registers (closed forms of mednet_dice_bwd /
+ * mednet_ce_bwd) and writes dz (N x spatial x cin, storage type), dw [ncls][cin], dbias (nullable) and -- gn_y and gn_partial,
+ * which go together -- gn_partial[n][rows][cin][2] = {sum du, sum du * gn_y}, du = dz * act'(z), rows =
+ * mednet_head_seg_gn_rows(spatial) = ceil(ceil(spatial / 128) / 64), for mednet_gn_act_bwd_fused_res.
+ * Workspace: mednet_head_seg_ws_bytes(n, spatial, ncls) for both calls (n * rows rows of 32 * 33 floats in the backward).
+ * _supported: cin == 32, 5 <= ncls <= 16, dtype MEDNET_BF16 | MEDNET_F16, label_dtype MEDNET_U8, spatial % 4 == 0, tuning option
+ * head_seg_mfma != 0.  Results equal the unfused launches (mednet_conv3d_fwd k=1, mednet_dice_* / mednet_ce_*,
+ * mednet_head_dgrad_gn, mednet_conv3d_wgrad k=1) up to fp32 summation order; every sum is made in a fixed order. */
+int mednet_head_seg_supported(int cin, int ncls, int dtype, int label_dtype, size_t spatial);
+size_t mednet_head_seg_ws_bytes(int n, size_t spatial, int ncls);
+int mednet_head_seg_gn_rows(size_t spatial);
+int mednet_head_seg_fwd(const void* z, const void* packed, const float* bias, const void* labels, int64_t label_stride_n,
+                        const float* class_weight, float* logits, float* loss, float* saved, int n, size_t spatial, int cin,
+                        int ncls, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
+                        mednet_stream stream);
+int mednet_head_seg_bwd(const void* z, const void* packed, const float* bias, const void* labels, int64_t label_stride_n,
+                        const float* class_weight, const float* saved, const float* dloss, void* dz, const void* gn_y, int gn_act,
+                        float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int ncls, int class_kind,
+                        float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
 /* nn.CrossEntropyLoss(weight)  segmentation.py:49: sum w_y * -log softmax_y / sum w_y.  saved[0] = sum w_y. */
 int mednet_ce_fwd(const float* logits, const int64_t* labels, const float* weight, float* loss, float* saved,
                   int n, int c, size_t spatial, int64_t stride_n, int64_t stride_c, int ignore_index, void* ws,

@@ -577,6 +577,54 @@ extern "C" int mednet_head_landmark_cls_bwd(const void* z, const void* packed, c
                   ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- the segmentation head for 5 .. 16 classes fused with Dice or cross-entropy (head_mfma.hip, head_seg_kernel) ----------
+extern "C" int mednet_head_seg_supported(int cin, int ncls, int dtype, int label_dtype, size_t spatial) {
+  return is16(dtype) && label_dtype == MEDNET_U8 && ELT_CALL(dtype, head_seg_supported, cin, ncls, dtype, spatial) ? 1 : 0;
+}
+extern "C" size_t mednet_head_seg_ws_bytes(int n, size_t spatial, int ncls) { return head_seg_ws_bytes(n, spatial, ncls); }
+extern "C" int mednet_head_seg_gn_rows(size_t spatial) { return head_lm_chunks(spatial); }
+extern "C" int mednet_head_seg_fwd(const void* z, const void* packed, const float* bias, const void* labels, int64_t label_stride_n,
+                                   const float* class_weight, float* logits, float* loss, float* saved, int n, size_t spatial, int cin,
+                                   int ncls, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
+                                   size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED,
+                 "head_seg_fwd: class-loss kind %d", class_kind);
+  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED, "head_seg_fwd: cross-entropy is a softmax form");
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && loss && saved && ws, MEDNET_E_SHAPE, "head_seg_fwd: bad arguments");
+  MEDNET_REQUIRE(mednet_head_seg_supported(cin, ncls, z_dtype, MEDNET_U8, spatial), MEDNET_E_UNSUPPORTED,
+                 "head_seg_fwd: %d -> %d classes, dtype %d, %zu voxels", cin, ncls, z_dtype, spatial);
+  MEDNET_REQUIRE(ws_bytes >= head_seg_ws_bytes(n, spatial, ncls), MEDNET_E_WORKSPACE, "head_seg_fwd: workspace too small");
+  const PackLayout L = pack_layout(cin, ncls, 1);
+  const float* W = (const float*)((const char*)packed + L.f32_bwd);  // [co][ci]
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = head_lm_chunks(spatial);
+  const int ce = class_kind == MEDNET_CLASS_CE;
+  float* partial = (float*)ws;
+  int rc = ELT_CALL(z_dtype, launch_head_seg_fwd, z, W, bias, labels, label_stride_n, class_weight, logits, partial, n, spatial, ncls,
+                    ce, sigmoid, ignore_index, s);
+  if (rc) return rc;
+  if (ce) return launch_ce_finalize(partial, loss, saved, n * chunks, s);
+  return launch_dice_finalize(partial, class_weight, loss, saved, ncls, n * chunks, eps, s);
+}
+extern "C" int mednet_head_seg_bwd(const void* z, const void* packed, const float* bias, const void* labels, int64_t label_stride_n,
+                                   const float* class_weight, const float* saved, const float* dloss, void* dz, const void* gn_y,
+                                   int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int ncls,
+                                   int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
+                                   mednet_stream stream) {
+  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED,
+                 "head_seg_bwd: class-loss kind %d", class_kind);
+  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED, "head_seg_bwd: cross-entropy is a softmax form");
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && saved && dloss && dz && dw && ws, MEDNET_E_SHAPE,
+                 "head_seg_bwd: bad arguments");
+  MEDNET_REQUIRE(mednet_head_seg_supported(cin, ncls, z_dtype, MEDNET_U8, spatial), MEDNET_E_UNSUPPORTED,
+                 "head_seg_bwd: %d -> %d classes, dtype %d, %zu voxels", cin, ncls, z_dtype, spatial);
+  const PackLayout L = pack_layout(cin, ncls, 1);
+  const float* W = (const float*)((const char*)packed + L.f32_bwd);
+  return ELT_CALL(z_dtype, launch_head_seg_bwd, z, W, bias, labels, label_stride_n, saved, class_weight, dloss, eps, dz, gn_y, gn_act,
+                  gn_partial, dw, dbias, n, spatial, ncls, class_kind == MEDNET_CLASS_CE, sigmoid, ignore_index, ws, ws_bytes,
+                  (hipStream_t)stream);
+}
+
 extern "C" int mednet_conv3d_dgrad_gn_rows(int n, int d, int h, int w, int cin, int cout, int algo) {
   if (!tuning_option("conv_fuse_gnb", 1) || !mednet_conv3d_act_supported(n, d, h, w, cout, cin, algo)) return 0;
   // (the kernel reads the layer's Cout channels, writes its Cin; 16-bit storage only, so the split-weight request counts as given)

@@ -89,3 +89,15 @@ int launch_head_lm_ce_bwd(const void* z, const float* W, const float* bias, cons
                           int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
                           const float* dreg, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db, int n,
                           size_t spatial, int nh, int ncls, int kind, int ignore, void* ws, size_t ws_bytes, hipStream_t s);
+
+// head_mfma.hip: the segmentation head (1x1x1 conv 32 -> 5 .. 16 classes) fused with DiceLoss (ce = 0) or nn.CrossEntropyLoss
+// (ce = 1, softmax), matrix-core form.  `partial`: [n][chunk][ncls][2] for dice_finalize (ce = 0), [n][chunk][2] for ce_finalize
+// (ce = 1); chunks = head_lm_chunks(spatial).  Labels uint8, base and sample stride multiples of 4 bytes.
+bool head_seg_supported(int cin, int ncls, int dtype, size_t spatial);
+size_t head_seg_ws_bytes(int n, size_t spatial, int ncls);
+int launch_head_seg_fwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* cls_weight,
+                        float* logits, float* partial, int n, size_t spatial, int ncls, int ce, int sigmoid, int ignore, hipStream_t s);
+int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* saved,
+                        const float* cls_weight, const float* dloss, float eps, void* dz, const void* gn_y, int gn_act,
+                        float* gn_partial, float* dw, float* db, int n, size_t spatial, int ncls, int ce, int sigmoid, int ignore,
+                        void* ws, size_t ws_bytes, hipStream_t s);

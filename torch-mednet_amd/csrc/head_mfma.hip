@@ -535,6 +535,374 @@ __global__ __launch_bounds__(256) void head_lm_wfinal_kernel(const float* __rest
   }
 }
 
+// ---- the segmentation head: 32 features -> ncls classes, 5 <= ncls <= 16, fused with DiceLoss (loss.py:114-130) or
+// nn.CrossEntropyLoss (segmentation.py:49) ---------------------------------------------------------------------------------
+// head_lm_kernel's heat-map rows carrying the classes: lane (g, h) holds, of its voxels 4g .. 4g+3, the logits of classes 8h .. 8h+7
+// in acc[0..7] (weight rows of classes >= ncls are zero), so a voxel's classes live in the two lanes l and l ^ 32.  The softmax
+// exchanges the half maximum and the half sum of those two lanes with v_permlane32_swap (common.h: plain VALU, no LDS queue); the
+// Dice backward exchanges sum_k p_k g_k, the CE backward the label's weight, the same way.  Every exchange runs with all 64 lanes
+// active, on predicated values (a dead lane's logits are the biases: finite).  HlmArgs with nh = 0: `ncls` classes, no targets.
+//   forward   {I, D} per class (dice_finalize_kernel's rows) or {sum w_y nll, sum w_y} (ce_finalize_kernel's rows)
+//   backward  logits rebuilt, dl from dice_bwd_kernel's / ce_bwd_kernel's closed form, dz^T = W^T dl^T stored once, dW through the
+//             wave-private tiles (dl columns 0 .. 15; 16 .. 31 stay zero), db by lane sums, GroupNorm-3's first pass from the stored rows.
+constexpr int HSG_MAXC = 16;
+
+__device__ __forceinline__ float xor32_max(float v) {  // max(v(l), v(l ^ 32)) in every lane: xor32_sum's idiom
+  float a = v, b = v;
+  MEDNET_SWAP_PAIR("v_permlane32_swap_b32", a, b);
+  return fmaxf(a, b);
+}
+
+template <bool BWD, bool CE>
+__global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+  __shared__ __attribute__((aligned(16))) char smem[256 * HLM_SCR * 4];
+  __shared__ float cst[2][24];
+  __shared__ u32x4 wops[6][64];  // 0,1: logits hi (k-steps); 2,3: lo; 4: dz hi; 5: dz lo
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane & 31, h = lane >> 5;
+  const int n = blockIdx.y, chunk = blockIdx.x;
+  const int nv = min(8, max(0, a.ncls - 8 * h));  // classes of this lane half
+
+  // ---- weight operands (head_lm_kernel's, the classes in the heat maps' place) ----------------------------------------------
+  const int ri = lane & 31, rq = ri >> 3, rhh = (ri & 7) >> 2, rt = ri & 3;
+  const int lrow = (rq < 2 && 8 * rhh + 4 * rq + rt < a.ncls) ? 8 * rhh + 4 * rq + rt : -1;
+  if (wv == 0) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      eltx8 hi, lo;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float w = lrow >= 0 ? a.W[lrow * 32 + 16 * s + 8 * h + e] : 0.f;
+        hi[e] = (elt)w;
+        lo[e] = (elt)(w - (float)hi[e]);
+      }
+      wops[s][lane] = __builtin_bit_cast(u32x4, hi);
+      wops[2 + s][lane] = __builtin_bit_cast(u32x4, lo);
+    }
+  }
+  if (BWD && wv == 1) {
+    eltx8 hi, lo;
+    const int ch = (rq >> 1) * 16 + 8 * rhh + (rq & 1) * 4 + rt;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float w = 8 * h + e < a.ncls ? a.W[(8 * h + e) * 32 + ch] : 0.f;
+      hi[e] = (elt)w;
+      lo[e] = (elt)(w - (float)hi[e]);
+    }
+    wops[4][lane] = __builtin_bit_cast(u32x4, hi);
+    wops[5][lane] = __builtin_bit_cast(u32x4, lo);
+  }
+  // ---- constants of a lane half: the biases of its 8 classes [0..7]; CE forward: the class weights [8..15]; CE backward:
+  // w_k dloss / sum w [8..15]; Dice backward: gI [8..15], gD [16..23] (dice_bwd_kernel)
+  if (wv == 2 && (lane & 31) < 24) {
+    const int hh = lane >> 5, i = lane & 31, k = 8 * hh + (i & 7);
+    float v = 0.f;
+    if (k < a.ncls) {
+      const float w = a.cls_weight ? a.cls_weight[k] : 1.f;
+      if (i < 8) v = a.bias ? a.bias[k] : 0.f;
+      else if (CE) v = i < 16 ? (BWD ? w * (*a.dcls / a.saved[0]) : w) : 0.f;
+      else if (BWD) {
+        const float gc = *a.dcls;
+        const float I = a.saved[2 * k], D = a.saved[2 * k + 1];
+        const float Dc = fmaxf(D, a.eps);
+        v = i < 16 ? -2.f * w / ((float)a.ncls * Dc) * gc + ((I != I || D != D) ? __builtin_nanf("") : 0.f)
+                   : (D >= a.eps ? 2.f * w * I / ((float)a.ncls * Dc * Dc) : 0.f) * gc;
+      }
+    }
+    cst[hh][i] = v;
+  }
+  __syncthreads();
+  const u32x4* wbase = &wops[0][lane];
+  const float* cbase = &cst[h][0];
+  auto wop = [&](int i) { return __builtin_bit_cast(eltx8, wbase[i * 64]); };
+  // ---- accumulators ---------------------------------------------------------------------------------------------------
+  float dI[8], dD[8];                 // forward (Dice)
+  float ss[16], sq[16], dbc[8];       // backward
+  f32x16 accw;
+  bool bad = false;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) dI[e] = dD[e] = dbc[e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) ss[i] = sq[i] = accw[i] = 0.f;
+
+  char* zt = smem + wv * 6144;
+  char* dlh = zt + 2048;
+  char* dll = zt + 4096;
+  float* const ce_acc = reinterpret_cast<float*>(smem) + tid * HLM_SCR + 16;  // (the forward has no tiles: head_lm_kernel)
+  if constexpr (CE && !BWD) ce_acc[0] = ce_acc[1] = 0.f;
+  const int tq = (lane & 15) >> 2, tp = lane & 3, tg = lane >> 4;
+  const int troff = (8 * h + tq) * 64 + (16 * (tg & 1) + 4 * tp) * 2;
+  if constexpr (BWD) {  // columns 16 .. 31 of the dl tiles are never written
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+    *reinterpret_cast<u32x4*>(dlh + lane * 32) = zero;
+    *reinterpret_cast<u32x4*>(dlh + lane * 32 + 16) = zero;
+    *reinterpret_cast<u32x4*>(dll + lane * 32) = zero;
+    *reinterpret_cast<u32x4*>(dll + lane * 32 + 16) = zero;
+    wave_lds_fence();
+  }
+
+  const elt* zs = a.z + (size_t)n * a.spatial * 32;
+  const elt* ys = (BWD && a.gn_y) ? a.gn_y + (size_t)n * a.spatial * 32 : nullptr;
+  elt* dzs = BWD ? a.dz + (size_t)n * a.spatial * 32 : nullptr;
+  const uint8_t* lb8 = a.lab + (size_t)n * a.lab_sn;
+  const int run_end = min(a.runs, (chunk + 1) * a.chunk_runs);
+
+  for (int run = chunk * a.chunk_runs + wv; run < run_end; run += 4) {
+    const size_t vb = (size_t)run * HLM_RUN + 4 * g;
+    const bool live = vb < a.spatial;  // (spatial % 4 == 0: all four voxels or none)
+    u32x4 zp[4][2], yp[2][2];
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) zp[j][s] = live ? *reinterpret_cast<const u32x4*>(zs + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
+    auto fetch_y = [&](int j) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        yp[j & 1][s] = (live && ys) ? *reinterpret_cast<const u32x4*>(ys + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
+    };
+    if constexpr (BWD) fetch_y(0);
+    const unsigned lb = live ? *reinterpret_cast<const unsigned*>(lb8 + vb) : 0u;  // (both halves: each owns 8 of the classes)
+
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      asm volatile("" : "+v"(wbase), "+v"(cbase));
+      if constexpr (BWD) {
+        if (j < 3) fetch_y(j + 1);
+      }
+      f32x16 lg;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) lg[i] = 0.f;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const eltx8 zb = __builtin_bit_cast(eltx8, zp[j][s]);
+        lg = MEDNET_MFMA_32x32x16(wop(s), zb, lg, 0, 0, 0);
+        lg = MEDNET_MFMA_32x32x16(wop(2 + s), zb, lg, 0, 0, 0);
+      }
+      float lc[8], p[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) lc[e] = lg[e] + cbase[e];
+      if (!BWD && a.logits && live) {
+        float* lo = a.logits + ((size_t)n * a.ncls + 8 * h) * a.spatial + vb + j;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (e < nv) lo[(size_t)e * a.spatial] = lc[e];
+      }
+      const int yl = (int)((lb >> (8 * j)) & 0xFFu);
+      const int yk = yl - 8 * h;  // the label's slot in this half, if in 0 .. nv-1
+      float lse = 0.f;
+      if (a.sigmoid) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) p[e] = e < nv ? 1.f / (1.f + expf(-lc[e])) : 0.f;
+      } else {
+        float mx = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (e < nv) mx = fmaxf(mx, lc[e]);
+        mx = xor32_max(mx);
+        float den = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          p[e] = e < nv ? expf(lc[e] - mx) : 0.f;
+          den += p[e];
+        }
+        den = xor32_sum(den);
+        const float inv = 1.f / den;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) p[e] *= inv;
+        if (CE) lse = mx + logf(den);
+      }
+      if constexpr (!BWD) {
+        if constexpr (CE) {
+          // ce_fwd_kernel; the half that owns the label's class takes the voxel's term
+          if (live && h == 0 && yl != a.ignore && yl >= a.ncls) ce_acc[0] = __builtin_nanf("");
+          if (live && yl != a.ignore && yk >= 0 && yk < nv) {
+            float zy = 0.f, w = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (e == yk) {
+                zy = lc[e];
+                w = cbase[8 + e];
+              }
+            ce_acc[0] = fmaf(w, lse - zy, ce_acc[0]);
+            ce_acc[1] += w;
+          }
+        } else {
+          bad |= live && yl >= a.ncls;
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (e < nv) {
+              const float t = (e == yk) ? 1.f : 0.f;
+              const float mk = (!live || (a.ignore != MEDNET_NO_IGNORE && t == (float)a.ignore)) ? 0.f : 1.f;
+              dI[e] = fmaf(p[e] * mk, t * mk, dI[e]);
+              dD[e] += (p[e] + t) * mk;
+            }
+        }
+      } else {
+        float dc[8];
+        if constexpr (CE) {
+          float wy = 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (e == yk) wy = cbase[8 + e];  // (0 for classes >= ncls)
+          wy = xor32_sum(wy);                // (the other half's lane has 0)
+          wy = (live && yl != a.ignore && yl < a.ncls) ? wy : 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            dc[e] = e < nv ? wy * (p[e] - (e == yk ? 1.f : 0.f)) : 0.f;
+            dbc[e] += dc[e];
+          }
+        } else {
+          float gg[8], dot = 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float t = (e == yk) ? 1.f : 0.f;
+            const float mk = (a.ignore != MEDNET_NO_IGNORE && t == (float)a.ignore) ? 0.f : 1.f;
+            gg[e] = e < nv ? mk * (cbase[8 + e] * t * mk + cbase[16 + e]) : 0.f;
+            dot = fmaf(p[e], gg[e], dot);
+          }
+          if (!a.sigmoid) dot = xor32_sum(dot);  // (uniform)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float v = a.sigmoid ? gg[e] * p[e] * (1.f - p[e]) : p[e] * (gg[e] - dot);
+            dc[e] = (live && e < nv) ? v : 0.f;
+            dbc[e] += dc[e];
+          }
+        }
+        eltx8 dc_hi, dc_lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          dc_hi[e] = (elt)dc[e];
+          dc_lo[e] = (elt)(dc[e] - (float)dc_hi[e]);
+        }
+        // ---- dz^T = W^T dl^T: hi hi, lo hi, hi lo
+        f32x16 dzv;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dzv[i] = 0.f;
+        dzv = MEDNET_MFMA_32x32x16(wop(4), dc_hi, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(wop(5), dc_hi, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(wop(4), dc_lo, dzv, 0, 0, 0);
+        eltx8 o0, o1;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          o0[e] = (elt)dzv[e];
+          o1[e] = (elt)dzv[8 + e];
+        }
+        if (live) {
+          *reinterpret_cast<u32x4*>(dzs + (vb + j) * 32 + 8 * h) = __builtin_bit_cast(u32x4, o0);
+          *reinterpret_cast<u32x4*>(dzs + (vb + j) * 32 + 16 + 8 * h) = __builtin_bit_cast(u32x4, o1);
+        }
+        if (ys) {  // (workgroup-uniform) first pass of the GroupNorm backward in front, from the STORED rows
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            const eltx8 zv = __builtin_bit_cast(eltx8, zp[j][s]), yv = __builtin_bit_cast(eltx8, yp[j & 1][s]);
+            const eltx8 ov = s ? o1 : o0;
+            float du[8], zz[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              du[e] = (float)ov[e];
+              zz[e] = (float)zv[e];
+            }
+            act_grad_n<8>(du, zz, a.gn_act);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              ss[8 * s + e] += du[e];
+              sq[8 * s + e] = fmaf(du[e], (float)yv[e], sq[8 * s + e]);
+            }
+          }
+        }
+        // ---- dW += dl^T z over these 32 voxels
+        wave_lds_fence();
+        *reinterpret_cast<u32x4*>(zt + g * 64 + 16 * h) = zp[j][0];
+        *reinterpret_cast<u32x4*>(zt + g * 64 + 32 + 16 * h) = zp[j][1];
+        *reinterpret_cast<u32x4*>(dlh + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, dc_hi);
+        *reinterpret_cast<u32x4*>(dll + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, dc_lo);
+        wave_lds_fence();
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const eltx8 fz = tr_operand(zt + ks * 1024 + troff, 256);
+          const eltx8 fh = tr_operand(dlh + ks * 1024 + troff, 256);
+          const eltx8 fl = tr_operand(dll + ks * 1024 + troff, 256);
+          accw = MEDNET_MFMA_32x32x16(fh, fz, accw, 0, 0, 0);
+          accw = MEDNET_MFMA_32x32x16(fl, fz, accw, 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // ---- end of kernel: lane and wave sums through LDS in a fixed order -----------------------------------------------
+  float* scr = reinterpret_cast<float*>(smem);
+  float* mine = scr + tid * HLM_SCR;
+  __syncthreads();
+  if constexpr (!BWD) {
+    if constexpr (CE) {  // values 16 / 17 of every thread are its ce_acc
+      if (tid < 2) {
+        float s = 0.f;
+        for (int t = 0; t < 256; ++t) s += scr[t * HLM_SCR + 16 + tid];
+        a.ce_partial[((size_t)n * a.chunks + chunk) * 2 + tid] = s;
+      }
+    } else {
+      if (bad) dI[0] = dD[0] = __builtin_nanf("");
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        mine[e] = dI[e];
+        mine[8 + e] = dD[e];
+      }
+      __syncthreads();
+      if (tid < 2 * HSG_MAXC) {  // class k = 8hh + e: lanes of half hh, value e (I) / 8 + e (D)
+        const int k = tid >> 1, which = tid & 1, hh = k >> 3, idx = 8 * which + (k & 7);
+        float s = 0.f;
+        for (int w = 0; w < 4; ++w)
+          for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + idx];
+        if (k < a.ncls) a.dice_partial[(((size_t)n * a.chunks + chunk) * a.ncls + k) * 2 + which] = s;
+      }
+    }
+  } else {
+    if (a.gn_partial) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        mine[i] = ss[i];
+        mine[16 + i] = sq[i];
+      }
+      __syncthreads();
+      if (tid < 64) {
+        const int which = tid & 1, idx = (tid >> 1) & 15, hh = tid >> 5;
+        float s = 0.f;
+        for (int w = 0; w < 4; ++w)
+          for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + which * 16 + idx];
+        const int ch = (idx >> 3) * 16 + 8 * hh + (idx & 7);
+        a.gn_partial[(((size_t)n * a.chunks + chunk) * 32 + ch) * 2 + which] = s;
+      }
+      __syncthreads();
+    }
+    // head_lm_kernel's rows: dW row k' = class k' (accumulator values 0 .. 7 of a lane; 8 .. 15 are the zero rows 16 .. 31, which
+    // head_lm_wfinal_kernel never reads with ncls = 0), db at 1024 + k'
+    float* wp = a.wpart + ((size_t)n * a.chunks + chunk) * HLM_WIDTH;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      mine[i] = accw[i];
+      mine[8 + i] = dbc[i];
+    }
+    __syncthreads();
+    for (int o = tid; o < 512; o += 256) {
+      const int L = o & 63, i = o >> 6;
+      const float s = (scr[(0 * 64 + L) * HLM_SCR + i] + scr[(1 * 64 + L) * HLM_SCR + i]) +
+                      (scr[(2 * 64 + L) * HLM_SCR + i] + scr[(3 * 64 + L) * HLM_SCR + i]);
+      const int kp = 8 * (i >> 2) + 4 * (L >> 5) + (i & 3);
+      wp[kp * 32 + (L & 31)] = s;
+    }
+    if (tid < HSG_MAXC) {
+      const int hh = tid >> 3, idx = 8 + (tid & 7);
+      float s = 0.f;
+      for (int w = 0; w < 4; ++w)
+        for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + idx];
+      wp[1024 + tid] = s;
+    }
+  }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 bool head_lm_supported(int cin, int nh, int ncls, int dtype, size_t spatial) {
   return cin == 32 && nh >= 1 && nh <= HLM_MAXH && ncls >= 1 && ncls <= HLM_MAXC && dtype == ELT_DTYPE && spatial % 4 == 0 &&
@@ -627,6 +995,60 @@ int launch_head_lm_ce_bwd(const void* z, const float* W, const float* bias, cons
                           size_t spatial, int nh, int ncls, int kind, int ignore, void* ws, size_t ws_bytes, hipStream_t s) {
   return head_lm_bwd_launch<true>(z, W, bias, tgt, tgt_sn, lab, lab_sn, saved, cls_weight, reg_weight, dcls, dreg, 0.f, dz, gn_y, gn_act,
                                   gn_partial, dw, db, n, spatial, nh, ncls, kind, 0, ignore, ws, ws_bytes, s);
+}
+
+// ---- the segmentation head (head_seg_kernel): head_lm's plan, partial rows and final sums -------------------------------------
+bool head_seg_supported(int cin, int ncls, int dtype, size_t spatial) {
+  return cin == 32 && ncls >= 5 && ncls <= HSG_MAXC && dtype == ELT_DTYPE && spatial % 4 == 0 && tuning_option("head_seg_mfma", 1);
+}
+size_t head_seg_ws_bytes(int n, size_t spatial, int ncls) {
+  const size_t chunks = head_lm_chunks(spatial);
+  const size_t fwd = (size_t)n * chunks * (2 * ncls + 2);  // Dice rows [n][chunk][ncls][2] or CE rows [n][chunk][2]
+  const size_t bwd = (size_t)n * chunks * HLM_WIDTH;
+  return ((fwd > bwd ? fwd : bwd) + 64) * sizeof(float);
+}
+static int head_seg_args(HlmArgs& a, const char* what, const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn,
+                         const float* cls_weight, size_t spatial, int ncls, int sigmoid, int ignore) {
+  a.z = (const elt*)z; a.W = W; a.bias = bias; a.lab = (const uint8_t*)lab; a.lab_sn = lab_sn;
+  a.spatial = spatial; a.nh = 0; a.ncls = ncls;
+  head_lm_plan(spatial, a.runs, a.chunk_runs, a.chunks);
+  a.sigmoid = sigmoid; a.ignore = ignore; a.cls_weight = cls_weight;
+  MEDNET_REQUIRE(lab_sn % 4 == 0 && ((uintptr_t)lab & 3) == 0, MEDNET_E_SHAPE, "%s: labels must be 4-byte aligned per sample", what);
+  return 0;
+}
+int launch_head_seg_fwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* cls_weight,
+                        float* logits, float* partial, int n, size_t spatial, int ncls, int ce, int sigmoid, int ignore, hipStream_t s) {
+  HlmArgs a = {};
+  const int rc = head_seg_args(a, "head_seg_fwd", z, W, bias, lab, lab_sn, cls_weight, spatial, ncls, sigmoid, ignore);
+  if (rc) return rc;
+  a.logits = logits;
+  if (ce) {
+    a.ce_partial = partial;
+    hipLaunchKernelGGL((head_seg_kernel<false, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  } else {
+    a.dice_partial = partial;
+    hipLaunchKernelGGL((head_seg_kernel<false, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  }
+  return check_launch(ce ? "head_seg_ce_fwd" : "head_seg_fwd");
+}
+int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* saved,
+                        const float* cls_weight, const float* dloss, float eps, void* dz, const void* gn_y, int gn_act,
+                        float* gn_partial, float* dw, float* db, int n, size_t spatial, int ncls, int ce, int sigmoid, int ignore,
+                        void* ws, size_t ws_bytes, hipStream_t s) {
+  HlmArgs a = {};
+  int rc = head_seg_args(a, "head_seg_bwd", z, W, bias, lab, lab_sn, cls_weight, spatial, ncls, sigmoid, ignore);
+  if (rc) return rc;
+  a.saved = saved; a.dcls = dloss; a.eps = eps;
+  a.dz = (elt*)dz; a.gn_y = (const elt*)gn_y; a.gn_act = gn_act; a.gn_partial = gn_partial;
+  MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "head_seg_bwd: gn_y and gn_partial go together");
+  MEDNET_REQUIRE(ws_bytes >= head_seg_ws_bytes(n, spatial, ncls), MEDNET_E_WORKSPACE, "head_seg_bwd: workspace too small");
+  a.wpart = (float*)ws;
+  if (ce) hipLaunchKernelGGL((head_seg_kernel<true, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_seg_kernel<true, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  rc = check_launch(ce ? "head_seg_ce_bwd" : "head_seg_bwd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((ncls * 33 + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, ncls, 0, dw, db);
+  return check_launch("head_seg_wfinal");
 }
 
 }  // namespace mednet

@@ -114,6 +114,12 @@ SIGNATURES = {
                                           _i, _i, _vp, _sz, _vp]),
     "mednet_head_landmark_cls_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i64] + [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i,
                                           _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_head_seg_supported": (_i, [_i, _i, _i, _i, _sz]),
+    "mednet_head_seg_ws_bytes": (_sz, [_i, _sz, _i]),
+    "mednet_head_seg_gn_rows": (_i, [_sz]),
+    "mednet_head_seg_fwd": (_i, [_vp, _vp, _vp, _vp, _i64] + [_vp] * 4 + [_i, _sz, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_head_seg_bwd": (_i, [_vp, _vp, _vp, _vp, _i64] + [_vp] * 5 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _i, _f, _i, _i, _i,
+                                 _vp, _sz, _vp]),
     "mednet_head_ce_supported": (_i, [_i] * 4),
     "mednet_head_ce_ws_bytes": (_sz, [_i, _sz, _i, _i]),
     "mednet_head_ce_gn_rows": (_i, [_i, _sz, _i]),

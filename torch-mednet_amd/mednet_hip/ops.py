@@ -1354,6 +1354,97 @@ def head_ce(x, weight, bias, packed, labels, loss_weight=None, ignore_index=-100
     return HeadCEFn.apply(x, weight, bias, packed, labels, loss_weight, ignore_index)
 
 
+def head_seg_supported(x: torch.Tensor, cin: int, ncls: int, labels: torch.Tensor) -> bool:
+    """Does the matrix-core segmentation head (5 .. 16 classes, 16-bit storage, uint8 labels) take this head?"""
+    if not (FUSE_HEAD_LOSS and x.is_cuda and x.dim() == 5 and labels.is_cuda):
+        return False
+    if x.dtype != config.act_dtype() or x.dtype == torch.float32 or not x.is_contiguous(memory_format=CL):
+        return False
+    # (a network whose last block ends in conv -> activation hands the head an activation mask to fold in: the stock path does that)
+    if getattr(x, "_mednet_actmask", None) is not None and _gn3_hook_of(x, x.dtype) is None:
+        return False
+    ld = L.U8 if labels.dtype == torch.uint8 else L.I64
+    return bool(L.lib().mednet_head_seg_supported(cin, ncls, L.dt(x), ld, x[0, 0].numel()))
+
+
+class HeadSegFn(Function):
+    """SegmentationNet's head and loss (segmentation.py:58-62) for 5 .. 16 classes as ONE autograd node in the 16-bit storage modes:
+    loss = DiceLoss | nn.CrossEntropyLoss (final_conv(x), labels).  Forward: one matrix-core pass over the features that writes nothing
+    but loss partials, and the planar fp32 logits only when `want_logits` (mednet_head_seg_fwd); backward: one pass that rebuilds the
+    logits the same way and produces the feature gradient, the head's weight / bias gradients and the first pass of the producing
+    block's GroupNorm-3 backward (mednet_head_seg_bwd).  No logit-gradient tensor exists.  Returns (logits or None, loss); the logits
+    are not a differentiable output of this node."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, packed, labels, loss_weight, eps, sigmoid, ignore_index, class_kind, want_logits):
+        L.require_gpu(x, "head_seg")
+        n, cin, d, h, w = x.shape
+        ncls = weight.shape[0]
+        spatial = d * h * w
+        if labels.dtype != torch.uint8:
+            raise RuntimeError(f"head_seg: labels must be uint8, not {labels.dtype} (see head_seg_supported)")
+        lab, lab_sn, _ = _label_view(labels, n, (d, h, w))
+        # the kernel reads labels four voxels at a time: a view whose base or sample stride is no multiple of 4 bytes is copied once
+        if lab.data_ptr() % 4 or (n > 1 and lab_sn % 4):
+            lab = lab.contiguous().clone() if lab.is_contiguous() else lab.contiguous()
+            lab_sn = spatial
+        wt = None if loss_weight is None else loss_weight.to(device=x.device, dtype=torch.float32).contiguous()
+        ii = (L.NO_IGNORE if class_kind == L.CLASS_DICE else -100) if ignore_index is None else int(ignore_index)
+        logits = torch.empty((n, ncls, d, h, w), dtype=torch.float32, device=x.device) if want_logits else None
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        saved = torch.empty((ncls, 2), dtype=torch.float32, device=x.device)
+        lib = L.lib()
+        ws = L.workspace(lib.mednet_head_seg_ws_bytes(n, spatial, ncls), x.device)
+        L.check(lib.mednet_head_seg_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_sn, L.ptr(wt), L.ptr(logits),
+                                        loss.data_ptr(), saved.data_ptr(), n, spatial, cin, ncls, class_kind, eps, int(sigmoid), ii,
+                                        L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_seg_fwd")
+        ctx.save_for_backward(x, packed, lab, wt, saved)
+        ctx.meta = (eps, int(sigmoid), ii, lab_sn, cin, ncls, class_kind)
+        ctx.params = (weight, bias)
+        ctx.gn3 = _gn3_hook_of(x, x.dtype)
+        if logits is not None:
+            ctx.mark_non_differentiable(logits)
+        if debug.TRACE is not None:
+            debug.trace("head_seg.fwd", loss, saved)
+        return logits, loss
+
+    @staticmethod
+    def backward(ctx, _dlogits, dloss):
+        x, packed, lab, wt, saved = ctx.saved_tensors
+        eps, sigmoid, ii, lab_sn, cin, ncls, class_kind = ctx.meta
+        weight, bias = ctx.params
+        n, _, d, h, w = x.shape
+        spatial = d * h * w
+        lib = L.lib()
+        dl = dloss.to(torch.float32).contiguous()
+        dx = torch.empty_like(x, memory_format=CL)
+        dw, direct_w = _grad_target(weight, (ncls, cin, 1, 1, 1))
+        db, direct_b = (None, True) if bias is None else _grad_target(bias, (ncls,))
+        hook = ctx.gn3
+        partial = None
+        if hook is not None:
+            partial = torch.empty((n, lib.mednet_head_seg_gn_rows(spatial), cin, 2), dtype=torch.float32, device=x.device)
+        ws = L.workspace(lib.mednet_head_seg_ws_bytes(n, spatial, ncls), x.device)
+        L.check(lib.mednet_head_seg_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_sn, L.ptr(wt), saved.data_ptr(),
+                                        dl.data_ptr(), dx.data_ptr(), None if hook is None else hook.gn_in.data_ptr(),
+                                        hook.act if hook is not None else 0, L.ptr(partial), dw.data_ptr(), L.ptr(db), n, spatial, cin,
+                                        ncls, class_kind, eps, sigmoid, ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()),
+                "head_seg_bwd")
+        if hook is not None:
+            hook.offer(dx, partial)
+        if debug.TRACE is not None:
+            debug.trace("head_seg.bwd", dx, partial, dw, db)
+        return (dx, (None if direct_w else dw), (None if (bias is None or direct_b) else db)) + (None,) * 8
+
+
+def head_seg(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5, sigmoid=False, ignore_index=None, class_loss="DICE",
+             want_logits=False):
+    """-> (logits N x C x D x H x W fp32 or None, loss) of SegmentationNet's loss on final_conv(x), 5 <= C <= 16; class_loss "DICE"
+    (DiceLoss) or "CE" (nn.CrossEntropyLoss: softmax, `ignore_index` as that module's, -100 by default there)."""
+    return HeadSegFn.apply(x, weight, bias, packed, labels, loss_weight, eps, sigmoid, ignore_index, _class_kind(class_loss),
+                           want_logits)
+
+
 def _heatmap_view(heatmaps: torch.Tensor, n: int, nh: int, spatial_shape):
     """uint8 heat-map targets as the fused landmark head takes them: N x nh x spatial, channels dense, any stride between samples
     (the first channels of a uint8 label volume are consumed where they lie, landmarks.py:69)."""

@@ -416,7 +416,9 @@ class SegmentationStep(_GraphedStep):
         """`outputs = self(inputs); loss = self.loss(outputs, labels)` (segmentation.py:61-62).  When the model is this package's
         U-Net with a 1x1x1 head of at most 4 classes and the loss is DiceLoss or CrossEntropyLoss, the head and the loss run as one
         fused node (ops.head_dice / ops.head_ce: logits written once, no logit-gradient tensor, the label volume's uint8 channel
-        consumed where it lies); anything else takes the two calls as they stand."""
+        consumed where it lies); with 5 to 16 classes on a 32-feature head in a 16-bit storage mode they run as the matrix-core node
+        ops.head_seg, which writes no logit tensor at all: `outputs` is None in that form (as LandmarkStep has no outputs tensor).
+        Anything else takes the two calls as they stand."""
         from .unet.model import _UNetCore
         m, fc = self.model, getattr(self.model, "final_conv", None)
         dice = isinstance(self.loss, HL.DiceLoss)
@@ -429,6 +431,12 @@ class SegmentationStep(_GraphedStep):
                                      self.loss.sigmoid_normalization, self.loss.ignore_index)
             if not dice and ops.head_ce_supported(feats, fc.in_channels, fc.out_channels, label_u8):
                 return ops.head_ce(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.ignore_index)
+            if ops.head_seg_supported(feats, fc.in_channels, fc.out_channels, label_u8):
+                if dice:
+                    return ops.head_seg(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon,
+                                        self.loss.sigmoid_normalization, self.loss.ignore_index, "DICE")
+                return ops.head_seg(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, ignore_index=self.loss.ignore_index,
+                                    class_loss="CE")
             outputs = fc(feats)
         else:
             outputs = m(inputs)
