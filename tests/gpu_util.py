@@ -197,3 +197,110 @@ def norm_lattice(tag, n, c, groups, shape, eps, batch=False, nonneg=False):
     return types.SimpleNamespace(x=vol(x), du=vol(du), gamma=f32(gamma), beta=f32(beta), beta_act=f32(beta_act), m=rows(m),
                                  sigma=rows(sigma), p=rows(p), q=rows(q), n=n, c=c, groups=groups, shape=tuple(shape), eps=float(eps),
                                  spatial=S, cg=cg, batch=batch)
+
+
+# ------------------------------------------------------------------------------- the fused heads' backward
+# Inputs and checkers of tests/test_gpu_head_backward.py and of the ELU cases of tests/test_gpu_exact.py; tests/test_exact_util.py
+# shows on the CPU that the checkers reject the faults they are there for.
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_ELU = 0, 1, 2, 3       # mednet_hip._lib's codes
+ELU_Z = (-0.75, -0.5, -0.25, 0.0, 1.0, 2.0)               # block outputs of an ELU: act' = z + 1 in {1/4, 1/2, 3/4, 1} for z <= 0
+U_STORE = {"bf16": 2.0 ** -8, "fp16": 2.0 ** -11, "fp32": 0.0}   # the rounding of a stored gradient
+EPS_FLOOR = 2.0 ** -15    # the matrix-core heads' own arithmetic (16-bit-pair image of dl, dropped lo * lo, fp32 sums), doubled
+SUM_BOUND = 2.0 ** -16    # < 256 fp32 roundings of 2^-24 per GroupNorm sum
+
+
+def split_weight(w0, mode):
+    """fp32 weights of the form hi + lo, both parts numbers of the mode's storage type (hi = round(w0), lo = round(w0 - hi)):
+    17 significant bits in bf16, 23 in fp16.  A kernel that splits its fp32 weights as hi' = round(w), lo' = round(w - hi')
+    reproduces them exactly, and both images carry data."""
+    hi = half_round(w0, mode)
+    return hi + half_round(w0 - hi, mode)
+
+
+def elu_lattice(tag, *shape, density=0.8, window_max=False):
+    """Seeded like `lattice`: block outputs on the dyadic lattice ELU_Z (bf16 and fp16 numbers; zero with probability
+    1 - density on top of the lattice's own zero), so that du = dx * (z + 1) is exact in fp32 in steps of 1/4 for an integer dx.
+    window_max: the three trailing dims are even and every 2 x 2 x 2 window has a UNIQUE maximum -- one element holds a lattice
+    value above -3/4 (negative ones included: a max pooling routes its gradient there), the seven others lie strictly below it."""
+    if not window_max:
+        return lattice(tag, *shape, values=ELU_Z, density=density)
+    d, h, w = shape[-3:]
+    lead = tuple(shape[:-3])
+    k = len(lead)
+    wshape = lead + (d // 2, h // 2, w // 2)
+    g = O._rng("in:" + tag + ":max")
+    top = g.integers(1, len(ELU_Z), size=wshape)                                   # index of the window's maximum
+    idx = np.floor(g.random(wshape + (8,)) * top[..., None]).astype(np.int64)      # the others: uniform below it
+    np.put_along_axis(idx, g.integers(0, 8, size=wshape)[..., None], top[..., None], axis=-1)
+    win = torch.from_numpy(np.asarray(ELU_Z, dtype=np.float32)[idx]).reshape(wshape + (2, 2, 2))
+    return win.permute(*range(k), k, k + 3, k + 1, k + 4, k + 2, k + 5).reshape(shape).contiguous()
+
+
+def act_grad_from_out(z, act):
+    """act'(.) through the activation OUTPUT z, in z's precision (ATen's in-place forms; LeakyReLU(0.1), ELU(alpha = 1))."""
+    one = torch.ones_like(z)
+    if act == ACT_RELU:
+        return (z > 0).to(z.dtype)
+    if act == ACT_LEAKY:
+        return torch.where(z > 0, one, 0.1 * one)
+    if act == ACT_ELU:
+        return torch.where(z > 0, one, z + 1)
+    return one
+
+
+def _first_bad(bad, got, ref, bound, first=6):
+    idx = bad.nonzero()[:first]
+    return " | ".join(f"{tuple(i.tolist())}: got {got[tuple(i.tolist())].item()!r} want {ref[tuple(i.tolist())].item()!r} "
+                      f"bound {bound[tuple(i.tolist())].item():.3e}" for i in idx)
+
+
+def ref_error(x32, x64, norm, what):
+    """r32 = max |x32 - x64| / norm over all elements: what ATen's fp32 evaluation shows against its fp64 one in the
+    normalisation of the bound (an element whose norm is 0 has no terms: both references must be 0 there).  -> (r32, eps_case),
+    eps_case = max(EPS_FLOOR, 8 * r32)."""
+    x32, x64, norm = x32.detach().double(), x64.detach().double(), norm.detach().double()
+    diff = (x32 - x64).abs()
+    dead = norm == 0
+    assert not bool((diff[dead] != 0).any()), f"{what}: the fp32 and fp64 references differ where the bound's norm is 0"
+    r32 = float((diff[~dead] / norm[~dead]).max()) if bool((~dead).any()) else 0.0
+    return r32, max(EPS_FLOOR, 8.0 * r32)
+
+
+def check_gradient(got, ref64, norm, eps, what, u=0.0, s=0.0):
+    """Every element, no NaN: |got - ref64| <= u * |ref64| + eps * norm + s.  -> the worst observed ratio
+    max(|got - ref64| - u * |ref64| - s, 0) / norm, to be read against eps."""
+    got, ref64, norm = got.detach().double().cpu(), ref64.detach().double(), norm.detach().double()
+    assert got.shape == ref64.shape == norm.shape, f"{what}: shapes {tuple(got.shape)} / {tuple(ref64.shape)} / {tuple(norm.shape)}"
+    nan = int(torch.isnan(got).sum())
+    assert nan == 0, f"{what}: {nan} of {got.numel()} elements are NaN (not written)"
+    diff = (got - ref64).abs()
+    bound = u * ref64.abs() + eps * norm + s
+    bad = diff > bound
+    nbad = int(bad.sum())
+    assert nbad == 0, f"{what}: {nbad} of {got.numel()} elements outside u |ref| + eps * norm + s (u {u:.3e} eps {eps:.3e} s {s:.3e}); first at " + _first_bad(bad, got, ref64, bound)
+    over = (diff - u * ref64.abs() - s).clamp(min=0)
+    live = norm > 0
+    return float((over[live] / norm[live]).max()) if bool(live.any()) else 0.0
+
+
+def check_gn_sums(partial, dz_stored, z, gn_y, act, what):
+    """gn_partial[n][rows][c][2] against {sum du, sum du * gn_y}, du = dz_stored * act'(z), in fp64 from the STORED gradient
+    (n x c x spatial dims, as z and gn_y): |got - want| <= SUM_BOUND * sum |terms| per (sample, channel, entry), no NaN.
+    -> the worst observed |got - want| / sum |terms|."""
+    p = partial.detach().double().cpu()
+    nan_rows = int(torch.isnan(p).any(-1).any(-1).sum())
+    assert nan_rows == 0, f"{what}: {nan_rows} of {p.shape[0] * p.shape[1]} rows of gn_partial hold a NaN (not written)"
+    got = p.sum(1)
+    z64, y64 = z.detach().double().cpu(), gn_y.detach().double().cpu()
+    du = dz_stored.detach().double().cpu() * act_grad_from_out(z64, act)
+    dims = tuple(range(2, du.dim()))
+    want = torch.stack((du.sum(dims), (du * y64).sum(dims)), -1)
+    mag = torch.stack((du.abs().sum(dims), (du * y64).abs().sum(dims)), -1)
+    assert got.shape == want.shape, f"{what}: gn_partial totals {tuple(got.shape)} != {tuple(want.shape)}"
+    diff = (got - want).abs()
+    bound = SUM_BOUND * mag
+    bad = diff > bound
+    nbad = int(bad.sum())
+    assert nbad == 0, f"{what}: {nbad} of {got.numel()} GroupNorm sums outside 2^-16 * sum |terms|; first at " + _first_bad(bad, got, want, bound)
+    live = mag > 0
+    return float((diff[live] / mag[live]).max()) if bool(live.any()) else 0.0

@@ -24,7 +24,7 @@ from mednet_hip import _lib as L
 from mednet_hip import nn as hnn
 from mednet_hip import ops
 
-from gpu_util import DEV, FP32_EXACT, assert_exact, assert_representable, assert_sums_exact, lattice
+from gpu_util import DEV, FP32_EXACT, assert_exact, assert_representable, assert_sums_exact, elu_lattice, lattice
 
 pytestmark = pytest.mark.gpu
 CL = torch.channels_last_3d
@@ -496,15 +496,17 @@ def test_conv_transpose_fp32_mode(x3, n, cin, cout, shape):
 
 
 # ------------------------------------------------------------------------------------------------ fused sums
-def check_sum_conditions(y, what, other=None):
-    """Condition 3: per sample and channel the totals of |y| and y^2 (resp. |du| and |du * gn_y|) over the WHOLE sample stay
-    below 2^24 (per channel PAIR: twice the worst channel bounds it) -- the accumulate-mode kernels keep one fp32 sum per wave
-    over many bricks."""
+def check_sum_conditions(y, what, other=None, unit=1.0):
+    """Condition 3: per sample and channel the totals of |y| and y^2 (resp. |du| and |du * gn_y|) over the WHOLE sample, counted
+    in lattice steps of `unit` (1/4 for the ELU cases: du = dx * (z + 1)), stay below 2^24 (per channel PAIR: twice the worst
+    channel bounds it) -- the accumulate-mode kernels keep one fp32 sum per wave over many bricks.  Every term must lie on the
+    lattice."""
     y = y.double()
     second = y * y if other is None else (y * other.double()).abs()
     for t, name in ((y.abs(), "sum |.|"), (second, "sum of the second moment")):
-        m = 2.0 * float(t.sum((2, 3, 4)).max())
-        assert m < FP32_EXACT, f"{what}: {name} reaches {m:.4g} >= 2^24 per channel pair"
+        assert bool((t / unit == torch.round(t / unit)).all()), f"{what}: {name} has terms off the lattice of step {unit}"
+        m = 2.0 * float(t.sum((2, 3, 4)).max()) / unit
+        assert m < FP32_EXACT, f"{what}: {name} reaches {m:.4g} lattice steps >= 2^24 per channel pair"
 
 
 def compare_pair_sums(partial, y, what, per_channel=False):
@@ -617,9 +619,20 @@ def test_fused_forward_sums_in_the_fp32_mode(n, c, shape, px, pw):
 
 
 # ------------------------------------------------------------------------------------------------ (e) data-gradient epilogues
-def gn_reference(dx, gn_pre, act):
-    """du = dx * act'(pre-activation) and the per-channel {sum du, sum du * gn_y}; act in (none, ReLU)."""
-    return dx if act == L.ACT_NONE else dx * (gn_pre > 0)
+GN_ACTS = (L.ACT_NONE, L.ACT_RELU, L.ACT_ELU)   # (LeakyReLU's 0.1 is no dyadic number: tests/test_gpu_head_backward.py covers it)
+SUM_UNIT = {L.ACT_NONE: 1.0, L.ACT_RELU: 1.0, L.ACT_ELU: 0.25}   # the lattice step of du
+
+
+def gn_reference(dx, gn_z, act):
+    """du = dx * act'(.) for the per-channel {sum du, sum du * gn_y}; act in (none, ReLU, ELU).  gn_z is the block OUTPUT for the
+    kernels that read it (act_grad_n: ELU' = z + 1 for z <= 0, ATen's elu_backward(is_result=true)); for none and ReLU a
+    pre-activation serves as well (only its sign is used)."""
+    if act == L.ACT_NONE:
+        return dx
+    if act == L.ACT_RELU:
+        return dx * (gn_z > 0)
+    assert act == L.ACT_ELU and float(gn_z.min()) > -1
+    return dx * torch.where(gn_z > 0, torch.ones_like(gn_z), gn_z + 1)
 
 
 def compare_channel_sums(partial, du, gy, what):
@@ -653,11 +666,18 @@ def dgrad_inputs(n, cin, cout, shape):
     # its sign is exact
     ca = lattice(tag + "ca", n, cin, values=(-2, -1, -0.5, 0.5, 1, 2), density=1.0)
     cb = lattice(tag + "cb", n, cin, values=(-1.5, -0.5, 0.5, 1.5), density=1.0)
+    # ELU: this kernel has no block output to read, it forms act' = exp(ca * gn_y + cb) from the recomputed PRE-activation
+    # (act_grad_pre_n), which is a dyadic number only at its ends.  ca * gn_y in {0, +-128, +-256, +-512} and cb in {0, +-256}: every
+    # pre-activation is a multiple of 128, so act' is exactly 1 (positive, or exp(0)) or exactly 0 (exp(-128) = 2.6e-56 is below
+    # the smallest fp32 number).  ReLU' differs from it at 0 and LeakyReLU' below 0.
+    ea = lattice(tag + "ea", n, cin, values=(-128, -64, 64, 128), density=1.0)
+    eb = lattice(tag + "eb", n, cin, values=(-256, 0, 0, 256), density=1.0)
     xr = torch.zeros(n, cin, *shape, dtype=torch.float64, requires_grad=True)
     F.conv3d(xr, w.double(), None, padding=1).backward(dy.double())
     xa = torch.zeros(n, cin, *shape, dtype=torch.float64, requires_grad=True)
     F.conv3d(xa, w.abs().double(), None, padding=1).backward(dy.abs().double())
-    return dict(dy=dy, w=w, add=add, gy=gy, coef=torch.stack((ca, cb), -1).contiguous(), dx=xr.grad, mag=xa.grad + add.abs().double())
+    return dict(dy=dy, w=w, add=add, gy=gy, coef=torch.stack((ca, cb), -1).contiguous(), coef_elu=torch.stack((ea, eb), -1).contiguous(),
+                dx=xr.grad, mag=xa.grad + add.abs().double())
 
 
 _DGRAD = {}
@@ -669,15 +689,18 @@ def dgrad_conditions(key, dt):
         _DGRAD[key] = dgrad_inputs(*key)
     t = _DGRAD[key]
     gy64 = t["gy"].double()
-    pre = t["coef"][..., 0].double()[:, :, None, None, None] * gy64 + t["coef"][..., 1].double()[:, :, None, None, None]
+    affine = lambda coef: coef[..., 0].double()[:, :, None, None, None] * gy64 + coef[..., 1].double()[:, :, None, None, None]
+    pre, pre_elu = affine(t["coef"]), affine(t["coef_elu"])
     assert float(pre.abs().min()) > 0
+    assert bool((pre_elu % 128 == 0).all()) and bool((pre_elu == 0).any()) and bool((pre_elu < 0).any()) and bool((pre_elu > 0).any())
+    elu_grad = (pre_elu >= 0).double()      # exp(0) = 1; exp(u) = 0 in fp32 for u <= -128
     assert_sums_exact(t["mag"], "dgrad dx")
     variants = {}
     for with_add in (False, True):
         dx = t["dx"] + (t["add"].double() if with_add else 0)
         assert_representable(dx, dt, "dx")
-        for act in (L.ACT_NONE, L.ACT_RELU):
-            du = gn_reference(dx, pre, act)
+        for act in GN_ACTS:
+            du = dx * elu_grad if act == L.ACT_ELU else gn_reference(dx, pre, act)
             check_sum_conditions(du, f"dgrad_gn {key}", other=gy64)
             variants[(with_add, act)] = (dx, du)
     return t, gy64, variants
@@ -685,8 +708,9 @@ def dgrad_conditions(key, dt):
 
 @pytest.mark.parametrize("mode,n,cin,cout,shape,kinds,opts", DGRAD_CASES)
 def test_fused_data_gradient_epilogues(mode, n, cin, cout, shape, kinds, opts):
-    """mednet_conv3d_dgrad_add (dx = dgrad(dy) + add) and mednet_conv3d_dgrad_gn with gn_act none / ReLU, add present / absent and
-    power-of-two gn_coef: dx exact and the summed rows EQUAL {sum du, sum du * gn_y} computed in fp64 from the reference dx."""
+    """mednet_conv3d_dgrad_add (dx = dgrad(dy) + add) and mednet_conv3d_dgrad_gn with gn_act none / ReLU / ELU, add present / absent
+    and power-of-two gn_coef: dx exact and the summed rows EQUAL {sum du, sum du * gn_y} computed in fp64 from the reference dx.
+    ELU has coefficients of its own (dgrad_inputs): this kernel's ELU' is exp(pre-activation), pinned where it is exactly 0 or 1."""
     key = (n, cin, cout, shape)
     dt, dcode = DT[mode], dcode_of(mode)
     t, gy64, variants = dgrad_conditions(key, dt)
@@ -694,7 +718,7 @@ def test_fused_data_gradient_epilogues(mode, n, cin, cout, shape, kinds, opts):
     d, h, wd = shape
     algo = L.ALGO_AUTO if mode == "fp32" else L.ALGO_MFMA
     dev = lambda a: a.to(DEV).to(dt).contiguous(memory_format=CL)
-    dyg, addg, gyg, coef = dev(t["dy"]), dev(t["add"]), dev(t["gy"]), t["coef"].to(DEV)
+    dyg, addg, gyg, coef, coef_elu = dev(t["dy"]), dev(t["add"]), dev(t["gy"]), t["coef"].to(DEV), t["coef_elu"].to(DEV)
     total = 0
     with options(**opts):
         if kinds is not None:
@@ -714,7 +738,7 @@ def test_fused_data_gradient_epilogues(mode, n, cin, cout, shape, kinds, opts):
             dx = torch.full((n, cin, *shape), float("nan"), device=DEV).to(dt).contiguous(memory_format=CL)
             part = torch.full((n, rows, cin, 2), float("nan"), device=DEV)
             L.check(lib.mednet_conv3d_dgrad_gn(dyg.data_ptr(), pk.data_ptr(), addg.data_ptr() if with_add else None, dx.data_ptr(),
-                                               gyg.data_ptr(), coef.data_ptr(), act, part.data_ptr(), n, d, h, wd, cin, cout, algo,
+                                               gyg.data_ptr(), (coef_elu if act == L.ACT_ELU else coef).data_ptr(), act, part.data_ptr(), n, d, h, wd, cin, cout, algo,
                                                dcode, L.stream()), "dgrad_gn")
             torch.cuda.synchronize()
             what = f"dgrad_gn {mode} {key} add={with_add} act={act}"
@@ -722,9 +746,36 @@ def test_fused_data_gradient_epilogues(mode, n, cin, cout, shape, kinds, opts):
     report("e", f"{key} {mode}", f"plan kinds {kinds}", total)
 
 
+POOL_GN_CASES = [(2, 32, (8, 12, 16), "max", True), (1, 64, (6, 4, 10), "avg", True), (2, 16, (4, 8, 6), "max", False)]
+
+
+def pool_gn_inputs(n, c, shape, pool, with_add, dt):
+    """-> dy of the pooling, add, gn_y and per activation (block output, reference dx, du), the exactness conditions asserted.
+    none / ReLU: a block output with ties inside the windows; ELU: the dyadic lattice gpu_util.ELU_Z with a unique maximum per
+    window (the pooling backward selects by this tensor, so dx is another one)."""
+    d, h, w = shape
+    tag = f"expg{n, c, shape, pool}"
+    dyp = lattice(tag + "g", n, c, d // 2, h // 2, w // 2, values=(-16, -8, 8, 16), density=0.6)   # multiples of 8: avg divides by 8
+    add = lattice(tag + "a", n, c, *shape, density=0.5) if with_add else None
+    gy = lattice(tag + "y", n, c, *shape, density=0.5)
+    outs = {False: lattice(tag + "o", n, c, *shape, values=(-2, -1, 1, 2, 3), density=0.7),      # block output: ties inside the windows
+            True: elu_lattice(tag + "e", n, c, *shape, window_max=True)}
+    refs = {}
+    for act in GN_ACTS:
+        out = outs[act == L.ACT_ELU]
+        xr = out.double().requires_grad_(True)
+        (F.max_pool3d if pool == "max" else F.avg_pool3d)(xr, 2).backward(dyp.double())
+        dx_ref = xr.grad + (add.double() if with_add else 0)
+        assert_representable(dx_ref, dt, "pool2_bwd_gn dx")
+        assert_representable(out, dt, "pool2_bwd_gn block output")
+        du = gn_reference(dx_ref, out.double(), act)
+        check_sum_conditions(du, tag, other=gy.double(), unit=SUM_UNIT[act])
+        refs[act] = (out, dx_ref, du)
+    return dyp, add, gy, refs
+
+
 @pytest.mark.parametrize("mode", ["bf16", "fp16", "fp32"])
-@pytest.mark.parametrize("n,c,shape,pool,with_add", [(2, 32, (8, 12, 16), "max", True), (1, 64, (6, 4, 10), "avg", True),
-                                                      (2, 16, (4, 8, 6), "max", False)])
+@pytest.mark.parametrize("n,c,shape,pool,with_add", POOL_GN_CASES)
 def test_pooling_backward_with_groupnorm_sums(mode, n, c, shape, pool, with_add):
     """mednet_pool2_bwd_gn: dx = pooling backward (+ add), du = dx * act'(block output), rows = {sum du, sum du * gn_y}."""
     dt, dcode = DT[mode], dcode_of(mode)
@@ -733,19 +784,11 @@ def test_pooling_backward_with_groupnorm_sums(mode, n, c, shape, pool, with_add)
     rows = lib.mednet_pool2_bwd_gn_rows(n, d, h, w, c, dcode)
     assert rows > 0
     tag = f"expg{n, c, shape, pool}"
-    out = lattice(tag + "o", n, c, *shape, values=(-2, -1, 1, 2, 3), density=0.7)      # block output: ties inside the windows
-    dyp = lattice(tag + "g", n, c, d // 2, h // 2, w // 2, values=(-16, -8, 8, 16), density=0.6)   # multiples of 8: avg divides by 8
-    add = lattice(tag + "a", n, c, *shape, density=0.5) if with_add else None
-    gy = lattice(tag + "y", n, c, *shape, density=0.5)
-    xr = out.double().requires_grad_(True)
-    (F.max_pool3d if pool == "max" else F.avg_pool3d)(xr, 2).backward(dyp.double())
-    dx_ref = xr.grad + (add.double() if with_add else 0)
-    assert_representable(dx_ref, dt, "pool2_bwd_gn dx")
+    dyp, add, gy, refs = pool_gn_inputs(n, c, shape, pool, with_add, dt)
     dev = lambda a: None if a is None else a.to(DEV).to(dt).contiguous(memory_format=CL)
     total = 0
-    for act in (L.ACT_NONE, L.ACT_RELU):
-        du = gn_reference(dx_ref, out.double(), act)
-        check_sum_conditions(du, tag, other=gy.double())
+    for act in GN_ACTS:
+        out, dx_ref, du = refs[act]
         dx = torch.full((n, c, *shape), float("nan"), device=DEV).to(dt).contiguous(memory_format=CL)
         part = torch.full((n, rows, c, 2), float("nan"), device=DEV)
         outg, dypg, addg, gyg = dev(out), dev(dyp), dev(add), dev(gy)
@@ -756,8 +799,31 @@ def test_pooling_backward_with_groupnorm_sums(mode, n, c, shape, pool, with_add)
     report("e", f"pool2_bwd_gn {n, c, shape, pool} {mode}", "pool2_bwd_gn", total)
 
 
+HEAD_GN_CASES = [(2, 32, 4, (6, 8, 10)), (1, 64, 2, (9, 11, 21)), (2, 16, 3, (5, 6, 7))]
+
+
+def head_gn_inputs(n, cin, cout, shape, dt):
+    """-> weights, dy, gn_y, the reference dx and per activation (block output, du), the exactness conditions asserted."""
+    tag = f"exhg{n, cin, cout, shape}"
+    wt = lattice(tag + "w", cout, cin, 1, 1, 1, values=(-3, -2, -1, 1, 2, 3), density=0.75)
+    dy = lattice(tag + "g", n, cout, *shape, density=0.5)
+    gy = lattice(tag + "y", n, cin, *shape, density=0.5)
+    gzs = {False: lattice(tag + "z", n, cin, *shape, values=(-1, 1, 2), density=0.7),      # the block output
+           True: elu_lattice(tag + "e", n, cin, *shape)}
+    dx_ref = torch.einsum("nozyx,oc->nczyx", dy.double(), wt.double()[:, :, 0, 0, 0])
+    assert_representable(dx_ref, dt, "head_dgrad_gn dx")
+    refs = {}
+    for act in GN_ACTS:
+        gz = gzs[act == L.ACT_ELU]
+        assert_representable(gz, dt, "head_dgrad_gn block output")
+        du = gn_reference(dx_ref, gz.double(), act)
+        check_sum_conditions(du, tag, other=gy.double(), unit=SUM_UNIT[act])
+        refs[act] = (gz, du)
+    return wt, dy, gy, dx_ref, refs
+
+
 @pytest.mark.parametrize("mode", ["bf16", "fp16", "fp32"])
-@pytest.mark.parametrize("n,cin,cout,shape", [(2, 32, 4, (6, 8, 10)), (1, 64, 2, (9, 11, 21)), (2, 16, 3, (5, 6, 7))])
+@pytest.mark.parametrize("n,cin,cout,shape", HEAD_GN_CASES)
 def test_head_data_gradient_with_groupnorm_sums(mode, n, cin, cout, shape):
     """mednet_head_dgrad_gn: dx = W^T dlogits (planar fp32 logit gradients), du = dx * act'(block output), rows = {sum du,
     sum du * gn_y}."""
@@ -766,21 +832,15 @@ def test_head_data_gradient_with_groupnorm_sums(mode, n, cin, cout, shape):
     d, h, w = shape
     rows = lib.mednet_head_dgrad_gn_rows(n, d, h, w, cin, dcode)
     assert rows > 0
-    tag = f"exhg{n, cin, cout, shape}"
-    wt = lattice(tag + "w", cout, cin, 1, 1, 1, values=(-3, -2, -1, 1, 2, 3), density=0.75)
-    dy = lattice(tag + "g", n, cout, *shape, density=0.5)
-    gy = lattice(tag + "y", n, cin, *shape, density=0.5)
-    gz = lattice(tag + "z", n, cin, *shape, values=(-1, 1, 2), density=0.7)      # the block output
-    dx_ref = torch.einsum("nozyx,oc->nczyx", dy.double(), wt.double()[:, :, 0, 0, 0])
-    assert_representable(dx_ref, dt, "head_dgrad_gn dx")
+    wt, dy, gy, dx_ref, refs = head_gn_inputs(n, cin, cout, shape, dt)
     with mednet_hip.precision(mode):
         pk = ops.pack_conv_weight(wt.to(DEV), 1, False)
     dev = lambda a: a.to(DEV).to(dt).contiguous(memory_format=CL)
-    dyg, gyg, gzg = dy.to(DEV).contiguous(), dev(gy), dev(gz)
+    dyg, gyg = dy.to(DEV).contiguous(), dev(gy)
     total = 0
-    for act in (L.ACT_NONE, L.ACT_RELU):
-        du = gn_reference(dx_ref, gz.double(), act)
-        check_sum_conditions(du, tag, other=gy.double())
+    for act in GN_ACTS:
+        gz, du = refs[act]
+        gzg = dev(gz)
         dx = torch.full((n, cin, *shape), float("nan"), device=DEV).to(dt).contiguous(memory_format=CL)
         part = torch.full((n, rows, cin, 2), float("nan"), device=DEV)
         L.check(lib.mednet_head_dgrad_gn(dyg.data_ptr(), pk.data_ptr(), dx.data_ptr(), gyg.data_ptr(), gzg.data_ptr(), act, part.data_ptr(),
@@ -790,31 +850,47 @@ def test_head_data_gradient_with_groupnorm_sums(mode, n, cin, cout, shape):
     report("e", f"head_dgrad_gn {n, cin, cout, shape} {mode}", "head_dgrad_gn", total)
 
 
+CONVT_GN_CASES = [(2, 64, 32, (3, 5, 9), 2), (1, 32, 32, (5, 9, 17), 2), (2, 64, 32, (16, 32, 32), 7)]
+
+
+def convt_gn_inputs(n, cin, cout, shape, mode):
+    """-> the ConvTranspose3d case, gn_y, the reference dx and per activation (block output, du), the conditions asserted."""
+    c = case("convt", n, cin, cout, shape, bias=True, skip=True)
+    c.check_conditions(mode)
+    dx_ref = c.ref()[0]["dx"]
+    tag = f"exct{n, cin, cout, shape}"
+    gy = lattice(tag + "y", n, cin, *shape, values=(-1, 1), density=0.25)
+    gzs = {False: lattice(tag + "z", n, cin, *shape, values=(-1, 1, 2), density=0.7), True: elu_lattice(tag + "e", n, cin, *shape)}
+    refs = {}
+    for act in GN_ACTS:
+        gz = gzs[act == L.ACT_ELU]
+        assert_representable(gz, DT[mode], "convt3d_dgrad_gn block output")
+        du = gn_reference(dx_ref, gz.double(), act)
+        check_sum_conditions(du, tag, other=gy.double(), unit=SUM_UNIT[act])
+        refs[act] = (gz, du)
+    return c, gy, dx_ref, refs
+
+
 @pytest.mark.parametrize("mode", MODES16)
-@pytest.mark.parametrize("n,cin,cout,shape,kind", [(2, 64, 32, (3, 5, 9), 2), (1, 32, 32, (5, 9, 17), 2), (2, 64, 32, (16, 32, 32), 7)])
+@pytest.mark.parametrize("n,cin,cout,shape,kind", CONVT_GN_CASES)
 def test_conv_transpose_data_gradient_with_groupnorm_sums(mode, n, cin, cout, shape, kind):
     """mednet_convt3d_dgrad_gn (conv_mfma_kernel<2> and convt_dgrad32_mfma_kernel): dx of the ConvTranspose3d, du = dx * act'(block
     output), rows = {sum du, sum du * gn_y}."""
     dt, dcode = DT[mode], dcode_of(mode)
     lib = L.lib()
     d, h, w = shape
-    c = case("convt", n, cin, cout, shape, bias=True, skip=True)
-    c.check_conditions(mode)
-    dx_ref = c.ref()[0]["dx"]
+    c, gy, dx_ref, refs = convt_gn_inputs(n, cin, cout, shape, mode)
     assert stats_plan(n, shape, cin, cout, dcode, gnb=1, stride=2)[0] == kind
     rows = lib.mednet_convt3d_dgrad_gn_rows(n, d, h, w, cin, cout, dcode, L.ALGO_MFMA)
     assert rows > 0
-    tag = f"exct{n, cin, cout, shape}"
-    gy = lattice(tag + "y", n, cin, *shape, values=(-1, 1), density=0.25)
-    gz = lattice(tag + "z", n, cin, *shape, values=(-1, 1, 2), density=0.7)
     with mednet_hip.precision(mode):
         pk = ops.pack_conv_weight(c.w.to(DEV), 3, True)
     dev = lambda a: a.to(DEV).to(dt).contiguous(memory_format=CL)
-    dyg, gyg, gzg = dev(c.g), dev(gy), dev(gz)
+    dyg, gyg = dev(c.g), dev(gy)
     total = 0
-    for act in (L.ACT_NONE, L.ACT_RELU):
-        du = gn_reference(dx_ref, gz.double(), act)
-        check_sum_conditions(du, tag, other=gy.double())
+    for act in GN_ACTS:
+        gz, du = refs[act]
+        gzg = dev(gz)
         dx = torch.full((n, cin, *shape), float("nan"), device=DEV).to(dt).contiguous(memory_format=CL)
         part = torch.full((n, rows, cin, 2), float("nan"), device=DEV)
         L.check(lib.mednet_convt3d_dgrad_gn(dyg.data_ptr(), pk.data_ptr(), dx.data_ptr(), gyg.data_ptr(), gzg.data_ptr(), act, part.data_ptr(),
