@@ -254,16 +254,17 @@ def _first_bad(bad, got, ref, bound, first=6):
                       f"bound {bound[tuple(i.tolist())].item():.3e}" for i in idx)
 
 
-def ref_error(x32, x64, norm, what):
+def ref_error(x32, x64, norm, what, floor=EPS_FLOOR, s=0.0):
     """r32 = max |x32 - x64| / norm over all elements: what ATen's fp32 evaluation shows against its fp64 one in the
     normalisation of the bound (an element whose norm is 0 has no terms: both references must be 0 there).  -> (r32, eps_case),
-    eps_case = max(EPS_FLOOR, 8 * r32)."""
+    eps_case = max(floor, 8 * r32); the floor is the kernel's own count of roundings (EPS_FLOOR for the matrix-core heads); s is
+    the absolute slack of the bound (check_gradient's s)."""
     x32, x64, norm = x32.detach().double(), x64.detach().double(), norm.detach().double()
-    diff = (x32 - x64).abs()
+    diff = ((x32 - x64).abs() - s).clamp(min=0)
     dead = norm == 0
     assert not bool((diff[dead] != 0).any()), f"{what}: the fp32 and fp64 references differ where the bound's norm is 0"
     r32 = float((diff[~dead] / norm[~dead]).max()) if bool((~dead).any()) else 0.0
-    return r32, max(EPS_FLOOR, 8.0 * r32)
+    return r32, max(floor, 8.0 * r32)
 
 
 def check_gradient(got, ref64, norm, eps, what, u=0.0, s=0.0):
@@ -304,3 +305,372 @@ def check_gn_sums(partial, dz_stored, z, gn_y, act, what):
     assert nbad == 0, f"{what}: {nbad} of {got.numel()} GroupNorm sums outside 2^-16 * sum |terms|; first at " + _first_bad(bad, got, want, bound)
     live = mag > 0
     return float((diff[live] / mag[live]).max()) if bool(live.any()) else 0.0
+
+
+# ------------------------------------------------------------------------------- the loss kernels and the Adam step
+# Inputs, fp64 references and checkers of tests/test_gpu_losses.py (csrc/loss.hip, the Adam kernels of csrc/norm_act.hip).
+# tests/test_loss_util.py runs all of them on the CPU: the exact inputs meet their premises, ATen's fp32 results pass the bounds,
+# and every checker rejects the fault it is there for.  Tensors of a case are [n, c, S] (S = the voxels of a sample).
+LOSS_BLOCK_VOX = 2048          # voxels per workgroup of loss.hip; one fp32 partial row per workgroup, the rows are added in fp64
+U32 = 2.0 ** -24               # one fp32 rounding
+LOSS_SUM_BOUND = 2.0 ** -18    # a sum of loss.hip: p a few ulp off (expf, reciprocal), 8 additions per lane, 8 levels of the
+#                                workgroup sum, fp64 from there: under 24 roundings of 2^-24, doubled
+LOSS_EPS_FLOOR = 2.0 ** -20    # a logit gradient of loss.hip / an Adam update: sixteen fp32 roundings
+F32_TINY = 2.0 ** -126         # fp32's smallest normal number: below it a result has no relative precision (a saturated softmax gives
+#                                logit gradients of 1e-48), so a logit gradient is admitted this absolute error on top of its bound
+
+
+def _np_rng(tag):
+    return O._rng("in:" + tag)
+
+
+def block_abs_sums(terms):
+    """terms [..., S] -> the fp64 sum of |terms| over every block of LOSS_BLOCK_VOX voxels [..., blocks]: what a workgroup adds."""
+    t = terms.detach().double().abs()
+    S = t.shape[-1]
+    nb = -(-S // LOSS_BLOCK_VOX)
+    t = torch.nn.functional.pad(t, (0, nb * LOSS_BLOCK_VOX - S))
+    return t.reshape(t.shape[:-1] + (nb, LOSS_BLOCK_VOX)).sum(-1)
+
+
+def f32_scalar(t):
+    """A 0-dim fp32 tensor (device or CPU) as numpy float32, bits kept."""
+    return np.float32(t.detach().float().cpu().numpy())
+
+
+def assert_same_f32(got, want, what):
+    """Bit-for-bit equality of two fp32 scalars (+0 == -0); a NaN is expected exactly where `want` is NaN."""
+    got, want = np.float32(got), np.float32(want)
+    if np.isnan(want):
+        assert np.isnan(got), f"{what}: got {got!r}, want NaN"
+    else:
+        assert got == want, f"{what}: got {got!r} want {want!r} (difference {float(got) - float(want):.3e})"
+
+
+# ---- A.1 heat-map regression on integers
+def hm_exact_case(tag, n, c, shape, tgt="u8"):
+    """Targets: channels [:-1] of an n x (c + 1) x shape volume of integers 0..255 (uint8, or fp32 holding them); out = target + delta,
+    delta an integer in [-64, 64] (a tenth of them 0); channel weights and dloss powers of two."""
+    g = _np_rng(tag)
+    S = int(np.prod(shape))
+    vol = g.integers(0, 256, size=(n, c + 1, S))
+    delta = g.integers(-64, 65, size=(n, c, S))
+    delta[g.random(delta.shape) < 0.1] = 0
+    volume = torch.from_numpy(vol.astype(np.uint8 if tgt == "u8" else np.float32)).reshape((n, c + 1) + tuple(shape))
+    out = torch.from_numpy((vol[:, :-1] + delta).astype(np.float32)).reshape((n, c) + tuple(shape))
+    w = torch.from_numpy((2.0 ** g.integers(-3, 2, size=c)).astype(np.float32))
+    return types.SimpleNamespace(n=n, c=c, shape=tuple(shape), spatial=S, volume=volume, target=volume[:, :-1], out=out, w=w, dloss=0.5,
+                                 count=n * S, tgt=tgt)
+
+
+def hm_reference(case, kind):
+    """fp64 sums S_c (exact integers), the loss as the finalize kernel forms it -- tot = f32(tot + f32(w_c) * f32(S_c / count)), c
+    ascending, S_c / count in fp64 -- and the gradient: fp64 for L2, the exact fp32 numbers sign(d) * f32(dloss * w_c) * f32(1 / count)
+    for L1.  Asserts the premise: the sum of |terms| of every workgroup is below 2^24, so its fp32 partial is exact in any order."""
+    n, c, S = case.n, case.c, case.spatial
+    d = (case.out.double() - case.target.double()).reshape(n, c, S)
+    assert float(d.abs().max()) <= 64 and bool((d == d.round()).all())
+    f = d * d if kind == "L2" else d.abs()
+    assert_sums_exact(block_abs_sums(f), f"heat-map {kind} block sums")
+    Sc = f.sum((0, 2))
+    w = case.w.numpy()
+    assert bool((np.log2(w) == np.round(np.log2(w))).all()), "channel weights must be powers of two"
+    tot = np.float32(0)
+    for k in range(c):
+        tot = np.float32(tot + np.float32(w[k]) * np.float32(float(Sc[k]) / case.count))
+    loss64 = float((case.w.double() * Sc / case.count).sum())
+    sgn = 2.0 * d if kind == "L2" else torch.sign(d)
+    grad64 = (case.dloss * case.w.double()[None, :, None] / case.count) * sgn
+    scale32 = (np.float32(case.dloss) * w) * np.float32(1.0 / case.count)
+    assert scale32.dtype == np.float32
+    grad_l1 = torch.sign(d).float() * torch.from_numpy(scale32)[None, :, None]
+    return types.SimpleNamespace(d=d, Sc=Sc, loss32=tot, loss64=loss64, grad64=grad64, grad_l1=grad_l1, kind=kind)
+
+
+def check_hm(case, ref, loss, dout, what):
+    """loss: the very bits of ref.loss32.  dout [n, c, S]: L1 equals +-scale exactly and is exactly 0 where d = 0; L2 is within
+    4 * 2^-24 * |ref64| per element (float(1 / count), the product with the weight and the final product round once each).
+    -> the worst observed |dout - ref64| / |ref64| (L2; 0 for L1)."""
+    assert_same_f32(loss, ref.loss32, what + ": loss")
+    dout = dout.detach().cpu().reshape(case.n, case.c, case.spatial)
+    if ref.kind == "L1":
+        assert_exact(dout, ref.grad_l1, what + ": dout")
+        return 0.0
+    return check_gradient(dout, ref.grad64, ref.grad64.abs(), 4.0 * U32, what + ": dout")
+
+
+# ---- A.2 cross-entropy with terms of w_y * 200 or 0
+CE_WEIGHTS = (0.25, 0.5, 1.0, 2.0, 4.0)
+
+
+def ce_exact_case(tag, n, c, shape, ignore=-100, ignored="some"):
+    """Logits -200 everywhere except one 0 per voxel at a random class (fp32 exp(-200) is exactly 0, so a voxel's term is
+    w_y * 200, or 0 where the label is that class); labels independent of that class; weights from CE_WEIGHTS; ignored: "some"
+    (a tenth of the voxels carry ignore_index), "sample" (also all of sample 0) or "all"."""
+    g = _np_rng(tag)
+    S = int(np.prod(shape))
+    hot = g.integers(0, c, size=(n, S))
+    lg = np.full((n, c, S), -200.0, dtype=np.float32)
+    np.put_along_axis(lg, hot[:, None, :], 0.0, axis=1)
+    lab = g.integers(0, c, size=(n, S)).astype(np.int64)
+    lab[g.random((n, S)) < 0.1] = ignore
+    if ignored == "sample":
+        lab[0] = ignore
+    elif ignored == "all":
+        lab[:] = ignore
+    w = torch.from_numpy(g.choice(np.asarray(CE_WEIGHTS), size=c).astype(np.float32))
+    return types.SimpleNamespace(n=n, c=c, shape=tuple(shape), spatial=S, lg=torch.from_numpy(lg), hot=torch.from_numpy(hot),
+                                 lab=torch.from_numpy(lab), w=w, ignore=ignore)
+
+
+def ce_exact_reference(case):
+    """num64 = sum w_y * 200 [y != the voxel's 0 class], den64 = sum w_y over the live voxels, both exact in fp64; the finalize kernel
+    divides in fp64 and rounds once: loss32 = f32(num64 / den64) (NaN when every voxel is ignored, as in ATen), saved32 = f32(den64).
+    Asserts the premise: every workgroup's sums are below 2^24 steps of 50 (num) and of 1/4 (den)."""
+    live = case.lab != case.ignore
+    wy = torch.where(live, case.w.double()[case.lab.clamp(0, case.c - 1)], torch.zeros((), dtype=torch.float64))
+    term = wy * 200.0 * (case.lab != case.hot)
+    assert_sums_exact(block_abs_sums(term), "CE numerator block sums", unit=50.0)
+    assert_sums_exact(block_abs_sums(wy), "CE denominator block sums", unit=0.25)
+    num64, den64 = float(term.sum()), float(wy.sum())
+    loss32 = np.float32(num64 / den64) if den64 != 0.0 else np.float32("nan")
+    return types.SimpleNamespace(num64=num64, den64=den64, loss32=loss32, saved32=np.float32(den64))
+
+
+def check_ce_exact(ref, loss, saved0, what):
+    assert_same_f32(saved0, ref.saved32, what + ": saved[0] against sum w_y")
+    assert_same_f32(loss, ref.loss32, what + ": loss against f32(num64 / den64)")
+
+
+# ---- A.3 Dice with probabilities in {0, 1/4, 1/2, 1}
+def dice_exact_case(tag, n, c, shape, sigmoid):
+    """softmax: logits in {0, -200} with 1, 2 or 4 zeros per voxel (as many as c allows): p in {0, 1/4, 1/2, 1} exactly (exp(-200) is
+    0 in fp32, the reciprocal of 1, 2, 4 is exact); sigmoid: logits in {-200, 0, 200}: p in {0, 1/2, 1}.  -> lg, the exact p (fp64),
+    labels, weights in [0.05, 1.05)."""
+    g = _np_rng(tag)
+    S = int(np.prod(shape))
+    if sigmoid:
+        lg = g.choice(np.asarray([-200.0, 0.0, 200.0]), size=(n, c, S))
+        p = (lg + 200.0) / 400.0
+    else:
+        k = g.choice(np.asarray([k for k in (1, 2, 4) if k <= c]), size=(n, 1, S))
+        rank = np.argsort(np.argsort(g.random((n, c, S)), axis=1), axis=1)
+        zero = rank < k
+        lg = np.where(zero, 0.0, -200.0)
+        p = zero / k
+    lab = g.integers(0, c, size=(n, S)).astype(np.int64)
+    w = torch.from_numpy((0.05 + g.random(c)).astype(np.float32))
+    return types.SimpleNamespace(n=n, c=c, shape=tuple(shape), spatial=S, lg=torch.from_numpy(lg.astype(np.float32)),
+                                 p=torch.from_numpy(p.astype(np.float64)), lab=torch.from_numpy(lab), w=w, sigmoid=sigmoid, eps=1e-5)
+
+
+def dice_sums(p, lab, ignore):
+    """One-hot target t, mask m (the reference masks where the ONE-HOT target equals ignore_index) and the Dice sums
+    I_c = sum p t m, D_c = sum (p + t) m over samples and voxels, in p's precision.  p [n, c, S], lab [n, S] in [0, c)."""
+    t = torch.nn.functional.one_hot(lab, p.shape[1]).permute(0, 2, 1).to(p.dtype)
+    m = torch.ones_like(t) if ignore is None else (t != ignore).to(p.dtype)
+    return t, m, (p * t * m).sum((0, 2)), ((p + t) * m).sum((0, 2))
+
+
+def dice_from_sums(I, D, w, eps):
+    dice = 2.0 * (w * I) / D.clamp(min=eps)
+    return dice, (1.0 - dice).mean()
+
+
+def dice_exact_reference(case, ignore):
+    """saved64 [c, 2] = {I_c, D_c}, dice64, loss64 from the exact probabilities.  Asserts the premise: the sums of a workgroup and
+    the totals are below 2^24 steps of 1/4 (fp32 partials and the fp32 `saved` hold them exactly)."""
+    t, m, I, D = dice_sums(case.p, case.lab, ignore)
+    assert_sums_exact(block_abs_sums((case.p + t) * m), "Dice block sums", unit=0.25)
+    assert_sums_exact(D, "Dice totals", unit=0.25)
+    dice, loss = dice_from_sums(I, D, case.w.double(), case.eps)
+    return types.SimpleNamespace(saved64=torch.stack((I, D), -1), dice64=dice, loss64=float(loss))
+
+
+def check_dice_exact(case, ref, saved, dice_out, loss, what):
+    """saved: every entry equals the fp64 sum.  dice_out: within 2 * 2^-24 * |dice64| (the product with the weight and the division
+    round once each).  loss: within (C + 4) * 2^-24 * (1 + max |dice64|) (product, division, 1 - dice, C - 1 additions, the division
+    by C).  -> the observed |loss - loss64| / ((1 + max |dice64|) * 2^-24), to be read against C + 4."""
+    assert_exact(saved.detach().cpu().reshape(case.c, 2), ref.saved64, what + ": saved")
+    if dice_out is not None:
+        check_gradient(dice_out.detach().cpu(), ref.dice64, ref.dice64.abs(), 2.0 * U32, what + ": dice_out")
+    got = float(loss)
+    unit = U32 * (1.0 + float(ref.dice64.abs().max()))
+    assert not np.isnan(got), what + ": loss is NaN"
+    err = abs(got - ref.loss64)
+    assert err <= (case.c + 4) * unit, f"{what}: |loss - loss64| = {err:.3e} > (C + 4) 2^-24 (1 + max |dice|) = {(case.c + 4) * unit:.3e}"
+    return err / unit
+
+
+# ---- B. random logits against fp64
+def loss_random_case(tag, n, c, shape, edge=False):
+    """Logits N(0, 2^2); 2% of the voxels have one channel pushed to +-30, 2% an exact tie of channels 0 and 1; weights in
+    [0.05, 1.05); a tenth of the voxels are marked for cross-entropy's ignore_index (case.ign).  edge: dloss = -2.5, eps = 1e-2, the
+    weight of class 1 is 0, and the last channel is dead -- logit -40 everywhere, never a label -- so its D is below eps (the zero
+    branch of the D gradient)."""
+    g = _np_rng(tag)
+    S = int(np.prod(shape))
+    lg = (2.0 * g.standard_normal((n, c, S))).astype(np.float32)
+    push = g.random((n, S)) < 0.02
+    ch = g.integers(0, c, size=(n, S))
+    val = np.where(g.random((n, S)) < 0.5, 30.0, -30.0).astype(np.float32)
+    cur = np.take_along_axis(lg, ch[:, None, :], axis=1)[:, 0]
+    np.put_along_axis(lg, ch[:, None, :], np.where(push, val, cur)[:, None, :], axis=1)
+    if c > 1:
+        tie = g.random((n, S)) < 0.02
+        lg[:, 1] = np.where(tie, lg[:, 0], lg[:, 1])
+    lab = g.integers(0, c, size=(n, S)).astype(np.int64)
+    w = (0.05 + g.random(c)).astype(np.float32)
+    ign = g.random((n, S)) < 0.1
+    eps, dloss = 1e-5, 1.0
+    if edge:
+        eps, dloss = 1e-2, -2.5
+        if c > 1:
+            w[1] = 0.0
+        if c > 2:
+            lg[:, c - 1] = -40.0
+            lab[lab == c - 1] = 0
+    return types.SimpleNamespace(n=n, c=c, shape=tuple(shape), spatial=S, lg=torch.from_numpy(lg), lab=torch.from_numpy(lab),
+                                 w=torch.from_numpy(w), ign=torch.from_numpy(ign), eps=eps, dloss=dloss, edge=edge)
+
+
+def dice_chain(case, sigmoid, ignore, dtype):
+    """The Dice loss as plain torch expressions in `dtype` on the CPU, autograd for the logit gradient."""
+    lg = case.lg.to(dtype).clone().requires_grad_(True)
+    p = torch.sigmoid(lg) if sigmoid else torch.softmax(lg, 1)
+    t, m, I, D = dice_sums(p, case.lab, ignore)
+    dice, loss = dice_from_sums(I, D, case.w.to(dtype), case.eps)
+    (loss * case.dloss).backward()
+    return types.SimpleNamespace(loss=float(loss.detach()), saved=torch.stack((I, D), -1).detach(), dice=dice.detach(), dlg=lg.grad, p=p.detach(),
+                                 t=t, m=m)
+
+
+def dice_grad_norm(case, r64, sigmoid):
+    """The sum of the absolute terms of a Dice logit gradient, in fp64: with g = dL/dp = m (gI t m + gD),
+    softmax: A[k, v] = p_k (|g_k| + sum_j p_j |g_j|); sigmoid: A[k, v] = |g_k| p_k (1 + p_k) (g p - g p^2: 1 - p cancels where the
+    sigmoid saturates)."""
+    I, D = r64.saved[:, 0], r64.saved[:, 1]
+    w, c = case.w.double(), case.c
+    Dc = D.clamp(min=case.eps)
+    gI = (-2.0 * w / (c * Dc) * case.dloss)[None, :, None]
+    gD = (torch.where(D >= case.eps, 2.0 * w * I / (c * Dc * Dc), torch.zeros_like(D)) * case.dloss)[None, :, None]
+    g = (r64.m * (gI * r64.t * r64.m + gD)).abs()
+    if sigmoid:
+        return g * r64.p * (1.0 + r64.p)
+    return r64.p * (g + (r64.p * g).sum(1, keepdim=True))
+
+
+def ce_labels(case, ignore):
+    lab = case.lab.clone()
+    lab[case.ign] = ignore
+    return lab
+
+
+def ce_chain(case, ignore, dtype):
+    """F.cross_entropy(weight, ignore_index) in `dtype` on the CPU with autograd; in addition den = sum w_y over the live voxels, the
+    sum of |terms| of the loss (sum w_y |nll| / den) and the sum of absolute terms of the gradient |dloss| w_y / den (p_k + t_k)."""
+    lab = ce_labels(case, ignore)
+    lg = case.lg.to(dtype).clone().requires_grad_(True)
+    w = case.w.to(dtype)
+    loss = torch.nn.functional.cross_entropy(lg, lab, weight=w, ignore_index=ignore)
+    (loss * case.dloss).backward()
+    live = lab != ignore
+    safe = lab.clamp(0, case.c - 1)
+    wy = torch.where(live, w[safe], torch.zeros((), dtype=dtype))
+    den = wy.sum()
+    logp = torch.log_softmax(lg.detach(), 1)
+    nll = -logp.gather(1, safe[:, None, :])[:, 0]
+    t = torch.nn.functional.one_hot(safe, case.c).permute(0, 2, 1).to(dtype)
+    norm = abs(case.dloss) * (wy / den)[:, None, :] * (logp.exp() + t)
+    return types.SimpleNamespace(loss=float(loss.detach()), den=float(den), loss_terms=float((wy * nll.abs()).sum() / den), dlg=lg.grad, norm=norm)
+
+
+def check_loss_scalar(got, want64, terms, what, bound=LOSS_SUM_BOUND):
+    """|got - want64| <= bound * terms (the sum of the absolute terms).  -> the observed ratio |got - want64| / terms."""
+    got = float(got)
+    assert not np.isnan(got), what + ": NaN"
+    err = abs(got - want64)
+    assert err <= bound * terms, f"{what}: |got - ref64| = {err:.3e} > {bound:.3e} * sum |terms| = {bound * terms:.3e} (got {got!r} want {want64!r})"
+    return err / terms if terms > 0 else 0.0
+
+
+def loss_grad_eps(x32, x64, norm, what):
+    """(r32, eps_case) of a logit gradient: eps_case = max(2^-20, 8 * r32), r32 from ATen's fp32 autograd against its fp64 one."""
+    return ref_error(x32, x64, norm, what, floor=LOSS_EPS_FLOOR, s=F32_TINY)
+
+
+def check_dice_random(case, r64, norm, eps_case, saved, loss, dlg, what):
+    """saved [c, 2] and the loss within 2^-18 * sum |terms| (the sums: of themselves, their terms are positive; the loss:
+    mean_c (1 + |dice64_c|)); dlogits [n, c, S] through check_gradient with the case's eps.  -> observed ratios."""
+    s64 = r64.saved
+    return dict(saved=check_gradient(saved.detach().cpu().reshape(case.c, 2), s64, s64.abs(), LOSS_SUM_BOUND, what + ": saved"),
+                loss=check_loss_scalar(loss, r64.loss, float((1.0 + r64.dice.abs()).mean()), what + ": loss"),
+                dlg=check_gradient(dlg.detach().cpu().reshape(case.n, case.c, case.spatial), r64.dlg, norm, eps_case, what + ": dlogits",
+                                   s=F32_TINY))
+
+
+def check_ce_random(case, r64, eps_case, saved0, loss, dlg, what):
+    return dict(saved=check_loss_scalar(saved0, r64.den, r64.den, what + ": saved[0]"),
+                loss=check_loss_scalar(loss, r64.loss, r64.loss_terms, what + ": loss"),
+                dlg=check_gradient(dlg.detach().cpu().reshape(case.n, case.c, case.spatial), r64.dlg, r64.norm, eps_case, what + ": dlogits",
+                                   s=F32_TINY))
+
+
+# ---- C. Adam
+ADAM_HP = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8)
+
+
+def adam_case(tag, count):
+    """One step from a given state: random p, m, g, v >= 0; every 16th element has g = 0 and v = 0 (the denominator is eps)."""
+    g = _np_rng(tag)
+    f = lambda a: torch.from_numpy(a.astype(np.float32))
+    p, m, gr = f(g.standard_normal(count)), f(0.1 * g.standard_normal(count)), f(g.standard_normal(count))
+    v = f(0.01 * g.standard_normal(count) ** 2)
+    gr[::16] = 0.0
+    v[::16] = 0.0
+    return types.SimpleNamespace(count=count, p=p, g=gr, m=m, v=v)
+
+
+def adam_lines(p, g, m, v, lr, b1, b2, eps, wd, step, gscale, dtype, bias_correction=True):
+    """torch.optim.Adam's step (weight decay added to the gradient, eps added after the bias correction of the denominator) restated:
+    every operand, the hyper-parameters included, is a tensor of `dtype`, so float32 evaluates each line in fp32.  The
+    hyper-parameters are the fp32 numbers the C ABI receives.  -> p', m', v', the update delta = p - p'."""
+    s = lambda x: torch.tensor(float(np.float32(x)), dtype=dtype)
+    p, g, m, v = (t.to(dtype) for t in (p, g, m, v))
+    lr, b1, b2, eps, wd, gscale, one = s(lr), s(b1), s(b2), s(eps), s(wd), s(gscale), s(1.0)
+    gr = g * gscale + wd * p
+    m1 = b1 * m + (one - b1) * gr
+    v1 = b2 * v + (one - b2) * gr * gr
+    t = s(step)
+    bc1, bc2 = (one - b1 ** t, one - b2 ** t) if bias_correction else (one, one)
+    denom = v1.sqrt() / bc2.sqrt() + eps
+    delta = (lr / bc1) * (m1 / denom)
+    terms_m = (b1 * m).abs() + (one - b1) * ((g * gscale).abs() + (wd * p).abs())
+    terms_v = b2 * v + (one - b2) * gr * gr
+    terms_d = (lr / bc1) * (terms_m / denom)     # (= |delta| wherever b1 m and (1 - b1) g do not cancel)
+    return types.SimpleNamespace(p=p - delta, m=m1, v=v1, delta=delta, terms_m=terms_m, terms_v=terms_v, terms_d=terms_d)
+
+
+def adam_reference(case, wd, step, gscale):
+    """fp64 and fp32 evaluations of adam_lines and eps_case per tensor: max(2^-20, 8 * r32), r32 the fp32 lines' error in the norm
+    of the bound (m, v: the sum of |terms|; p: the update's own size |delta64|).  Where b1 m and (1 - b1) g cancel, delta inherits m's
+    absolute error, which is large against |delta64| itself: that one element inflates r32 of p (1e-3 at 10 007 elements) and with it
+    the bound of every element.  So p is ALSO held to eps_case of the update's sum of absolute terms (lr / bc1) terms_m / denom
+    ("pt"), whose r32 stays at a few 1e-6; check_adam asserts both."""
+    r64 = adam_lines(case.p, case.g, case.m, case.v, wd=wd, step=step, gscale=gscale, dtype=torch.float64, **ADAM_HP)
+    r32 = adam_lines(case.p, case.g, case.m, case.v, wd=wd, step=step, gscale=gscale, dtype=torch.float32, **ADAM_HP)
+    out = types.SimpleNamespace(r64=r64, r32=r32, r32s={}, eps={})
+    for name, x32, x64, norm in (("m", r32.m, r64.m, r64.terms_m), ("v", r32.v, r64.v, r64.terms_v), ("p", r32.delta, r64.delta, r64.delta.abs()),
+                                 ("pt", r32.delta, r64.delta, r64.terms_d)):
+        out.r32s[name], out.eps[name] = ref_error(x32, x64, norm, "Adam " + name, floor=LOSS_EPS_FLOOR)
+    return out
+
+
+def check_adam(ref, p, m, v, what):
+    """m, v: |got - ref64| <= eps_case * sum |terms|; p: |p - p64| <= 2^-24 |p64| + eps_case * |delta64| and, with its own eps_case,
+    <= 2^-24 |p64| + eps_case * (the update's sum of |terms|).  Every element, no NaN.  -> observed ratios."""
+    r = ref.r64
+    return dict(m=check_gradient(m, r.m, r.terms_m, ref.eps["m"], what + ": m"),
+                v=check_gradient(v, r.v, r.terms_v, ref.eps["v"], what + ": v"),
+                p=check_gradient(p, r.p, r.delta.abs(), ref.eps["p"], what + ": p", u=U32),
+                pt=check_gradient(p, r.p, r.terms_d, ref.eps["pt"], what + ": p against the update's terms", u=U32))

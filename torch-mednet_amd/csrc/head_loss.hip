@@ -48,8 +48,14 @@ struct Raw8<float> {
   __device__ __forceinline__ float at(int j) const { return j < 4 ? a[j] : b[j - 4]; }
 };
 
+// A label as an int.  An int64 label that does not fit an int (2^32 + 1) must not narrow to a class: it becomes a negative value
+// that is not ignore_index, so the range tests below see it as out of range.  Every label that fits is returned as it is.
 template <typename TL>
-__device__ __forceinline__ int label_at(const TL* __restrict__ lab, size_t i) { return (int)lab[i]; }
+__device__ __forceinline__ int label_at(const TL* __restrict__ lab, size_t i, int ignore) {
+  const int64_t y = (int64_t)lab[i];
+  if (y == (int64_t)(int)y) return (int)y;
+  return ignore == -1 ? -2 : -1;
+}
 
 // softmax / sigmoid of the class logits of one voxel (loss.hip probs_of, on registers)
 __device__ __forceinline__ void probs_reg(const float* lg, int c, int sigmoid, float* p) {
@@ -107,7 +113,7 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
 #pragma unroll
         for (int j = 0; j < 8; ++j) zv[q * 8 + j] = t.v[j];
       }
-      const int yl = label_at(lab, (size_t)n * lab_sn + v);
+      const int yl = label_at(lab, (size_t)n * lab_sn + v, ignore);
       float lg[HL_MAXC], p[HL_MAXC];
 #pragma unroll
       for (int i = 0; i < HL_MAXC; ++i) {
@@ -285,7 +291,7 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
         lb[i] = i < m ? lgs[((size_t)n * m + i) * spatial + vbs] : 0.f;
       }
     }
-    const int ya = label_at(lab, (size_t)n * lab_sn + v), yb = label_at(lab, (size_t)n * lab_sn + vbs);
+    const int ya = label_at(lab, (size_t)n * lab_sn + v, ignore), yb = label_at(lab, (size_t)n * lab_sn + vbs, ignore);
     const size_t rowa = ((size_t)n * spatial + v) * K + cgi * 8, rowb = ((size_t)n * spatial + vbs) * K + cgi * 8;
     Raw8<TO> zva, zvb, yva, yvb;
     zva.load(gz, rowa);

@@ -45,6 +45,14 @@ __device__ __forceinline__ void probs_of(const float* __restrict__ lg, size_t ba
   }
 }
 
+// The class of a label, or -1 for a label outside [0, C).  The range test is made on the label's own type BEFORE narrowing: an
+// int64 label of 2^32 + 1 is out of range, not class 1.  In-range labels give the same int as a plain cast.
+template <typename TL>
+__device__ __forceinline__ int class_of(TL label, int c) {
+  const int64_t y = (int64_t)label;
+  return (y >= 0 && y < (int64_t)c) ? (int)y : -1;
+}
+
 // partial[n][block][c][2] = {sum p*t*mask, sum (p+t)*mask}
 template <int MAXC, typename TL>
 __global__ __launch_bounds__(256) void dice_fwd_kernel(const float* __restrict__ lg, const TL* __restrict__ lab, int64_t lab_sn,
@@ -62,10 +70,10 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(const float* __restrict__
     if (v < spatial) {
       float p[MAXC];
       probs_of<MAXC>(lg, (size_t)n * sn + v, sc, c, sigmoid, p);
-      const int y = (int)lab[(size_t)n * lab_sn + v];
+      const int y = class_of(lab[(size_t)n * lab_sn + v], c);
       // A label outside [0, C) makes the reference raise (scatter_ index error, loss.py:81-86).  Raising from a kernel
       // would cost a host sync per step; instead the loss (and with it every gradient) becomes NaN: loud, not silent.
-      bad |= (unsigned)y >= (unsigned)c;
+      bad |= y < 0;
 #pragma unroll
       for (int k = 0; k < MAXC; ++k)
         if (k < c) {
@@ -156,7 +164,7 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
     if (v < spatial) {
       float p[MAXC], g[MAXC];
       probs_of<MAXC>(lg, (size_t)n * sn + v, sc, c, sigmoid, p);
-      const int y = (int)lab[(size_t)n * lab_sn + v];
+      const int y = class_of(lab[(size_t)n * lab_sn + v], c);
       float dot = 0.f;
 #pragma unroll
       for (int k = 0; k < MAXC; ++k)
@@ -188,10 +196,12 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
   for (int it = 0; it < 8; ++it) {
     const size_t v = v0 + (size_t)it * 256 + threadIdx.x;
     if (v < spatial) {
-      const int y = (int)lab[(size_t)n * spatial + v];
+      const int64_t yl = lab[(size_t)n * spatial + v];
+      const int y = class_of(yl, c);
+      const bool ign = yl == (int64_t)ignore;
       // nll_loss raises for a class index outside [0, C) that is not ignore_index; here the loss becomes NaN (see dice_fwd)
-      if (y != ignore && (unsigned)y >= (unsigned)c) num = __builtin_nanf("");
-      if (y != ignore && y >= 0 && y < c) {
+      if (!ign && y < 0) num = __builtin_nanf("");
+      if (!ign && y >= 0) {
         const size_t base = (size_t)n * sn + v;
         float mx = -INFINITY, zy = 0.f;
 #pragma unroll
@@ -253,8 +263,9 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
   for (int it = 0; it < 8; ++it) {
     const size_t v = v0 + (size_t)it * 256 + threadIdx.x;
     if (v < spatial) {
-      const int y = (int)lab[(size_t)n * spatial + v];
-      const bool live = (y != ignore && y >= 0 && y < c);
+      const int64_t yl = lab[(size_t)n * spatial + v];
+      const int y = class_of(yl, c);
+      const bool live = y >= 0 && yl != (int64_t)ignore;
       float p[MAXC];
       probs_of<MAXC>(lg, (size_t)n * sn + v, sc, c, 0, p);
       const float w = live ? (weight ? weight[y] : 1.f) * scale : 0.f;
