@@ -346,6 +346,61 @@ def test_landmark_ce_head_honours_ignore_index_and_poisons_bad_labels(mode):
     assert torch.isnan(cl_bad) and torch.isfinite(cl_ign)
 
 
+@pytest.mark.parametrize("mode", ["bf16", "fp16"])
+@pytest.mark.parametrize("shape,n,nh,ncls,kind", [((12, 10, 6), 3, 5, 3, "L1"), ((24, 20, 21), 2, 16, 2, "L2")])
+def test_landmark_cls_entries_with_dice_equal_the_plain_entries_bit_for_bit(mode, shape, n, nh, ncls, kind):
+    """mednet_head_landmark_cls_fwd / _cls_bwd with MEDNET_CLASS_DICE and no metric against mednet_head_landmark_fwd / _bwd on the same
+    inputs, through the C ABI: both losses, `saved`, dz, the GroupNorm partial rows, dW and db bit for bit, with and without gn_y.
+    (12, 10, 6): one workgroup per sample with a ragged last run; (24, 20, 21): two workgroups, the second short."""
+    from mednet_hip import _lib as L
+    lib, dt = L.lib(), {"bf16": torch.bfloat16, "fp16": torch.float16}[mode]
+    tag, sp, m = f"lmcls{shape}{nh}", int(np.prod(shape)), nh + ncls
+    z = ops.to_cl(rnd(tag + "z", n, 32, *shape).to(DEV).to(dt))
+    gy = ops.to_cl(rnd(tag + "y", n, 32, *shape).to(DEV).to(dt))
+    w, b = rnd(tag + "w", m, 32, 1, 1, 1, scale=0.3).to(DEV), rnd(tag + "b", m).to(DEV)
+    with mednet_hip.precision(mode):
+        pk = ops.pack_conv_weight(w, 1, False)
+    g = np.random.Generator(np.random.PCG64(81))
+    hm = torch.from_numpy(g.integers(0, 256, size=(n, nh) + shape).astype(np.uint8)).to(DEV)
+    lab = torch.from_numpy(g.integers(0, ncls, size=(n,) + shape).astype(np.uint8)).to(DEV)
+    cw = torch.tensor([0.05, 1.0, 0.7][:ncls], device=DEV)
+    rw = torch.tensor([0.015 + 0.003 * i for i in range(nh)], device=DEV)
+    dc, dr = torch.tensor(3.0, device=DEV), torch.tensor(1.5, device=DEV)
+    rk, code = (L.REG_L2 if kind == "L2" else L.REG_L1), L.dt_of(dt)
+    assert lib.mednet_head_landmark_supported(32, nh, ncls, code, sp) == 1
+    ws = L.workspace(lib.mednet_head_landmark_ws_bytes(n, sp, nh, ncls), z.device)
+    rows = lib.mednet_head_landmark_gn_rows(sp)
+    front = (z.data_ptr(), pk.data_ptr(), b.data_ptr(), hm.data_ptr(), nh * sp, lab.data_ptr(), sp, cw.data_ptr(), rw.data_ptr())
+    tail = (1e-5, 0, L.NO_IGNORE, code, ws.data_ptr(), ws.numel(), L.stream())
+    out = {}
+    for cls in (False, True):
+        closs, rloss = (torch.full((), float("nan"), device=DEV) for _ in range(2))
+        saved = torch.full((ncls, 2), float("nan"), device=DEV)
+        if cls:
+            L.check(lib.mednet_head_landmark_cls_fwd(*front, None, closs.data_ptr(), rloss.data_ptr(), saved.data_ptr(), None, n, sp, 32, nh,
+                                                     ncls, rk, L.CLASS_DICE, *tail), "head_landmark_cls_fwd")
+        else:
+            L.check(lib.mednet_head_landmark_fwd(*front, None, closs.data_ptr(), rloss.data_ptr(), saved.data_ptr(), n, sp, 32, nh, ncls, rk,
+                                                 *tail), "head_landmark_fwd")
+        res = [closs, rloss, saved]
+        for with_gy in (True, False):
+            dz = torch.full_like(z, float("nan"))
+            part = torch.full((n, rows, 32, 2), float("nan"), device=DEV) if with_gy else None
+            dw, db = torch.full((m, 32), float("nan"), device=DEV), torch.full((m,), float("nan"), device=DEV)
+            mid = (saved.data_ptr(), dc.data_ptr(), dr.data_ptr(), dz.data_ptr(), gy.data_ptr() if with_gy else None, L.ACT_ELU,
+                   L.ptr(part), dw.data_ptr(), db.data_ptr(), n, sp, 32, nh, ncls, rk)
+            if cls:
+                L.check(lib.mednet_head_landmark_cls_bwd(*front, *mid, L.CLASS_DICE, *tail), "head_landmark_cls_bwd")
+            else:
+                L.check(lib.mednet_head_landmark_bwd(*front, *mid, *tail), "head_landmark_bwd")
+            res += [dz, dw, db] + ([part] if with_gy else [])
+        torch.cuda.synchronize()
+        out[cls] = res
+    names = ["class loss", "regression loss", "saved", "dz", "dW", "db", "GroupNorm rows", "dz (no gn_y)", "dW (no gn_y)", "db (no gn_y)"]
+    for name, a, c in zip(names, out[False], out[True]):
+        assert torch.isfinite(a.float()).all() and torch.equal(a, c), f"{name}: the _cls_ entry differs from the plain entry"
+
+
 def test_ce_caller_fixtures_meet_the_hip_path(golden_dir):
     """tests/golden/callers_ce.npz -- the reference's own callers (tools/make_golden.py) -- through the HIP path: SegmentationStep /
     SegmentationValidation with loss="CE", LandmarkStep(class_loss="CE") with L2 and L1, LandmarkValidation with DICE and CE.  The

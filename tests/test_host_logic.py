@@ -360,6 +360,37 @@ def test_fused_landmark_head_and_first_layer_entry_points_answer_without_a_devic
     rc = lib.mednet_head_landmark_fwd(None, None, None, None, 0, None, 0, None, None, None, None, None, None, 4, sp, 32, 16, 2, 0, 1e-5, 0,
                                       L.NO_IGNORE, L.BF16, None, 0, None)
     assert rc == -1 and "head_landmark_fwd" in lib.mednet_last_error().decode()
+    # the head family's other entries share their checks: each answers null pointers with MEDNET_E_SHAPE under its own name (codes as
+    # the library returned them before the entries were put on one implementation)
+    lm_dims = (4, sp, 32, 16, 2, 0)  # n, spatial, cin, nh, ncls, kind
+    lm_tail = (1e-5, 0, L.NO_IGNORE, L.BF16, None, 0, None)  # eps, sigmoid, ignore_index, dtype, ws, ws_bytes, stream
+    seg_dims = (4, sp, 32, 14)
+    nulls = {
+        "head_landmark_bwd": lambda: lib.mednet_head_landmark_bwd(None, None, None, None, 0, None, 0, *[None] * 7, 0, None, None, None,
+                                                                  *lm_dims, *lm_tail),
+        "head_landmark_cls_fwd": lambda: lib.mednet_head_landmark_cls_fwd(None, None, None, None, 0, None, 0, *[None] * 7, *lm_dims,
+                                                                          L.CLASS_CE, *lm_tail),
+        "head_landmark_cls_bwd": lambda: lib.mednet_head_landmark_cls_bwd(None, None, None, None, 0, None, 0, *[None] * 7, 0, None, None,
+                                                                          None, *lm_dims, L.CLASS_CE, *lm_tail),
+        "head_seg_fwd": lambda: lib.mednet_head_seg_fwd(None, None, None, None, 0, *[None] * 4, *seg_dims, L.CLASS_DICE, *lm_tail),
+        "head_seg_bwd": lambda: lib.mednet_head_seg_bwd(None, None, None, None, 0, *[None] * 5, 0, None, None, None, *seg_dims,
+                                                        L.CLASS_CE, *lm_tail),
+    }
+    for name, call in nulls.items():
+        rc = call()
+        assert rc == -1 and lib.mednet_last_error().decode().startswith(name + ":"), (name, rc, lib.mednet_last_error())
+    # Dice through the _cls_ entry: the same checks under the _cls_ name
+    rc = lib.mednet_head_landmark_cls_fwd(None, None, None, None, 0, None, 0, *[None] * 7, *lm_dims, L.CLASS_DICE, *lm_tail)
+    assert rc == -1 and lib.mednet_last_error().decode().startswith("head_landmark_cls_fwd:")
+    # cross-entropy is a softmax form; dice_metric of a Dice forward takes no ignore_index: refused before the pointers are looked at
+    import ctypes as C
+    metric = C.c_float()
+    rc = lib.mednet_head_landmark_cls_fwd(None, None, None, None, 0, None, 0, *[None] * 7, *lm_dims, L.CLASS_CE, 1e-5, 1, L.NO_IGNORE,
+                                          L.BF16, None, 0, None)
+    assert rc == -5 and "head_landmark_cls_fwd" in lib.mednet_last_error().decode()
+    rc = lib.mednet_head_landmark_cls_fwd(None, None, None, None, 0, None, 0, *[None] * 6, C.addressof(metric), *lm_dims, L.CLASS_DICE,
+                                          1e-5, 0, 1, L.BF16, None, 0, None)
+    assert rc == -5 and "head_landmark_cls_fwd" in lib.mednet_last_error().decode()
     # first layer (Cin = 1): 16 / 32 / 64 output channels, 16-bit gradients, patch fp32 or the same 16-bit type
     for dt in (L.BF16, L.F16):
         assert all(lib.mednet_conv3d_wgrad_c1_gn_supported(c, L.F32, dt) == 1 for c in (16, 32, 64))

@@ -1,14 +1,17 @@
 """Same-box step times of the class-loss choices at BASELINE shapes (bf16 storage, 128^3, batch 4): config 2 with loss="CE" and
 config 4 with class_loss="CE", each with the fused CE head and with MEDNET_FUSE_HEAD_LOSS off (the two-node path), back to back in
 one process, and config 4 with Dice beside them.  Prints one JSON line per case.  Usage: python tools/ce_head_timing.py [warmup]
-[steps] (defaults 10, 50)."""
+[steps] (defaults 10, 50).  CE_WHICH=cfg2ce,cfg4ce,cfg4dice picks the cases, CE_FUSED=1,0 the head forms.  To time another commit's
+package and library on the same box (the tools/ab_lib.sh way): CE_PKG=<directory that holds that commit's mednet_hip/>
+MEDNET_LIB_PATH=<its libmednet_hip.so> python tools/ce_head_timing.py."""
 import json
 import os
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "torch-mednet_amd")):
+PKG = os.environ.get("CE_PKG") or os.path.join(ROOT, "torch-mednet_amd")
+for p in (ROOT, PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
 
@@ -52,16 +55,18 @@ def timed(name, make, fused):
         dt = (time.perf_counter() - t0) / STEPS
         loss = float(out[0] if isinstance(out, tuple) else out)
         step.flat.release()
-    print(json.dumps({"case": name, "fused_head": fused, "ms_per_step": round(dt * 1e3, 3), "patches_per_s": round(4 / dt, 2),
+    print(json.dumps({"case": name, "fused_head": fused, "package": os.path.dirname(os.path.abspath(mednet_hip.__file__)),
+                      "ms_per_step": round(dt * 1e3, 3), "patches_per_s": round(4 / dt, 2),
                       "warmup": WARM, "steps": STEPS, "last_loss": loss}), flush=True)
 
 
 which = os.environ.get("CE_WHICH", "cfg2ce,cfg4ce,cfg4dice")
+forms = [bool(int(f)) for f in os.environ.get("CE_FUSED", "1,0").split(",")]
 if "cfg2ce" in which:
-    for fused in (True, False):
+    for fused in forms:
         timed("cfg2 loss=CE", lambda: seg("CE"), fused)
 if "cfg4ce" in which:
-    for fused in (True, False):
+    for fused in forms:
         timed("cfg4 class_loss=CE", lambda: ldmk("CE"), fused)
 if "cfg4dice" in which:
     timed("cfg4 class_loss=DICE", lambda: ldmk("DICE"), True)

@@ -1,0 +1,203 @@
+"""SHA-256 digests of what the fused head + loss nodes compute -- the matrix-core landmark head (ops.head_landmark / _eval), the
+matrix-core segmentation head for 5-16 classes (ops.head_seg) and the VALU heads for <= 4 classes (ops.head_dice / ops.head_ce) -- on
+seeded random fp32 inputs that are NOT numbers of the storage type: two commits whose kernels run the same arithmetic in the same
+order print the same lines.  Only the package's public surface is used, so the tool runs against any commit's package and library:
+HD_PKG=<directory that holds that commit's mednet_hip/> MEDNET_LIB_PATH=<its libmednet_hip.so> python tools/head_digest.py
+(as tools/first_layer_digest.py); without them it takes this tree's.  One process per package; compare the outputs with diff.
+
+A case is one combination of a head's own axes (below); it runs in every storage mode of that head, both forms and both shapes.
+One JSON line per case: its name and ONE SHA-256 over the digests of all its tensors (DIGEST_FULL=1 adds the digest of every
+tensor under "mode/form/shape/tensor", to find which one moved).  form = "op": the node on random features, no GroupNorm hook -> the losses (the Dice metric of the _eval
+form), the logits where the node returns them, dx, dw, db (the `saved` sums show through the backward).  form = "block": the
+features come out of ExtResNetBlock(cin, cin, "cge"), so the node takes the first pass of that block's GroupNorm-3 backward ->
+the losses and every parameter gradient of block and head.
+Shapes: (12, 10, 6) with n = 3 (720 voxels: five whole runs of 128 and a ragged sixth, one chunk of 64 runs) and (24, 20, 21) with
+n = 2 (10080 voxels: two chunks, the second short with a ragged last run).
+Cases.  landmark (bf16, fp16): (nh, ncls, regression) in {(16, 2, L2), (5, 3, L1), (1, 4, L2)} x class loss Dice softmax / Dice
+sigmoid / CE x class and regression weights on / off, one ignore_index case per class loss; head_landmark_eval on the same inputs is
+part of every softmax case without a Dice mask.  seg (bf16, fp16): C in {5, 8, 9, 16} x the three losses x want_logits x weights,
+one ignore_index case per loss, labels at an odd byte offset once per loss.  valu (fp32, bf16, fp16): head_dice / head_ce x cin in
+{16, 32, 64} x C in {1, 4} x uint8 / int64 labels.
+Usage: python tools/head_digest.py [heads, default landmark,seg,valu] > digest.jsonl"""
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.environ.get("HD_PKG") or os.path.join(ROOT, "torch-mednet_amd")
+for p in (ROOT, PKG):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+import mednet_hip  # noqa: E402
+from mednet_hip import nn as hnn  # noqa: E402
+from mednet_hip import ops  # noqa: E402
+from mednet_hip.unet import components as HC  # noqa: E402
+from oracle import ref_cpu as O  # noqa: E402
+
+DEV = "cuda:0"
+SHAPES = [(3, (12, 10, 6)), (2, (24, 20, 21))]
+FULL = os.environ.get("DIGEST_FULL", "0") == "1"
+HEADS = (sys.argv[1] if len(sys.argv) > 1 else "landmark,seg,valu").split(",")
+_CACHE = {}
+
+
+def _gen(tag):
+    return torch.Generator().manual_seed(int.from_bytes(hashlib.sha256(tag.encode()).digest()[:6], "little"))
+
+
+def rnd(tag, *shape):
+    """Seeded on the CPU by the tag alone; cached, so every case of a shape sees the same tensor."""
+    if (tag, shape) not in _CACHE:
+        _CACHE[(tag, shape)] = torch.randn(*shape, generator=_gen(tag), dtype=torch.float32)
+    return _CACHE[(tag, shape)]
+
+
+def labels(tag, hi, *shape):
+    """uint8 values in [0, hi), seeded by the tag."""
+    if (tag, hi, shape) not in _CACHE:
+        _CACHE[(tag, hi, shape)] = torch.randint(0, hi, shape, generator=_gen(tag), dtype=torch.uint8)
+    return _CACHE[(tag, hi, shape)]
+
+
+def digest(t):
+    if t is None:
+        return None
+    t = t.detach().contiguous().cpu()
+    if t.dtype in (torch.bfloat16, torch.float16):
+        t = t.view(torch.int16)
+    return hashlib.sha256(t.numpy().tobytes()).hexdigest()
+
+
+def weights(c):
+    return torch.tensor([0.05] + [0.6 + 0.1 * (k % 7) for k in range(1, c)])
+
+
+def features(form, cin, n, shape):
+    """-> (features for the head, the leaf to read dx from or None, the block or None)."""
+    x = rnd(f"x{cin}", n, cin, *shape).to(DEV)
+    if form == "op":
+        xg = ops.to_cl(x.to(mednet_hip.config.act_dtype())).requires_grad_(True)
+        return xg, xg, None
+    blk = O.keyed_init_(HC.ExtResNetBlock(cin, cin, order="cge", num_groups=8)).to(DEV)
+    return blk(x), None, blk
+
+
+def head_conv(cin, cout):
+    conv = hnn.Conv3d(cin, cout, 1, planar_output=True).to(DEV)
+    with torch.no_grad():
+        conv.weight.copy_(rnd(f"w{cin}_{cout}", cout, cin, 1, 1, 1) * 0.3)
+        conv.bias.copy_(rnd(f"b{cout}", cout))
+    return conv
+
+
+def finish(out, total, leaf, blk, conv, mode):
+    """Backward of `total` (scaled as train.LossScaler does where fp16 stores the feature gradient) and the gradients' digests."""
+    (total * (3.0 * 16384.0 if mode == "fp16" else 3.0)).backward()
+    torch.cuda.synchronize()
+    if leaf is not None:
+        out["dx"] = digest(leaf.grad)
+    out["dw"], out["db"] = digest(conv.weight.grad), digest(conv.bias.grad)
+    if blk is not None:
+        for k, p in blk.named_parameters():
+            out["d_" + k] = digest(p.grad)
+    return out
+
+
+def sh(shape):
+    return "x".join(map(str, shape))
+
+
+def landmark_cases():
+    for nh, ncls, kind in ((16, 2, "L2"), (5, 3, "L1"), (1, 4, "L2")):
+        cases = [(cl, sig, wtd, None) for cl, sig in (("DICE", False), ("DICE", True), ("CE", False)) for wtd in (True, False)]
+        for cl, sig, wtd, ign in cases + ([("DICE", False, True, 1), ("CE", False, True, 1)] if ncls == 3 else []):
+            yield f"landmark nh={nh} ncls={ncls} {kind} {cl} sig={int(sig)} w={int(wtd)} ign={ign}", (nh, ncls, kind, cl, sig, wtd, ign)
+
+
+def landmark(mode, form, n, shape, nh, ncls, kind, cl, sig, wtd, ign):
+    hm = labels(f"hm{nh}", 256, n, nh, *shape).to(DEV)
+    lab = labels(f"lab{ncls}", ncls, n, *shape).to(DEV)
+    cw = weights(ncls).to(DEV) if wtd else None
+    rw = [0.015 + 0.003 * i for i in range(nh)] if wtd else None
+    x, leaf, blk = features(form, 32, n, shape)
+    fc = head_conv(32, nh + ncls)
+    if not ops.head_landmark_supported(x, 32, nh, ncls, hm, lab):
+        raise RuntimeError("head_landmark does not take this case")
+    closs, rloss = ops.head_landmark(x, fc.weight, fc.bias, fc._packed(), hm, lab, cw, rw, kind, 1e-5, sig, ign, cl)
+    out = finish({"class_loss": digest(closs), "reg_loss": digest(rloss)}, closs * 0.75 + rloss * 1.25, leaf, blk, fc, mode)
+    if form == "op" and not sig and not (cl == "DICE" and ign is not None):  # (the metric is a softmax form without a mask)
+        with torch.no_grad():
+            ev = ops.head_landmark_eval(x.detach(), fc.weight, fc.bias, fc._packed(), hm, lab, cw, rw, kind, 1e-5, ign, cl)
+        torch.cuda.synchronize()
+        out.update({"eval_class_loss": digest(ev[0]), "eval_reg_loss": digest(ev[1]), "eval_dice": digest(ev[2])})
+    return out
+
+
+def seg_cases():
+    for c in (5, 8, 9, 16):
+        cases = [(cl, sig, wtd, None, wl, False) for cl, sig in (("DICE", False), ("DICE", True), ("CE", False)) for wtd in (True, False)
+                 for wl in (False, True)]
+        if c == 9:
+            cases += [("DICE", False, True, 2, False, False), ("CE", False, True, 3, False, False),
+                      ("DICE", False, False, None, False, True), ("CE", False, False, None, False, True)]
+        for cl, sig, wtd, ign, wl, odd in cases:
+            yield f"seg C={c} {cl} sig={int(sig)} w={int(wtd)} ign={ign} logits={int(wl)} odd={int(odd)}", (c, cl, sig, wtd, ign, wl, odd)
+
+
+def seg(mode, form, n, shape, c, cl, sig, wtd, ign, wl, odd):
+    lab = labels(f"lab{c}", c, n, *shape).to(DEV)
+    if odd:  # the same labels behind an odd base address
+        buf = torch.zeros(lab.numel() + 1, dtype=torch.uint8, device=DEV)
+        buf[1:] = lab.flatten()
+        lab = buf[1:].view(n, *shape)
+    wt = weights(c).to(DEV) if wtd else None
+    x, leaf, blk = features(form, 32, n, shape)
+    fc = head_conv(32, c)
+    if not ops.head_seg_supported(x, 32, c, lab):
+        raise RuntimeError("head_seg does not take this case")
+    lg, loss = ops.head_seg(x, fc.weight, fc.bias, fc._packed(), lab, wt, 1e-5, sig, ign, cl, wl)
+    return finish({"loss": digest(loss), "logits": digest(lg)}, loss, leaf, blk, fc, mode)
+
+
+def valu_cases():
+    for cl in ("DICE", "CE"):
+        for cin in (16, 32, 64):
+            for c in (1, 4):
+                for u8 in (True, False):
+                    yield f"valu {cl} cin={cin} C={c} labels={'u8' if u8 else 'i64'}", (cl, cin, c, u8)
+
+
+def valu(mode, form, n, shape, cl, cin, c, u8):
+    lab = labels(f"lab{c}", c, n, *shape).to(DEV)
+    lab = lab if u8 else lab.long()
+    x, leaf, blk = features(form, cin, n, shape)
+    fc = head_conv(cin, c)
+    wt = weights(c).to(DEV)
+    if not (ops.head_dice_supported if cl == "DICE" else ops.head_ce_supported)(x, cin, c, lab):
+        raise RuntimeError(f"head_{cl.lower()} does not take this case")
+    if cl == "DICE":
+        lg, loss = ops.head_dice(x, fc.weight, fc.bias, fc._packed(), lab, wt, 1e-5, c == 1, None)
+    else:
+        lg, loss = ops.head_ce(x, fc.weight, fc.bias, fc._packed(), lab, wt, -100)
+    return finish({"loss": digest(loss), "logits": digest(lg)}, loss, leaf, blk, fc, mode)
+
+
+RUN = {"landmark": (landmark_cases, landmark, ("bf16", "fp16")), "seg": (seg_cases, seg, ("bf16", "fp16")),
+       "valu": (valu_cases, valu, ("fp32", "bf16", "fp16"))}
+for head in HEADS:
+    cases, fn, modes = RUN[head]
+    for name, axes in cases():
+        res = {}
+        for mode in modes:
+            for form in ("op", "block"):
+                for n, shape in SHAPES:
+                    with mednet_hip.precision(mode):
+                        for k, v in fn(mode, form, n, shape, *axes).items():
+                            res[f"{mode}/{form}/{sh(shape)}/{k}"] = v
+        line = {"case": name, "sha256": hashlib.sha256("".join(f"{k}={v};" for k, v in res.items()).encode()).hexdigest()}
+        print(json.dumps({**line, **res} if FULL else line), flush=True)
+        torch.cuda.empty_cache()

@@ -452,9 +452,8 @@ extern "C" int mednet_head_dgrad_gn(const void* dy, const void* packed, void* dx
                  MEDNET_E_SHAPE, "head_dgrad_gn: bad arguments");
   MEDNET_REQUIRE(mednet_head_dgrad_gn_rows(n, d, h, w, cin, dtype) > 0, MEDNET_E_UNSUPPORTED,
                  "head_dgrad_gn: cin=%d dtype=%d not supported", cin, dtype);
-  const PackLayout L = pack_layout(cin, cout, 1);
-  return launch_head_dgrad_gn(dy, (const float*)((const char*)packed + L.f32_bwd), dx, gn_y, gn_z, gn_act, gn_partial, n,
-                              (size_t)d * h * w, cout, cin, dtype, (hipStream_t)stream);
+  return launch_head_dgrad_gn(dy, head_weights_f32(packed, cin, cout), dx, gn_y, gn_z, gn_act, gn_partial, n, (size_t)d * h * w, cout,
+                              cin, dtype, (hipStream_t)stream);
 }
 
 // ---- the landmark head fused with its two losses (head_mfma.hip) ---------------------------------------------------------
@@ -465,30 +464,61 @@ extern "C" size_t mednet_head_landmark_ws_bytes(int n, size_t spatial, int nh, i
   return head_lm_ws_bytes(n, spatial, nh, ncls);
 }
 extern "C" int mednet_head_landmark_gn_rows(size_t spatial) { return head_lm_chunks(spatial); }
+// One forward and one backward behind the four entries: `what` names the entry the caller used, `class_kind` the class term
+// (MEDNET_CLASS_DICE: DiceLoss; MEDNET_CLASS_CE: nn.CrossEntropyLoss, softmax), `dice_metric` (nullable) takes dice_metric of the
+// class channels from the same pass.
+static int head_landmark_fwd(const char* what, const void* z, const void* packed, const float* bias, const void* heatmaps,
+                             int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n, const float* class_weight,
+                             const float* reg_weight, float* logits, float* class_loss, float* reg_loss, float* saved, float* dice_metric,
+                             int n, size_t spatial, int cin, int nh, int ncls, int kind, int class_kind, float eps, int sigmoid,
+                             int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && heatmaps && labels && class_loss && reg_loss && saved && ws, MEDNET_E_SHAPE,
+                 "%s: bad arguments", what);
+  MEDNET_REQUIRE(mednet_head_landmark_supported(cin, nh, ncls, z_dtype, spatial), MEDNET_E_UNSUPPORTED,
+                 "%s: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", what, cin, nh, ncls, z_dtype, spatial);
+  MEDNET_REQUIRE(kind == MEDNET_REG_L2 || kind == MEDNET_REG_L1, MEDNET_E_UNSUPPORTED, "%s: regression kind %d", what, kind);
+  MEDNET_REQUIRE(ws_bytes >= head_lm_ws_bytes(n, spatial, nh, ncls), MEDNET_E_WORKSPACE, "%s: workspace too small", what);
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = head_lm_chunks(spatial);
+  const int ce = class_kind == MEDNET_CLASS_CE;
+  float* hm_partial = (float*)ws;
+  float* dice_partial = hm_partial + (size_t)n * nh * chunks;
+  float* ce_partial = dice_partial + (size_t)n * chunks * ncls * 2;
+  float* metric_saved = ce_partial + (size_t)n * chunks * 2;  // [ncls][2]: (the forward's fp64 combine writes its sums somewhere)
+  int rc = ELT_CALL(z_dtype, launch_head_lm_fwd, z, head_weights_f32(packed, cin, nh + ncls), bias, heatmaps, heatmap_stride_n, labels,
+                    label_stride_n, class_weight, logits, hm_partial, dice_partial, ce_partial, n, spatial, nh, ncls, kind, ce, sigmoid,
+                    ignore_index, s);
+  if (rc) return rc;
+  rc = launch_hm_finalize(hm_partial, reg_weight, reg_loss, n, nh, chunks, spatial, s);
+  if (rc) return rc;
+  rc = ce ? launch_ce_finalize(ce_partial, class_loss, saved, n * chunks, s)
+          : launch_dice_finalize(dice_partial, class_weight, class_loss, saved, ncls, n * chunks, eps, s);
+  if (rc || !dice_metric) return rc;
+  return launch_dice_finalize(dice_partial, nullptr, nullptr, metric_saved, ncls, n * chunks, 1e-5f, s, dice_metric);
+}
+static int head_landmark_bwd(const char* what, const void* z, const void* packed, const float* bias, const void* heatmaps,
+                             int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n, const float* class_weight,
+                             const float* reg_weight, const float* saved, const float* dclass_loss, const float* dreg_loss, void* dz,
+                             const void* gn_y, int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin,
+                             int nh, int ncls, int kind, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
+                             size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && heatmaps && labels && saved && dclass_loss && dreg_loss && dz && dw && ws,
+                 MEDNET_E_SHAPE, "%s: bad arguments", what);
+  MEDNET_REQUIRE(mednet_head_landmark_supported(cin, nh, ncls, z_dtype, spatial), MEDNET_E_UNSUPPORTED,
+                 "%s: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", what, cin, nh, ncls, z_dtype, spatial);
+  return ELT_CALL(z_dtype, launch_head_lm_bwd, z, head_weights_f32(packed, cin, nh + ncls), bias, heatmaps, heatmap_stride_n, labels,
+                  label_stride_n, saved, class_weight, reg_weight, dclass_loss, dreg_loss, eps, dz, gn_y, gn_act, gn_partial, dw, dbias, n,
+                  spatial, nh, ncls, kind, class_kind == MEDNET_CLASS_CE, sigmoid, ignore_index, ws, ws_bytes, (hipStream_t)stream);
+}
 extern "C" int mednet_head_landmark_fwd(const void* z, const void* packed, const float* bias, const void* heatmaps,
                                         int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n,
                                         const float* class_weight, const float* reg_weight, float* logits, float* class_loss,
                                         float* reg_loss, float* saved, int n, size_t spatial, int cin, int nh, int ncls, int kind,
                                         float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
                                         mednet_stream stream) {
-  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && heatmaps && labels && class_loss && reg_loss && saved && ws, MEDNET_E_SHAPE,
-                 "head_landmark_fwd: bad arguments");
-  MEDNET_REQUIRE(mednet_head_landmark_supported(cin, nh, ncls, z_dtype, spatial), MEDNET_E_UNSUPPORTED,
-                 "head_landmark_fwd: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", cin, nh, ncls, z_dtype, spatial);
-  MEDNET_REQUIRE(kind == MEDNET_REG_L2 || kind == MEDNET_REG_L1, MEDNET_E_UNSUPPORTED, "head_landmark_fwd: regression kind %d", kind);
-  MEDNET_REQUIRE(ws_bytes >= head_lm_ws_bytes(n, spatial, nh, ncls), MEDNET_E_WORKSPACE, "head_landmark_fwd: workspace too small");
-  const PackLayout L = pack_layout(cin, nh + ncls, 1);
-  const float* W = (const float*)((const char*)packed + L.f32_bwd);  // [co][ci]
-  hipStream_t s = (hipStream_t)stream;
-  const int chunks = head_lm_chunks(spatial);
-  float* hm_partial = (float*)ws;
-  float* dice_partial = hm_partial + (size_t)n * nh * chunks;
-  int rc = ELT_CALL(z_dtype, launch_head_lm_fwd, z, W, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, logits, hm_partial,
-                    dice_partial, n, spatial, nh, ncls, kind, sigmoid, ignore_index, s);
-  if (rc) return rc;
-  rc = launch_hm_finalize(hm_partial, reg_weight, reg_loss, n, nh, chunks, spatial, s);
-  if (rc) return rc;
-  return launch_dice_finalize(dice_partial, class_weight, class_loss, saved, ncls, n * chunks, eps, s);
+  return head_landmark_fwd("head_landmark_fwd", z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight,
+                           reg_weight, logits, class_loss, reg_loss, saved, nullptr, n, spatial, cin, nh, ncls, kind, MEDNET_CLASS_DICE,
+                           eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 extern "C" int mednet_head_landmark_bwd(const void* z, const void* packed, const float* bias, const void* heatmaps,
                                         int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n,
@@ -497,19 +527,12 @@ extern "C" int mednet_head_landmark_bwd(const void* z, const void* packed, const
                                         float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int nh, int ncls,
                                         int kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
                                         mednet_stream stream) {
-  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && heatmaps && labels && saved && dclass_loss && dreg_loss && dz && dw && ws,
-                 MEDNET_E_SHAPE, "head_landmark_bwd: bad arguments");
-  MEDNET_REQUIRE(mednet_head_landmark_supported(cin, nh, ncls, z_dtype, spatial), MEDNET_E_UNSUPPORTED,
-                 "head_landmark_bwd: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", cin, nh, ncls, z_dtype, spatial);
-  const PackLayout L = pack_layout(cin, nh + ncls, 1);
-  const float* W = (const float*)((const char*)packed + L.f32_bwd);
-  return ELT_CALL(z_dtype, launch_head_lm_bwd, z, W, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, saved, class_weight,
-                  reg_weight, dclass_loss, dreg_loss, eps, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, nh, ncls, kind,
-                  sigmoid, ignore_index, ws, ws_bytes, (hipStream_t)stream);
+  return head_landmark_bwd("head_landmark_bwd", z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight,
+                           reg_weight, saved, dclass_loss, dreg_loss, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, cin, nh, ncls,
+                           kind, MEDNET_CLASS_DICE, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
-// ... with the class-loss kind as an argument (MEDNET_CLASS_DICE: the calls above; MEDNET_CLASS_CE: nn.CrossEntropyLoss) and, from the
-// forward, dice_metric of the class channels
+// ... with the class-loss kind as an argument and, from the forward, dice_metric of the class channels
 extern "C" int mednet_head_landmark_cls_fwd(const void* z, const void* packed, const float* bias, const void* heatmaps,
                                             int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n,
                                             const float* class_weight, const float* reg_weight, float* logits, float* class_loss,
@@ -522,36 +545,9 @@ extern "C" int mednet_head_landmark_cls_fwd(const void* z, const void* packed, c
                  "head_landmark_cls_fwd: cross-entropy and dice_metric are softmax forms");
   MEDNET_REQUIRE(!(class_kind == MEDNET_CLASS_DICE && dice_metric) || ignore_index == MEDNET_NO_IGNORE, MEDNET_E_UNSUPPORTED,
                  "head_landmark_cls_fwd: dice_metric of a Dice forward needs ignore_index == MEDNET_NO_IGNORE");
-  hipStream_t s = (hipStream_t)stream;
-  const int chunks = head_lm_chunks(spatial);
-  float* hm_partial = (float*)ws;
-  float* dice_partial = hm_partial + (size_t)n * nh * chunks;
-  float* ce_partial = dice_partial + (size_t)n * chunks * ncls * 2;
-  float* metric_saved = ce_partial + (size_t)n * chunks * 2;  // [ncls][2]: (the forward's fp64 combine writes its sums somewhere)
-  int rc;
-  if (class_kind == MEDNET_CLASS_DICE) {
-    rc = mednet_head_landmark_fwd(z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight, reg_weight, logits,
-                                  class_loss, reg_loss, saved, n, spatial, cin, nh, ncls, kind, eps, sigmoid, ignore_index, z_dtype, ws,
-                                  ws_bytes, stream);
-    if (rc || !dice_metric) return rc;
-  } else {
-    MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && heatmaps && labels && class_loss && reg_loss && saved && ws, MEDNET_E_SHAPE,
-                   "head_landmark_cls_fwd: bad arguments");
-    MEDNET_REQUIRE(mednet_head_landmark_supported(cin, nh, ncls, z_dtype, spatial), MEDNET_E_UNSUPPORTED,
-                   "head_landmark_cls_fwd: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", cin, nh, ncls, z_dtype, spatial);
-    MEDNET_REQUIRE(kind == MEDNET_REG_L2 || kind == MEDNET_REG_L1, MEDNET_E_UNSUPPORTED, "head_landmark_cls_fwd: regression kind %d", kind);
-    MEDNET_REQUIRE(ws_bytes >= head_lm_ws_bytes(n, spatial, nh, ncls), MEDNET_E_WORKSPACE, "head_landmark_cls_fwd: workspace too small");
-    const PackLayout L = pack_layout(cin, nh + ncls, 1);
-    const float* W = (const float*)((const char*)packed + L.f32_bwd);
-    rc = ELT_CALL(z_dtype, launch_head_lm_ce_fwd, z, W, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight, logits,
-                  hm_partial, dice_partial, ce_partial, n, spatial, nh, ncls, kind, ignore_index, s);
-    if (rc) return rc;
-    rc = launch_hm_finalize(hm_partial, reg_weight, reg_loss, n, nh, chunks, spatial, s);
-    if (rc) return rc;
-    rc = launch_ce_finalize(ce_partial, class_loss, saved, n * chunks, s);
-    if (rc || !dice_metric) return rc;
-  }
-  return launch_dice_finalize(dice_partial, nullptr, nullptr, metric_saved, ncls, n * chunks, 1e-5f, s, dice_metric);
+  return head_landmark_fwd("head_landmark_cls_fwd", z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight,
+                           reg_weight, logits, class_loss, reg_loss, saved, dice_metric, n, spatial, cin, nh, ncls, kind, class_kind, eps,
+                           sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 extern "C" int mednet_head_landmark_cls_bwd(const void* z, const void* packed, const float* bias, const void* heatmaps,
                                             int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n,
@@ -560,21 +556,13 @@ extern "C" int mednet_head_landmark_cls_bwd(const void* z, const void* packed, c
                                             float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int nh, int ncls,
                                             int kind, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
                                             size_t ws_bytes, mednet_stream stream) {
-  if (class_kind == MEDNET_CLASS_DICE)
-    return mednet_head_landmark_bwd(z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight, reg_weight, saved,
-                                    dclass_loss, dreg_loss, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, cin, nh, ncls, kind, eps,
-                                    sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
-  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED, "head_landmark_cls_bwd: class-loss kind %d", class_kind);
-  MEDNET_REQUIRE(sigmoid == 0, MEDNET_E_UNSUPPORTED, "head_landmark_cls_bwd: cross-entropy is a softmax form");
-  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && heatmaps && labels && saved && dclass_loss && dreg_loss && dz && dw && ws,
-                 MEDNET_E_SHAPE, "head_landmark_cls_bwd: bad arguments");
-  MEDNET_REQUIRE(mednet_head_landmark_supported(cin, nh, ncls, z_dtype, spatial), MEDNET_E_UNSUPPORTED,
-                 "head_landmark_cls_bwd: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", cin, nh, ncls, z_dtype, spatial);
-  const PackLayout L = pack_layout(cin, nh + ncls, 1);
-  const float* W = (const float*)((const char*)packed + L.f32_bwd);
-  return ELT_CALL(z_dtype, launch_head_lm_ce_bwd, z, W, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, saved, class_weight,
-                  reg_weight, dclass_loss, dreg_loss, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, nh, ncls, kind, ignore_index,
-                  ws, ws_bytes, (hipStream_t)stream);
+  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED,
+                 "head_landmark_cls_bwd: class-loss kind %d", class_kind);
+  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED,
+                 "head_landmark_cls_bwd: cross-entropy is a softmax form");
+  return head_landmark_bwd("head_landmark_cls_bwd", z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight,
+                           reg_weight, saved, dclass_loss, dreg_loss, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, cin, nh, ncls,
+                           kind, class_kind, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
 // ---- the segmentation head for 5 .. 16 classes fused with Dice or cross-entropy (head_mfma.hip, head_seg_kernel) ----------
@@ -583,25 +571,31 @@ extern "C" int mednet_head_seg_supported(int cin, int ncls, int dtype, int label
 }
 extern "C" size_t mednet_head_seg_ws_bytes(int n, size_t spatial, int ncls) { return head_seg_ws_bytes(n, spatial, ncls); }
 extern "C" int mednet_head_seg_gn_rows(size_t spatial) { return head_lm_chunks(spatial); }
+// the checks both directions share; `ok` = the direction's own pointers
+static int head_seg_checks(const char* what, bool ok, const void* z, const void* packed, const void* labels, const void* saved,
+                           const void* ws, int n, size_t spatial, int cin, int ncls, int class_kind, int sigmoid, int z_dtype) {
+  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED, "%s: class-loss kind %d", what,
+                 class_kind);
+  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED, "%s: cross-entropy is a softmax form", what);
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && saved && ws && ok, MEDNET_E_SHAPE, "%s: bad arguments", what);
+  MEDNET_REQUIRE(mednet_head_seg_supported(cin, ncls, z_dtype, MEDNET_U8, spatial), MEDNET_E_UNSUPPORTED,
+                 "%s: %d -> %d classes, dtype %d, %zu voxels", what, cin, ncls, z_dtype, spatial);
+  return 0;
+}
 extern "C" int mednet_head_seg_fwd(const void* z, const void* packed, const float* bias, const void* labels, int64_t label_stride_n,
                                    const float* class_weight, float* logits, float* loss, float* saved, int n, size_t spatial, int cin,
                                    int ncls, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
                                    size_t ws_bytes, mednet_stream stream) {
-  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED,
-                 "head_seg_fwd: class-loss kind %d", class_kind);
-  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED, "head_seg_fwd: cross-entropy is a softmax form");
-  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && loss && saved && ws, MEDNET_E_SHAPE, "head_seg_fwd: bad arguments");
-  MEDNET_REQUIRE(mednet_head_seg_supported(cin, ncls, z_dtype, MEDNET_U8, spatial), MEDNET_E_UNSUPPORTED,
-                 "head_seg_fwd: %d -> %d classes, dtype %d, %zu voxels", cin, ncls, z_dtype, spatial);
+  int rc = head_seg_checks("head_seg_fwd", loss != nullptr, z, packed, labels, saved, ws, n, spatial, cin, ncls, class_kind, sigmoid,
+                           z_dtype);
+  if (rc) return rc;
   MEDNET_REQUIRE(ws_bytes >= head_seg_ws_bytes(n, spatial, ncls), MEDNET_E_WORKSPACE, "head_seg_fwd: workspace too small");
-  const PackLayout L = pack_layout(cin, ncls, 1);
-  const float* W = (const float*)((const char*)packed + L.f32_bwd);  // [co][ci]
   hipStream_t s = (hipStream_t)stream;
   const int chunks = head_lm_chunks(spatial);
   const int ce = class_kind == MEDNET_CLASS_CE;
   float* partial = (float*)ws;
-  int rc = ELT_CALL(z_dtype, launch_head_seg_fwd, z, W, bias, labels, label_stride_n, class_weight, logits, partial, n, spatial, ncls,
-                    ce, sigmoid, ignore_index, s);
+  rc = ELT_CALL(z_dtype, launch_head_seg_fwd, z, head_weights_f32(packed, cin, ncls), bias, labels, label_stride_n, class_weight, logits,
+                partial, n, spatial, ncls, ce, sigmoid, ignore_index, s);
   if (rc) return rc;
   if (ce) return launch_ce_finalize(partial, loss, saved, n * chunks, s);
   return launch_dice_finalize(partial, class_weight, loss, saved, ncls, n * chunks, eps, s);
@@ -611,18 +605,12 @@ extern "C" int mednet_head_seg_bwd(const void* z, const void* packed, const floa
                                    int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int ncls,
                                    int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
                                    mednet_stream stream) {
-  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED,
-                 "head_seg_bwd: class-loss kind %d", class_kind);
-  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED, "head_seg_bwd: cross-entropy is a softmax form");
-  MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && saved && dloss && dz && dw && ws, MEDNET_E_SHAPE,
-                 "head_seg_bwd: bad arguments");
-  MEDNET_REQUIRE(mednet_head_seg_supported(cin, ncls, z_dtype, MEDNET_U8, spatial), MEDNET_E_UNSUPPORTED,
-                 "head_seg_bwd: %d -> %d classes, dtype %d, %zu voxels", cin, ncls, z_dtype, spatial);
-  const PackLayout L = pack_layout(cin, ncls, 1);
-  const float* W = (const float*)((const char*)packed + L.f32_bwd);
-  return ELT_CALL(z_dtype, launch_head_seg_bwd, z, W, bias, labels, label_stride_n, saved, class_weight, dloss, eps, dz, gn_y, gn_act,
-                  gn_partial, dw, dbias, n, spatial, ncls, class_kind == MEDNET_CLASS_CE, sigmoid, ignore_index, ws, ws_bytes,
-                  (hipStream_t)stream);
+  const int rc = head_seg_checks("head_seg_bwd", dloss && dz && dw, z, packed, labels, saved, ws, n, spatial, cin, ncls, class_kind,
+                                 sigmoid, z_dtype);
+  if (rc) return rc;
+  return ELT_CALL(z_dtype, launch_head_seg_bwd, z, head_weights_f32(packed, cin, ncls), bias, labels, label_stride_n, saved, class_weight,
+                  dloss, eps, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, ncls, class_kind == MEDNET_CLASS_CE, sigmoid,
+                  ignore_index, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int mednet_conv3d_dgrad_gn_rows(int n, int d, int h, int w, int cin, int cout, int algo) {

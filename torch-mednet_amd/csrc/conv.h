@@ -72,6 +72,10 @@ int launch_ce_finalize(const float* partial, float* loss, float* saved, int nblo
 // 16-bit matrix-core kernels, conv_mfma.hip (namespace mednet: bf16; api.hip declares the same set in namespace mednet_f16
 // for the fp16 build of that file)
 #include "conv_mfma_decl.inc"
+// the fp32 weights W[co][ci] of a 1x1x1 head inside its packed buffer: the backward section of its one tap, Pb[0][co][ci]
+inline const float* head_weights_f32(const void* packed, int cin, int cout) {
+  return (const float*)((const char*)packed + pack_layout(cin, cout, 1).f32_bwd);
+}
 
 // fp32 matrix-core kernels (v_mfma_f32_32x32x2_f32), conv_f32_mfma.hip: the parity mode's 3x3x3 family
 bool conv_f32_mfma_enabled();

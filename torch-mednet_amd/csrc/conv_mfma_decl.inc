@@ -72,23 +72,17 @@ int launch_wgrad_first_mfma(const void* x, int x_layout, int x_dtype, const void
 bool head_lm_supported(int cin, int nh, int ncls, int dtype, size_t spatial);
 int head_lm_chunks(size_t spatial);  // workgroups per sample = rows per sample of every partial
 size_t head_lm_ws_bytes(int n, size_t spatial, int nh, int ncls);
+// ce = 0: the class term is DiceLoss.  ce = 1: nn.CrossEntropyLoss(cls_weight, ignore) (softmax; `sigmoid` and `eps` are not read):
+// ce_partial [n][chunk][2] for ce_finalize, and dice_partial takes dice_metric's unweighted, unmasked sums; the backward reads
+// saved[0] = sum w_y of that forward.
 int launch_head_lm_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                       int64_t lab_sn, float* logits, float* hm_partial, float* dice_partial, int n, size_t spatial, int nh, int ncls,
-                       int kind, int sigmoid, int ignore, hipStream_t s);
+                       int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial, float* ce_partial,
+                       int n, size_t spatial, int nh, int ncls, int kind, int ce, int sigmoid, int ignore, hipStream_t s);
 int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
                        int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
                        const float* dreg, float eps, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db,
-                       int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, void* ws, size_t ws_bytes,
+                       int n, size_t spatial, int nh, int ncls, int kind, int ce, int sigmoid, int ignore, void* ws, size_t ws_bytes,
                        hipStream_t s);
-// ... with nn.CrossEntropyLoss(weight, ignore_index) as the class term (softmax): ce_partial [n][chunk][2] for ce_finalize, and
-// dice_partial takes dice_metric's unweighted, unmasked sums.  The backward reads saved[0] = sum w_y of the CE forward.
-int launch_head_lm_ce_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                          int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial, float* ce_partial,
-                          int n, size_t spatial, int nh, int ncls, int kind, int ignore, hipStream_t s);
-int launch_head_lm_ce_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                          int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
-                          const float* dreg, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db, int n,
-                          size_t spatial, int nh, int ncls, int kind, int ignore, void* ws, size_t ws_bytes, hipStream_t s);
 
 // head_mfma.hip: the segmentation head (1x1x1 conv 32 -> 5 .. 16 classes) fused with DiceLoss (ce = 0) or nn.CrossEntropyLoss
 // (ce = 1, softmax), matrix-core form.  `partial`: [n][chunk][ncls][2] for dice_finalize (ce = 0), [n][chunk][2] for ce_finalize

@@ -459,8 +459,7 @@ static int head_loss_fwd(const char* what, const void* z, const void* packed, co
                  "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
   MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && logits && loss && saved, MEDNET_E_SHAPE, "%s: bad arguments", what);
   MEDNET_REQUIRE(ws_bytes >= mednet_head_dice_ws_bytes(n, spatial, cin, cout), MEDNET_E_WORKSPACE, "%s: workspace too small", what);
-  const PackLayout L = pack_layout(cin, cout, 1);
-  const float* Pb = (const float*)((const char*)packed + L.f32_bwd);  // Pb[t = 0][co][ci] = W[co][ci]
+  const float* Pb = head_weights_f32(packed, cin, cout);
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = hl_fwd_blocks(spatial);
   float* partial = (float*)ws;
@@ -491,8 +490,7 @@ static int head_loss_bwd(const char* what, const float* logits, const void* labe
   MEDNET_REQUIRE(n > 0 && spatial > 0 && logits && labels && packed && saved && dloss && dz && z && dw, MEDNET_E_SHAPE, "%s: bad arguments", what);
   MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "%s: gn_y and gn_partial go together", what);
   MEDNET_REQUIRE(ws_bytes >= mednet_head_dice_ws_bytes(n, spatial, cin, cout), MEDNET_E_WORKSPACE, "%s: workspace too small", what);
-  const PackLayout L = pack_layout(cin, cout, 1);
-  const float* Pb = (const float*)((const char*)packed + L.f32_bwd);
+  const float* Pb = head_weights_f32(packed, cin, cout);
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = hl_bwd_blocks(spatial, cin);
   float* wpart = (float*)ws;

@@ -19,6 +19,12 @@
 // j = voxels {4g + j}) and, of each voxel row, the two 16-byte pieces at bytes 16h and 32 + 16h -- channels 8h .. 8h+7 and
 // 16+8h .. 16+8h+7 -- for z, the GroupNorm input and dz alike: the row order of the weight operands is permuted (free: they
 // are built once per wave from the fp32 weights) so that every MFMA result lands in the lane that owns those bytes.
+//
+// The file holds two kernels of this shape -- head_lm_kernel (nh heat maps + up to 4 classes in the lanes of half 0) and, further down,
+// head_seg_kernel (5 .. 16 classes spread over both lane halves, softmax through v_permlane32_swap) -- and ONE copy of everything they
+// do alike: the hlm_* / Hlm* building blocks below HlmArgs (weight operands, row loads, logit MFMAs, dz store + GroupNorm pass, the dW
+// tiles, the end-of-kernel sums), head_lm_wfinal_kernel, and on the host one HlmArgs filler behind launch_head_lm_{fwd,bwd} and
+// launch_head_seg_{fwd,bwd}, which take the class loss as `int ce`.
 #include "conv.h"
 #include "elt16.inc"
 
@@ -60,12 +66,223 @@ struct HlmArgs {
   float* ce_partial;     // CE forward: [n][chunk][2] = {sum w_y nll, sum w_y}  (ce_finalize_kernel's layout)
 };
 
+// ---- building blocks of head_lm_kernel and head_seg_kernel -------------------------------------------------------------------
+// Everything the two kernels do alike, written once; what differs between them is where the classes live (below).
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+__device__ __forceinline__ void hlm_split(const float (&v)[8], eltx8& hi, eltx8& lo) {  // v = hi + lo in the storage type
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    hi[e] = (elt)v[e];
+    lo[e] = (elt)(v[e] - (float)hi[e]);
+  }
+}
+
+// Row i = 8q + 4hh + t of a 32-row weight operand, as lane i (and i + 32) builds it
+struct HlmRow {
+  int q, hh, t;
+  __device__ __forceinline__ explicit HlmRow(int lane) : q((lane & 31) >> 3), hh((lane & 7) >> 2), t(lane & 3) {}
+  __device__ __forceinline__ int out() const { return 8 * hh + 4 * q + t; }                          // logits: q 0/1 -> output 8hh + 4q + t
+  __device__ __forceinline__ int channel() const { return (q >> 1) * 16 + 8 * hh + (q & 1) * 4 + t; }  // dz: the channel this row stands for
+};
+
+// logits^T [output row][voxel]: wops[0,1] = hi, [2,3] = lo parts of row `lrow` of W (-1: a zero row), k-steps of 16 channels
+__device__ __forceinline__ void hlm_logit_operands(u32x4 (*wops)[64], const float* W, int lrow, int lane) {
+  const int h = lane >> 5;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    float w[8];
+    eltx8 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = lrow >= 0 ? W[lrow * 32 + 16 * s + 8 * h + e] : 0.f;
+    hlm_split(w, hi, lo);
+    wops[s][lane] = __builtin_bit_cast(u32x4, hi);
+    wops[2 + s][lane] = __builtin_bit_cast(u32x4, lo);
+  }
+}
+// dz^T [channel row][voxel], one k-block: k-slot 8h + e = row `row0 + e` of W for e < cnt (the others zero), this lane's channel
+__device__ __forceinline__ void hlm_dz_operand(u32x4& hi_out, u32x4& lo_out, const float* W, int row0, int cnt, int ch) {
+  float w[8];
+  eltx8 hi, lo;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) w[e] = e < cnt ? W[(row0 + e) * 32 + ch] : 0.f;
+  hlm_split(w, hi, lo);
+  hi_out = __builtin_bit_cast(u32x4, hi);
+  lo_out = __builtin_bit_cast(u32x4, lo);
+}
+__device__ __forceinline__ eltx8 hlm_wop(const u32x4* wbase, int i) { return __builtin_bit_cast(eltx8, wbase[i * 64]); }
+
+// loss.hip dice_bwd_kernel's per-class terms: gI (the factor of the one-hot target) and gD
+__device__ __forceinline__ float hlm_dice_gI(float w, float I, float D, float eps, int ncls, float gc) {
+  return -2.f * w / ((float)ncls * fmaxf(D, eps)) * gc + ((I != I || D != D) ? __builtin_nanf("") : 0.f);
+}
+__device__ __forceinline__ float hlm_dice_gD(float w, float I, float D, float eps, int ncls, float gc) {
+  const float Dc = fmaxf(D, eps);
+  return (D >= eps ? 2.f * w * I / ((float)ncls * Dc * Dc) : 0.f) * gc;
+}
+
+// The lane's 4 voxel rows (2 pieces of 16 bytes each) of z for a run, and of the GroupNorm input two sub-tiles at a time: sub-tile j
+// in yp[j & 1], sub-tile j + 1 fetched at the top of trip j
+struct HlmRows {
+  u32x4 zp[4][2], yp[2][2];
+  __device__ __forceinline__ void load_z(const elt* zs, size_t vb, int h, bool live) {
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) zp[j][s] = live ? *reinterpret_cast<const u32x4*>(zs + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
+  }
+  __device__ __forceinline__ void fetch_y(const elt* ys, size_t vb, int h, bool live, int j) {
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      yp[j & 1][s] = (live && ys) ? *reinterpret_cast<const u32x4*>(ys + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
+  }
+};
+
+// logits of the 32 voxels of a sub-tile: 4 MFMAs (2 k-steps x hi / lo)
+__device__ __forceinline__ f32x16 hlm_logits(const u32x4* wbase, const u32x4 (&zp)[2]) {
+  f32x16 lg;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) lg[i] = 0.f;
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const eltx8 zb = __builtin_bit_cast(eltx8, zp[s]);
+    lg = MEDNET_MFMA_32x32x16(hlm_wop(wbase, s), zb, lg, 0, 0, 0);
+    lg = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 2 + s), zb, lg, 0, 0, 0);
+  }
+  return lg;
+}
+
+// dz of a voxel row: converted, stored (`dzrow`: the lane's first piece), and the first pass of the GroupNorm backward in front taken
+// from the STORED values (head_dgrad_gn_kernel): du = dz * act'(z), ss += du, sq += du * gn_y.  `gn` is workgroup-uniform.
+__device__ __forceinline__ void hlm_store_dz(const f32x16& dzv, elt* dzrow, bool live, bool gn, const u32x4 (&zp)[2], const u32x4 (&yp)[2],
+                                             int gn_act, float (&ss)[16], float (&sq)[16]) {
+  eltx8 o0, o1;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    o0[e] = (elt)dzv[e];
+    o1[e] = (elt)dzv[8 + e];
+  }
+  if (live) {
+    *reinterpret_cast<u32x4*>(dzrow) = __builtin_bit_cast(u32x4, o0);
+    *reinterpret_cast<u32x4*>(dzrow + 16) = __builtin_bit_cast(u32x4, o1);
+  }
+  if (gn) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const eltx8 zv = __builtin_bit_cast(eltx8, zp[s]), yv = __builtin_bit_cast(eltx8, yp[s]);
+      const eltx8 ov = s ? o1 : o0;
+      float du[8], zz[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        du[e] = (float)ov[e];
+        zz[e] = (float)zv[e];
+      }
+      act_grad_n<8>(du, zz, gn_act);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        ss[8 * s + e] += du[e];
+        sq[8 * s + e] = fmaf(du[e], (float)yv[e], sq[8 * s + e]);
+      }
+    }
+  }
+}
+
+// Wave-private LDS tiles of the backward, 32 voxel rows x 64 B each: z, dl (hi) and dl (lo).  dW += dl^T z over a sub-tile goes through
+// them: every lane writes its voxel row, the operands are read back transposed (contraction over the 32 voxels).
+struct HlmTiles {
+  char *zt, *dlh, *dll;
+  int troff;  // tr_operand: voxel rows 8h + tq (+ 4), 4 columns
+  __device__ __forceinline__ HlmTiles(char* smem, int wv, int lane) : zt(smem + wv * 6144), dlh(zt + 2048), dll(zt + 4096) {
+    const int tq = (lane & 15) >> 2, tp = lane & 3, tg = lane >> 4, h = lane >> 5;
+    troff = (8 * h + tq) * 64 + (16 * (tg & 1) + 4 * tp) * 2;
+  }
+  // the dl columns that no step writes are zeroed once (rows of dW that nobody reads, but no NaNs)
+  __device__ __forceinline__ void zero_dl(int lane) const {
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+    *reinterpret_cast<u32x4*>(dlh + lane * 32) = zero;
+    *reinterpret_cast<u32x4*>(dlh + lane * 32 + 16) = zero;
+    *reinterpret_cast<u32x4*>(dll + lane * 32) = zero;
+    *reinterpret_cast<u32x4*>(dll + lane * 32 + 16) = zero;
+    wave_lds_fence();
+  }
+  // d_hi / d_lo: the lane's 8 dl columns 8h .. 8h+7; x_hi / x_lo (nullable, lanes of h = 0): 4 more columns at 16 .. 19
+  __device__ __forceinline__ void dw_step(int g, int h, const u32x4 (&zp)[2], const eltx8& d_hi, const eltx8& d_lo, const eltx8* x_hi,
+                                          const eltx8* x_lo, f32x16& accw) const {
+    wave_lds_fence();  // (the reads of the previous sub-tile are above these writes)
+    *reinterpret_cast<u32x4*>(zt + g * 64 + 16 * h) = zp[0];
+    *reinterpret_cast<u32x4*>(zt + g * 64 + 32 + 16 * h) = zp[1];
+    *reinterpret_cast<u32x4*>(dlh + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, d_hi);
+    *reinterpret_cast<u32x4*>(dll + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, d_lo);
+    if (x_hi && h == 0) {
+      typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+      const u32x4 ch4 = __builtin_bit_cast(u32x4, *x_hi), cl4 = __builtin_bit_cast(u32x4, *x_lo);
+      const u32x2 ch2 = {ch4[0], ch4[1]}, cl2 = {cl4[0], cl4[1]};
+      *reinterpret_cast<u32x2*>(dlh + g * 64 + 32) = ch2;
+      *reinterpret_cast<u32x2*>(dll + g * 64 + 32) = cl2;
+    }
+    wave_lds_fence();  // the rows below were written by OTHER lanes of this wave
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const eltx8 fz = tr_operand(zt + ks * 1024 + troff, 256);
+      const eltx8 fh = tr_operand(dlh + ks * 1024 + troff, 256);
+      const eltx8 fl = tr_operand(dll + ks * 1024 + troff, 256);
+      accw = MEDNET_MFMA_32x32x16(fh, fz, accw, 0, 0, 0);
+      accw = MEDNET_MFMA_32x32x16(fl, fz, accw, 0, 0, 0);
+    }
+  }
+};
+
+// ---- end of kernel: every thread has put its values at scr[tid * HLM_SCR + .]; sums in a fixed order -----------------------------
+// value `idx` summed over the 4 waves x 32 lanes of lane half hh
+__device__ __forceinline__ float hlm_lane_sum(const float* scr, int hh, int idx) {
+  float s = 0.f;
+  for (int w = 0; w < 4; ++w)
+    for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + idx];
+  return s;
+}
+// GroupNorm sums: 16 channels x {ss, sq} per lane -> out[32][2] (this workgroup's row of gn_partial)
+__device__ __forceinline__ void hlm_gn_writeout(float* scr, int tid, const float (&ss)[16], const float (&sq)[16], float* out) {
+  float* mine = scr + tid * HLM_SCR;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    mine[i] = ss[i];
+    mine[16 + i] = sq[i];
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const int which = tid & 1, idx = (tid >> 1) & 15, hh = tid >> 5;
+    const float s = hlm_lane_sum(scr, hh, which * 16 + idx);
+    const int ch = (idx >> 3) * 16 + 8 * hh + (idx & 7);
+    out[ch * 2 + which] = s;
+  }
+  __syncthreads();
+}
+// dW and db of the workgroup -> wp[HLM_WIDTH].  Staged by the caller: the first NV accumulator values of every lane (dW rows k' =
+// 8 (i / 4) + 4h + i % 4; NV = 8: rows 0 .. 15 only), behind them 8 db values per lane half (k' = 8h + e) and, for NDB > 16, NDB - 16
+// more in the lanes of half 0 (k' = 16 + e)
+template <int NV, int NDB>
+__device__ __forceinline__ void hlm_dw_db_writeout(const float* scr, int tid, float* wp) {
+  __syncthreads();
+  for (int o = tid; o < 64 * NV; o += 256) {
+    const int L = o & 63, i = o >> 6;
+    const float s = (scr[(0 * 64 + L) * HLM_SCR + i] + scr[(1 * 64 + L) * HLM_SCR + i]) +
+                    (scr[(2 * 64 + L) * HLM_SCR + i] + scr[(3 * 64 + L) * HLM_SCR + i]);
+    const int kp = 8 * (i >> 2) + 4 * (L >> 5) + (i & 3);  // row k' of dW, column (input channel) L % 32
+    wp[kp * 32 + (L & 31)] = s;
+  }
+  if (tid < NDB) {
+    const int hh = tid < 16 ? tid >> 3 : 0, idx = tid < 16 ? NV + (tid & 7) : NV + 8 + (tid - 16);
+    wp[1024 + tid] = hlm_lane_sum(scr, hh, idx);
+  }
+}
+
 // CE: the class term is nn.CrossEntropyLoss(weight, ignore_index) (landmarks.py:49) instead of Dice: the forward accumulates
 // ce_fwd_kernel's {sum w_y nll, sum w_y} and, for dice_metric (loss.py:51-55), the unweighted, unmasked softmax sums {I, D} into
 // dice_partial; the backward's class gradient is ce_bwd_kernel's closed form (dcls / sum w) w_y (p_k - [k == y]).  Softmax only.
 template <bool BWD, bool CE = false>
 __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
   __shared__ __attribute__((aligned(16))) char smem[256 * HLM_SCR * 4];
   __shared__ float cst[2][32];
   __shared__ u32x4 wops[8][64];  // the 8 weight operands (below), one 16-byte fragment per lane: the same in every wave
@@ -78,43 +295,15 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
   // ---- weight operands, built once: hi + lo parts of the fp32 weights ---------------------------------------------
   // logits^T [k' row i][voxel]: A = W rows in the order that gives lane (g, h) its heat maps 8h .. 8h+7 in acc[0..7] and (h = 0)
   // the classes in acc[8..11]: row i = 8q + 4hh + t -> q 0/1: heat map 8hh + 4q + t; q 2, hh 0: class t
-  const int ri = lane & 31, rq = ri >> 3, rhh = (ri & 7) >> 2, rt = ri & 3;
-  const int lrow = rq < 2 ? (8 * rhh + 4 * rq + rt < a.nh ? 8 * rhh + 4 * rq + rt : -1)
-                          : ((rq == 2 && rhh == 0 && rt < a.ncls) ? a.nh + rt : -1);
-  if (wv == 0) {
-    eltx8 wl_hi[2], wl_lo[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float w = lrow >= 0 ? a.W[lrow * 32 + 16 * s + 8 * h + e] : 0.f;
-        wl_hi[s][e] = (elt)w;
-        wl_lo[s][e] = (elt)(w - (float)wl_hi[s][e]);
-      }
-      wops[s][lane] = __builtin_bit_cast(u32x4, wl_hi[s]);
-      wops[2 + s][lane] = __builtin_bit_cast(u32x4, wl_lo[s]);
-    }
-  }
+  const HlmRow r(lane);
+  const int lrow = r.q < 2 ? (r.out() < a.nh ? r.out() : -1) : ((r.q == 2 && r.hh == 0 && r.t < a.ncls) ? a.nh + r.t : -1);
+  if (wv == 0) hlm_logit_operands(wops, a.W, lrow, lane);
   // dz^T [channel row i][voxel]: row i = 8q + 4hh + t stands for channel (q / 2) * 16 + 8hh + (q % 2) * 4 + t, so that lane
   // (g, h) receives channels 8h .. 8h+7 in acc[0..7] and 16+8h .. in acc[8..15]; k-slots 8h + e: block 0 = heat map 8h + e,
   // block 1 = class e (lanes of h = 0)
   if (BWD && wv == 1) {
-    eltx8 wd_hi[2], wd_lo[2];
-    const int ch = (rq >> 1) * 16 + 8 * rhh + (rq & 1) * 4 + rt;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float w0 = 8 * h + e < a.nh ? a.W[(8 * h + e) * 32 + ch] : 0.f;
-      const float w1 = (h == 0 && e < a.ncls) ? a.W[(a.nh + e) * 32 + ch] : 0.f;
-      wd_hi[0][e] = (elt)w0;
-      wd_lo[0][e] = (elt)(w0 - (float)wd_hi[0][e]);
-      wd_hi[1][e] = (elt)w1;
-      wd_lo[1][e] = (elt)(w1 - (float)wd_hi[1][e]);
-    }
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      wops[4 + b][lane] = __builtin_bit_cast(u32x4, wd_hi[b]);
-      wops[6 + b][lane] = __builtin_bit_cast(u32x4, wd_lo[b]);
-    }
+    hlm_dz_operand(wops[4][lane], wops[6][lane], a.W, 8 * h, a.nh - 8 * h, r.channel());
+    hlm_dz_operand(wops[5][lane], wops[7][lane], a.W, a.nh, h == 0 ? a.ncls : 0, r.channel());
   }
   // ---- constants of a lane half, in LDS (they would hold 36 registers for the whole kernel): per h the biases of its 8 heat maps
   // [0..7] and of the classes [8..11], the heat maps' gradient scales [12..19] and the Dice gradient terms gI [20..23], gD [24..27]
@@ -133,11 +322,8 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
       if (CE && k < a.ncls) {
         v = i < 24 ? (a.cls_weight ? a.cls_weight[k] : 1.f) * (*a.dcls / a.saved[0]) : 0.f;  // (ce_bwd_kernel's `w`)
       } else if (k < a.ncls) {
-        const float gc = *a.dcls, w = a.cls_weight ? a.cls_weight[k] : 1.f;
-        const float I = a.saved[2 * k], D = a.saved[2 * k + 1];
-        const float Dc = fmaxf(D, a.eps);
-        v = i < 24 ? -2.f * w / ((float)a.ncls * Dc) * gc + ((I != I || D != D) ? __builtin_nanf("") : 0.f)
-                   : (D >= a.eps ? 2.f * w * I / ((float)a.ncls * Dc * Dc) : 0.f) * gc;
+        const float w = a.cls_weight ? a.cls_weight[k] : 1.f, I = a.saved[2 * k], D = a.saved[2 * k + 1];
+        v = i < 24 ? hlm_dice_gI(w, I, D, a.eps, a.ncls, *a.dcls) : hlm_dice_gD(w, I, D, a.eps, a.ncls, *a.dcls);
       }
     }
     cst[hh][i] = v;
@@ -147,7 +333,6 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
   // eight loop-invariant fragments back into 32 registers for the whole kernel
   const u32x4* wbase = &wops[0][lane];
   const float* cbase = &cst[h][0];
-  auto wop = [&](int i) { return __builtin_bit_cast(eltx8, wbase[i * 64]); };
   // ---- accumulators ---------------------------------------------------------------------------------------------------
   float hm_acc[8], dI[HLM_MAXC], dD[HLM_MAXC];  // forward
   float ss[16], sq[16], dbh[8], dbc[HLM_MAXC];  // backward
@@ -160,24 +345,12 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) ss[i] = sq[i] = accw[i] = 0.f;
 
-  // wave-private LDS tiles of the backward: 32 voxel rows x 64 B each of z, dl (hi) and dl (lo)
-  char* zt = smem + wv * 6144;
-  char* dlh = zt + 2048;
-  char* dll = zt + 4096;
+  const HlmTiles tiles(smem, wv, lane);
   // CE forward: {sum w_y nll, sum w_y} of this thread in its own slot of the end-of-kernel scratch (idle until then): as two more
   // loop-carried registers they took the form past its Dice twin's 148 VGPRs
   float* const ce_acc = reinterpret_cast<float*>(smem) + tid * HLM_SCR + 16;
   if constexpr (CE && !BWD) ce_acc[0] = ce_acc[1] = 0.f;
-  const int tq = (lane & 15) >> 2, tp = lane & 3, tg = lane >> 4;
-  const int troff = (8 * h + tq) * 64 + (16 * (tg & 1) + 4 * tp) * 2;  // tr_operand: voxel rows 8h + tq (+ 4), 4 columns
-  if constexpr (BWD) {  // columns 20 .. 31 of the dl tiles are never written: zero once (rows of dW that nobody reads, but no NaNs)
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-    *reinterpret_cast<u32x4*>(dlh + lane * 32) = zero;
-    *reinterpret_cast<u32x4*>(dlh + lane * 32 + 16) = zero;
-    *reinterpret_cast<u32x4*>(dll + lane * 32) = zero;
-    *reinterpret_cast<u32x4*>(dll + lane * 32 + 16) = zero;
-    wave_lds_fence();
-  }
+  if constexpr (BWD) tiles.zero_dl(lane);  // (columns 20 .. 31 of the dl tiles are never written)
 
   const elt* zs = a.z + (size_t)n * a.spatial * 32;
   const elt* ys = (BWD && a.gn_y) ? a.gn_y + (size_t)n * a.spatial * 32 : nullptr;
@@ -192,18 +365,9 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
     const size_t vb = (size_t)run * HLM_RUN + 4 * g;  // this lane's first voxel
     const bool live = vb < a.spatial;                 // (spatial % 4 == 0: all four voxels or none)
     // ---- loads: the lane's 4 voxel rows (2 pieces each) of z and of the GroupNorm input, 4 target bytes per heat map, 4 labels
-    u32x4 zp[4][2], yp[2][2];  // (yp: sub-tile j in yp[j & 1], sub-tile j + 1 fetched at the top of trip j)
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) zp[j][s] = live ? *reinterpret_cast<const u32x4*>(zs + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
-    auto fetch_y = [&](int j) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-        yp[j & 1][s] = (live && ys) ? *reinterpret_cast<const u32x4*>(ys + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
-    };
-    if constexpr (BWD) fetch_y(0);
+    HlmRows rows;
+    rows.load_z(zs, vb, h, live);
+    if constexpr (BWD) rows.fetch_y(ys, vb, h, live, 0);
     unsigned tb[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e)
@@ -214,18 +378,9 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
     for (int j = 0; j < 4; ++j) {
       asm volatile("" : "+v"(wbase), "+v"(cbase));
       if constexpr (BWD) {
-        if (j < 3) fetch_y(j + 1);
+        if (j < 3) rows.fetch_y(ys, vb, h, live, j + 1);
       }
-      // ---- logits of the 32 voxels {4g + j}: 4 MFMAs (2 k-steps x hi / lo)
-      f32x16 lg;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) lg[i] = 0.f;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const eltx8 zb = __builtin_bit_cast(eltx8, zp[j][s]);
-        lg = MEDNET_MFMA_32x32x16(wop(s), zb, lg, 0, 0, 0);
-        lg = MEDNET_MFMA_32x32x16(wop(2 + s), zb, lg, 0, 0, 0);
-      }
+      const f32x16 lg = hlm_logits(wbase, rows.zp[j]);  // the 32 voxels {4g + j}
       float lh[8], lc[HLM_MAXC], p[HLM_MAXC];
 #pragma unroll
       for (int e = 0; e < 8; ++e) lh[e] = lg[e] + cbase[e];
@@ -346,77 +501,24 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
             dbc[k] += dc[k];
           }
         }
-        eltx8 dh_hi, dh_lo, dc_hi, dc_lo;
+        float dc8[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          dh_hi[e] = (elt)dh[e];
-          dh_lo[e] = (elt)(dh[e] - (float)dh_hi[e]);
-          const float c = e < HLM_MAXC ? dc[e & (HLM_MAXC - 1)] : 0.f;
-          dc_hi[e] = (elt)c;
-          dc_lo[e] = (elt)(c - (float)dc_hi[e]);
-        }
+        for (int e = 0; e < 8; ++e) dc8[e] = e < HLM_MAXC ? dc[e & (HLM_MAXC - 1)] : 0.f;
+        eltx8 dh_hi, dh_lo, dc_hi, dc_lo;
+        hlm_split(dh, dh_hi, dh_lo);
+        hlm_split(dc8, dc_hi, dc_lo);
         // ---- dz^T = W^T dl^T: 6 MFMAs (two k-blocks x {hi hi, lo hi, hi lo})
         f32x16 dzv;
 #pragma unroll
         for (int i = 0; i < 16; ++i) dzv[i] = 0.f;
-        dzv = MEDNET_MFMA_32x32x16(wop(4), dh_hi, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(wop(6), dh_hi, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(wop(4), dh_lo, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(wop(5), dc_hi, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(wop(7), dc_hi, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(wop(5), dc_lo, dzv, 0, 0, 0);
-        eltx8 o0, o1;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          o0[e] = (elt)dzv[e];
-          o1[e] = (elt)dzv[8 + e];
-        }
-        if (live) {
-          *reinterpret_cast<u32x4*>(dzs + (vb + j) * 32 + 8 * h) = __builtin_bit_cast(u32x4, o0);
-          *reinterpret_cast<u32x4*>(dzs + (vb + j) * 32 + 16 + 8 * h) = __builtin_bit_cast(u32x4, o1);
-        }
-        // ---- first pass of the GroupNorm backward in front, from the STORED rows (head_dgrad_gn_kernel): du = dz * act'(z)
-        if (ys) {  // (workgroup-uniform)
-#pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const eltx8 zv = __builtin_bit_cast(eltx8, zp[j][s]), yv = __builtin_bit_cast(eltx8, yp[j & 1][s]);
-            const eltx8 ov = s ? o1 : o0;
-            float du[8], zz[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              du[e] = (float)ov[e];
-              zz[e] = (float)zv[e];
-            }
-            act_grad_n<8>(du, zz, a.gn_act);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              ss[8 * s + e] += du[e];
-              sq[8 * s + e] = fmaf(du[e], (float)yv[e], sq[8 * s + e]);
-            }
-          }
-        }
-        // ---- dW += dl^T z over these 32 voxels: tiles [voxel row g][64 B] in this wave's LDS, read back transposed
-        wave_lds_fence();  // (the reads of the previous sub-tile are above these writes)
-        *reinterpret_cast<u32x4*>(zt + g * 64 + 16 * h) = zp[j][0];
-        *reinterpret_cast<u32x4*>(zt + g * 64 + 32 + 16 * h) = zp[j][1];
-        *reinterpret_cast<u32x4*>(dlh + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, dh_hi);
-        *reinterpret_cast<u32x4*>(dll + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, dh_lo);
-        if (h == 0) {
-          typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-          const u32x4 ch4 = __builtin_bit_cast(u32x4, dc_hi), cl4 = __builtin_bit_cast(u32x4, dc_lo);
-          const u32x2 ch2 = {ch4[0], ch4[1]}, cl2 = {cl4[0], cl4[1]};
-          *reinterpret_cast<u32x2*>(dlh + g * 64 + 32) = ch2;
-          *reinterpret_cast<u32x2*>(dll + g * 64 + 32) = cl2;
-        }
-        wave_lds_fence();  // the rows below were written by OTHER lanes of this wave
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const eltx8 fz = tr_operand(zt + ks * 1024 + troff, 256);
-          const eltx8 fh = tr_operand(dlh + ks * 1024 + troff, 256);
-          const eltx8 fl = tr_operand(dll + ks * 1024 + troff, 256);
-          accw = MEDNET_MFMA_32x32x16(fh, fz, accw, 0, 0, 0);
-          accw = MEDNET_MFMA_32x32x16(fl, fz, accw, 0, 0, 0);
-        }
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 4), dh_hi, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 6), dh_hi, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 4), dh_lo, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 5), dc_hi, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 7), dc_hi, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 5), dc_lo, dzv, 0, 0, 0);
+        hlm_store_dz(dzv, dzs + (vb + j) * 32 + 8 * h, live, ys != nullptr, rows.zp[j], rows.yp[j & 1], a.gn_act, ss, sq);
+        tiles.dw_step(g, h, rows.zp[j], dh_hi, dh_lo, &dc_hi, &dc_lo, accw);  // dW += dl^T z over these 32 voxels
       }
     }
   }
@@ -437,17 +539,12 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
     __syncthreads();  // (CE: values 16 / 17 are the thread's ce_acc)
     if (CE && tid >= 16 + 2 * HLM_MAXC && tid < 18 + 2 * HLM_MAXC) {  // CE sums: lanes of half 0, values 16 / 17
       const int which = tid - (16 + 2 * HLM_MAXC);
-      float s = 0.f;
-      for (int w = 0; w < 4; ++w)
-        for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + gg) * HLM_SCR + 16 + which];
-      a.ce_partial[((size_t)n * a.chunks + chunk) * 2 + which] = s;
+      a.ce_partial[((size_t)n * a.chunks + chunk) * 2 + which] = hlm_lane_sum(scr, 0, 16 + which);
     }
     if (tid < 16 + 2 * HLM_MAXC) {
       // heat map c = 8hh + e: lanes of half hh, value e; class sums: lanes of half 0
       const int hh = tid < 16 ? tid >> 3 : 0, idx = tid < 16 ? tid & 7 : tid - 8;
-      float s = 0.f;
-      for (int w = 0; w < 4; ++w)
-        for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + idx];
+      const float s = hlm_lane_sum(scr, hh, idx);
       if (tid < 16) {
         if (tid < a.nh) a.hm_partial[((size_t)n * a.nh + tid) * a.chunks + chunk] = s;
       } else {
@@ -456,48 +553,15 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
       }
     }
   } else {
-    // (a) GroupNorm sums: 16 channels x {ss, sq} per lane
-    if (a.gn_partial) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        mine[i] = ss[i];
-        mine[16 + i] = sq[i];
-      }
-      __syncthreads();
-      if (tid < 64) {
-        const int which = tid & 1, idx = (tid >> 1) & 15, hh = tid >> 5;
-        float s = 0.f;
-        for (int w = 0; w < 4; ++w)
-          for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + which * 16 + idx];
-        const int ch = (idx >> 3) * 16 + 8 * hh + (idx & 7);
-        a.gn_partial[(((size_t)n * a.chunks + chunk) * 32 + ch) * 2 + which] = s;
-      }
-      __syncthreads();
-    }
-    float* wp = a.wpart + ((size_t)n * a.chunks + chunk) * HLM_WIDTH;
-    // (b) dW: 16 accumulator values per lane, summed over the 4 waves
+    if (a.gn_partial) hlm_gn_writeout(scr, tid, ss, sq, a.gn_partial + ((size_t)n * a.chunks + chunk) * 64);
+    // dW: 16 accumulator values per lane; db behind them: the heat maps', then the classes' (k' = heat map c, or 16 + class)
 #pragma unroll
     for (int i = 0; i < 16; ++i) mine[i] = accw[i];
-    // (c) db behind them
 #pragma unroll
     for (int e = 0; e < 8; ++e) mine[16 + e] = dbh[e];
 #pragma unroll
     for (int k = 0; k < HLM_MAXC; ++k) mine[24 + k] = dbc[k];
-    __syncthreads();
-    for (int o = tid; o < 1024; o += 256) {
-      const int L = o & 63, i = o >> 6;
-      const float s = (scr[(0 * 64 + L) * HLM_SCR + i] + scr[(1 * 64 + L) * HLM_SCR + i]) +
-                      (scr[(2 * 64 + L) * HLM_SCR + i] + scr[(3 * 64 + L) * HLM_SCR + i]);
-      const int kp = 8 * (i >> 2) + 4 * (L >> 5) + (i & 3);  // row k' of dW, column (input channel) L % 32
-      wp[kp * 32 + (L & 31)] = s;
-    }
-    if (tid < 16 + HLM_MAXC) {
-      const int hh = tid < 16 ? tid >> 3 : 0, idx = tid < 16 ? 16 + (tid & 7) : 24 + (tid - 16);
-      float s = 0.f;
-      for (int w = 0; w < 4; ++w)
-        for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + idx];
-      wp[1024 + tid] = s;  // k' = heat map tid, or 16 + class
-    }
+    hlm_dw_db_writeout<16, 16 + HLM_MAXC>(scr, tid, a.wpart + ((size_t)n * a.chunks + chunk) * HLM_WIDTH);
   }
 }
 
@@ -555,7 +619,6 @@ __device__ __forceinline__ float xor32_max(float v) {  // max(v(l), v(l ^ 32)) i
 
 template <bool BWD, bool CE>
 __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
   __shared__ __attribute__((aligned(16))) char smem[256 * HLM_SCR * 4];
   __shared__ float cst[2][24];
   __shared__ u32x4 wops[6][64];  // 0,1: logits hi (k-steps); 2,3: lo; 4: dz hi; 5: dz lo
@@ -566,34 +629,9 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
   const int nv = min(8, max(0, a.ncls - 8 * h));  // classes of this lane half
 
   // ---- weight operands (head_lm_kernel's, the classes in the heat maps' place) ----------------------------------------------
-  const int ri = lane & 31, rq = ri >> 3, rhh = (ri & 7) >> 2, rt = ri & 3;
-  const int lrow = (rq < 2 && 8 * rhh + 4 * rq + rt < a.ncls) ? 8 * rhh + 4 * rq + rt : -1;
-  if (wv == 0) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      eltx8 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float w = lrow >= 0 ? a.W[lrow * 32 + 16 * s + 8 * h + e] : 0.f;
-        hi[e] = (elt)w;
-        lo[e] = (elt)(w - (float)hi[e]);
-      }
-      wops[s][lane] = __builtin_bit_cast(u32x4, hi);
-      wops[2 + s][lane] = __builtin_bit_cast(u32x4, lo);
-    }
-  }
-  if (BWD && wv == 1) {
-    eltx8 hi, lo;
-    const int ch = (rq >> 1) * 16 + 8 * rhh + (rq & 1) * 4 + rt;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float w = 8 * h + e < a.ncls ? a.W[(8 * h + e) * 32 + ch] : 0.f;
-      hi[e] = (elt)w;
-      lo[e] = (elt)(w - (float)hi[e]);
-    }
-    wops[4][lane] = __builtin_bit_cast(u32x4, hi);
-    wops[5][lane] = __builtin_bit_cast(u32x4, lo);
-  }
+  const HlmRow r(lane);
+  if (wv == 0) hlm_logit_operands(wops, a.W, (r.q < 2 && r.out() < a.ncls) ? r.out() : -1, lane);
+  if (BWD && wv == 1) hlm_dz_operand(wops[4][lane], wops[5][lane], a.W, 8 * h, a.ncls - 8 * h, r.channel());
   // ---- constants of a lane half: the biases of its 8 classes [0..7]; CE forward: the class weights [8..15]; CE backward:
   // w_k dloss / sum w [8..15]; Dice backward: gI [8..15], gD [16..23] (dice_bwd_kernel)
   if (wv == 2 && (lane & 31) < 24) {
@@ -604,11 +642,8 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
       if (i < 8) v = a.bias ? a.bias[k] : 0.f;
       else if (CE) v = i < 16 ? (BWD ? w * (*a.dcls / a.saved[0]) : w) : 0.f;
       else if (BWD) {
-        const float gc = *a.dcls;
         const float I = a.saved[2 * k], D = a.saved[2 * k + 1];
-        const float Dc = fmaxf(D, a.eps);
-        v = i < 16 ? -2.f * w / ((float)a.ncls * Dc) * gc + ((I != I || D != D) ? __builtin_nanf("") : 0.f)
-                   : (D >= a.eps ? 2.f * w * I / ((float)a.ncls * Dc * Dc) : 0.f) * gc;
+        v = i < 16 ? hlm_dice_gI(w, I, D, a.eps, a.ncls, *a.dcls) : hlm_dice_gD(w, I, D, a.eps, a.ncls, *a.dcls);
       }
     }
     cst[hh][i] = v;
@@ -616,7 +651,6 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
   __syncthreads();
   const u32x4* wbase = &wops[0][lane];
   const float* cbase = &cst[h][0];
-  auto wop = [&](int i) { return __builtin_bit_cast(eltx8, wbase[i * 64]); };
   // ---- accumulators ---------------------------------------------------------------------------------------------------
   float dI[8], dD[8];                 // forward (Dice)
   float ss[16], sq[16], dbc[8];       // backward
@@ -627,21 +661,10 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) ss[i] = sq[i] = accw[i] = 0.f;
 
-  char* zt = smem + wv * 6144;
-  char* dlh = zt + 2048;
-  char* dll = zt + 4096;
+  const HlmTiles tiles(smem, wv, lane);
   float* const ce_acc = reinterpret_cast<float*>(smem) + tid * HLM_SCR + 16;  // (the forward has no tiles: head_lm_kernel)
   if constexpr (CE && !BWD) ce_acc[0] = ce_acc[1] = 0.f;
-  const int tq = (lane & 15) >> 2, tp = lane & 3, tg = lane >> 4;
-  const int troff = (8 * h + tq) * 64 + (16 * (tg & 1) + 4 * tp) * 2;
-  if constexpr (BWD) {  // columns 16 .. 31 of the dl tiles are never written
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-    *reinterpret_cast<u32x4*>(dlh + lane * 32) = zero;
-    *reinterpret_cast<u32x4*>(dlh + lane * 32 + 16) = zero;
-    *reinterpret_cast<u32x4*>(dll + lane * 32) = zero;
-    *reinterpret_cast<u32x4*>(dll + lane * 32 + 16) = zero;
-    wave_lds_fence();
-  }
+  if constexpr (BWD) tiles.zero_dl(lane);  // (columns 16 .. 31 of the dl tiles are never written)
 
   const elt* zs = a.z + (size_t)n * a.spatial * 32;
   const elt* ys = (BWD && a.gn_y) ? a.gn_y + (size_t)n * a.spatial * 32 : nullptr;
@@ -652,35 +675,18 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
   for (int run = chunk * a.chunk_runs + wv; run < run_end; run += 4) {
     const size_t vb = (size_t)run * HLM_RUN + 4 * g;
     const bool live = vb < a.spatial;  // (spatial % 4 == 0: all four voxels or none)
-    u32x4 zp[4][2], yp[2][2];
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) zp[j][s] = live ? *reinterpret_cast<const u32x4*>(zs + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
-    auto fetch_y = [&](int j) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-        yp[j & 1][s] = (live && ys) ? *reinterpret_cast<const u32x4*>(ys + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
-    };
-    if constexpr (BWD) fetch_y(0);
+    HlmRows rows;
+    rows.load_z(zs, vb, h, live);
+    if constexpr (BWD) rows.fetch_y(ys, vb, h, live, 0);
     const unsigned lb = live ? *reinterpret_cast<const unsigned*>(lb8 + vb) : 0u;  // (both halves: each owns 8 of the classes)
 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       asm volatile("" : "+v"(wbase), "+v"(cbase));
       if constexpr (BWD) {
-        if (j < 3) fetch_y(j + 1);
+        if (j < 3) rows.fetch_y(ys, vb, h, live, j + 1);
       }
-      f32x16 lg;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) lg[i] = 0.f;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const eltx8 zb = __builtin_bit_cast(eltx8, zp[j][s]);
-        lg = MEDNET_MFMA_32x32x16(wop(s), zb, lg, 0, 0, 0);
-        lg = MEDNET_MFMA_32x32x16(wop(2 + s), zb, lg, 0, 0, 0);
-      }
+      const f32x16 lg = hlm_logits(wbase, rows.zp[j]);
       float lc[8], p[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) lc[e] = lg[e] + cbase[e];
@@ -772,62 +778,16 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
           }
         }
         eltx8 dc_hi, dc_lo;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          dc_hi[e] = (elt)dc[e];
-          dc_lo[e] = (elt)(dc[e] - (float)dc_hi[e]);
-        }
+        hlm_split(dc, dc_hi, dc_lo);
         // ---- dz^T = W^T dl^T: hi hi, lo hi, hi lo
         f32x16 dzv;
 #pragma unroll
         for (int i = 0; i < 16; ++i) dzv[i] = 0.f;
-        dzv = MEDNET_MFMA_32x32x16(wop(4), dc_hi, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(wop(5), dc_hi, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(wop(4), dc_lo, dzv, 0, 0, 0);
-        eltx8 o0, o1;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          o0[e] = (elt)dzv[e];
-          o1[e] = (elt)dzv[8 + e];
-        }
-        if (live) {
-          *reinterpret_cast<u32x4*>(dzs + (vb + j) * 32 + 8 * h) = __builtin_bit_cast(u32x4, o0);
-          *reinterpret_cast<u32x4*>(dzs + (vb + j) * 32 + 16 + 8 * h) = __builtin_bit_cast(u32x4, o1);
-        }
-        if (ys) {  // (workgroup-uniform) first pass of the GroupNorm backward in front, from the STORED rows
-#pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const eltx8 zv = __builtin_bit_cast(eltx8, zp[j][s]), yv = __builtin_bit_cast(eltx8, yp[j & 1][s]);
-            const eltx8 ov = s ? o1 : o0;
-            float du[8], zz[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              du[e] = (float)ov[e];
-              zz[e] = (float)zv[e];
-            }
-            act_grad_n<8>(du, zz, a.gn_act);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              ss[8 * s + e] += du[e];
-              sq[8 * s + e] = fmaf(du[e], (float)yv[e], sq[8 * s + e]);
-            }
-          }
-        }
-        // ---- dW += dl^T z over these 32 voxels
-        wave_lds_fence();
-        *reinterpret_cast<u32x4*>(zt + g * 64 + 16 * h) = zp[j][0];
-        *reinterpret_cast<u32x4*>(zt + g * 64 + 32 + 16 * h) = zp[j][1];
-        *reinterpret_cast<u32x4*>(dlh + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, dc_hi);
-        *reinterpret_cast<u32x4*>(dll + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, dc_lo);
-        wave_lds_fence();
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const eltx8 fz = tr_operand(zt + ks * 1024 + troff, 256);
-          const eltx8 fh = tr_operand(dlh + ks * 1024 + troff, 256);
-          const eltx8 fl = tr_operand(dll + ks * 1024 + troff, 256);
-          accw = MEDNET_MFMA_32x32x16(fh, fz, accw, 0, 0, 0);
-          accw = MEDNET_MFMA_32x32x16(fl, fz, accw, 0, 0, 0);
-        }
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 4), dc_hi, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 5), dc_hi, dzv, 0, 0, 0);
+        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 4), dc_lo, dzv, 0, 0, 0);
+        hlm_store_dz(dzv, dzs + (vb + j) * 32 + 8 * h, live, ys != nullptr, rows.zp[j], rows.yp[j & 1], a.gn_act, ss, sq);
+        tiles.dw_step(g, h, rows.zp[j], dc_hi, dc_lo, nullptr, nullptr, accw);  // dW += dl^T z over these 32 voxels
       }
     }
   }
@@ -852,54 +812,21 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
       }
       __syncthreads();
       if (tid < 2 * HSG_MAXC) {  // class k = 8hh + e: lanes of half hh, value e (I) / 8 + e (D)
-        const int k = tid >> 1, which = tid & 1, hh = k >> 3, idx = 8 * which + (k & 7);
-        float s = 0.f;
-        for (int w = 0; w < 4; ++w)
-          for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + idx];
+        const int k = tid >> 1, which = tid & 1;
+        const float s = hlm_lane_sum(scr, k >> 3, 8 * which + (k & 7));
         if (k < a.ncls) a.dice_partial[(((size_t)n * a.chunks + chunk) * a.ncls + k) * 2 + which] = s;
       }
     }
   } else {
-    if (a.gn_partial) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        mine[i] = ss[i];
-        mine[16 + i] = sq[i];
-      }
-      __syncthreads();
-      if (tid < 64) {
-        const int which = tid & 1, idx = (tid >> 1) & 15, hh = tid >> 5;
-        float s = 0.f;
-        for (int w = 0; w < 4; ++w)
-          for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + which * 16 + idx];
-        const int ch = (idx >> 3) * 16 + 8 * hh + (idx & 7);
-        a.gn_partial[(((size_t)n * a.chunks + chunk) * 32 + ch) * 2 + which] = s;
-      }
-      __syncthreads();
-    }
+    if (a.gn_partial) hlm_gn_writeout(scr, tid, ss, sq, a.gn_partial + ((size_t)n * a.chunks + chunk) * 64);
     // head_lm_kernel's rows: dW row k' = class k' (accumulator values 0 .. 7 of a lane; 8 .. 15 are the zero rows 16 .. 31, which
     // head_lm_wfinal_kernel never reads with ncls = 0), db at 1024 + k'
-    float* wp = a.wpart + ((size_t)n * a.chunks + chunk) * HLM_WIDTH;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       mine[i] = accw[i];
       mine[8 + i] = dbc[i];
     }
-    __syncthreads();
-    for (int o = tid; o < 512; o += 256) {
-      const int L = o & 63, i = o >> 6;
-      const float s = (scr[(0 * 64 + L) * HLM_SCR + i] + scr[(1 * 64 + L) * HLM_SCR + i]) +
-                      (scr[(2 * 64 + L) * HLM_SCR + i] + scr[(3 * 64 + L) * HLM_SCR + i]);
-      const int kp = 8 * (i >> 2) + 4 * (L >> 5) + (i & 3);
-      wp[kp * 32 + (L & 31)] = s;
-    }
-    if (tid < HSG_MAXC) {
-      const int hh = tid >> 3, idx = 8 + (tid & 7);
-      float s = 0.f;
-      for (int w = 0; w < 4; ++w)
-        for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + idx];
-      wp[1024 + tid] = s;
-    }
+    hlm_dw_db_writeout<8, HSG_MAXC>(scr, tid, a.wpart + ((size_t)n * a.chunks + chunk) * HLM_WIDTH);
   }
 }
 
@@ -926,75 +853,63 @@ size_t head_lm_ws_bytes(int n, size_t spatial, int nh, int ncls) {
   return ((fwd > bwd ? fwd : bwd) + 64) * sizeof(float);
 }
 
-template <bool CE>
-static int head_lm_fwd_launch(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                              int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial,
-                              float* ce_partial, int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, hipStream_t s) {
-  HlmArgs a = {};
+// Everything both directions of both heads share; the segmentation head is nh = 0 without targets.  `tgt` and `lab` are read four
+// voxels at a time.
+static int hlm_args(HlmArgs& a, const char* what, const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn,
+                    const void* lab, int64_t lab_sn, const float* cls_weight, size_t spatial, int nh, int ncls, int kind, int sigmoid,
+                    int ignore) {
   a.z = (const elt*)z; a.W = W; a.bias = bias; a.tgt = (const uint8_t*)tgt; a.lab = (const uint8_t*)lab;
   a.tgt_sn = tgt_sn; a.lab_sn = lab_sn; a.spatial = spatial; a.nh = nh; a.ncls = ncls;
   head_lm_plan(spatial, a.runs, a.chunk_runs, a.chunks);
-  a.kind = kind; a.sigmoid = sigmoid; a.ignore = ignore;
-  a.hm_partial = hm_partial; a.dice_partial = dice_partial; a.logits = logits;
-  a.cls_weight = cls_weight; a.ce_partial = ce_partial;
+  a.kind = kind; a.sigmoid = sigmoid; a.ignore = ignore; a.cls_weight = cls_weight;
   MEDNET_REQUIRE(tgt_sn % 4 == 0 && lab_sn % 4 == 0 && ((uintptr_t)tgt & 3) == 0 && ((uintptr_t)lab & 3) == 0, MEDNET_E_SHAPE,
-                 "head_lm: targets and labels must be 4-byte aligned per sample");
-  hipLaunchKernelGGL((head_lm_kernel<false, CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  return check_launch(CE ? "head_lm_ce_fwd" : "head_lm_fwd");
+                 "%s: %s must be 4-byte aligned per sample", what, tgt ? "targets and labels" : "labels");
+  return 0;
 }
-int launch_head_lm_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                       int64_t lab_sn, float* logits, float* hm_partial, float* dice_partial, int n, size_t spatial, int nh, int ncls,
-                       int kind, int sigmoid, int ignore, hipStream_t s) {
-  return head_lm_fwd_launch<false>(z, W, bias, tgt, tgt_sn, lab, lab_sn, nullptr, logits, hm_partial, dice_partial, nullptr, n, spatial,
-                                   nh, ncls, kind, sigmoid, ignore, s);
-}
-int launch_head_lm_ce_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                          int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial, float* ce_partial,
-                          int n, size_t spatial, int nh, int ncls, int kind, int ignore, hipStream_t s) {
-  return head_lm_fwd_launch<true>(z, W, bias, tgt, tgt_sn, lab, lab_sn, cls_weight, logits, hm_partial, dice_partial, ce_partial, n,
-                                  spatial, nh, ncls, kind, 0, ignore, s);
+// ... and what the backward adds; its workspace holds the dW / db partial rows
+static int hlm_bwd_args(HlmArgs& a, const char* what, const float* saved, const float* dcls, float eps, void* dz, const void* gn_y,
+                        int gn_act, float* gn_partial, void* ws, size_t ws_bytes, size_t ws_need) {
+  a.saved = saved; a.dcls = dcls; a.eps = eps;
+  a.dz = (elt*)dz; a.gn_y = (const elt*)gn_y; a.gn_act = gn_act; a.gn_partial = gn_partial;
+  MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "%s: gn_y and gn_partial go together", what);
+  MEDNET_REQUIRE(ws_bytes >= ws_need, MEDNET_E_WORKSPACE, "%s: workspace too small", what);
+  a.wpart = (float*)ws;
+  return 0;
 }
 
-template <bool CE>
-static int head_lm_bwd_launch(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                              int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
-                              const float* dreg, float eps, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db,
-                              int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, void* ws, size_t ws_bytes,
-                              hipStream_t s) {
+// ce = 1: nn.CrossEntropyLoss(cls_weight, ignore) as the class term (softmax; `sigmoid` and `eps` are not read): ce_partial [n][chunk][2]
+// for ce_finalize, and dice_partial takes dice_metric's unweighted, unmasked sums; the backward reads saved[0] = sum w_y of that forward.
+int launch_head_lm_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
+                       int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial, float* ce_partial,
+                       int n, size_t spatial, int nh, int ncls, int kind, int ce, int sigmoid, int ignore, hipStream_t s) {
   HlmArgs a = {};
-  a.z = (const elt*)z; a.W = W; a.bias = bias; a.tgt = (const uint8_t*)tgt; a.lab = (const uint8_t*)lab;
-  a.tgt_sn = tgt_sn; a.lab_sn = lab_sn; a.spatial = spatial; a.nh = nh; a.ncls = ncls;
-  head_lm_plan(spatial, a.runs, a.chunk_runs, a.chunks);
-  a.kind = kind; a.sigmoid = sigmoid; a.ignore = ignore;
-  a.saved = saved; a.cls_weight = cls_weight; a.reg_weight = reg_weight; a.dcls = dcls; a.dreg = dreg;
-  a.eps = eps; a.inv_count = (float)(1.0 / ((double)n * (double)spatial));
-  a.dz = (elt*)dz; a.gn_y = (const elt*)gn_y; a.gn_act = gn_act; a.gn_partial = gn_partial;
-  MEDNET_REQUIRE(tgt_sn % 4 == 0 && lab_sn % 4 == 0 && ((uintptr_t)tgt & 3) == 0 && ((uintptr_t)lab & 3) == 0, MEDNET_E_SHAPE,
-                 "head_lm: targets and labels must be 4-byte aligned per sample");
-  MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "head_lm_bwd: gn_y and gn_partial go together");
-  MEDNET_REQUIRE(ws_bytes >= head_lm_ws_bytes(n, spatial, nh, ncls), MEDNET_E_WORKSPACE, "head_lm_bwd: workspace too small");
-  a.wpart = (float*)ws;
-  hipLaunchKernelGGL((head_lm_kernel<true, CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  int rc = check_launch(CE ? "head_lm_ce_bwd" : "head_lm_bwd");
+  const int rc = hlm_args(a, "head_lm", z, W, bias, tgt, tgt_sn, lab, lab_sn, ce ? cls_weight : nullptr, spatial, nh, ncls, kind,
+                          ce ? 0 : sigmoid, ignore);
   if (rc) return rc;
-  const int total = (nh + ncls) * 33;
-  hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((total + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, nh, ncls, dw, db);
-  return check_launch("head_lm_wfinal");
+  a.hm_partial = hm_partial; a.dice_partial = dice_partial; a.logits = logits; a.ce_partial = ce ? ce_partial : nullptr;
+  if (ce) hipLaunchKernelGGL((head_lm_kernel<false, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_lm_kernel<false, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  return check_launch(ce ? "head_lm_ce_fwd" : "head_lm_fwd");
 }
 int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
                        int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
                        const float* dreg, float eps, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db,
-                       int n, size_t spatial, int nh, int ncls, int kind, int sigmoid, int ignore, void* ws, size_t ws_bytes,
+                       int n, size_t spatial, int nh, int ncls, int kind, int ce, int sigmoid, int ignore, void* ws, size_t ws_bytes,
                        hipStream_t s) {
-  return head_lm_bwd_launch<false>(z, W, bias, tgt, tgt_sn, lab, lab_sn, saved, cls_weight, reg_weight, dcls, dreg, eps, dz, gn_y, gn_act,
-                                   gn_partial, dw, db, n, spatial, nh, ncls, kind, sigmoid, ignore, ws, ws_bytes, s);
-}
-int launch_head_lm_ce_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
-                          int64_t lab_sn, const float* saved, const float* cls_weight, const float* reg_weight, const float* dcls,
-                          const float* dreg, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* db, int n,
-                          size_t spatial, int nh, int ncls, int kind, int ignore, void* ws, size_t ws_bytes, hipStream_t s) {
-  return head_lm_bwd_launch<true>(z, W, bias, tgt, tgt_sn, lab, lab_sn, saved, cls_weight, reg_weight, dcls, dreg, 0.f, dz, gn_y, gn_act,
-                                  gn_partial, dw, db, n, spatial, nh, ncls, kind, 0, ignore, ws, ws_bytes, s);
+  HlmArgs a = {};
+  int rc = hlm_args(a, "head_lm", z, W, bias, tgt, tgt_sn, lab, lab_sn, cls_weight, spatial, nh, ncls, kind, ce ? 0 : sigmoid, ignore);
+  if (rc) return rc;
+  rc = hlm_bwd_args(a, "head_lm_bwd", saved, dcls, ce ? 0.f : eps, dz, gn_y, gn_act, gn_partial, ws, ws_bytes,
+                    head_lm_ws_bytes(n, spatial, nh, ncls));
+  if (rc) return rc;
+  a.reg_weight = reg_weight; a.dreg = dreg; a.inv_count = (float)(1.0 / ((double)n * (double)spatial));
+  if (ce) hipLaunchKernelGGL((head_lm_kernel<true, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_lm_kernel<true, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  rc = check_launch(ce ? "head_lm_ce_bwd" : "head_lm_bwd");
+  if (rc) return rc;
+  const int total = (nh + ncls) * 33;
+  hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((total + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, nh, ncls, dw, db);
+  return check_launch("head_lm_wfinal");
 }
 
 // ---- the segmentation head (head_seg_kernel): head_lm's plan, partial rows and final sums -------------------------------------
@@ -1007,28 +922,15 @@ size_t head_seg_ws_bytes(int n, size_t spatial, int ncls) {
   const size_t bwd = (size_t)n * chunks * HLM_WIDTH;
   return ((fwd > bwd ? fwd : bwd) + 64) * sizeof(float);
 }
-static int head_seg_args(HlmArgs& a, const char* what, const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn,
-                         const float* cls_weight, size_t spatial, int ncls, int sigmoid, int ignore) {
-  a.z = (const elt*)z; a.W = W; a.bias = bias; a.lab = (const uint8_t*)lab; a.lab_sn = lab_sn;
-  a.spatial = spatial; a.nh = 0; a.ncls = ncls;
-  head_lm_plan(spatial, a.runs, a.chunk_runs, a.chunks);
-  a.sigmoid = sigmoid; a.ignore = ignore; a.cls_weight = cls_weight;
-  MEDNET_REQUIRE(lab_sn % 4 == 0 && ((uintptr_t)lab & 3) == 0, MEDNET_E_SHAPE, "%s: labels must be 4-byte aligned per sample", what);
-  return 0;
-}
 int launch_head_seg_fwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* cls_weight,
                         float* logits, float* partial, int n, size_t spatial, int ncls, int ce, int sigmoid, int ignore, hipStream_t s) {
   HlmArgs a = {};
-  const int rc = head_seg_args(a, "head_seg_fwd", z, W, bias, lab, lab_sn, cls_weight, spatial, ncls, sigmoid, ignore);
+  const int rc = hlm_args(a, "head_seg_fwd", z, W, bias, nullptr, 0, lab, lab_sn, cls_weight, spatial, 0, ncls, 0, sigmoid, ignore);
   if (rc) return rc;
   a.logits = logits;
-  if (ce) {
-    a.ce_partial = partial;
-    hipLaunchKernelGGL((head_seg_kernel<false, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  } else {
-    a.dice_partial = partial;
-    hipLaunchKernelGGL((head_seg_kernel<false, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  }
+  (ce ? a.ce_partial : a.dice_partial) = partial;
+  if (ce) hipLaunchKernelGGL((head_seg_kernel<false, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_seg_kernel<false, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
   return check_launch(ce ? "head_seg_ce_fwd" : "head_seg_fwd");
 }
 int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* saved,
@@ -1036,13 +938,10 @@ int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const 
                         float* gn_partial, float* dw, float* db, int n, size_t spatial, int ncls, int ce, int sigmoid, int ignore,
                         void* ws, size_t ws_bytes, hipStream_t s) {
   HlmArgs a = {};
-  int rc = head_seg_args(a, "head_seg_bwd", z, W, bias, lab, lab_sn, cls_weight, spatial, ncls, sigmoid, ignore);
+  int rc = hlm_args(a, "head_seg_bwd", z, W, bias, nullptr, 0, lab, lab_sn, cls_weight, spatial, 0, ncls, 0, sigmoid, ignore);
   if (rc) return rc;
-  a.saved = saved; a.dcls = dloss; a.eps = eps;
-  a.dz = (elt*)dz; a.gn_y = (const elt*)gn_y; a.gn_act = gn_act; a.gn_partial = gn_partial;
-  MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "head_seg_bwd: gn_y and gn_partial go together");
-  MEDNET_REQUIRE(ws_bytes >= head_seg_ws_bytes(n, spatial, ncls), MEDNET_E_WORKSPACE, "head_seg_bwd: workspace too small");
-  a.wpart = (float*)ws;
+  rc = hlm_bwd_args(a, "head_seg_bwd", saved, dloss, eps, dz, gn_y, gn_act, gn_partial, ws, ws_bytes, head_seg_ws_bytes(n, spatial, ncls));
+  if (rc) return rc;
   if (ce) hipLaunchKernelGGL((head_seg_kernel<true, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((head_seg_kernel<true, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
   rc = check_launch(ce ? "head_seg_ce_bwd" : "head_seg_bwd");

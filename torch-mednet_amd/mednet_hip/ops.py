@@ -1174,8 +1174,21 @@ def dice_loss(logits, labels, weight=None, eps=1e-5, sigmoid=False, ignore_index
     return DiceLossFn.apply(logits, labels, weight, eps, sigmoid, ignore_index)
 
 
-# ------------------------------------------------------------------------------------------------- 1x1x1 head + Dice, one node
+# ------------------------------------------------------------------------------------------------- 1x1x1 head + loss, one node
 FUSE_HEAD_LOSS = os.environ.get("MEDNET_FUSE_HEAD_LOSS", "1") == "1"  # A/B knob
+
+
+def _dense_view(t: torch.Tensor, block_shape):
+    """`t` = N x block_shape with every sample's block dense and any stride between samples (a block that is no such view is copied)
+    -> (tensor, sample stride)."""
+    n = t.shape[0]
+    dense, acc = [], 1
+    for sdim in reversed(tuple(block_shape)):
+        dense.insert(0, acc)
+        acc *= sdim
+    if tuple(t.stride()[1:]) != tuple(dense) or (n > 1 and t.stride(0) < acc):
+        t = t.contiguous()
+    return t, (t.stride(0) if n > 1 else acc)
 
 
 def _label_view(labels: torch.Tensor, n: int, spatial_shape):
@@ -1185,22 +1198,128 @@ def _label_view(labels: torch.Tensor, n: int, spatial_shape):
         labels = labels.long()
     if tuple(labels.shape) != (n,) + tuple(spatial_shape):
         raise AssertionError("'input' and 'target' must have the same shape")
-    dense, acc = [], 1
-    for sdim in reversed(spatial_shape):
-        dense.insert(0, acc)
-        acc *= sdim
-    if tuple(labels.stride()[1:]) != tuple(dense) or (n > 1 and labels.stride(0) < acc):
-        labels = labels.contiguous()
-    return labels, (labels.stride(0) if n > 1 else acc), (L.U8 if labels.dtype == torch.uint8 else L.I64)
+    labels, sn = _dense_view(labels, spatial_shape)
+    return labels, sn, _label_dt(labels)
 
 
-def head_dice_supported(x: torch.Tensor, cin: int, cout: int, labels: torch.Tensor) -> bool:
-    if not (FUSE_HEAD_LOSS and x.is_cuda and x.dim() == 5 and labels.is_cuda):
+def _heatmap_view(heatmaps: torch.Tensor, n: int, nh: int, spatial_shape):
+    """uint8 heat-map targets as the fused landmark head takes them: N x nh x spatial, channels dense, any stride between samples
+    (the first channels of a uint8 label volume are consumed where they lie, landmarks.py:69)."""
+    if tuple(heatmaps.shape) != (n, nh) + tuple(spatial_shape):
+        raise RuntimeError(f"heatmap_loss: target shape {tuple(heatmaps.shape)} != output {(n, nh) + tuple(spatial_shape)}")
+    return _dense_view(heatmaps, (nh,) + tuple(spatial_shape))
+
+
+def _aligned4(t: torch.Tensor, sn: int):
+    """The matrix-core heads read uint8 targets and labels four voxels at a time: base pointer and sample stride must be multiples of
+    4 bytes.  A view with an odd storage offset / stride (e.g. a label volume sliced at an odd channel offset) is copied once."""
+    if t.data_ptr() % 4 or (t.shape[0] > 1 and sn % 4):
+        t = t.contiguous().clone() if t.is_contiguous() else t.contiguous()
+        sn = t[0].numel()
+    return t, sn
+
+
+def _loss_weight(weight, device):
+    """Per-class / per-channel loss weights (a tensor or a list), or None -> fp32 on the device."""
+    return None if weight is None else torch.as_tensor(weight, dtype=torch.float32, device=device).contiguous()
+
+
+def _head_supported(x: torch.Tensor, *targets, mfma: bool) -> bool:
+    """The gate of every fused head + loss node; the library's own `_supported` answer comes after it.  `mfma`: the matrix-core heads
+    (16-bit storage, uint8 targets, and no activation mask to fold in)."""
+    if not (FUSE_HEAD_LOSS and x.is_cuda and x.dim() == 5 and all(t.is_cuda for t in targets)):
         return False
     if x.dtype != config.act_dtype() or not x.is_contiguous(memory_format=CL):
         return False
-    ld = L.U8 if labels.dtype == torch.uint8 else L.I64
-    return bool(L.lib().mednet_head_dice_supported(cin, cout, L.dt(x), ld))
+    if not mfma:
+        return True
+    if x.dtype == torch.float32 or any(t.dtype != torch.uint8 for t in targets):
+        return False
+    # (a network whose last block ends in conv -> activation hands the head an activation mask to fold in: the stock path does that)
+    return getattr(x, "_mednet_actmask", None) is None or _gn3_hook_of(x, x.dtype) is not None
+
+
+def _label_dt(labels):
+    return L.U8 if labels.dtype == torch.uint8 else L.I64
+
+
+class _HeadBackward:
+    """What the backward of every fused head + loss node sets up -- the feature gradient, the targets of the head's weight / bias
+    gradients, the producing block's GroupNorm-3 hook with this node's partial rows (`gn_rows()` of them per sample) or the activation
+    mask of a fused conv -> activation layer, the workspace -- and how it ends (`finish`)."""
+
+    def __init__(self, ctx, x, cout, gn_rows, ws_bytes):
+        weight, self.bias = ctx.params
+        n, cin = x.shape[:2]
+        self.dx = torch.empty_like(x, memory_format=CL)
+        self.dw, self.direct_w = _grad_target(weight, (cout, cin, 1, 1, 1))
+        self.db, self.direct_b = (None, True) if self.bias is None else _grad_target(self.bias, (cout,))
+        self.hook, self.inmask = ctx.gn3, getattr(ctx, "inmask", None)
+        self.partial = None if self.hook is None else torch.empty((n, gn_rows(), cin, 2), dtype=torch.float32, device=x.device)
+        self.gn_in = None if self.hook is None else self.hook.gn_in.data_ptr()
+        self.act = self.hook.act if self.hook is not None else (self.inmask.act if self.inmask is not None else 0)
+        self.ws = L.workspace(ws_bytes, x.device)
+
+    def finish(self, name, n_inputs):
+        """Offers dx (and the rows) to the hook or the mask -> the node's gradients, None for every input behind x, weight, bias."""
+        if self.hook is not None:
+            self.hook.offer(self.dx, self.partial)
+        elif self.inmask is not None:
+            self.inmask.offer(self.dx)
+        if debug.TRACE is not None:
+            debug.trace(name + ".bwd", self.dx, self.partial, self.dw, self.db)
+        return (self.dx, (None if self.direct_w else self.dw),
+                (None if (self.bias is None or self.direct_b) else self.db)) + (None,) * (n_inputs - 3)
+
+
+def head_dice_supported(x: torch.Tensor, cin: int, cout: int, labels: torch.Tensor) -> bool:
+    return _head_supported(x, labels, mfma=False) and bool(L.lib().mednet_head_dice_supported(cin, cout, L.dt(x), _label_dt(labels)))
+
+
+def _valu_head_fwd(ctx, name, x, weight, bias, packed, labels, loss_weight, saved_shape, scalars):
+    """Forward of HeadDiceFn / HeadCEFn: mednet_<name>_fwd, whose arguments differ in `scalars` (between cout and the dtype) only."""
+    L.require_gpu(x, name)
+    n, cin, d, h, w = x.shape
+    cout = weight.shape[0]
+    spatial = d * h * w
+    lab, lab_sn, lab_dt = _label_view(labels, n, (d, h, w))
+    wt = _loss_weight(loss_weight, x.device)
+    logits = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    saved = torch.empty(saved_shape, dtype=torch.float32, device=x.device)
+    lib = L.lib()
+    ws = L.workspace(getattr(lib, f"mednet_{name}_ws_bytes")(n, spatial, cin, cout), x.device)
+    L.check(getattr(lib, f"mednet_{name}_fwd")(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt),
+                                               logits.data_ptr(), loss.data_ptr(), saved.data_ptr(), n, spatial, cin, cout, *scalars,
+                                               L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), name + "_fwd")
+    ctx.save_for_backward(x, packed, logits, lab, wt, saved)
+    ctx.meta = (scalars, lab_sn, lab_dt)
+    ctx.params = (weight, bias)
+    ctx.gn3 = _gn3_hook_of(x, x.dtype)
+    # x is the output of a fused conv -> activation layer (UNet3D's last block): the backward folds act'(x) into the feature
+    # gradient it stores and that layer skips its activation pass (ActMaskHook), as SkipPool2Fn does for the encoder levels
+    ctx.inmask = getattr(x, "_mednet_actmask", None) if (ctx.gn3 is None and FUSE_GN3 and POOL_ACT_MASK) else None
+    ctx.mark_non_differentiable(logits)
+    if debug.TRACE is not None:
+        debug.trace(name + ".fwd", logits, loss, saved)
+    return logits, loss
+
+
+def _valu_head_bwd(ctx, name, dloss, n_inputs):
+    x, packed, logits, lab, wt, saved = ctx.saved_tensors
+    scalars, lab_sn, lab_dt = ctx.meta
+    n, cin = x.shape[:2]
+    cout = logits.shape[1]
+    spatial = x[0, 0].numel()
+    lib = L.lib()
+    dl = dloss.to(torch.float32).contiguous()
+    b = _HeadBackward(ctx, x, cout, lambda: getattr(lib, f"mednet_{name}_gn_rows")(n, spatial, cin),
+                      getattr(lib, f"mednet_{name}_ws_bytes")(n, spatial, cin, cout))
+    L.check(getattr(lib, f"mednet_{name}_bwd")(logits.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, packed.data_ptr(), L.ptr(wt),
+                                               saved.data_ptr(), dl.data_ptr(), b.dx.data_ptr(), b.gn_in, x.data_ptr(), b.act,
+                                               L.ptr(b.partial), b.dw.data_ptr(), L.ptr(b.db), n, spatial, cin, cout, *scalars,
+                                               L.dt(x), b.ws.data_ptr(), b.ws.numel(), L.stream()), name + "_bwd")
+    return b.finish(name, n_inputs)
 
 
 class HeadDiceFn(Function):
@@ -1212,63 +1331,13 @@ class HeadDiceFn(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, packed, labels, loss_weight, eps, sigmoid, ignore_index):
-        L.require_gpu(x, "head_dice")
-        n, cin, d, h, w = x.shape
-        cout = weight.shape[0]
-        spatial = d * h * w
-        lab, lab_sn, lab_dt = _label_view(labels, n, (d, h, w))
-        wt = None if loss_weight is None else loss_weight.to(device=x.device, dtype=torch.float32).contiguous()
-        logits = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        saved = torch.empty((cout, 2), dtype=torch.float32, device=x.device)
-        lib = L.lib()
-        ws = L.workspace(lib.mednet_head_dice_ws_bytes(n, spatial, cin, cout), x.device)
         ii = L.NO_IGNORE if ignore_index is None else int(ignore_index)
-        L.check(lib.mednet_head_dice_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt),
-                                         logits.data_ptr(), loss.data_ptr(), saved.data_ptr(), n, spatial, cin, cout, eps,
-                                         int(sigmoid), ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_dice_fwd")
-        ctx.save_for_backward(x, packed, logits, lab, wt, saved)
-        ctx.meta = (eps, int(sigmoid), ii, lab_sn, lab_dt, cin, cout)
-        ctx.params = (weight, bias)
-        ctx.gn3 = _gn3_hook_of(x, x.dtype)
-        # x is the output of a fused conv -> activation layer (UNet3D's last block): the backward folds act'(x) into the feature
-        # gradient it stores and that layer skips its activation pass (ActMaskHook), as SkipPool2Fn does for the encoder levels
-        ctx.inmask = getattr(x, "_mednet_actmask", None) if (ctx.gn3 is None and FUSE_GN3 and POOL_ACT_MASK) else None
-        ctx.mark_non_differentiable(logits)
-        if debug.TRACE is not None:
-            debug.trace("head_dice.fwd", logits, loss, saved)
-        return logits, loss
+        return _valu_head_fwd(ctx, "head_dice", x, weight, bias, packed, labels, loss_weight, (weight.shape[0], 2),
+                              (eps, int(sigmoid), ii))
 
     @staticmethod
     def backward(ctx, _dlogits, dloss):
-        x, packed, logits, lab, wt, saved = ctx.saved_tensors
-        eps, sigmoid, ii, lab_sn, lab_dt, cin, cout = ctx.meta
-        weight, bias = ctx.params
-        n, _, d, h, w = x.shape
-        spatial = d * h * w
-        lib = L.lib()
-        dl = dloss.to(torch.float32).contiguous()
-        dx = torch.empty_like(x, memory_format=CL)
-        dw, direct_w = _grad_target(weight, (cout, cin, 1, 1, 1))
-        db, direct_b = (None, True) if bias is None else _grad_target(bias, (cout,))
-        hook = ctx.gn3
-        partial = None
-        if hook is not None:
-            partial = torch.empty((n, lib.mednet_head_dice_gn_rows(n, spatial, cin), cin, 2), dtype=torch.float32, device=x.device)
-        ws = L.workspace(lib.mednet_head_dice_ws_bytes(n, spatial, cin, cout), x.device)
-        L.check(lib.mednet_head_dice_bwd(logits.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, packed.data_ptr(), L.ptr(wt),
-                                         saved.data_ptr(), dl.data_ptr(), dx.data_ptr(),
-                                         None if hook is None else hook.gn_in.data_ptr(), x.data_ptr(),
-                                         hook.act if hook is not None else (ctx.inmask.act if ctx.inmask is not None else 0),
-                                         L.ptr(partial), dw.data_ptr(), L.ptr(db), n, spatial, cin,
-                                         cout, eps, sigmoid, ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_dice_bwd")
-        if hook is not None:
-            hook.offer(dx, partial)
-        elif ctx.inmask is not None:
-            ctx.inmask.offer(dx)
-        if debug.TRACE is not None:
-            debug.trace("head_dice.bwd", dx, partial, dw, db)
-        return dx, (None if direct_w else dw), (None if (bias is None or direct_b) else db), None, None, None, None, None, None
+        return _valu_head_bwd(ctx, "head_dice", dloss, 9)
 
 
 def head_dice(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5, sigmoid=False, ignore_index=None):
@@ -1277,12 +1346,7 @@ def head_dice(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5, sigmo
 
 
 def head_ce_supported(x: torch.Tensor, cin: int, cout: int, labels: torch.Tensor) -> bool:
-    if not (FUSE_HEAD_LOSS and x.is_cuda and x.dim() == 5 and labels.is_cuda):
-        return False
-    if x.dtype != config.act_dtype() or not x.is_contiguous(memory_format=CL):
-        return False
-    ld = L.U8 if labels.dtype == torch.uint8 else L.I64
-    return bool(L.lib().mednet_head_ce_supported(cin, cout, L.dt(x), ld))
+    return _head_supported(x, labels, mfma=False) and bool(L.lib().mednet_head_ce_supported(cin, cout, L.dt(x), _label_dt(labels)))
 
 
 class HeadCEFn(Function):
@@ -1292,61 +1356,11 @@ class HeadCEFn(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, packed, labels, loss_weight, ignore_index):
-        L.require_gpu(x, "head_ce")
-        n, cin, d, h, w = x.shape
-        cout = weight.shape[0]
-        spatial = d * h * w
-        lab, lab_sn, lab_dt = _label_view(labels, n, (d, h, w))
-        wt = None if loss_weight is None else loss_weight.to(device=x.device, dtype=torch.float32).contiguous()
-        logits = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        saved = torch.empty((2,), dtype=torch.float32, device=x.device)
-        lib = L.lib()
-        ws = L.workspace(lib.mednet_head_ce_ws_bytes(n, spatial, cin, cout), x.device)
-        ii = int(ignore_index)
-        L.check(lib.mednet_head_ce_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt),
-                                       logits.data_ptr(), loss.data_ptr(), saved.data_ptr(), n, spatial, cin, cout, ii, L.dt(x),
-                                       ws.data_ptr(), ws.numel(), L.stream()), "head_ce_fwd")
-        ctx.save_for_backward(x, packed, logits, lab, wt, saved)
-        ctx.meta = (ii, lab_sn, lab_dt, cin, cout)
-        ctx.params = (weight, bias)
-        ctx.gn3 = _gn3_hook_of(x, x.dtype)
-        ctx.inmask = getattr(x, "_mednet_actmask", None) if (ctx.gn3 is None and FUSE_GN3 and POOL_ACT_MASK) else None
-        ctx.mark_non_differentiable(logits)
-        if debug.TRACE is not None:
-            debug.trace("head_ce.fwd", logits, loss, saved)
-        return logits, loss
+        return _valu_head_fwd(ctx, "head_ce", x, weight, bias, packed, labels, loss_weight, (2,), (int(ignore_index),))
 
     @staticmethod
     def backward(ctx, _dlogits, dloss):
-        x, packed, logits, lab, wt, saved = ctx.saved_tensors
-        ii, lab_sn, lab_dt, cin, cout = ctx.meta
-        weight, bias = ctx.params
-        n, _, d, h, w = x.shape
-        spatial = d * h * w
-        lib = L.lib()
-        dl = dloss.to(torch.float32).contiguous()
-        dx = torch.empty_like(x, memory_format=CL)
-        dw, direct_w = _grad_target(weight, (cout, cin, 1, 1, 1))
-        db, direct_b = (None, True) if bias is None else _grad_target(bias, (cout,))
-        hook = ctx.gn3
-        partial = None
-        if hook is not None:
-            partial = torch.empty((n, lib.mednet_head_ce_gn_rows(n, spatial, cin), cin, 2), dtype=torch.float32, device=x.device)
-        ws = L.workspace(lib.mednet_head_ce_ws_bytes(n, spatial, cin, cout), x.device)
-        L.check(lib.mednet_head_ce_bwd(logits.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, packed.data_ptr(), L.ptr(wt),
-                                       saved.data_ptr(), dl.data_ptr(), dx.data_ptr(),
-                                       None if hook is None else hook.gn_in.data_ptr(), x.data_ptr(),
-                                       hook.act if hook is not None else (ctx.inmask.act if ctx.inmask is not None else 0),
-                                       L.ptr(partial), dw.data_ptr(), L.ptr(db), n, spatial, cin, cout, ii, L.dt(x),
-                                       ws.data_ptr(), ws.numel(), L.stream()), "head_ce_bwd")
-        if hook is not None:
-            hook.offer(dx, partial)
-        elif ctx.inmask is not None:
-            ctx.inmask.offer(dx)
-        if debug.TRACE is not None:
-            debug.trace("head_ce.bwd", dx, partial, dw, db)
-        return dx, (None if direct_w else dw), (None if (bias is None or direct_b) else db), None, None, None, None
+        return _valu_head_bwd(ctx, "head_ce", dloss, 7)
 
 
 def head_ce(x, weight, bias, packed, labels, loss_weight=None, ignore_index=-100):
@@ -1356,15 +1370,7 @@ def head_ce(x, weight, bias, packed, labels, loss_weight=None, ignore_index=-100
 
 def head_seg_supported(x: torch.Tensor, cin: int, ncls: int, labels: torch.Tensor) -> bool:
     """Does the matrix-core segmentation head (5 .. 16 classes, 16-bit storage, uint8 labels) take this head?"""
-    if not (FUSE_HEAD_LOSS and x.is_cuda and x.dim() == 5 and labels.is_cuda):
-        return False
-    if x.dtype != config.act_dtype() or x.dtype == torch.float32 or not x.is_contiguous(memory_format=CL):
-        return False
-    # (a network whose last block ends in conv -> activation hands the head an activation mask to fold in: the stock path does that)
-    if getattr(x, "_mednet_actmask", None) is not None and _gn3_hook_of(x, x.dtype) is None:
-        return False
-    ld = L.U8 if labels.dtype == torch.uint8 else L.I64
-    return bool(L.lib().mednet_head_seg_supported(cin, ncls, L.dt(x), ld, x[0, 0].numel()))
+    return _head_supported(x, labels, mfma=True) and bool(L.lib().mednet_head_seg_supported(cin, ncls, L.dt(x), L.U8, x[0, 0].numel()))
 
 
 class HeadSegFn(Function):
@@ -1383,12 +1389,8 @@ class HeadSegFn(Function):
         spatial = d * h * w
         if labels.dtype != torch.uint8:
             raise RuntimeError(f"head_seg: labels must be uint8, not {labels.dtype} (see head_seg_supported)")
-        lab, lab_sn, _ = _label_view(labels, n, (d, h, w))
-        # the kernel reads labels four voxels at a time: a view whose base or sample stride is no multiple of 4 bytes is copied once
-        if lab.data_ptr() % 4 or (n > 1 and lab_sn % 4):
-            lab = lab.contiguous().clone() if lab.is_contiguous() else lab.contiguous()
-            lab_sn = spatial
-        wt = None if loss_weight is None else loss_weight.to(device=x.device, dtype=torch.float32).contiguous()
+        lab, lab_sn = _aligned4(*_label_view(labels, n, (d, h, w))[:2])
+        wt = _loss_weight(loss_weight, x.device)
         ii = (L.NO_IGNORE if class_kind == L.CLASS_DICE else -100) if ignore_index is None else int(ignore_index)
         logits = torch.empty((n, ncls, d, h, w), dtype=torch.float32, device=x.device) if want_logits else None
         loss = torch.empty((), dtype=torch.float32, device=x.device)
@@ -1399,7 +1401,7 @@ class HeadSegFn(Function):
                                         loss.data_ptr(), saved.data_ptr(), n, spatial, cin, ncls, class_kind, eps, int(sigmoid), ii,
                                         L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_seg_fwd")
         ctx.save_for_backward(x, packed, lab, wt, saved)
-        ctx.meta = (eps, int(sigmoid), ii, lab_sn, cin, ncls, class_kind)
+        ctx.meta = (eps, int(sigmoid), ii, lab_sn, ncls, class_kind)
         ctx.params = (weight, bias)
         ctx.gn3 = _gn3_hook_of(x, x.dtype)
         if logits is not None:
@@ -1411,30 +1413,17 @@ class HeadSegFn(Function):
     @staticmethod
     def backward(ctx, _dlogits, dloss):
         x, packed, lab, wt, saved = ctx.saved_tensors
-        eps, sigmoid, ii, lab_sn, cin, ncls, class_kind = ctx.meta
-        weight, bias = ctx.params
-        n, _, d, h, w = x.shape
-        spatial = d * h * w
+        eps, sigmoid, ii, lab_sn, ncls, class_kind = ctx.meta
+        n, cin = x.shape[:2]
+        spatial = x[0, 0].numel()
         lib = L.lib()
         dl = dloss.to(torch.float32).contiguous()
-        dx = torch.empty_like(x, memory_format=CL)
-        dw, direct_w = _grad_target(weight, (ncls, cin, 1, 1, 1))
-        db, direct_b = (None, True) if bias is None else _grad_target(bias, (ncls,))
-        hook = ctx.gn3
-        partial = None
-        if hook is not None:
-            partial = torch.empty((n, lib.mednet_head_seg_gn_rows(spatial), cin, 2), dtype=torch.float32, device=x.device)
-        ws = L.workspace(lib.mednet_head_seg_ws_bytes(n, spatial, ncls), x.device)
-        L.check(lib.mednet_head_seg_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_sn, L.ptr(wt), saved.data_ptr(),
-                                        dl.data_ptr(), dx.data_ptr(), None if hook is None else hook.gn_in.data_ptr(),
-                                        hook.act if hook is not None else 0, L.ptr(partial), dw.data_ptr(), L.ptr(db), n, spatial, cin,
-                                        ncls, class_kind, eps, sigmoid, ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()),
-                "head_seg_bwd")
-        if hook is not None:
-            hook.offer(dx, partial)
-        if debug.TRACE is not None:
-            debug.trace("head_seg.bwd", dx, partial, dw, db)
-        return (dx, (None if direct_w else dw), (None if (bias is None or direct_b) else db)) + (None,) * 8
+        b = _HeadBackward(ctx, x, ncls, lambda: lib.mednet_head_seg_gn_rows(spatial), lib.mednet_head_seg_ws_bytes(n, spatial, ncls))
+        L.check(lib.mednet_head_seg_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(b.bias), lab.data_ptr(), lab_sn, L.ptr(wt), saved.data_ptr(),
+                                        dl.data_ptr(), b.dx.data_ptr(), b.gn_in, b.act, L.ptr(b.partial), b.dw.data_ptr(), L.ptr(b.db), n,
+                                        spatial, cin, ncls, class_kind, eps, sigmoid, ii, L.dt(x), b.ws.data_ptr(), b.ws.numel(),
+                                        L.stream()), "head_seg_bwd")
+        return b.finish("head_seg", 11)
 
 
 def head_seg(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5, sigmoid=False, ignore_index=None, class_loss="DICE",
@@ -1445,54 +1434,31 @@ def head_seg(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5, sigmoi
                            want_logits)
 
 
-def _heatmap_view(heatmaps: torch.Tensor, n: int, nh: int, spatial_shape):
-    """uint8 heat-map targets as the fused landmark head takes them: N x nh x spatial, channels dense, any stride between samples
-    (the first channels of a uint8 label volume are consumed where they lie, landmarks.py:69)."""
-    if tuple(heatmaps.shape) != (n, nh) + tuple(spatial_shape):
-        raise RuntimeError(f"heatmap_loss: target shape {tuple(heatmaps.shape)} != output {(n, nh) + tuple(spatial_shape)}")
-    dense, acc = [], 1
-    for sdim in reversed((nh,) + tuple(spatial_shape)):
-        dense.insert(0, acc)
-        acc *= sdim
-    if tuple(heatmaps.stride()[1:]) != tuple(dense) or (n > 1 and heatmaps.stride(0) < acc):
-        heatmaps = heatmaps.contiguous()
-    return heatmaps, (heatmaps.stride(0) if n > 1 else acc)
-
-
 def head_landmark_supported(x: torch.Tensor, cin: int, nh: int, ncls: int, heatmaps: torch.Tensor, labels: torch.Tensor) -> bool:
-    if not (FUSE_HEAD_LOSS and x.is_cuda and x.dim() == 5 and labels.is_cuda and heatmaps.is_cuda):
-        return False
-    if x.dtype != config.act_dtype() or x.dtype == torch.float32 or not x.is_contiguous(memory_format=CL):
-        return False
-    if heatmaps.dtype != torch.uint8 or labels.dtype != torch.uint8:
-        return False
-    # (a network whose last block ends in conv -> activation hands the head an activation mask to fold in: the stock path does that)
-    if getattr(x, "_mednet_actmask", None) is not None and _gn3_hook_of(x, x.dtype) is None:
-        return False
-    return bool(L.lib().mednet_head_landmark_supported(cin, nh, ncls, L.dt(x), x[0, 0].numel()))
+    return (_head_supported(x, labels, heatmaps, mfma=True)
+            and bool(L.lib().mednet_head_landmark_supported(cin, nh, ncls, L.dt(x), x[0, 0].numel())))
 
 
 class HeadLandmarkFn(Function):
     """LandmarkNet's head and loss (landmarks.py:66-83, 125-134) as ONE autograd node in the 16-bit storage modes:
     outputs = final_conv(x) (model.py:207), class_loss = DiceLoss(outputs[:, nh:], labels), regression_loss = sum_c w_c *
     mean f(outputs[:, c] - heatmaps[:, c]).  Forward: one matrix-core pass over the features that writes nothing but loss partials
-    (mednet_head_landmark_fwd); backward: one pass that rebuilds the logits the same way and produces the feature gradient, the
+    (mednet_head_landmark_cls_fwd); backward: one pass that rebuilds the logits the same way and produces the feature gradient, the
     head's weight / bias gradients and the first pass of the producing block's GroupNorm-3 backward
-    (mednet_head_landmark_bwd).  No logit or logit-gradient tensor exists.  Returns (class_loss, regression_loss).
-    class_kind CLASS_CE: the class term is nn.CrossEntropyLoss(class_weight, ignore_index) (landmarks.py:49; the _cls_ entry points)."""
+    (mednet_head_landmark_cls_bwd).  No logit or logit-gradient tensor exists.  Returns (class_loss, regression_loss).
+    class_kind CLASS_CE: the class term is nn.CrossEntropyLoss(class_weight, ignore_index) (landmarks.py:49)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, packed, heatmaps, labels, class_weight, reg_weight, kind, eps, sigmoid, ignore_index,
                 class_kind=L.CLASS_DICE):
         L.require_gpu(x, "head_landmark")
-        n, cin = x.shape[:2]
         nh = heatmaps.shape[1]
         ncls = weight.shape[0] - nh
         hm, hm_sn, lab, lab_sn, cw, rw, ii = _landmark_operands(x, heatmaps, labels, class_weight, reg_weight, ignore_index)
         closs, rloss, saved, _ = _landmark_fwd(x, packed, bias, hm, hm_sn, lab, lab_sn, cw, rw, nh, ncls, kind, eps, sigmoid, ii,
                                                class_kind, False)
         ctx.save_for_backward(x, packed, hm, lab, cw, rw, saved)
-        ctx.meta = (kind, eps, int(sigmoid), ii, hm_sn, lab_sn, cin, nh, ncls, class_kind)
+        ctx.meta = (kind, eps, int(sigmoid), ii, hm_sn, lab_sn, nh, ncls, class_kind)
         ctx.params = (weight, bias)
         ctx.gn3 = _gn3_hook_of(x, x.dtype)
         if debug.TRACE is not None:
@@ -1502,42 +1468,23 @@ class HeadLandmarkFn(Function):
     @staticmethod
     def backward(ctx, dclass, dreg):
         x, packed, hm, lab, cw, rw, saved = ctx.saved_tensors
-        kind, eps, sigmoid, ii, hm_sn, lab_sn, cin, nh, ncls, class_kind = ctx.meta
-        weight, bias = ctx.params
-        n, _, d, h, w = x.shape
-        spatial = d * h * w
+        kind, eps, sigmoid, ii, hm_sn, lab_sn, nh, ncls, class_kind = ctx.meta
+        n, cin = x.shape[:2]
+        spatial = x[0, 0].numel()
         lib = L.lib()
         zero = None
         if dclass is None or dreg is None:
             zero = torch.zeros((), dtype=torch.float32, device=x.device)
         dc = zero if dclass is None else dclass.to(torch.float32).contiguous()
         dr = zero if dreg is None else dreg.to(torch.float32).contiguous()
-        dx = torch.empty_like(x, memory_format=CL)
-        dw, direct_w = _grad_target(weight, (nh + ncls, cin, 1, 1, 1))
-        db, direct_b = (None, True) if bias is None else _grad_target(bias, (nh + ncls,))
-        hook = ctx.gn3
-        partial = None
-        if hook is not None:
-            partial = torch.empty((n, lib.mednet_head_landmark_gn_rows(spatial), cin, 2), dtype=torch.float32, device=x.device)
-        ws = L.workspace(lib.mednet_head_landmark_ws_bytes(n, spatial, nh, ncls), x.device)
-        if class_kind == L.CLASS_DICE:
-            L.check(lib.mednet_head_landmark_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(), lab_sn,
-                                                 L.ptr(cw), L.ptr(rw), saved.data_ptr(), dc.data_ptr(), dr.data_ptr(), dx.data_ptr(),
-                                                 None if hook is None else hook.gn_in.data_ptr(), hook.act if hook is not None else 0,
-                                                 L.ptr(partial), dw.data_ptr(), L.ptr(db), n, spatial, cin, nh, ncls, kind, eps, sigmoid,
-                                                 ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_landmark_bwd")
-        else:
-            L.check(lib.mednet_head_landmark_cls_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(),
-                                                     lab_sn, L.ptr(cw), L.ptr(rw), saved.data_ptr(), dc.data_ptr(), dr.data_ptr(),
-                                                     dx.data_ptr(), None if hook is None else hook.gn_in.data_ptr(),
-                                                     hook.act if hook is not None else 0, L.ptr(partial), dw.data_ptr(), L.ptr(db), n,
-                                                     spatial, cin, nh, ncls, kind, class_kind, eps, sigmoid, ii, L.dt(x), ws.data_ptr(),
-                                                     ws.numel(), L.stream()), "head_landmark_cls_bwd")
-        if hook is not None:
-            hook.offer(dx, partial)
-        if debug.TRACE is not None:
-            debug.trace("head_landmark.bwd", dx, partial, dw, db)
-        return (dx, (None if direct_w else dw), (None if (bias is None or direct_b) else db)) + (None,) * 10
+        b = _HeadBackward(ctx, x, nh + ncls, lambda: lib.mednet_head_landmark_gn_rows(spatial),
+                          lib.mednet_head_landmark_ws_bytes(n, spatial, nh, ncls))
+        L.check(lib.mednet_head_landmark_cls_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(b.bias), hm.data_ptr(), hm_sn, lab.data_ptr(),
+                                                 lab_sn, L.ptr(cw), L.ptr(rw), saved.data_ptr(), dc.data_ptr(), dr.data_ptr(),
+                                                 b.dx.data_ptr(), b.gn_in, b.act, L.ptr(b.partial), b.dw.data_ptr(), L.ptr(b.db), n,
+                                                 spatial, cin, nh, ncls, kind, class_kind, eps, sigmoid, ii, L.dt(x), b.ws.data_ptr(),
+                                                 b.ws.numel(), L.stream()), "head_landmark_cls_bwd")
+        return b.finish("head_landmark", 13)
 
 
 def head_landmark(x, weight, bias, packed, heatmaps, labels, class_weight=None, reg_weight=None, kind="L2", eps=1e-5, sigmoid=False,
@@ -1569,43 +1516,25 @@ def _class_kind(class_loss):
 
 def _landmark_operands(x, heatmaps, labels, class_weight, reg_weight, ignore_index):
     n, _, d, h, w = x.shape
-    nh = heatmaps.shape[1]
-    spatial = d * h * w
-    hm, hm_sn = _heatmap_view(heatmaps, n, nh, (d, h, w))
-    lab, lab_sn, _ = _label_view(labels, n, (d, h, w))
-    # launch_head_lm_* reads targets and labels four voxels at a time: base pointers and sample strides must be multiples of 4
-    # bytes.  A view with an odd storage offset / stride (e.g. a label volume sliced at an odd channel offset) is copied once.
-    if hm.data_ptr() % 4 or (n > 1 and hm_sn % 4):
-        hm = hm.contiguous().clone() if hm.is_contiguous() else hm.contiguous()
-        hm_sn = nh * spatial
-    if lab.data_ptr() % 4 or (n > 1 and lab_sn % 4):
-        lab = lab.contiguous().clone() if lab.is_contiguous() else lab.contiguous()
-        lab_sn = spatial
-    cw = None if class_weight is None else class_weight.to(device=x.device, dtype=torch.float32).contiguous()
-    rw = None if reg_weight is None else torch.as_tensor(reg_weight, dtype=torch.float32, device=x.device).contiguous()
+    hm, hm_sn = _aligned4(*_heatmap_view(heatmaps, n, heatmaps.shape[1], (d, h, w)))
+    lab, lab_sn = _aligned4(*_label_view(labels, n, (d, h, w))[:2])
     ii = L.NO_IGNORE if ignore_index is None else int(ignore_index)
-    return hm, hm_sn, lab, lab_sn, cw, rw, ii
+    return hm, hm_sn, lab, lab_sn, _loss_weight(class_weight, x.device), _loss_weight(reg_weight, x.device), ii
 
 
 def _landmark_fwd(x, packed, bias, hm, hm_sn, lab, lab_sn, cw, rw, nh, ncls, kind, eps, sigmoid, ii, class_kind, metric):
-    n, cin, d, h, w = x.shape
-    spatial = d * h * w
+    n, cin = x.shape[:2]
+    spatial = x[0, 0].numel()
     closs = torch.empty((), dtype=torch.float32, device=x.device)
     rloss = torch.empty((), dtype=torch.float32, device=x.device)
     saved = torch.empty((ncls, 2), dtype=torch.float32, device=x.device)
     dice = torch.empty((ncls,), dtype=torch.float32, device=x.device) if metric else None
     lib = L.lib()
     ws = L.workspace(lib.mednet_head_landmark_ws_bytes(n, spatial, nh, ncls), x.device)
-    if class_kind == L.CLASS_DICE and not metric:
-        L.check(lib.mednet_head_landmark_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(), lab_sn,
-                                             L.ptr(cw), L.ptr(rw), None, closs.data_ptr(), rloss.data_ptr(), saved.data_ptr(), n,
-                                             spatial, cin, nh, ncls, kind, eps, int(sigmoid), ii, L.dt(x), ws.data_ptr(), ws.numel(),
-                                             L.stream()), "head_landmark_fwd")
-    else:
-        L.check(lib.mednet_head_landmark_cls_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(),
-                                                 lab_sn, L.ptr(cw), L.ptr(rw), None, closs.data_ptr(), rloss.data_ptr(), saved.data_ptr(),
-                                                 L.ptr(dice), n, spatial, cin, nh, ncls, kind, class_kind, eps, int(sigmoid), ii, L.dt(x),
-                                                 ws.data_ptr(), ws.numel(), L.stream()), "head_landmark_cls_fwd")
+    L.check(lib.mednet_head_landmark_cls_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), hm.data_ptr(), hm_sn, lab.data_ptr(), lab_sn,
+                                             L.ptr(cw), L.ptr(rw), None, closs.data_ptr(), rloss.data_ptr(), saved.data_ptr(),
+                                             L.ptr(dice), n, spatial, cin, nh, ncls, kind, class_kind, eps, int(sigmoid), ii, L.dt(x),
+                                             ws.data_ptr(), ws.numel(), L.stream()), "head_landmark_cls_fwd")
     return closs, rloss, saved, dice
 
 
