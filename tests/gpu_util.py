@@ -674,3 +674,248 @@ def check_adam(ref, p, m, v, what):
                 v=check_gradient(v, r.v, r.terms_v, ref.eps["v"], what + ": v"),
                 p=check_gradient(p, r.p, r.delta.abs(), ref.eps["p"], what + ": p", u=U32),
                 pt=check_gradient(p, r.p, r.terms_d, ref.eps["pt"], what + ": p against the update's terms", u=U32))
+
+
+# ------------------------------------------------------------------------------- the data path: augmentation
+# Inputs, the fp64 restatement and the checkers of tests/test_gpu_data_path.py (csrc/augment.hip).  tests/test_data_path_util.py
+# runs them on the CPU against a numpy model of the kernels' block decomposition with injectable faults.  Arrays of a case are
+# numpy [b, c, S] (S = the voxels of one channel); profiles/data_path_bounds.md derives the bound.
+AUG_BLOCK_VOX = 2048           # AUG_BLOCK of augment.hip: one partial (min/max pair, then sum) per workgroup
+AUG_FINALIZE_STRIDE = 64       # both finalize kernels walk the partials with i += 64
+AUG_EPS_FLOOR = 2.0 ** -20     # sixteen fp32 roundings
+AUG_SURE = 2.0 ** -16          # an element this far (in the bound's own terms) beyond lo / hi is clipped in any evaluation held to
+#                                eps <= 2^-16: its error is that of lo / hi alone
+
+
+def aug_blocks(spatial):
+    return -(-int(spatial) // AUG_BLOCK_VOX)
+
+
+def augment_ref64(data, params):
+    """The three transforms of oracle/ref_augment.apply with the brightness add, the sample's minimum and its range in fp32 (what
+    numpy does on the reference's float32 patches, and what the kernels do bit for bit) and everything after that in fp64.
+    data [b, c, ...] fp32, params [b, c, 3] fp32 {add, gamma, factor} (gamma of each channel as given: the reference draws one per
+    sample).  -> out and its parts, all [b, c, S] / [b, c, 1] fp64, and the per-element norm of the bound:
+      e_g  = (g - minm) + |g|                                   the terms of g = p * rnge + minm
+      e_m  = mean(e_g) + mean(|g|)                              the mean's
+      unc  = |f| (e_g + e_m + |g - mean|) + e_m + |unclipped|   the contrast line's
+      norm = e_g at the channel's end where the element is clipped beyond doubt, else max(unc, e_g at both ends)."""
+    data = np.asarray(data, dtype=np.float32)
+    params = np.asarray(params, dtype=np.float32)
+    b, c = data.shape[:2]
+    s = data.reshape(b, c, -1) + params[:, :, 0:1]
+    assert s.dtype == np.float32
+    minm = s.min(axis=(1, 2))
+    rnge = s.max(axis=(1, 2)) - minm
+    assert minm.dtype == np.float32 and rnge.dtype == np.float32
+    m64, r64 = minm.astype(np.float64)[:, None, None], rnge.astype(np.float64)[:, None, None]
+    gamma, f = params[:, :, 1:2].astype(np.float64), params[:, :, 2:3].astype(np.float64)
+    t = (s.astype(np.float64) - m64) / (r64 + 1e-7)
+    g = np.power(t, gamma) * r64 + m64
+    mean, lo, hi = g.mean(-1, keepdims=True), g.min(-1, keepdims=True), g.max(-1, keepdims=True)
+    unclipped = (g - mean) * f + mean
+    out = np.clip(unclipped, lo, hi)
+    e_g = (g - m64) + np.abs(g)
+    e_m = e_g.mean(-1, keepdims=True) + np.abs(g).mean(-1, keepdims=True)
+    e_lo = np.take_along_axis(e_g, g.argmin(-1)[..., None], -1)
+    e_hi = np.take_along_axis(e_g, g.argmax(-1)[..., None], -1)
+    unc = np.abs(f) * (e_g + e_m + np.abs(g - mean)) + e_m + np.abs(unclipped)
+    sure_hi = unclipped - hi > AUG_SURE * (unc + e_hi)
+    sure_lo = lo - unclipped > AUG_SURE * (unc + e_lo)
+    norm = np.where(sure_hi, e_hi, np.where(sure_lo, e_lo, np.maximum(unc, np.maximum(e_lo, e_hi))))
+    return types.SimpleNamespace(out=out, s=s, minm=minm, rnge=rnge, t=t, g=g, mean=mean, lo=lo, hi=hi, unclipped=unclipped, norm=norm,
+                                 sure_lo=sure_lo, sure_hi=sure_hi)
+
+
+def aug_eps(data, params, ref, what):
+    """(r32, eps_case): r32 = the error of oracle/ref_augment.apply (numpy fp32 on the CPU) against augment_ref64 in the norm of
+    the bound; eps_case = max(2^-20, 8 * r32), which must stay below AUG_SURE (the norm's clip decision relies on it)."""
+    from oracle import ref_augment as A
+    x32 = A.apply(np.asarray(data, dtype=np.float32), params).reshape(ref.out.shape)
+    r32, eps = ref_error(torch.from_numpy(x32), torch.from_numpy(ref.out), torch.from_numpy(ref.norm), what, floor=AUG_EPS_FLOOR)
+    assert eps < AUG_SURE, f"{what}: eps_case {eps:.3e} reaches the clip decision's margin 2^-16 (r32 {r32:.3e})"
+    return r32, eps
+
+
+def check_augment(got, ref, eps, what):
+    """Every element, none excluded: |got - ref64| <= eps * norm, no NaN.  -> the worst observed |got - ref64| / norm."""
+    got = torch.from_numpy(np.asarray(got, dtype=np.float32).reshape(ref.out.shape))
+    return check_gradient(got, torch.from_numpy(ref.out), torch.from_numpy(ref.norm), eps, what)
+
+
+def aug_random_case(tag, b, c, shape, kind="positive", params="drawn"):
+    """standard_normal * 40 + 100 like the suite's whole-tensor test; kind "negative": * 40 - 100; "scaled": channel 1 is 1000 times
+    channel 0's scale.  With more than AUG_FINALIZE_STRIDE partials the sample's maximum sits in the LAST voxel of channel 0 and its
+    minimum in the last voxel of channel c - 1 (the block behind partial 64).  params: "drawn" (oracle.ref_augment.draw_parameters,
+    seeded by the tag) or a (shift, gamma, factor) corner given to every sample, the shift's sign alternating by channel."""
+    from oracle import ref_augment as A
+    g = _np_rng(tag)
+    S = int(np.prod(shape))
+    x = g.standard_normal((b, c, S)) * 40 + (-100 if kind == "negative" else 100)
+    if kind == "scaled" and c > 1:
+        x[:, 1] *= 1000.0
+    if aug_blocks(S) > AUG_FINALIZE_STRIDE:
+        x[:, 0, -1] = x.max(axis=(1, 2)) + 50.0
+        x[:, c - 1, -1 if c > 1 else -2] = x.min(axis=(1, 2)) - 50.0
+    if isinstance(params, str):
+        state = np.random.get_state()
+        np.random.seed(int(g.integers(0, 2 ** 31)))
+        prm = A.draw_parameters(b, c)
+        np.random.set_state(state)
+    else:
+        prm = np.zeros((b, c, 3), dtype=np.float32)
+        prm[:, :, 0] = params[0] * np.where(np.arange(c) % 2, -1.0, 1.0)[None]
+        prm[:, :, 1], prm[:, :, 2] = params[1], params[2]
+    return types.SimpleNamespace(b=b, c=c, shape=tuple(shape), spatial=S, x=x.astype(np.float32), params=prm)
+
+
+# ---- the two-valued lattice
+def aug_lattice_case(tag, b, c, shape, lh=None, shifted=True):
+    """After the brightness shift every channel of sample i holds only L_i and H_i: integers, |.| <= 4096, H - L >= 2 (lh: the (L, H)
+    pairs to use).  The shifts are integers, different for every channel of a sample (all 0 with shifted=False); x = {L, H} - add.  The number of H voxels
+    differs for every (sample, channel); voxel k * 2048 of every block k and the last voxel hold H, voxel 1 holds L, the rest are
+    placed at random.  Then grange = H - L = fl(grange + 1e-7f), t is exactly 0 or 1, powf gives 0 and 1 for any gamma, g is L or H,
+    every fp32 block partial is an integer below 2^24 in any order and the fp64 total is exact."""
+    g = _np_rng(tag)
+    S = int(np.prod(shape))
+    nb = aug_blocks(S)
+    assert S >= 8 and c <= 64
+    forced = np.unique(np.concatenate([np.arange(nb) * AUG_BLOCK_VOX, [S - 1]]))
+    free = np.setdiff1d(np.arange(S), np.concatenate([forced, [1]]))
+    room = len(free) - 1
+    assert room >= b * c, "too few voxels for a different count per (sample, channel)"
+    step = max(1, (room * 3 // 4) // (b * c))
+    if lh is None:
+        lo = g.integers(-4096, 4000, size=b)
+        lh = [(int(v), int(v) + int(g.integers(2, 4097 - v))) for v in lo]
+    low = np.asarray([p[0] for p in lh], dtype=np.int64)
+    high = np.asarray([p[1] for p in lh], dtype=np.int64)
+    add = np.stack([g.permutation(np.arange(-40, 41))[:c] for _ in range(b)]).astype(np.int64) * int(shifted)
+    mask = np.zeros((b, c, S), dtype=bool)
+    mask[:, :, forced] = True
+    order = g.permutation(b * c)
+    for i in range(b):
+        for ch in range(c):
+            extra = 1 + int(order[i * c + ch]) * step
+            mask[i, ch, g.permutation(free)[:extra]] = True
+    lat = np.where(mask, high[:, None, None], low[:, None, None])
+    x = (lat - add[:, :, None]).astype(np.float32)
+    case = types.SimpleNamespace(b=b, c=c, shape=tuple(shape), spatial=S, x=x, add=add.astype(np.float32), mask=mask, low=low, high=high,
+                                 lat=lat.astype(np.float32), nhigh=mask.sum(-1), shifted=shifted)
+    aug_lattice_premises(case)
+    return case
+
+
+def aug_lattice_premises(case):
+    """The premises of the exact part, in fp32 on the CPU.  -> the exact sums [b, c] (Python integers in an object array)."""
+    low, high = case.low, case.high
+    assert bool((np.abs(low) <= 4096).all() and (np.abs(high) <= 4096).all() and (high - low >= 2).all())
+    assert len(set(case.nhigh.reshape(-1).tolist())) == case.b * case.c, "the H counts must differ per (sample, channel)"
+    for i in range(case.b):
+        assert not case.shifted or len(set(case.add[i].tolist())) == case.c, "the shifts must differ per channel"
+    s = case.x + case.add[:, :, None]
+    assert s.dtype == np.float32 and np.array_equal(s, case.lat)                       # the shifted values are L and H exactly
+    gmin, gmax = s.min(axis=(1, 2)), s.max(axis=(1, 2))
+    assert np.array_equal(gmin, low.astype(np.float32)) and np.array_equal(gmax, high.astype(np.float32))
+    grange = gmax - gmin
+    assert grange.dtype == np.float32 and np.array_equal(grange + np.float32(1e-7), grange)      # fl(grange + 1e-7f) = grange
+    t = (s - gmin[:, None, None]) / (grange + np.float32(1e-7))[:, None, None]
+    assert t.dtype == np.float32 and set(np.unique(t).tolist()) <= {0.0, 1.0} and np.array_equal(t == 1.0, case.mask)
+    for gamma in (0.7, 1.0, 1.3):
+        assert set(np.unique(np.power(t, np.float32(gamma))).tolist()) <= {0.0, 1.0}
+    nb = aug_blocks(case.spatial)
+    pad = np.zeros((case.b, case.c, nb * AUG_BLOCK_VOX))
+    pad[:, :, :case.spatial] = np.abs(case.lat)
+    part = pad.reshape(case.b, case.c, nb, AUG_BLOCK_VOX).sum(-1)
+    assert float(part.max()) < FP32_EXACT, "a block's sum of |g| reaches 2^24"
+    assert bool((case.mask.reshape(case.b, case.c, -1)[:, :, np.arange(nb) * AUG_BLOCK_VOX]).all()) and bool(case.mask[:, :, -1].all())
+    sums = np.empty((case.b, case.c), dtype=object)
+    for i in range(case.b):
+        for ch in range(case.c):
+            k = int(case.nhigh[i, ch])
+            sums[i, ch] = k * int(high[i]) + (case.spatial - k) * int(low[i])
+    return sums
+
+
+def aug_lattice_mean32(case):
+    """What aug_finalize2_kernel stores: (float)(sum / count), both exact in fp64.  [b, c] fp32, strictly between L and H."""
+    sums = aug_lattice_premises(case)
+    mean = np.empty((case.b, case.c), dtype=np.float32)
+    for i in range(case.b):
+        for ch in range(case.c):
+            mean[i, ch] = np.float32(np.float64(sums[i, ch]) / np.float64(case.spatial))
+    assert bool((mean > case.low[:, None]).all() and (mean < case.high[:, None]).all())
+    return mean
+
+
+def aug_lattice_params(case, gamma, factor, shift=True):
+    prm = np.zeros((case.b, case.c, 3), dtype=np.float32)
+    if shift:
+        prm[:, :, 0] = case.add
+    prm[:, :, 1], prm[:, :, 2] = gamma, factor
+    return prm
+
+
+def _as5(a, case):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape((case.b, case.c, 1) + case.shape)))
+
+
+def check_aug_lattice_mean(got, case, what):
+    """Contrast factor 0: clip(fma(g - mean, 0, mean), lo, hi) is the channel's mean in every voxel, bit for bit."""
+    want = np.broadcast_to(aug_lattice_mean32(case)[:, :, None], (case.b, case.c, case.spatial))
+    return assert_exact(_as5(got, case), _as5(want, case), what + ": factor 0 -> f32(S / count)")
+
+
+def check_aug_lattice_extremes(got, case, what):
+    """Contrast factor 2^40: a voxel that held L becomes lo = L, one that held H becomes hi = H, bit for bit."""
+    return assert_exact(_as5(got, case), _as5(case.lat, case), what + ": factor 2^40 -> L / H")
+
+
+def check_aug_lattice_factor(got, case, factor, what):
+    """A factor of few bits: |got - ref64| <= 2^-24 (|f| |g - mean| + |out|) against the fp64 evaluation of
+    clip(fma(fl32(g - mean), f, mean), L, H) with the exact fp32 mean.  -> the number of voxels that are not bit-equal to the
+    reference rounded to fp32."""
+    mean = aug_lattice_mean32(case)[:, :, None]
+    d32 = case.lat - mean
+    assert d32.dtype == np.float32
+    lo, hi = case.low.astype(np.float64)[:, None, None], case.high.astype(np.float64)[:, None, None]
+    ref = np.clip(d32.astype(np.float64) * float(factor) + mean.astype(np.float64), lo, hi)
+    norm = abs(float(factor)) * np.abs(case.lat.astype(np.float64) - mean.astype(np.float64)) + np.abs(ref)
+    got = np.asarray(got, dtype=np.float32).reshape(ref.shape)
+    check_gradient(torch.from_numpy(got), torch.from_numpy(ref), torch.from_numpy(norm), U32, what + f": factor {factor}")
+    return int((got != ref.astype(np.float32)).sum())
+
+
+def aug_two_channel_case(tag, b, shape):
+    """Samples of two channels after the shift: channel 0 holds L and M, channel 1 holds M and H, M = (L + H) / 2, H - L a multiple
+    of 4: the sample's minimum lies in channel 0 and its maximum in channel 1, t is 0, 1/2 or 1 exactly.  lo / hi of channel 0 are
+    L and g(1/2), of channel 1 g(1/2) and H, while gmin and grange are the sample's."""
+    g = _np_rng(tag)
+    S = int(np.prod(shape))
+    low = g.integers(-2000, 1000, size=b)
+    high = low + 4 * g.integers(1, 500, size=b)
+    mid = (low + high) // 2
+    add = np.stack([g.permutation(np.arange(-9, 10))[:2] for _ in range(b)]).astype(np.int64)
+    upper = g.random((b, 2, S)) < 0.4
+    upper[:, :, 0], upper[:, :, 1], upper[:, :, -1] = True, False, True
+    lat = np.empty((b, 2, S), dtype=np.int64)
+    lat[:, 0] = np.where(upper[:, 0], mid[:, None], low[:, None])
+    lat[:, 1] = np.where(upper[:, 1], high[:, None], mid[:, None])
+    x = (lat - add[:, :, None]).astype(np.float32)
+    half = lat == mid[:, None, None]
+    s = x + add.astype(np.float32)[:, :, None]
+    t = (s - s.min(axis=(1, 2), keepdims=True)) / ((s.max(axis=(1, 2)) - s.min(axis=(1, 2))) + np.float32(1e-7))[:, None, None]
+    assert t.dtype == np.float32 and set(np.unique(t).tolist()) == {0.0, 0.5, 1.0} and np.array_equal(t == 0.5, half)
+    return types.SimpleNamespace(b=b, c=2, shape=tuple(shape), spatial=S, x=x, add=add.astype(np.float32), lat=lat.astype(np.float32),
+                                 half=half, low=low, high=high)
+
+
+def check_aug_two_channel(got, case, ref, eps, what):
+    """Contrast factor 2^40 on aug_two_channel_case: the voxels that held L and H come back as L and H bit for bit (each channel is
+    clipped to ITS OWN ends, the gamma map runs on the SAMPLE's range); the voxels at t = 1/2 are an end of their channel, g(1/2), held
+    to the random part's bound."""
+    got = np.asarray(got, dtype=np.float32).reshape(case.b, 2, case.spatial)
+    bad = (got != case.lat) & ~case.half
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {int((~case.half).sum())} L / H voxels differ; first at {tuple(np.argwhere(bad)[0])}"
+    assert bool((ref.sure_lo | ref.sure_hi).all()), what + ": a voxel is not clipped beyond doubt at factor 2^40"
+    return check_augment(got, ref, eps, what)

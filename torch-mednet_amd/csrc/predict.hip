@@ -53,6 +53,14 @@ __global__ __launch_bounds__(256) void predict_assemble_kernel(const float* __re
   const int z = (int)(r / cy);
   const int gz = pos[b * 3] + z, gy = pos[b * 3 + 1] + y, gx = pos[b * 3 + 2] + x;
   if (gz >= d || gy >= h || gx >= w) return;  // the part of the last patches that hangs over the volume
+  // The windows of one launch can overlap: the grid step on axis 0 is pd - 2 o0, the window pd - o0 - o1 long, so with o0 > o1
+  // neighbours share o0 - o1 planes.  add_processed_batch writes the items in order -- the LAST row covering a voxel wins.  Items
+  // of a launch have no order, so a thread leaves its voxel to any later row whose window holds it (rows are three ints, batches
+  // small, the loads uniform); across launches stream order gives the same rule.
+  for (int j = b + 1; j < (int)gridDim.y; ++j) {
+    const int qz = gz - pos[j * 3], qy = gy - pos[j * 3 + 1], qx = gx - pos[j * 3 + 2];
+    if (qz >= 0 && qz < cz && qy >= 0 && qy < cy && qx >= 0 && qx < cx) return;
+  }
   const size_t pvox = (size_t)pd * ph * pw;
   const float* src = logits + (size_t)b * (nh + ncls) * pvox + ((size_t)(z + cs0) * ph + (y + cs1)) * pw + (x + cs2);
   const size_t vox = (size_t)d * h * w, dst = ((size_t)gz * h + gy) * w + gx;
