@@ -177,9 +177,12 @@ def case(kind, n, cin, cout, shape, **kw):
     return _CASES[key]
 
 
-def run_layer(c, mode, algo="auto"):
-    """The case through hnn.Conv3d / hnn.ConvTranspose3d in a storage mode -> {y, dx, dw, db} on the CPU."""
+def run_layer(c, mode, algo="auto", put=None):
+    """The case through hnn.Conv3d / hnn.ConvTranspose3d in a storage mode -> {y, dx, dw, db} on the CPU.  `put`: where every
+    device tensor the layer is given goes first, as put(tensor, cl); cl: an activation, which the library wants channels-last, not
+    a parameter (tests/test_gpu_footprint.py: fence.put)."""
     dt = DT[mode]
+    put = put or (lambda t, cl: t)
     mednet_hip.set_conv_algo(algo)
     try:
         with mednet_hip.precision(mode):
@@ -193,15 +196,17 @@ def run_layer(c, mode, algo="auto"):
                     mod.bias.copy_(c.b)
                 elif c.kind == "convt":
                     mod.bias.zero_()
+                for p in mod.parameters():
+                    p.data = put(p.data, False)
             # (the network input of a first layer arrives in fp32; every other tensor in the mode's storage type, so that the
             #  matrix-core kernels take the call)
-            xg = (c.x.to(DEV) if c.cin == 1 else c.x.to(DEV).to(dt)).requires_grad_(True)
+            xg = put(c.x.to(DEV) if c.cin == 1 else c.x.to(DEV).to(dt), True).requires_grad_(True)
             if c.kind == "convt":
-                y = mod(xg, skip=None if c.skip is None else c.skip.to(DEV).to(dt))
+                y = mod(xg, skip=None if c.skip is None else put(c.skip.to(DEV).to(dt), True))
             else:
                 y = mod(xg)
             assert y.dtype == dt and tuple(y.shape) == (c.n, c.cout, *c.oshape)
-            y.backward(c.g.to(DEV).to(dt))
+            y.backward(put(c.g.to(DEV).to(dt), True))
             torch.cuda.synchronize()
             has_b = c.b is not None
             return dict(y=y.detach().cpu(), dx=xg.grad.cpu(), dw=mod.weight.grad.cpu(), db=mod.bias.grad.cpu() if has_b else None)
