@@ -62,7 +62,7 @@ enum { MEDNET_PACK_LOW = 0x100,
         * multiples of 32) it must re-pack that layer in full (mednet_conv3d_pack_elt).  mednet_hip.nn does (`_packed(x)`). */
        MEDNET_PACK_HIGH_ONLY = 0x200 };
 enum { MEDNET_REG_L2 = 0, MEDNET_REG_L1 = 1 };
-enum { MEDNET_CLASS_DICE = 0, MEDNET_CLASS_CE = 1 };  /* class-loss kind of mednet_head_landmark_cls_fwd / _bwd */
+enum { MEDNET_CLASS_DICE = 0, MEDNET_CLASS_CE = 1, MEDNET_CLASS_DICE_CE = 2 };  /* class-loss kind of mednet_head_landmark_cls_* / mednet_head_seg_* */
 enum {
   MEDNET_OK = 0, MEDNET_E_SHAPE = -1, MEDNET_E_DTYPE = -2, MEDNET_E_WORKSPACE = -3, MEDNET_E_HIP = -4,
   MEDNET_E_UNSUPPORTED = -5
@@ -380,6 +380,23 @@ int mednet_dice_fwd_lt(const float* logits, const void* labels, int label_dtype,
 int mednet_dice_bwd_lt(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const float* weight,
                        const float* saved, const float* dloss, float* dlogits, int n, int c, size_t spatial, int64_t stride_n,
                        int64_t stride_c, float eps, int sigmoid, int ignore_index, mednet_stream stream);
+/* Dice + cross-entropy, the compound class loss, in one pass over the logits each way (additive to ABI 3):
+ *   loss = DiceLoss(weight, eps, softmax)(x, y) + nn.CrossEntropyLoss(weight)(x, y), unit coefficients, one class-weight vector.
+ * Softmax only and no ignore_index (the entries have neither argument).  Logits, labels and dlogits as mednet_dice_fwd_lt / _bwd_lt
+ * take them; 1 <= c <= 32.  saved: 2 c + 1 floats, [c][2] = {I_c, D_c} followed by sum w_y.  dice_out (nullable): the per-channel
+ * dice.  Workspace: mednet_dice_ce_ws_bytes (the Dice rows and the CE rows of every workgroup; mednet_loss_ws_bytes is too small).
+ * A label outside [0, c) makes the loss and every logit gradient NaN.
+ * Bit-identity: the two terms are accumulated with the instructions and in the order of mednet_dice_fwd_lt (sigmoid 0,
+ * MEDNET_NO_IGNORE) and mednet_ce_fwd and combined by the same fp64 fixed-order sums, so *loss is the fp32 sum of those two
+ * entries' losses and saved holds their saved values; dlogits is, element by element, the fp32 sum of mednet_dice_bwd_lt's and
+ * mednet_ce_bwd's results for the same *dloss (what autograd forms of the two-kernel composition), written with one store. */
+size_t mednet_dice_ce_ws_bytes(int n, int c, size_t spatial);
+int mednet_dice_ce_fwd_lt(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const float* weight,
+                          float* loss, float* saved, float* dice_out, int n, int c, size_t spatial, int64_t stride_n,
+                          int64_t stride_c, float eps, void* ws, size_t ws_bytes, mednet_stream stream);
+int mednet_dice_ce_bwd_lt(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const float* weight,
+                          const float* saved, const float* dloss, float* dlogits, int n, int c, size_t spatial, int64_t stride_n,
+                          int64_t stride_c, float eps, mednet_stream stream);
 /* The 1x1x1 head (model.py:207 final_conv: nn.Conv3d(f_maps[0], out_channels, 1)) fused with DiceLoss (loss.py:114-130) --
  * what `outputs = self(inputs); loss = self.loss(outputs, labels)` (segmentation.py:61-62) runs between the last decoder block and
  * the scalar loss.  Forward: logits (N x C x spatial fp32, written once, for the caller) + loss + saved[c] = {I_c, D_c} in one pass
@@ -443,7 +460,10 @@ int mednet_head_landmark_bwd(const void* z, const void* packed, const float* bia
  * class channels (ignore_index honoured, out-of-range labels -> NaN) and saved[0] = sum w_y; _bwd reads saved[0].  dice_metric
  * (nullable, [ncls]): dice_metric(outputs[:, nh:], labels) (loss.py:51-55: softmax, no weight, no mask) from the same pass; with
  * MEDNET_CLASS_DICE it requires sigmoid == 0 and ignore_index == MEDNET_NO_IGNORE.  Workspace: mednet_head_landmark_ws_bytes.
- * Results equal the unfused launches (mednet_ce_* for the class term) up to fp32 summation order. */
+ * MEDNET_CLASS_DICE_CE (sigmoid must be 0 and ignore_index MEDNET_NO_IGNORE, else MEDNET_E_UNSUPPORTED): class_loss = Dice + CE of
+ * the class channels with one class-weight vector, as mednet_dice_ce_fwd_lt; saved holds 2 ncls + 1 floats, [ncls][2] = {I, D}
+ * followed by sum w_y; dice_metric as with MEDNET_CLASS_DICE.
+ * Results equal the unfused launches (mednet_ce_* / mednet_dice_ce_* for the class term) up to fp32 summation order. */
 int mednet_head_ce_supported(int cin, int cout, int dtype, int label_dtype);
 size_t mednet_head_ce_ws_bytes(int n, size_t spatial, int cin, int cout);
 int mednet_head_ce_gn_rows(int n, size_t spatial, int cin);
@@ -454,6 +474,26 @@ int mednet_head_ce_bwd(const float* logits, const void* labels, int label_dtype,
                        const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
                        int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
                        int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+/* mednet_head_dice_ce_*: the segmentation head of mednet_head_dice_* (cin in {16, 32, 64}, cout <= 4, f32 / bf16 / f16 features) with
+ * the compound class loss DiceLoss(weight, eps) + nn.CrossEntropyLoss(weight) of mednet_dice_ce_fwd_lt.  Additive to ABI 3.  Same
+ * arguments, layouts, label forms, GroupNorm rows and fold rule as mednet_head_dice_*; softmax only and no ignore_index: sigmoid != 0
+ * or ignore_index != MEDNET_NO_IGNORE is MEDNET_E_UNSUPPORTED.  saved: 2 cout + 1 floats, [cout][2] = {I, D} followed by sum w_y.
+ * Workspace: mednet_head_dice_ce_ws_bytes -- the forward writes the Dice rows and the CE rows of every workgroup, so
+ * mednet_head_dice_ws_bytes is too small.  A label outside [0, cout) makes the loss and every gradient NaN.
+ * Logits, loss, dz and the GroupNorm sums are bit-identical to mednet_conv3d_fwd + mednet_dice_ce_fwd_lt / _bwd_lt +
+ * mednet_head_dgrad_gn (hence to the sum of the mednet_dice_* and mednet_ce_* results); dW / dbias are summed in another fixed
+ * order, as for mednet_head_dice_bwd. */
+int mednet_head_dice_ce_supported(int cin, int cout, int dtype, int label_dtype);
+size_t mednet_head_dice_ce_ws_bytes(int n, size_t spatial, int cin, int cout);
+int mednet_head_dice_ce_gn_rows(int n, size_t spatial, int cin);
+int mednet_head_dice_ce_fwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                            int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
+                            size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
+                            size_t ws_bytes, mednet_stream stream);
+int mednet_head_dice_ce_bwd(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const void* packed,
+                            const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
+                            int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
+                            float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
 int mednet_head_landmark_cls_fwd(const void* z, const void* packed, const float* bias, const void* heatmaps, int64_t heatmap_stride_n,
                                  const void* labels, int64_t label_stride_n, const float* class_weight, const float* reg_weight,
                                  float* logits, float* class_loss, float* reg_loss, float* saved, float* dice_metric, int n,
@@ -468,7 +508,10 @@ int mednet_head_landmark_cls_bwd(const void* z, const void* packed, const float*
 /* The segmentation head for 5 .. 16 classes (SegmentationNet, segmentation.py:30-31, 58-62: final_conv 32 -> ncls) fused with its
  * loss on the matrix cores, 16-bit storage only.  Additive to ABI 3; mednet_head_dice_* / mednet_head_ce_* (<= 4 classes) are
  * unchanged.  class_kind MEDNET_CLASS_DICE: DiceLoss (loss.py:114-130: class weight in the numerator, eps, sigmoid | softmax,
- * ignore_index on the one-hot target); MEDNET_CLASS_CE: nn.CrossEntropyLoss(weight, ignore_index) (softmax: sigmoid must be 0).
+ * ignore_index on the one-hot target); MEDNET_CLASS_CE: nn.CrossEntropyLoss(weight, ignore_index) (softmax: sigmoid must be 0);
+ * MEDNET_CLASS_DICE_CE: their sum with one class-weight vector, as mednet_dice_ce_fwd_lt (sigmoid must be 0 and ignore_index
+ * MEDNET_NO_IGNORE, else MEDNET_E_UNSUPPORTED; saved holds 2 ncls + 1 floats: [ncls][2] = {I, D}, then sum w_y; the workspace
+ * query already covers the Dice rows plus the CE rows).
  * z: N x spatial x cin (NDHWC); labels: MEDNET_U8, N x spatial, sample stride label_stride_n, base pointer and stride multiples
  * of 4 bytes; `packed` = the head's mednet_conv3d_pack image (its fp32 [co][ci] block, split hi + lo for the MFMAs).
  * _fwd writes loss and saved (Dice: [ncls][2] = {I, D}; CE: saved[0] = sum w_y, saved holds 2 floats), both required, and the

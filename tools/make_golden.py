@@ -364,6 +364,49 @@ def loss_cases(out, rloss):
     np.savez_compressed(os.path.join(out, "losses.npz"), **rec)
 
 
+# Dice + cross-entropy, the compound class loss (tests/golden/dice_ce.npz): class counts, weights per count
+DICE_CE_CLASSES = (2, 4, 14)
+DICE_CE_SHAPE = (2, (6, 5, 4))
+
+
+def dice_ce_weights(c):
+    return torch.tensor([0.05] + [0.6 + 0.1 * (k % 7) for k in range(1, c)])
+
+
+def dice_ce_cases(out, rloss):
+    """The reference's DiceLoss(weight=w)(x, y) + torch.nn.CrossEntropyLoss(w)(x, y) -- what its callers would write for the compound
+    class loss (segmentation.py:43-49, landmarks.py:49) -- against the oracle's composition O.DiceLoss + F.cross_entropy, bit for bit;
+    then logits, labels, weight, the loss, both terms and dlogits per case."""
+    import torch.nn.functional as F
+    rec = {}
+    g = np.random.Generator(np.random.PCG64(791))
+    n, shp = DICE_CE_SHAPE
+    for c in DICE_CE_CLASSES:
+        logits_np = (g.standard_normal((n, c) + shp) * 2).astype(np.float32)
+        labels_np = g.integers(0, c, size=(n,) + shp).astype(np.int64)
+        rec[f"c{c}.logits"], rec[f"c{c}.labels"] = logits_np, labels_np.astype(np.uint8)
+        for wtag, w in (("plain", None), ("weight", dice_ce_weights(c))):
+            res = []
+            for which in ("reference", "oracle"):
+                z = torch.from_numpy(logits_np).clone().requires_grad_(True)
+                y = torch.from_numpy(labels_np)
+                if which == "reference":
+                    dice, ce = rloss.DiceLoss(weight=w)(z, y), torch.nn.CrossEntropyLoss(w)(z, y[...])
+                else:
+                    dice, ce = O.DiceLoss(weight=w)(z, y), F.cross_entropy(z, y, weight=w)
+                total = dice + ce
+                total.backward()
+                res.append((total.detach(), dice.detach(), ce.detach(), z.grad.clone()))
+            tag = f"c{c}.{wtag}"
+            for name, a, b in zip(("loss", "dice", "ce", "dlogits"), res[0], res[1]):
+                assert_same(f"dice_ce {tag}:{name}", a, b)
+                rec[f"{tag}.{name}"] = a.numpy()
+            if w is not None:
+                rec[f"c{c}.weight"] = w.numpy()
+            print(f"[make_golden] dice_ce {tag}: ok")
+    np.savez_compressed(os.path.join(out, "dice_ce.npz"), **rec)
+
+
 def caller_cases(out):
     """SegmentationNet / LandmarkNet training_step on the reference (segmentation.py:58-65, landmarks.py:66-83)."""
     rseg, rldm = import_reference_callers()
@@ -653,6 +696,8 @@ def main():
         block_cases(a.out, rcomp)
     if want("losses"):
         loss_cases(a.out, rloss)
+    if want("dice_ce"):
+        dice_ce_cases(a.out, rloss)
     if want("callers"):
         caller_cases(a.out)
     if want("callers_ce"):

@@ -456,6 +456,17 @@ extern "C" int mednet_head_dgrad_gn(const void* dy, const void* packed, void* dx
                               cin, dtype, (hipStream_t)stream);
 }
 
+// The class-loss kind of the matrix-core heads: MEDNET_CLASS_DICE, MEDNET_CLASS_CE (softmax) or MEDNET_CLASS_DICE_CE (their sum:
+// softmax, and no ignore_index -- Dice's mask on the one-hot target and cross-entropy's voxel rule do not compose)
+static int class_kind_checks(const char* what, int class_kind, int sigmoid, int ignore_index) {
+  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE || class_kind == MEDNET_CLASS_DICE_CE,
+                 MEDNET_E_UNSUPPORTED, "%s: class-loss kind %d", what, class_kind);
+  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED, "%s: cross-entropy is a softmax form", what);
+  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_DICE_CE || (sigmoid == 0 && ignore_index == MEDNET_NO_IGNORE), MEDNET_E_UNSUPPORTED,
+                 "%s: Dice + cross-entropy is a softmax form without ignore_index", what);
+  return 0;
+}
+
 // ---- the landmark head fused with its two losses (head_mfma.hip) ---------------------------------------------------------
 extern "C" int mednet_head_landmark_supported(int cin, int nh, int ncls, int dtype, size_t spatial) {
   return is16(dtype) && ELT_CALL(dtype, head_lm_supported, cin, nh, ncls, dtype, spatial) ? 1 : 0;
@@ -465,7 +476,8 @@ extern "C" size_t mednet_head_landmark_ws_bytes(int n, size_t spatial, int nh, i
 }
 extern "C" int mednet_head_landmark_gn_rows(size_t spatial) { return head_lm_chunks(spatial); }
 // One forward and one backward behind the four entries: `what` names the entry the caller used, `class_kind` the class term
-// (MEDNET_CLASS_DICE: DiceLoss; MEDNET_CLASS_CE: nn.CrossEntropyLoss, softmax), `dice_metric` (nullable) takes dice_metric of the
+// (MEDNET_CLASS_DICE: DiceLoss; MEDNET_CLASS_CE: nn.CrossEntropyLoss, softmax; MEDNET_CLASS_DICE_CE: their sum -- the CE forward's
+// rows hold both terms' sums, see head_lm_kernel), `dice_metric` (nullable) takes dice_metric of the
 // class channels from the same pass.
 static int head_landmark_fwd(const char* what, const void* z, const void* packed, const float* bias, const void* heatmaps,
                              int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n, const float* class_weight,
@@ -480,7 +492,7 @@ static int head_landmark_fwd(const char* what, const void* z, const void* packed
   MEDNET_REQUIRE(ws_bytes >= head_lm_ws_bytes(n, spatial, nh, ncls), MEDNET_E_WORKSPACE, "%s: workspace too small", what);
   hipStream_t s = (hipStream_t)stream;
   const int chunks = head_lm_chunks(spatial);
-  const int ce = class_kind == MEDNET_CLASS_CE;
+  const int ce = class_kind != MEDNET_CLASS_DICE;
   float* hm_partial = (float*)ws;
   float* dice_partial = hm_partial + (size_t)n * nh * chunks;
   float* ce_partial = dice_partial + (size_t)n * chunks * ncls * 2;
@@ -491,8 +503,10 @@ static int head_landmark_fwd(const char* what, const void* z, const void* packed
   if (rc) return rc;
   rc = launch_hm_finalize(hm_partial, reg_weight, reg_loss, n, nh, chunks, spatial, s);
   if (rc) return rc;
-  rc = ce ? launch_ce_finalize(ce_partial, class_loss, saved, n * chunks, s)
-          : launch_dice_finalize(dice_partial, class_weight, class_loss, saved, ncls, n * chunks, eps, s);
+  rc = class_kind == MEDNET_CLASS_DICE_CE
+           ? launch_dice_ce_finalize(dice_partial, ce_partial, class_weight, class_loss, saved, ncls, n * chunks, eps, s)
+           : ce ? launch_ce_finalize(ce_partial, class_loss, saved, n * chunks, s)
+                : launch_dice_finalize(dice_partial, class_weight, class_loss, saved, ncls, n * chunks, eps, s);
   if (rc || !dice_metric) return rc;
   return launch_dice_finalize(dice_partial, nullptr, nullptr, metric_saved, ncls, n * chunks, 1e-5f, s, dice_metric);
 }
@@ -508,7 +522,7 @@ static int head_landmark_bwd(const char* what, const void* z, const void* packed
                  "%s: %d -> %d heat maps + %d classes, dtype %d, %zu voxels", what, cin, nh, ncls, z_dtype, spatial);
   return ELT_CALL(z_dtype, launch_head_lm_bwd, z, head_weights_f32(packed, cin, nh + ncls), bias, heatmaps, heatmap_stride_n, labels,
                   label_stride_n, saved, class_weight, reg_weight, dclass_loss, dreg_loss, eps, dz, gn_y, gn_act, gn_partial, dw, dbias, n,
-                  spatial, nh, ncls, kind, class_kind == MEDNET_CLASS_CE, sigmoid, ignore_index, ws, ws_bytes, (hipStream_t)stream);
+                  spatial, nh, ncls, kind, class_kind, sigmoid, ignore_index, ws, ws_bytes, (hipStream_t)stream);
 }
 extern "C" int mednet_head_landmark_fwd(const void* z, const void* packed, const float* bias, const void* heatmaps,
                                         int64_t heatmap_stride_n, const void* labels, int64_t label_stride_n,
@@ -539,8 +553,8 @@ extern "C" int mednet_head_landmark_cls_fwd(const void* z, const void* packed, c
                                             float* reg_loss, float* saved, float* dice_metric, int n, size_t spatial, int cin, int nh,
                                             int ncls, int kind, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype,
                                             void* ws, size_t ws_bytes, mednet_stream stream) {
-  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED,
-                 "head_landmark_cls_fwd: class-loss kind %d", class_kind);
+  const int rc = class_kind_checks("head_landmark_cls_fwd", class_kind, sigmoid, ignore_index);
+  if (rc) return rc;
   MEDNET_REQUIRE(!(class_kind == MEDNET_CLASS_CE || dice_metric) || sigmoid == 0, MEDNET_E_UNSUPPORTED,
                  "head_landmark_cls_fwd: cross-entropy and dice_metric are softmax forms");
   MEDNET_REQUIRE(!(class_kind == MEDNET_CLASS_DICE && dice_metric) || ignore_index == MEDNET_NO_IGNORE, MEDNET_E_UNSUPPORTED,
@@ -556,10 +570,8 @@ extern "C" int mednet_head_landmark_cls_bwd(const void* z, const void* packed, c
                                             float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int nh, int ncls,
                                             int kind, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
                                             size_t ws_bytes, mednet_stream stream) {
-  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED,
-                 "head_landmark_cls_bwd: class-loss kind %d", class_kind);
-  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED,
-                 "head_landmark_cls_bwd: cross-entropy is a softmax form");
+  const int rc = class_kind_checks("head_landmark_cls_bwd", class_kind, sigmoid, ignore_index);
+  if (rc) return rc;
   return head_landmark_bwd("head_landmark_cls_bwd", z, packed, bias, heatmaps, heatmap_stride_n, labels, label_stride_n, class_weight,
                            reg_weight, saved, dclass_loss, dreg_loss, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, cin, nh, ncls,
                            kind, class_kind, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
@@ -573,10 +585,10 @@ extern "C" size_t mednet_head_seg_ws_bytes(int n, size_t spatial, int ncls) { re
 extern "C" int mednet_head_seg_gn_rows(size_t spatial) { return head_lm_chunks(spatial); }
 // the checks both directions share; `ok` = the direction's own pointers
 static int head_seg_checks(const char* what, bool ok, const void* z, const void* packed, const void* labels, const void* saved,
-                           const void* ws, int n, size_t spatial, int cin, int ncls, int class_kind, int sigmoid, int z_dtype) {
-  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE, MEDNET_E_UNSUPPORTED, "%s: class-loss kind %d", what,
-                 class_kind);
-  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_CE || sigmoid == 0, MEDNET_E_UNSUPPORTED, "%s: cross-entropy is a softmax form", what);
+                           const void* ws, int n, size_t spatial, int cin, int ncls, int class_kind, int sigmoid, int ignore_index,
+                           int z_dtype) {
+  const int rc = class_kind_checks(what, class_kind, sigmoid, ignore_index);
+  if (rc) return rc;
   MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && saved && ws && ok, MEDNET_E_SHAPE, "%s: bad arguments", what);
   MEDNET_REQUIRE(mednet_head_seg_supported(cin, ncls, z_dtype, MEDNET_U8, spatial), MEDNET_E_UNSUPPORTED,
                  "%s: %d -> %d classes, dtype %d, %zu voxels", what, cin, ncls, z_dtype, spatial);
@@ -587,7 +599,7 @@ extern "C" int mednet_head_seg_fwd(const void* z, const void* packed, const floa
                                    int ncls, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws,
                                    size_t ws_bytes, mednet_stream stream) {
   int rc = head_seg_checks("head_seg_fwd", loss != nullptr, z, packed, labels, saved, ws, n, spatial, cin, ncls, class_kind, sigmoid,
-                           z_dtype);
+                           ignore_index, z_dtype);
   if (rc) return rc;
   MEDNET_REQUIRE(ws_bytes >= head_seg_ws_bytes(n, spatial, ncls), MEDNET_E_WORKSPACE, "head_seg_fwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -595,8 +607,10 @@ extern "C" int mednet_head_seg_fwd(const void* z, const void* packed, const floa
   const int ce = class_kind == MEDNET_CLASS_CE;
   float* partial = (float*)ws;
   rc = ELT_CALL(z_dtype, launch_head_seg_fwd, z, head_weights_f32(packed, cin, ncls), bias, labels, label_stride_n, class_weight, logits,
-                partial, n, spatial, ncls, ce, sigmoid, ignore_index, s);
+                partial, n, spatial, ncls, class_kind, sigmoid, ignore_index, s);
   if (rc) return rc;
+  if (class_kind == MEDNET_CLASS_DICE_CE)  // (the Dice rows, behind all of them the CE rows: launch_head_seg_fwd)
+    return launch_dice_ce_finalize(partial, partial + (size_t)n * chunks * ncls * 2, class_weight, loss, saved, ncls, n * chunks, eps, s);
   if (ce) return launch_ce_finalize(partial, loss, saved, n * chunks, s);
   return launch_dice_finalize(partial, class_weight, loss, saved, ncls, n * chunks, eps, s);
 }
@@ -606,10 +620,10 @@ extern "C" int mednet_head_seg_bwd(const void* z, const void* packed, const floa
                                    int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
                                    mednet_stream stream) {
   const int rc = head_seg_checks("head_seg_bwd", dloss && dz && dw, z, packed, labels, saved, ws, n, spatial, cin, ncls, class_kind,
-                                 sigmoid, z_dtype);
+                                 sigmoid, ignore_index, z_dtype);
   if (rc) return rc;
   return ELT_CALL(z_dtype, launch_head_seg_bwd, z, head_weights_f32(packed, cin, ncls), bias, labels, label_stride_n, saved, class_weight,
-                  dloss, eps, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, ncls, class_kind == MEDNET_CLASS_CE, sigmoid,
+                  dloss, eps, dz, gn_y, gn_act, gn_partial, dw, dbias, n, spatial, ncls, class_kind, sigmoid,
                   ignore_index, ws, ws_bytes, (hipStream_t)stream);
 }
 

@@ -68,6 +68,9 @@ int launch_dice_finalize(const float* partial, const float* weight, float* loss,
                          hipStream_t s, float* dice_out = nullptr);
 // partial[nblocks][2] = {sum w_y nll, sum w_y} -> *loss = num / den, saved[0] = den (ce_finalize_kernel)
 int launch_ce_finalize(const float* partial, float* loss, float* saved, int nblocks, hipStream_t s);
+// Dice rows + CE rows -> *loss = fl(dice + ce), saved = [c][2] {I, D} then sum w_y (dice_ce_finalize_kernel)
+int launch_dice_ce_finalize(const float* partial, const float* partial_ce, const float* weight, float* loss, float* saved, int c,
+                            int nblocks, float eps, hipStream_t s, float* dice_out = nullptr);
 
 // 16-bit matrix-core kernels, conv_mfma.hip (namespace mednet: bf16; api.hip declares the same set in namespace mednet_f16
 // for the fp16 build of that file)

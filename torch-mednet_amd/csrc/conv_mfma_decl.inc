@@ -74,7 +74,8 @@ int head_lm_chunks(size_t spatial);  // workgroups per sample = rows per sample 
 size_t head_lm_ws_bytes(int n, size_t spatial, int nh, int ncls);
 // ce = 0: the class term is DiceLoss.  ce = 1: nn.CrossEntropyLoss(cls_weight, ignore) (softmax; `sigmoid` and `eps` are not read):
 // ce_partial [n][chunk][2] for ce_finalize, and dice_partial takes dice_metric's unweighted, unmasked sums; the backward reads
-// saved[0] = sum w_y of that forward.
+// saved[0] = sum w_y of that forward.  ce = 2: Dice + cross-entropy (softmax, no ignore_index); the forward runs the ce = 1 form, whose
+// rows hold both terms' sums, the backward reads saved = [ncls][2] {I, D}, then sum w_y.
 int launch_head_lm_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
                        int64_t lab_sn, const float* cls_weight, float* logits, float* hm_partial, float* dice_partial, float* ce_partial,
                        int n, size_t spatial, int nh, int ncls, int kind, int ce, int sigmoid, int ignore, hipStream_t s);
@@ -86,7 +87,8 @@ int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const v
 
 // head_mfma.hip: the segmentation head (1x1x1 conv 32 -> 5 .. 16 classes) fused with DiceLoss (ce = 0) or nn.CrossEntropyLoss
 // (ce = 1, softmax), matrix-core form.  `partial`: [n][chunk][ncls][2] for dice_finalize (ce = 0), [n][chunk][2] for ce_finalize
-// (ce = 1); chunks = head_lm_chunks(spatial).  Labels uint8, base and sample stride multiples of 4 bytes.
+// (ce = 1), the first followed by the second for their sum (ce = 2: softmax, no ignore_index; saved = [ncls][2], then sum w_y);
+// chunks = head_lm_chunks(spatial).  Labels uint8, base and sample stride multiples of 4 bytes.
 bool head_seg_supported(int cin, int ncls, int dtype, size_t spatial);
 size_t head_seg_ws_bytes(int n, size_t spatial, int ncls);
 int launch_head_seg_fwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* cls_weight,

@@ -21,6 +21,8 @@ namespace mednet {
 constexpr int HL_BLOCK_VOX = 256 * 8;  // = LOSS_BLOCK_VOX of loss.hip: the partial rows are dice_finalize_kernel's
 constexpr int HL_MAXC = 4;              // classes kept in registers (the segmentation heads of the callers: 2 and 4)
 constexpr int HL_VPT = 32;              // = HEAD_GN_VPT of conv_direct.hip: the GroupNorm rows are head_dgrad_gn_kernel's
+// the class loss of an instantiation (= MEDNET_CLASS_*): DiceLoss, nn.CrossEntropyLoss, or their sum
+constexpr int HL_DICE = 0, HL_CE = 1, HL_DICE_CE = 2;
 
 // a voxel's 8-channel piece as it lies in memory (4 registers for the 16-bit types): converted where it is used, so rows in
 // flight do not hold 8 registers each
@@ -88,13 +90,16 @@ __device__ __forceinline__ void probs_reg(const float* lg, int c, int sigmoid, f
 // ---- forward: one voxel per lane, weights wave-uniform (SGPR operands), 8 voxels per thread ------------------------------
 // logits[n][i][v] = bias[i] + sum_k z[n][v][k] W[i][k];  partial[n][block][c][2] = {sum p t mask, sum (p + t) mask}
 // CE (head_ce): partial[n][block][2] = {sum w_y nll, sum w_y} instead (loss.hip ce_fwd_kernel's rows, for ce_finalize_kernel);
-// cw = the class weights (nullable; read by this form only), `sigmoid` unused
-template <typename TI, int K, typename TL, bool CE = false>
+// cw = the class weights (nullable; read by the CE terms only), `sigmoid` unused
+// Dice + CE (head_dice_ce): both, the Dice rows first and behind all of them the CE rows; loss.hip dice_ce_fwd_kernel on registers
+// (one softmax per voxel; softmax only, `ignore` is MEDNET_NO_IGNORE)
+template <typename TI, int K, typename TL, int KIND = HL_DICE>
 __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict__ z, const float* __restrict__ Pb /*[m][K]*/,
                                                             const float* __restrict__ bias, const TL* __restrict__ lab,
                                                             int64_t lab_sn, float* __restrict__ y, float* __restrict__ partial,
                                                             size_t spatial, int m, int sigmoid, int ignore,
                                                             const float* __restrict__ cw = nullptr) {
+  constexpr bool CE = KIND == HL_CE;
   __shared__ float scratch[4];
   const int n = blockIdx.y;
   float I[HL_MAXC], D[HL_MAXC];
@@ -150,6 +155,39 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
         }
         continue;
       }
+      if constexpr (KIND == HL_DICE_CE) {
+        const bool ok = (unsigned)yl < (unsigned)m;
+        float mx = -INFINITY, zy = 0.f;
+#pragma unroll
+        for (int k = 0; k < HL_MAXC; ++k)
+          if (k < m) {
+            mx = fmaxf(mx, lg[k]);
+            if (k == yl) zy = lg[k];
+          }
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < HL_MAXC; ++k)
+          if (k < m) {
+            p[k] = expf(lg[k] - mx);
+            s += p[k];
+          }
+        const float inv = 1.f / s;
+        bad |= !ok;
+#pragma unroll
+        for (int k = 0; k < HL_MAXC; ++k)
+          if (k < m) {
+            p[k] *= inv;
+            const float t = (k == yl) ? 1.f : 0.f;
+            I[k] = fmaf(p[k], t, I[k]);
+            D[k] += p[k] + t;
+          }
+        if (ok) {
+          const float w = cw ? cw[yl] : 1.f;
+          num = fmaf(w, (mx + logf(s)) - zy, num);
+          den += w;
+        }
+        continue;
+      }
       probs_reg(lg, m, sigmoid, p);
       bad |= (unsigned)yl >= (unsigned)m;  // (loss.hip dice_fwd_kernel: an out-of-range label poisons the loss)
 #pragma unroll
@@ -184,6 +222,16 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
         out[2 * k + 1] = b;
       }
     }
+  if constexpr (KIND == HL_DICE_CE) {
+    if (bad) num = __builtin_nanf("");
+    num = block_sum<4>(num, scratch);
+    den = block_sum<4>(den, scratch);
+    if (threadIdx.x == 0) {
+      float* o = partial + (size_t)gridDim.y * gridDim.x * m * 2 + ((size_t)n * gridDim.x + blockIdx.x) * 2;
+      o[0] = num;
+      o[1] = den;
+    }
+  }
 }
 
 // ---- backward: K/8 lanes per voxel, each owns 8 channels of the voxel's row; two voxels per trip --------------------------
@@ -192,7 +240,9 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
 // stored gradient carries act'(z).  Its own instantiation: as a runtime branch it cost the main form its third wave per SIMD.
 // CE (head_ce): the logit gradient is loss.hip ce_bwd_kernel's closed form (dloss / saved[0]) w_y (p_k - [k == y]), 0 for an
 // ignored or out-of-range label; saved = {sum w_y} of the CE forward, `eps` and `sigmoid` unused.  Everything after it is shared.
-template <typename TO, int K, typename TL, bool FOLD = false, bool CE = false>
+// Dice + CE (head_dice_ce): the sum of the two closed forms, loss.hip dice_ce_bwd_kernel's (each term in a statement of its own, added
+// by a plain add: one expression would contract the CE product into the add); saved = [m][2] {I, D}, then sum w_y.
+template <typename TO, int K, typename TL, bool FOLD = false, int KIND = HL_DICE>
 __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_dice_bwd_kernel(const float* __restrict__ lgs, const TL* __restrict__ lab, int64_t lab_sn,
                                                             const float* __restrict__ Pb /*[m][K]*/, const float* __restrict__ weight,
                                                             const float* __restrict__ saved, const float* __restrict__ dloss,
@@ -201,6 +251,7 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
                                                             float* __restrict__ gn_partial /*nullable*/, float* __restrict__ wpart,
                                                             size_t spatial, int m) {
   constexpr int CG = K / 8, VPW = 256 / CG;
+  constexpr bool CE = KIND == HL_CE;
   const int n = blockIdx.y;
   const int cgi = threadIdx.x % CG, vi = threadIdx.x / CG;
   float wreg[HL_MAXC][8];
@@ -211,10 +262,36 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
   // per-class coefficients of the closed form (loss.hip dice_bwd_kernel; CE: gI[k] = w_k dloss / saved[0], ce_bwd_kernel's `w`)
   const float go = *dloss;
   float gI[HL_MAXC], gD[HL_MAXC];
+  // Dice + CE: gI, gD and ce_bwd_kernel's `w` per class are twelve loop-invariant values; in registers they took the 16-bit forms
+  // past the 168 of three waves per SIMD (2 to 8 spilled), so they live in LDS [gI | gD | w] and are read where they are used
+  // (`koff` is made opaque once per trip: left alone, the compiler hoists the reads back into registers)
+  [[maybe_unused]] float* hk = nullptr;
+  [[maybe_unused]] int koff = 0;
+  if constexpr (KIND == HL_DICE_CE) {
+    __shared__ float hk_s[3 * HL_MAXC];
+    if (threadIdx.x < HL_MAXC) {
+      const int k = threadIdx.x;
+      float a = 0.f, b = 0.f, cw = 0.f;
+      if (k < m) {
+        const float w = weight ? weight[k] : 1.f;
+        const float I = saved[2 * k], D = saved[2 * k + 1];
+        const float Dc = fmaxf(D, eps);
+        a = -2.f * w / ((float)m * Dc) * go + ((I != I || D != D) ? __builtin_nanf("") : 0.f);
+        b = (D >= eps ? 2.f * w * I / ((float)m * Dc * Dc) : 0.f) * go;
+        cw = w * (go / saved[2 * m]);
+      }
+      hk_s[k] = a;
+      hk_s[HL_MAXC + k] = b;
+      hk_s[2 * HL_MAXC + k] = cw;
+    }
+    __syncthreads();
+    hk = hk_s;
+  }
 #pragma unroll
   for (int k = 0; k < HL_MAXC; ++k) {
     gI[k] = gD[k] = 0.f;
-    if (CE && k < m) {
+    if (KIND == HL_DICE_CE) {
+    } else if (CE && k < m) {
       gI[k] = (weight ? weight[k] : 1.f) * (go / saved[0]);
     } else if (k < m) {
       const float w = weight ? weight[k] : 1.f;
@@ -235,6 +312,26 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
       w = (yl != ignore && yl >= 0 && yl < m) ? w : 0.f;
 #pragma unroll
       for (int k = 0; k < HL_MAXC; ++k) dl[k] = k < m ? w * (p[k] - (k == yl ? 1.f : 0.f)) : 0.f;
+      return;
+    }
+    if constexpr (KIND == HL_DICE_CE) {
+      float p[HL_MAXC], g[HL_MAXC];
+      probs_reg(lg, m, 0, p);
+      float dot = 0.f, w = 0.f;
+#pragma unroll
+      for (int k = 0; k < HL_MAXC; ++k)
+        if (k < m) {
+          const float t = (k == yl) ? 1.f : 0.f;
+          g[k] = hk[koff + k] * t + hk[koff + HL_MAXC + k];  // (gI * t is exact: the Dice form's g with mask 1, fused or not)
+          dot = fmaf(p[k], g[k], dot);
+          if (k == yl) w = hk[koff + 2 * HL_MAXC + k];
+        }
+#pragma unroll
+      for (int k = 0; k < HL_MAXC; ++k) {
+        const float dl_dice = p[k] * (g[k] - dot);
+        const float dl_ce = w * (p[k] - (k == yl ? 1.f : 0.f));
+        dl[k] = k < m ? dl_dice + dl_ce : 0.f;
+      }
       return;
     }
     float p[HL_MAXC], g[HL_MAXC];
@@ -304,6 +401,7 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
       yvb = zvb;
     }
     float da[HL_MAXC], db[HL_MAXC];
+    if constexpr (KIND == HL_DICE_CE) asm volatile("" : "+v"(koff));
     dlogits_of(la, ya, da);
     dlogits_of(lb, yb, db);
     if (!hb) {
@@ -448,9 +546,16 @@ extern "C" int mednet_head_dice_gn_rows(int n, size_t spatial, int cin) {
   (void)n;
   return 4 * (int)hl_bwd_blocks(spatial, cin);
 }
+// Dice + CE: the forward writes the Dice rows AND the CE rows of every workgroup
+extern "C" size_t mednet_head_dice_ce_ws_bytes(int n, size_t spatial, int cin, int cout) {
+  const size_t fwd = ((size_t)n * hl_fwd_blocks(spatial) * ((size_t)cout * 2 + 2) + 64) * sizeof(float);
+  const size_t bwd = mednet_head_dice_ws_bytes(n, spatial, cin, cout);  // (the backward's rows do not depend on the loss)
+  return fwd > bwd ? fwd : bwd;
+}
 
-// the forward / backward launches of both loss forms (CE: head_dice_*_kernel<..., CE = true>, ce_finalize instead of dice_finalize)
-template <bool CE>
+// the forward / backward launches of the three loss forms (head_dice_*_kernel<..., KIND>; CE: ce_finalize instead of dice_finalize,
+// Dice + CE: dice_ce_finalize and a workspace query of its own)
+template <int KIND>
 static int head_loss_fwd(const char* what, const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
                          int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n, size_t spatial,
                          int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
@@ -458,13 +563,15 @@ static int head_loss_fwd(const char* what, const void* z, const void* packed, co
   MEDNET_REQUIRE(mednet_head_dice_supported(cin, cout, z_dtype, label_dtype), MEDNET_E_UNSUPPORTED,
                  "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
   MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && logits && loss && saved, MEDNET_E_SHAPE, "%s: bad arguments", what);
-  MEDNET_REQUIRE(ws_bytes >= mednet_head_dice_ws_bytes(n, spatial, cin, cout), MEDNET_E_WORKSPACE, "%s: workspace too small", what);
+  constexpr bool CE = KIND == HL_CE;
+  const size_t need = KIND == HL_DICE_CE ? mednet_head_dice_ce_ws_bytes(n, spatial, cin, cout) : mednet_head_dice_ws_bytes(n, spatial, cin, cout);
+  MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "%s: workspace too small", what);
   const float* Pb = head_weights_f32(packed, cin, cout);
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = hl_fwd_blocks(spatial);
   float* partial = (float*)ws;
   const dim3 grid(nb, n);
-#define HF(TI_, K_, TL_) hipLaunchKernelGGL((head_dice_fwd_kernel<TI_, K_, TL_, CE>), grid, dim3(256), 0, s, (const TI_*)z, Pb, bias, (const TL_*)labels, label_stride_n, logits, partial, spatial, cout, sigmoid, ignore_index, CE ? weight : nullptr)
+#define HF(TI_, K_, TL_) hipLaunchKernelGGL((head_dice_fwd_kernel<TI_, K_, TL_, KIND>), grid, dim3(256), 0, s, (const TI_*)z, Pb, bias, (const TL_*)labels, label_stride_n, logits, partial, spatial, cout, sigmoid, ignore_index, KIND != HL_DICE ? weight : nullptr)
 #define HF_L(TI_, K_) do { if (label_dtype == MEDNET_U8) HF(TI_, K_, uint8_t); else HF(TI_, K_, int64_t); } while (0)
 #define HF_K(TI_) do { if (cin == 16) HF_L(TI_, 16); else if (cin == 32) HF_L(TI_, 32); else HF_L(TI_, 64); } while (0)
   if (z_dtype == MEDNET_F32) HF_K(float);
@@ -476,11 +583,14 @@ static int head_loss_fwd(const char* what, const void* z, const void* packed, co
   int rc = check_launch(what);
   if (rc) return rc;
   if (CE) return launch_ce_finalize(partial, loss, saved, (int)(nb * n), s);
+  if (KIND == HL_DICE_CE) {
+    return launch_dice_ce_finalize(partial, partial + (size_t)n * nb * cout * 2, weight, loss, saved, cout, (int)(nb * n), eps, s);
+  }
   hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, s, partial, weight, loss, saved, (float*)nullptr, cout, (int)(nb * n), eps);
   return check_launch("dice_finalize");
 }
 
-template <bool CE>
+template <int KIND>
 static int head_loss_bwd(const char* what, const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
                          const void* packed, const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y,
                          const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
@@ -489,14 +599,15 @@ static int head_loss_bwd(const char* what, const float* logits, const void* labe
                  "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
   MEDNET_REQUIRE(n > 0 && spatial > 0 && logits && labels && packed && saved && dloss && dz && z && dw, MEDNET_E_SHAPE, "%s: bad arguments", what);
   MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "%s: gn_y and gn_partial go together", what);
-  MEDNET_REQUIRE(ws_bytes >= mednet_head_dice_ws_bytes(n, spatial, cin, cout), MEDNET_E_WORKSPACE, "%s: workspace too small", what);
+  const size_t need = KIND == HL_DICE_CE ? mednet_head_dice_ce_ws_bytes(n, spatial, cin, cout) : mednet_head_dice_ws_bytes(n, spatial, cin, cout);
+  MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "%s: workspace too small", what);
   const float* Pb = head_weights_f32(packed, cin, cout);
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = hl_bwd_blocks(spatial, cin);
   float* wpart = (float*)ws;
   const dim3 grid(nb, n);
   const bool fold = gn_y == nullptr && gn_act != MEDNET_ACT_NONE;
-#define HB_(TO_, K_, TL_, F_) hipLaunchKernelGGL((head_dice_bwd_kernel<TO_, K_, TL_, F_, CE>), grid, dim3(256), 0, s, logits, (const TL_*)labels, label_stride_n, Pb, weight, saved, dloss, eps, sigmoid, ignore_index, (TO_*)dz, (const TO_*)gn_y, (const TO_*)z, gn_act, gn_partial, wpart, spatial, cout)
+#define HB_(TO_, K_, TL_, F_) hipLaunchKernelGGL((head_dice_bwd_kernel<TO_, K_, TL_, F_, KIND>), grid, dim3(256), 0, s, logits, (const TL_*)labels, label_stride_n, Pb, weight, saved, dloss, eps, sigmoid, ignore_index, (TO_*)dz, (const TO_*)gn_y, (const TO_*)z, gn_act, gn_partial, wpart, spatial, cout)
 #define HB(TO_, K_, TL_) do { if (fold) HB_(TO_, K_, TL_, true); else HB_(TO_, K_, TL_, false); } while (0)
 #define HB_L(TO_, K_) do { if (label_dtype == MEDNET_U8) HB(TO_, K_, uint8_t); else HB(TO_, K_, int64_t); } while (0)
 #define HB_K(TO_) do { if (cin == 16) HB_L(TO_, 16); else if (cin == 32) HB_L(TO_, 32); else HB_L(TO_, 64); } while (0)
@@ -520,7 +631,7 @@ extern "C" int mednet_head_dice_fwd(const void* z, const void* packed, const flo
                                     int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
                                     size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
                                     void* ws, size_t ws_bytes, mednet_stream stream) {
-  return head_loss_fwd<false>("head_dice_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
+  return head_loss_fwd<HL_DICE>("head_dice_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
                               cin, cout, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
@@ -529,7 +640,7 @@ extern "C" int mednet_head_dice_bwd(const float* logits, const void* labels, int
                                     const void* gn_y, const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n,
                                     size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
                                     void* ws, size_t ws_bytes, mednet_stream stream) {
-  return head_loss_bwd<false>("head_dice_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
+  return head_loss_bwd<HL_DICE>("head_dice_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
                               gn_partial, dw, dbias, n, spatial, cin, cout, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
@@ -546,7 +657,7 @@ extern "C" int mednet_head_ce_fwd(const void* z, const void* packed, const float
                                   int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
                                   size_t spatial, int cin, int cout, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
                                   mednet_stream stream) {
-  return head_loss_fwd<true>("head_ce_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
+  return head_loss_fwd<HL_CE>("head_ce_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
                              cin, cout, 0.f, 0, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
@@ -554,6 +665,35 @@ extern "C" int mednet_head_ce_bwd(const float* logits, const void* labels, int l
                                   const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
                                   int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
                                   int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
-  return head_loss_bwd<true>("head_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
+  return head_loss_bwd<HL_CE>("head_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
                              gn_partial, dw, dbias, n, spatial, cin, cout, 0.f, 0, ignore_index, z_dtype, ws, ws_bytes, stream);
+}
+
+// ---- the same head fused with DiceLoss + nn.CrossEntropyLoss, one class-weight vector: the Dice + CE instantiations ----------------
+// (softmax only, no ignore_index: the arguments are mednet_head_dice_*'s and must be 0 / MEDNET_NO_IGNORE)
+extern "C" int mednet_head_dice_ce_supported(int cin, int cout, int dtype, int label_dtype) {
+  return mednet_head_dice_supported(cin, cout, dtype, label_dtype);
+}
+extern "C" int mednet_head_dice_ce_gn_rows(int n, size_t spatial, int cin) { return mednet_head_dice_gn_rows(n, spatial, cin); }
+
+extern "C" int mednet_head_dice_ce_fwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                                       int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
+                                       size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
+                                       void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(sigmoid == 0 && ignore_index == MEDNET_NO_IGNORE, MEDNET_E_UNSUPPORTED,
+                 "head_dice_ce_fwd: Dice + cross-entropy is a softmax form without ignore_index");
+  return head_loss_fwd<HL_DICE_CE>("head_dice_ce_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n,
+                                   spatial, cin, cout, eps, 0, MEDNET_NO_IGNORE, z_dtype, ws, ws_bytes, stream);
+}
+
+extern "C" int mednet_head_dice_ce_bwd(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
+                                       const void* packed, const float* weight, const float* saved, const float* dloss, void* dz,
+                                       const void* gn_y, const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n,
+                                       size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
+                                       void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(sigmoid == 0 && ignore_index == MEDNET_NO_IGNORE, MEDNET_E_UNSUPPORTED,
+                 "head_dice_ce_bwd: Dice + cross-entropy is a softmax form without ignore_index");
+  return head_loss_bwd<HL_DICE_CE>("head_dice_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z,
+                                   gn_act, gn_partial, dw, dbias, n, spatial, cin, cout, eps, 0, MEDNET_NO_IGNORE, z_dtype, ws, ws_bytes,
+                                   stream);
 }

@@ -35,6 +35,8 @@ constexpr int HLM_MAXH = 16;       // heat maps (one MFMA k-block)
 constexpr int HLM_MAXC = 4;        // classes (second k-block, lanes 0..31)
 constexpr int HLM_WIDTH = 32 * 33; // per-workgroup partial of (dW [32 k'][32 ci], db [32 k']); k' = heat map c, or 16 + class
 constexpr int HLM_SCR = 33;        // floats per thread of the end-of-kernel LDS scratch
+// the class loss of an instantiation (= MEDNET_CLASS_*; the launches take it as `int ce`): DiceLoss, nn.CrossEntropyLoss, or their sum
+constexpr int HLM_DICE = 0, HLM_CE = 1, HLM_DICE_CE = 2;
 
 struct HlmArgs {
   const elt* z;          // [n][spatial][32]: head input (the last block's output)
@@ -52,7 +54,7 @@ struct HlmArgs {
   float* dice_partial;   // [n][chunk][ncls][2]              (dice_finalize_kernel's layout)
   float* logits;         // nullable: [n][nh + ncls][spatial] fp32
   // backward
-  const float* saved;    // [ncls][2] = {I, D} of the Dice forward
+  const float* saved;    // [ncls][2] = {I, D} of the Dice forward (CE: sum w_y; Dice + CE: [ncls][2], then sum w_y)
   const float* cls_weight;  // [ncls] nullable
   const float* reg_weight;  // [nh] nullable
   const float* dcls;     // upstream gradient of the class loss (scalar)
@@ -281,8 +283,13 @@ __device__ __forceinline__ void hlm_dw_db_writeout(const float* scr, int tid, fl
 // CE: the class term is nn.CrossEntropyLoss(weight, ignore_index) (landmarks.py:49) instead of Dice: the forward accumulates
 // ce_fwd_kernel's {sum w_y nll, sum w_y} and, for dice_metric (loss.py:51-55), the unweighted, unmasked softmax sums {I, D} into
 // dice_partial; the backward's class gradient is ce_bwd_kernel's closed form (dcls / sum w) w_y (p_k - [k == y]).  Softmax only.
-template <bool BWD, bool CE = false>
+// Dice + CE (HLM_DICE_CE, softmax, no ignore_index): the class term is the sum of the two.  Its forward IS the CE forward -- without a
+// mask the Dice sums are dice_metric's sums, the class weight enters in the finalize -- so only a backward is instantiated: the
+// sum of the two closed forms, with w_k dcls / sum w in the last four constants of the lane half.
+template <bool BWD, int KIND = HLM_DICE>
 __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
+  constexpr bool CE = KIND == HLM_CE;
+  static_assert(BWD || KIND != HLM_DICE_CE, "the Dice + CE forward is the CE forward");
   __shared__ __attribute__((aligned(16))) char smem[256 * HLM_SCR * 4];
   __shared__ float cst[2][32];
   __shared__ u32x4 wops[8][64];  // the 8 weight operands (below), one 16-byte fragment per lane: the same in every wave
@@ -325,6 +332,8 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
         const float w = a.cls_weight ? a.cls_weight[k] : 1.f, I = a.saved[2 * k], D = a.saved[2 * k + 1];
         v = i < 24 ? hlm_dice_gI(w, I, D, a.eps, a.ncls, *a.dcls) : hlm_dice_gD(w, I, D, a.eps, a.ncls, *a.dcls);
       }
+    } else if (BWD && KIND == HLM_DICE_CE && i - 28 < a.ncls) {  // [28..31]: ce_bwd_kernel's `w` per class
+      v = (a.cls_weight ? a.cls_weight[i - 28] : 1.f) * (*a.dcls / a.saved[2 * a.ncls]);
     }
     cst[hh][i] = v;
   }
@@ -485,6 +494,22 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
             dc[k] = (cls_lane && k < a.ncls) ? wy * (p[k] - (k == yl ? 1.f : 0.f)) : 0.f;
             dbc[k] += dc[k];
           }
+        } else if constexpr (KIND == HLM_DICE_CE) {
+          float gg[HLM_MAXC], dot = 0.f, wy = 0.f;
+#pragma unroll
+          for (int k = 0; k < HLM_MAXC; ++k) {
+            const float t = (k == yl) ? 1.f : 0.f;
+            gg[k] = k < a.ncls ? cbase[20 + k] * t + cbase[24 + k] : 0.f;
+            dot = fmaf(p[k], gg[k], dot);
+            if (k == yl) wy = cbase[28 + k];  // (0 for k >= ncls)
+          }
+#pragma unroll
+          for (int k = 0; k < HLM_MAXC; ++k) {
+            const float dl_dice = p[k] * (gg[k] - dot);
+            const float dl_ce = wy * (p[k] - (k == yl ? 1.f : 0.f));
+            dc[k] = (cls_lane && k < a.ncls) ? dl_dice + dl_ce : 0.f;
+            dbc[k] += dc[k];
+          }
         } else {
           float gg[HLM_MAXC], dot = 0.f;
 #pragma unroll
@@ -617,10 +642,14 @@ __device__ __forceinline__ float xor32_max(float v) {  // max(v(l), v(l ^ 32)) i
   return fmaxf(a, b);
 }
 
-template <bool BWD, bool CE>
+// Dice + CE (HLM_DICE_CE, softmax, no ignore_index): the forward keeps the Dice accumulators in registers and the CE sums in the idle
+// LDS slot; the backward adds the two closed forms, with w_k dloss / sum w in eight more constants of the lane half.
+template <bool BWD, int KIND>
 __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
+  constexpr bool CE = KIND == HLM_CE;
+  constexpr int NCST = (BWD && KIND == HLM_DICE_CE) ? 32 : 24;
   __shared__ __attribute__((aligned(16))) char smem[256 * HLM_SCR * 4];
-  __shared__ float cst[2][24];
+  __shared__ float cst[2][NCST];
   __shared__ u32x4 wops[6][64];  // 0,1: logits hi (k-steps); 2,3: lo; 4: dz hi; 5: dz lo
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -633,13 +662,16 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
   if (wv == 0) hlm_logit_operands(wops, a.W, (r.q < 2 && r.out() < a.ncls) ? r.out() : -1, lane);
   if (BWD && wv == 1) hlm_dz_operand(wops[4][lane], wops[5][lane], a.W, 8 * h, a.ncls - 8 * h, r.channel());
   // ---- constants of a lane half: the biases of its 8 classes [0..7]; CE forward: the class weights [8..15]; CE backward:
-  // w_k dloss / sum w [8..15]; Dice backward: gI [8..15], gD [16..23] (dice_bwd_kernel)
-  if (wv == 2 && (lane & 31) < 24) {
+  // w_k dloss / sum w [8..15]; Dice backward: gI [8..15], gD [16..23] (dice_bwd_kernel); Dice + CE: the forward as CE, the backward as
+  // Dice and w_k dloss / sum w [24..31]
+  if (wv == 2 && (lane & 31) < NCST) {
     const int hh = lane >> 5, i = lane & 31, k = 8 * hh + (i & 7);
     float v = 0.f;
     if (k < a.ncls) {
       const float w = a.cls_weight ? a.cls_weight[k] : 1.f;
       if (i < 8) v = a.bias ? a.bias[k] : 0.f;
+      else if (KIND == HLM_DICE_CE && !BWD) v = i < 16 ? w : 0.f;
+      else if (KIND == HLM_DICE_CE && i >= 24) v = w * (*a.dcls / a.saved[2 * a.ncls]);
       else if (CE) v = i < 16 ? (BWD ? w * (*a.dcls / a.saved[0]) : w) : 0.f;
       else if (BWD) {
         const float I = a.saved[2 * k], D = a.saved[2 * k + 1];
@@ -663,7 +695,7 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
 
   const HlmTiles tiles(smem, wv, lane);
   float* const ce_acc = reinterpret_cast<float*>(smem) + tid * HLM_SCR + 16;  // (the forward has no tiles: head_lm_kernel)
-  if constexpr (CE && !BWD) ce_acc[0] = ce_acc[1] = 0.f;
+  if constexpr (KIND != HLM_DICE && !BWD) ce_acc[0] = ce_acc[1] = 0.f;
   if constexpr (BWD) tiles.zero_dl(lane);  // (columns 16 .. 31 of the dl tiles are never written)
 
   const elt* zs = a.z + (size_t)n * a.spatial * 32;
@@ -718,10 +750,10 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
         const float inv = 1.f / den;
 #pragma unroll
         for (int e = 0; e < 8; ++e) p[e] *= inv;
-        if (CE) lse = mx + logf(den);
+        if (KIND != HLM_DICE) lse = mx + logf(den);
       }
       if constexpr (!BWD) {
-        if constexpr (CE) {
+        if constexpr (KIND != HLM_DICE) {
           // ce_fwd_kernel; the half that owns the label's class takes the voxel's term
           if (live && h == 0 && yl != a.ignore && yl >= a.ncls) ce_acc[0] = __builtin_nanf("");
           if (live && yl != a.ignore && yk >= 0 && yk < nv) {
@@ -735,7 +767,8 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
             ce_acc[0] = fmaf(w, lse - zy, ce_acc[0]);
             ce_acc[1] += w;
           }
-        } else {
+        }
+        if constexpr (!CE) {
           bad |= live && yl >= a.ncls;
 #pragma unroll
           for (int e = 0; e < 8; ++e)
@@ -758,6 +791,25 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             dc[e] = e < nv ? wy * (p[e] - (e == yk ? 1.f : 0.f)) : 0.f;
+            dbc[e] += dc[e];
+          }
+        } else if constexpr (KIND == HLM_DICE_CE) {
+          float gg[8], dot = 0.f, wy = 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float t = (e == yk) ? 1.f : 0.f;
+            gg[e] = e < nv ? cbase[8 + e] * t + cbase[16 + e] : 0.f;
+            dot = fmaf(p[e], gg[e], dot);
+            if (e == yk) wy = cbase[24 + e];  // (0 for classes >= ncls)
+          }
+          dot = xor32_sum(dot);
+          wy = xor32_sum(wy);  // (the other half's lane has 0)
+          wy = (live && yl < a.ncls) ? wy : 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float dl_dice = p[e] * (gg[e] - dot);
+            const float dl_ce = wy * (p[e] - (e == yk ? 1.f : 0.f));
+            dc[e] = (live && e < nv) ? dl_dice + dl_ce : 0.f;
             dbc[e] += dc[e];
           }
         } else {
@@ -797,13 +849,14 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
   float* mine = scr + tid * HLM_SCR;
   __syncthreads();
   if constexpr (!BWD) {
-    if constexpr (CE) {  // values 16 / 17 of every thread are its ce_acc
+    if constexpr (KIND != HLM_DICE) {  // values 16 / 17 of every thread are its ce_acc
       if (tid < 2) {
         float s = 0.f;
         for (int t = 0; t < 256; ++t) s += scr[t * HLM_SCR + 16 + tid];
         a.ce_partial[((size_t)n * a.chunks + chunk) * 2 + tid] = s;
       }
-    } else {
+    }
+    if constexpr (!CE) {
       if (bad) dI[0] = dD[0] = __builtin_nanf("");
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -877,6 +930,7 @@ static int hlm_bwd_args(HlmArgs& a, const char* what, const float* saved, const 
   return 0;
 }
 
+// ce = 2 (HLM_DICE_CE): the forward is the CE form's (the caller finalises both rows); the backward reads saved = [ncls][2], then sum w_y.
 // ce = 1: nn.CrossEntropyLoss(cls_weight, ignore) as the class term (softmax; `sigmoid` and `eps` are not read): ce_partial [n][chunk][2]
 // for ce_finalize, and dice_partial takes dice_metric's unweighted, unmasked sums; the backward reads saved[0] = sum w_y of that forward.
 int launch_head_lm_fwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
@@ -887,8 +941,8 @@ int launch_head_lm_fwd(const void* z, const float* W, const float* bias, const v
                           ce ? 0 : sigmoid, ignore);
   if (rc) return rc;
   a.hm_partial = hm_partial; a.dice_partial = dice_partial; a.logits = logits; a.ce_partial = ce ? ce_partial : nullptr;
-  if (ce) hipLaunchKernelGGL((head_lm_kernel<false, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((head_lm_kernel<false, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  if (ce) hipLaunchKernelGGL((head_lm_kernel<false, HLM_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_lm_kernel<false, HLM_DICE>), dim3(a.chunks, n), dim3(256), 0, s, a);
   return check_launch(ce ? "head_lm_ce_fwd" : "head_lm_fwd");
 }
 int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const void* tgt, int64_t tgt_sn, const void* lab,
@@ -899,13 +953,14 @@ int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const v
   HlmArgs a = {};
   int rc = hlm_args(a, "head_lm", z, W, bias, tgt, tgt_sn, lab, lab_sn, cls_weight, spatial, nh, ncls, kind, ce ? 0 : sigmoid, ignore);
   if (rc) return rc;
-  rc = hlm_bwd_args(a, "head_lm_bwd", saved, dcls, ce ? 0.f : eps, dz, gn_y, gn_act, gn_partial, ws, ws_bytes,
+  rc = hlm_bwd_args(a, "head_lm_bwd", saved, dcls, ce == HLM_CE ? 0.f : eps, dz, gn_y, gn_act, gn_partial, ws, ws_bytes,
                     head_lm_ws_bytes(n, spatial, nh, ncls));
   if (rc) return rc;
   a.reg_weight = reg_weight; a.dreg = dreg; a.inv_count = (float)(1.0 / ((double)n * (double)spatial));
-  if (ce) hipLaunchKernelGGL((head_lm_kernel<true, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((head_lm_kernel<true, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  rc = check_launch(ce ? "head_lm_ce_bwd" : "head_lm_bwd");
+  if (ce == HLM_DICE_CE) hipLaunchKernelGGL((head_lm_kernel<true, HLM_DICE_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else if (ce) hipLaunchKernelGGL((head_lm_kernel<true, HLM_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_lm_kernel<true, HLM_DICE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  rc = check_launch(ce == HLM_DICE_CE ? "head_lm_dice_ce_bwd" : ce ? "head_lm_ce_bwd" : "head_lm_bwd");
   if (rc) return rc;
   const int total = (nh + ncls) * 33;
   hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((total + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, nh, ncls, dw, db);
@@ -928,9 +983,14 @@ int launch_head_seg_fwd(const void* z, const float* W, const float* bias, const 
   const int rc = hlm_args(a, "head_seg_fwd", z, W, bias, nullptr, 0, lab, lab_sn, cls_weight, spatial, 0, ncls, 0, sigmoid, ignore);
   if (rc) return rc;
   a.logits = logits;
-  (ce ? a.ce_partial : a.dice_partial) = partial;
-  if (ce) hipLaunchKernelGGL((head_seg_kernel<false, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((head_seg_kernel<false, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  (ce == HLM_CE ? a.ce_partial : a.dice_partial) = partial;
+  if (ce == HLM_DICE_CE) {  // the Dice rows, behind all of them the CE rows
+    a.ce_partial = partial + (size_t)n * a.chunks * ncls * 2;
+    hipLaunchKernelGGL((head_seg_kernel<false, HLM_DICE_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+    return check_launch("head_seg_dice_ce_fwd");
+  }
+  if (ce) hipLaunchKernelGGL((head_seg_kernel<false, HLM_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_seg_kernel<false, HLM_DICE>), dim3(a.chunks, n), dim3(256), 0, s, a);
   return check_launch(ce ? "head_seg_ce_fwd" : "head_seg_fwd");
 }
 int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* saved,
@@ -942,9 +1002,10 @@ int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const 
   if (rc) return rc;
   rc = hlm_bwd_args(a, "head_seg_bwd", saved, dloss, eps, dz, gn_y, gn_act, gn_partial, ws, ws_bytes, head_seg_ws_bytes(n, spatial, ncls));
   if (rc) return rc;
-  if (ce) hipLaunchKernelGGL((head_seg_kernel<true, true>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((head_seg_kernel<true, false>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  rc = check_launch(ce ? "head_seg_ce_bwd" : "head_seg_bwd");
+  if (ce == HLM_DICE_CE) hipLaunchKernelGGL((head_seg_kernel<true, HLM_DICE_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else if (ce) hipLaunchKernelGGL((head_seg_kernel<true, HLM_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_seg_kernel<true, HLM_DICE>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  rc = check_launch(ce == HLM_DICE_CE ? "head_seg_dice_ce_bwd" : ce ? "head_seg_ce_bwd" : "head_seg_bwd");
   if (rc) return rc;
   hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((ncls * 33 + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, ncls, 0, dw, db);
   return check_launch("head_seg_wfinal");

@@ -99,13 +99,11 @@ __global__ __launch_bounds__(256) void dice_fwd_kernel(const float* __restrict__
     }
 }
 
-// single workgroup: fp64 fixed-order combine, then the scalar
-__global__ __launch_bounds__(256) void dice_finalize_kernel(const float* __restrict__ partial,
-                                                            const float* __restrict__ weight, float* __restrict__ loss,
-                                                            float* __restrict__ saved, float* __restrict__ dice_out,
-                                                            int c, int nblocks, float eps) {
-  __shared__ double sh[2][256];
-  __shared__ double dice_s[64];
+// single workgroup: fp64 fixed-order combine, then the scalar.  dice_combine: the combine of the Dice rows (on thread 0 -> mean(1 - dice)),
+// shared by dice_finalize_kernel and dice_ce_finalize_kernel; it ends on a barrier, so `sh` is free again when it returns
+__device__ __forceinline__ float dice_combine(const float* __restrict__ partial, const float* __restrict__ weight,
+                                              float* __restrict__ saved, float* __restrict__ dice_out, int c, int nblocks, float eps,
+                                              double (*sh)[256], double* dice_s) {
   for (int k = 0; k < c; ++k) {
     double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += 256) {
@@ -133,11 +131,21 @@ __global__ __launch_bounds__(256) void dice_finalize_kernel(const float* __restr
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0 && loss) {
-    float s = 0.f;
+  float s = 0.f;
+  if (threadIdx.x == 0) {
     for (int k = 0; k < c; ++k) s += (float)dice_s[k];
-    *loss = s / (float)c;
+    s = s / (float)c;
   }
+  return s;
+}
+__global__ __launch_bounds__(256) void dice_finalize_kernel(const float* __restrict__ partial,
+                                                            const float* __restrict__ weight, float* __restrict__ loss,
+                                                            float* __restrict__ saved, float* __restrict__ dice_out,
+                                                            int c, int nblocks, float eps) {
+  __shared__ double sh[2][256];
+  __shared__ double dice_s[64];
+  const float s = dice_combine(partial, weight, saved, dice_out, c, nblocks, eps, sh, dice_s);
+  if (threadIdx.x == 0 && loss) *loss = s;
 }
 
 template <int MAXC, typename TL>
@@ -229,9 +237,9 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
     o[1] = den;
   }
 }
-__global__ __launch_bounds__(256) void ce_finalize_kernel(const float* __restrict__ partial, float* __restrict__ loss,
-                                                          float* __restrict__ saved, int nblocks) {
-  __shared__ double sh[2][256];
+// the combine of the CE rows (on thread 0: saved_w[0] = sum w_y, -> sum w_y nll / sum w_y), shared like dice_combine
+__device__ __forceinline__ float ce_combine(const float* __restrict__ partial, float* __restrict__ saved_w, int nblocks,
+                                            double (*sh)[256]) {
   double a = 0.0, b = 0.0;
   for (int i = threadIdx.x; i < nblocks; i += 256) {
     a += (double)partial[2 * (size_t)i];
@@ -247,10 +255,15 @@ __global__ __launch_bounds__(256) void ce_finalize_kernel(const float* __restric
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    saved[0] = (float)sh[1][0];
-    *loss = (float)(sh[0][0] / sh[1][0]);
-  }
+  if (threadIdx.x != 0) return 0.f;
+  saved_w[0] = (float)sh[1][0];
+  return (float)(sh[0][0] / sh[1][0]);
+}
+__global__ __launch_bounds__(256) void ce_finalize_kernel(const float* __restrict__ partial, float* __restrict__ loss,
+                                                          float* __restrict__ saved, int nblocks) {
+  __shared__ double sh[2][256];
+  const float s = ce_combine(partial, saved, nblocks, sh);
+  if (threadIdx.x == 0) *loss = s;
 }
 template <int MAXC>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ lg, const int64_t* __restrict__ lab,
@@ -272,6 +285,141 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
 #pragma unroll
       for (int k = 0; k < MAXC; ++k)
         if (k < c) dlg[(size_t)n * sn + (size_t)k * sc + v] = w * (p[k] - (k == y ? 1.f : 0.f));
+    }
+  }
+}
+
+// ---- Dice + cross-entropy, one pass each way (softmax only, no ignore_index): DiceLoss(weight, eps)(x, y) + nn.CrossEntropyLoss(weight)(x, y)
+// The softmax of a voxel is computed once: probs_of's numerators are ce_fwd_kernel's expf(lg - mx) terms and its `den` is that kernel's `s`
+// (same terms, same order).  Every accumulation is the one of dice_fwd_kernel / ce_fwd_kernel without the ignore mask (a factor of 1.f
+// there), so the partial rows, and after the shared combines the two terms, are those kernels' bit for bit.
+// partial = Dice rows [n][block][c][2], then CE rows [n][block][2]
+template <int MAXC, typename TL>
+__global__ __launch_bounds__(256) void dice_ce_fwd_kernel(const float* __restrict__ lg, const TL* __restrict__ lab, int64_t lab_sn,
+                                                          const float* __restrict__ weight, float* __restrict__ partial,
+                                                          float* __restrict__ partial_ce, int c, size_t spatial, int64_t sn,
+                                                          int64_t sc) {
+  __shared__ float scratch[4];
+  const int n = blockIdx.y;
+  float I[MAXC], D[MAXC];
+  float num = 0.f, wsum = 0.f;
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k) I[k] = D[k] = 0.f;
+  const size_t v0 = (size_t)blockIdx.x * LOSS_BLOCK_VOX;
+  for (int it = 0; it < 8; ++it) {
+    const size_t v = v0 + (size_t)it * 256 + threadIdx.x;
+    if (v < spatial) {
+      const size_t base = (size_t)n * sn + v;
+      const int y = class_of(lab[(size_t)n * lab_sn + v], c);
+      float p[MAXC];
+      float mx = -INFINITY, zy = 0.f;
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k)
+        if (k < c) {
+          p[k] = lg[base + (size_t)k * sc];
+          mx = fmaxf(mx, p[k]);
+          if (k == y) zy = p[k];
+        }
+      float den = 0.f;
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k)
+        if (k < c) {
+          p[k] = expf(p[k] - mx);
+          den += p[k];
+        }
+      const float inv = 1.f / den;
+      bad |= y < 0;  // (a label outside [0, C): both terms become NaN, as in dice_fwd_kernel / ce_fwd_kernel)
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k)
+        if (k < c) {
+          p[k] *= inv;
+          const float t = (k == y) ? 1.f : 0.f;
+          I[k] = fmaf(p[k], t, I[k]);
+          D[k] += p[k] + t;
+        }
+      if (y >= 0) {
+        const float w = weight ? weight[y] : 1.f;
+        num = fmaf(w, (mx + logf(den)) - zy, num);
+        wsum += w;
+      }
+    }
+  }
+  if (bad) I[0] = D[0] = num = __builtin_nanf("");
+  const size_t row = (size_t)n * gridDim.x + blockIdx.x;
+  float* out = partial + row * c * 2;
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k)
+    if (k < c) {
+      const float a = block_sum<4>(I[k], scratch);
+      const float b = block_sum<4>(D[k], scratch);
+      if (threadIdx.x == 0) {
+        out[2 * k] = a;
+        out[2 * k + 1] = b;
+      }
+    }
+  num = block_sum<4>(num, scratch);
+  wsum = block_sum<4>(wsum, scratch);
+  if (threadIdx.x == 0) {
+    partial_ce[2 * row] = num;
+    partial_ce[2 * row + 1] = wsum;
+  }
+}
+// saved = [c][2] {I, D}, then sum w_y;  loss = fl(dice + ce), one rounded fp32 add of the two finalised terms
+__global__ __launch_bounds__(256) void dice_ce_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ partial_ce,
+                                                               const float* __restrict__ weight, float* __restrict__ loss,
+                                                               float* __restrict__ saved, float* __restrict__ dice_out, int c,
+                                                               int nblocks, float eps) {
+  __shared__ double sh[2][256];
+  __shared__ double dice_s[64];
+  const float dice = dice_combine(partial, weight, saved, dice_out, c, nblocks, eps, sh, dice_s);
+  const float ce = ce_combine(partial_ce, saved + 2 * c, nblocks, sh);
+  if (threadIdx.x == 0) *loss = dice + ce;
+}
+// One store per logit: dice_bwd_kernel's closed form plus ce_bwd_kernel's.  The two terms are formed in statements of their own and
+// added by a plain add: inside one expression -ffp-contract=on would fuse w * (p - t) into the add, and the sum would no longer be
+// the fp32 add of the two kernels' results that autograd makes of them.
+template <int MAXC, typename TL>
+__global__ __launch_bounds__(256) void dice_ce_bwd_kernel(const float* __restrict__ lg, const TL* __restrict__ lab, int64_t lab_sn,
+                                                          const float* __restrict__ weight, const float* __restrict__ saved,
+                                                          const float* __restrict__ dloss, float* __restrict__ dlg, int c,
+                                                          size_t spatial, int64_t sn, int64_t sc, float eps) {
+  const int n = blockIdx.y;
+  const float go = *dloss;
+  const float scale = go / saved[2 * c];
+  float gI[MAXC], gD[MAXC];
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k)
+    if (k < c) {
+      const float w = weight ? weight[k] : 1.f;
+      const float I = saved[2 * k], D = saved[2 * k + 1];
+      const float Dc = fmaxf(D, eps);
+      gI[k] = -2.f * w / ((float)c * Dc) * go + ((I != I || D != D) ? __builtin_nanf("") : 0.f);
+      gD[k] = (D >= eps ? 2.f * w * I / ((float)c * Dc * Dc) : 0.f) * go;
+    }
+  const size_t v0 = (size_t)blockIdx.x * LOSS_BLOCK_VOX;
+  for (int it = 0; it < 8; ++it) {
+    const size_t v = v0 + (size_t)it * 256 + threadIdx.x;
+    if (v < spatial) {
+      float p[MAXC], g[MAXC];
+      probs_of<MAXC>(lg, (size_t)n * sn + v, sc, c, 0, p);
+      const int y = class_of(lab[(size_t)n * lab_sn + v], c);
+      const float wce = y >= 0 ? (weight ? weight[y] : 1.f) * scale : 0.f;
+      float dot = 0.f;
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k)
+        if (k < c) {
+          const float t = (k == y) ? 1.f : 0.f;
+          g[k] = gI[k] * t + gD[k];  // (gI * t is exact: fused or not, this is dice_bwd_kernel's g with mask 1)
+          dot = fmaf(p[k], g[k], dot);
+        }
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k)
+        if (k < c) {
+          const float dl_dice = p[k] * (g[k] - dot);
+          const float dl_ce = wce * (p[k] - (k == y ? 1.f : 0.f));
+          dlg[(size_t)n * sn + (size_t)k * sc + v] = dl_dice + dl_ce;
+        }
     }
   }
 }
@@ -362,6 +510,12 @@ int launch_dice_finalize(const float* partial, const float* weight, float* loss,
 int launch_ce_finalize(const float* partial, float* loss, float* saved, int nblocks, hipStream_t s) {
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, loss, saved, nblocks);
   return check_launch("ce_finalize");
+}
+// (for the fused Dice + CE heads: Dice rows in dice_fwd_kernel's layout, CE rows in ce_fwd_kernel's)
+int launch_dice_ce_finalize(const float* partial, const float* partial_ce, const float* weight, float* loss, float* saved, int c,
+                            int nblocks, float eps, hipStream_t s, float* dice_out) {
+  hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, partial_ce, weight, loss, saved, dice_out, c, nblocks, eps);
+  return check_launch("dice_ce_finalize");
 }
 
 }  // namespace mednet
@@ -473,6 +627,55 @@ extern "C" int mednet_ce_bwd(const float* logits, const int64_t* labels, const f
 #undef CALL
   return check_launch("ce_bwd");
 }
+
+// ---- Dice + CE in one pass each way: labels as mednet_dice_*_lt takes them, softmax only, no ignore_index --------------------------
+extern "C" size_t mednet_dice_ce_ws_bytes(int n, int c, size_t spatial) {
+  return ((size_t)n * loss_blocks(spatial) * ((size_t)c * 2 + 2) + 64) * sizeof(float);
+}
+
+#define DICE_CE_LAUNCH(KERNEL, M, ...)                                                                                              \
+  do {                                                                                                                              \
+    if (label_dtype == MEDNET_U8)                                                                                                   \
+      hipLaunchKernelGGL((KERNEL<M, uint8_t>), dim3(nb, n), dim3(256), 0, s, logits, (const uint8_t*)labels, label_stride_n, __VA_ARGS__); \
+    else                                                                                                                            \
+      hipLaunchKernelGGL((KERNEL<M, int64_t>), dim3(nb, n), dim3(256), 0, s, logits, (const int64_t*)labels, label_stride_n, __VA_ARGS__); \
+  } while (0)
+
+extern "C" int mednet_dice_ce_fwd_lt(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const float* weight,
+                                     float* loss, float* saved, float* dice_out, int n, int c, size_t spatial, int64_t stride_n,
+                                     int64_t stride_c, float eps, void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(logits && labels && loss && saved && ws, MEDNET_E_SHAPE, "dice_ce_fwd: bad arguments");
+  MEDNET_REQUIRE(n > 0 && n <= 65535 && spatial > 0, MEDNET_E_SHAPE, "dice_ce_fwd: empty input");
+  MEDNET_REQUIRE(c >= 1 && c <= 32, MEDNET_E_UNSUPPORTED, "dice_ce_fwd: C=%d (supported: 1..32)", c);
+  MEDNET_REQUIRE(label_dtype == MEDNET_I64 || label_dtype == MEDNET_U8, MEDNET_E_DTYPE, "dice_ce_fwd: labels are int64 or uint8 (got %d)", label_dtype);
+  MEDNET_REQUIRE(ws_bytes >= mednet_dice_ce_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "dice_ce_fwd: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nb = loss_blocks(spatial);
+  float* partial = (float*)ws;
+  float* partial_ce = partial + (size_t)n * nb * c * 2;
+#define CALL(M) DICE_CE_LAUNCH(dice_ce_fwd_kernel, M, weight, partial, partial_ce, c, spatial, stride_n, stride_c)
+  LOSS_DISPATCH_C(c, CALL);
+#undef CALL
+  int rc = check_launch("dice_ce_fwd");
+  if (rc) return rc;
+  return launch_dice_ce_finalize(partial, partial_ce, weight, loss, saved, c, (int)(nb * n), eps, s, dice_out);
+}
+
+extern "C" int mednet_dice_ce_bwd_lt(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const float* weight,
+                                     const float* saved, const float* dloss, float* dlogits, int n, int c, size_t spatial,
+                                     int64_t stride_n, int64_t stride_c, float eps, mednet_stream stream) {
+  MEDNET_REQUIRE(logits && labels && saved && dloss && dlogits, MEDNET_E_SHAPE, "dice_ce_bwd: bad arguments");
+  MEDNET_REQUIRE(n > 0 && n <= 65535 && spatial > 0, MEDNET_E_SHAPE, "dice_ce_bwd: empty input");
+  MEDNET_REQUIRE(c >= 1 && c <= 32, MEDNET_E_UNSUPPORTED, "dice_ce_bwd: C=%d (supported: 1..32)", c);
+  MEDNET_REQUIRE(label_dtype == MEDNET_I64 || label_dtype == MEDNET_U8, MEDNET_E_DTYPE, "dice_ce_bwd: labels are int64 or uint8 (got %d)", label_dtype);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nb = loss_blocks(spatial);
+#define CALL(M) DICE_CE_LAUNCH(dice_ce_bwd_kernel, M, weight, saved, dloss, dlogits, c, spatial, stride_n, stride_c, eps)
+  LOSS_DISPATCH_C(c, CALL);
+#undef CALL
+  return check_launch("dice_ce_bwd");
+}
+#undef DICE_CE_LAUNCH
 
 // target_stride_n: element stride between the samples of `target` (channel ch of sample n at + n * target_stride_n + ch * spatial):
 // the heat-map channels of a label volume are consumed where they lie, no .contiguous() copy (landmarks.py:68)

@@ -24,7 +24,7 @@ ALGO_SPLITW_BIT = 8  # OR-ed onto any choice: 16-bit modes multiply the LOW weig
 PACK_LOW = 0x100     # OR-ed onto the element type of a pack call: an fp16 pack with the low images
 PACK_HIGH_ONLY = 0x200  # mednet_conv3d_pack_many: only the images the 16-bit matrix-core kernels read (see mednet_hip.h)
 REG_L2, REG_L1 = 0, 1
-CLASS_DICE, CLASS_CE = 0, 1
+CLASS_DICE, CLASS_CE, CLASS_DICE_CE = 0, 1, 2
 PAD_CONSTANT, PAD_SYMMETRIC = 0, 1
 MIP_MEAN, MIP_MAX = 0, 1
 F16, U8, I64 = 2, 3, 4  # F16: fp16 storage / resident volumes; U8, I64: label types
@@ -130,8 +130,16 @@ SIGNATURES = {
     "mednet_head_dice_gn_rows": (_i, [_i, _sz, _i]),
     "mednet_head_dice_fwd": (_i, [_vp] * 4 + [_i, _i64, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
     "mednet_head_dice_bwd": (_i, [_vp, _vp, _i, _i64] + [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_head_dice_ce_supported": (_i, [_i] * 4),
+    "mednet_head_dice_ce_ws_bytes": (_sz, [_i, _sz, _i, _i]),
+    "mednet_head_dice_ce_gn_rows": (_i, [_i, _sz, _i]),
+    "mednet_head_dice_ce_fwd": (_i, [_vp] * 4 + [_i, _i64, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_head_dice_ce_bwd": (_i, [_vp, _vp, _i, _i64] + [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
     "mednet_dice_fwd_lt": (_i, [_vp, _vp, _i, _i64] + [_vp] * 4 + [_i, _i, _sz, _i64, _i64, _f, _i, _i, _vp, _sz, _vp]),
     "mednet_dice_bwd_lt": (_i, [_vp, _vp, _i, _i64] + [_vp] * 4 + [_i, _i, _sz, _i64, _i64, _f, _i, _i, _vp]),
+    "mednet_dice_ce_ws_bytes": (_sz, [_i, _i, _sz]),
+    "mednet_dice_ce_fwd_lt": (_i, [_vp, _vp, _i, _i64] + [_vp] * 4 + [_i, _i, _sz, _i64, _i64, _f, _vp, _sz, _vp]),
+    "mednet_dice_ce_bwd_lt": (_i, [_vp, _vp, _i, _i64] + [_vp] * 4 + [_i, _i, _sz, _i64, _i64, _f, _vp]),
     "mednet_heatmap_loss_fwd_strided": (_i, [_vp, _vp, _i64, _vp, _vp] + [_i, _i, _sz, _i64, _i64, _i, _i, _vp, _sz, _vp]),
     "mednet_heatmap_loss_bwd_strided": (_i, [_vp, _vp, _i64, _vp, _vp, _vp] + [_i, _i, _sz, _i64, _i64, _i, _i, _vp]),
     "mednet_ce_fwd": (_i, [_vp] * 5 + [_i, _i, _sz, _i64, _i64, _i, _vp, _sz, _vp]),

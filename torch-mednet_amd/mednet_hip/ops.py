@@ -1277,7 +1277,7 @@ def head_dice_supported(x: torch.Tensor, cin: int, cout: int, labels: torch.Tens
 
 
 def _valu_head_fwd(ctx, name, x, weight, bias, packed, labels, loss_weight, saved_shape, scalars):
-    """Forward of HeadDiceFn / HeadCEFn: mednet_<name>_fwd, whose arguments differ in `scalars` (between cout and the dtype) only."""
+    """Forward of HeadDiceFn / HeadCEFn / HeadDiceCEFn: mednet_<name>_fwd, whose arguments differ in `scalars` (between cout and the dtype) only."""
     L.require_gpu(x, name)
     n, cin, d, h, w = x.shape
     cout = weight.shape[0]
@@ -1368,6 +1368,30 @@ def head_ce(x, weight, bias, packed, labels, loss_weight=None, ignore_index=-100
     return HeadCEFn.apply(x, weight, bias, packed, labels, loss_weight, ignore_index)
 
 
+def head_dice_ce_supported(x: torch.Tensor, cin: int, cout: int, labels: torch.Tensor) -> bool:
+    return _head_supported(x, labels, mfma=False) and bool(L.lib().mednet_head_dice_ce_supported(cin, cout, L.dt(x), _label_dt(labels)))
+
+
+class HeadDiceCEFn(Function):
+    """logits = final_conv(x) and loss = DiceLoss(weight, eps)(logits, labels) + nn.CrossEntropyLoss(weight)(logits, labels) as ONE
+    autograd node -- HeadDiceFn with the sum of the two closed forms (mednet_head_dice_ce_fwd / _bwd): one softmax per voxel each way,
+    no logit-gradient tensor.  Softmax only, no ignore_index.  Returns (logits, loss); the logits are not a differentiable output."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, packed, labels, loss_weight, eps):
+        return _valu_head_fwd(ctx, "head_dice_ce", x, weight, bias, packed, labels, loss_weight, (2 * weight.shape[0] + 1,),
+                              (eps, 0, L.NO_IGNORE))
+
+    @staticmethod
+    def backward(ctx, _dlogits, dloss):
+        return _valu_head_bwd(ctx, "head_dice_ce", dloss, 7)
+
+
+def head_dice_ce(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5):
+    """-> (logits N x C x D x H x W fp32, Dice + cross-entropy loss)."""
+    return HeadDiceCEFn.apply(x, weight, bias, packed, labels, loss_weight, eps)
+
+
 def head_seg_supported(x: torch.Tensor, cin: int, ncls: int, labels: torch.Tensor) -> bool:
     """Does the matrix-core segmentation head (5 .. 16 classes, 16-bit storage, uint8 labels) take this head?"""
     return _head_supported(x, labels, mfma=True) and bool(L.lib().mednet_head_seg_supported(cin, ncls, L.dt(x), L.U8, x[0, 0].numel()))
@@ -1391,10 +1415,10 @@ class HeadSegFn(Function):
             raise RuntimeError(f"head_seg: labels must be uint8, not {labels.dtype} (see head_seg_supported)")
         lab, lab_sn = _aligned4(*_label_view(labels, n, (d, h, w))[:2])
         wt = _loss_weight(loss_weight, x.device)
-        ii = (L.NO_IGNORE if class_kind == L.CLASS_DICE else -100) if ignore_index is None else int(ignore_index)
+        nsaved, ii = _class_operands(class_kind, ncls, sigmoid, ignore_index, "head_seg")
         logits = torch.empty((n, ncls, d, h, w), dtype=torch.float32, device=x.device) if want_logits else None
         loss = torch.empty((), dtype=torch.float32, device=x.device)
-        saved = torch.empty((ncls, 2), dtype=torch.float32, device=x.device)
+        saved = torch.empty((ncls, 2) if nsaved == 2 * ncls else (nsaved,), dtype=torch.float32, device=x.device)
         lib = L.lib()
         ws = L.workspace(lib.mednet_head_seg_ws_bytes(n, spatial, ncls), x.device)
         L.check(lib.mednet_head_seg_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_sn, L.ptr(wt), L.ptr(logits),
@@ -1429,7 +1453,8 @@ class HeadSegFn(Function):
 def head_seg(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5, sigmoid=False, ignore_index=None, class_loss="DICE",
              want_logits=False):
     """-> (logits N x C x D x H x W fp32 or None, loss) of SegmentationNet's loss on final_conv(x), 5 <= C <= 16; class_loss "DICE"
-    (DiceLoss) or "CE" (nn.CrossEntropyLoss: softmax, `ignore_index` as that module's, -100 by default there)."""
+    (DiceLoss), "CE" (nn.CrossEntropyLoss: softmax, `ignore_index` as that module's, -100 by default there) or "DICE_CE" (their sum
+    with one class-weight vector: softmax, no ignore_index)."""
     return HeadSegFn.apply(x, weight, bias, packed, labels, loss_weight, eps, sigmoid, ignore_index, _class_kind(class_loss),
                            want_logits)
 
@@ -1489,8 +1514,9 @@ class HeadLandmarkFn(Function):
 
 def head_landmark(x, weight, bias, packed, heatmaps, labels, class_weight=None, reg_weight=None, kind="L2", eps=1e-5, sigmoid=False,
                   ignore_index=None, class_loss="DICE"):
-    """-> (class_loss, regression_loss) of LandmarkNet.loss on final_conv(x); class_loss "DICE" (DiceLoss) or "CE"
-    (nn.CrossEntropyLoss: softmax, `ignore_index` as that module's, -100 by default there)."""
+    """-> (class_loss, regression_loss) of LandmarkNet.loss on final_conv(x); class_loss "DICE" (DiceLoss), "CE"
+    (nn.CrossEntropyLoss: softmax, `ignore_index` as that module's, -100 by default there) or "DICE_CE" (their sum with one
+    class-weight vector: softmax, no ignore_index)."""
     return HeadLandmarkFn.apply(x, weight, bias, packed, heatmaps, labels, class_weight, reg_weight,
                                 L.REG_L2 if kind == "L2" else L.REG_L1, eps, sigmoid, ignore_index, _class_kind(class_loss))
 
@@ -1509,9 +1535,21 @@ def head_landmark_eval(x, weight, bias, packed, heatmaps, labels, class_weight=N
 
 
 def _class_kind(class_loss):
-    if class_loss not in ("DICE", "CE"):
-        raise ValueError(f"class_loss must be 'DICE' or 'CE', not {class_loss!r}")
-    return L.CLASS_DICE if class_loss == "DICE" else L.CLASS_CE
+    if class_loss not in ("DICE", "CE", "DICE_CE"):
+        raise ValueError(f"class_loss must be 'DICE', 'CE' or 'DICE_CE', not {class_loss!r}")
+    return {"DICE": L.CLASS_DICE, "CE": L.CLASS_CE, "DICE_CE": L.CLASS_DICE_CE}[class_loss]
+
+
+def _class_operands(class_kind, ncls, sigmoid, ignore_index, who):
+    """-> (floats of `saved`, ignore_index as the C entries take it) for a class-loss kind.  "DICE_CE" is a softmax form without
+    ignore_index."""
+    if class_kind == L.CLASS_DICE_CE:
+        if sigmoid or ignore_index is not None:
+            raise ValueError(f"{who}: class_loss 'DICE_CE' is a softmax form without ignore_index")
+        return 2 * ncls + 1, L.NO_IGNORE
+    if ignore_index is None:
+        return 2 * ncls, (L.NO_IGNORE if class_kind == L.CLASS_DICE else -100)
+    return 2 * ncls, int(ignore_index)
 
 
 def _landmark_operands(x, heatmaps, labels, class_weight, reg_weight, ignore_index):
@@ -1527,7 +1565,8 @@ def _landmark_fwd(x, packed, bias, hm, hm_sn, lab, lab_sn, cw, rw, nh, ncls, kin
     spatial = x[0, 0].numel()
     closs = torch.empty((), dtype=torch.float32, device=x.device)
     rloss = torch.empty((), dtype=torch.float32, device=x.device)
-    saved = torch.empty((ncls, 2), dtype=torch.float32, device=x.device)
+    # (Dice + CE: [ncls][2] = {I, D}, then sum w_y)
+    saved = torch.empty((2 * ncls + 1,) if class_kind == L.CLASS_DICE_CE else (ncls, 2), dtype=torch.float32, device=x.device)
     dice = torch.empty((ncls,), dtype=torch.float32, device=x.device) if metric else None
     lib = L.lib()
     ws = L.workspace(lib.mednet_head_landmark_ws_bytes(n, spatial, nh, ncls), x.device)
@@ -1593,6 +1632,52 @@ class CrossEntropyFn(Function):
 
 def cross_entropy(logits, labels, weight=None, ignore_index=-100):
     return CrossEntropyFn.apply(logits, labels, weight, ignore_index)
+
+
+class DiceCELossFn(Function):
+    """DiceLoss(weight, eps)(logits, labels) + nn.CrossEntropyLoss(weight)(logits, labels) (softmax, no ignore_index) as ONE node: one
+    pass over the logits each way, one softmax per voxel, one logit-gradient tensor (mednet_dice_ce_fwd_lt / _bwd_lt).  Loss and
+    gradient are bit for bit those of dice_loss(...) + cross_entropy(...) on the same tensors; uint8 labels are consumed where they lie."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, eps):
+        L.require_gpu(logits, "dice_ce_loss")
+        lg, sn, sc = _planar_logits(logits)
+        n, c = lg.shape[:2]
+        spatial = lg[0, 0].numel()
+        lab, lab_sn, lab_dt = _label_view(labels, n, tuple(lg.shape[2:]))
+        wt = None if weight is None else weight.to(device=lg.device, dtype=torch.float32).contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=lg.device)
+        saved = torch.empty((2 * c + 1,), dtype=torch.float32, device=lg.device)  # [c][2] = {I, D}, then sum w_y
+        lib = L.lib()
+        ws = L.workspace(lib.mednet_dice_ce_ws_bytes(n, c, spatial), lg.device)
+        L.check(lib.mednet_dice_ce_fwd_lt(lg.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt), loss.data_ptr(), saved.data_ptr(),
+                                          None, n, c, spatial, sn, sc, eps, ws.data_ptr(), ws.numel(), L.stream()), "dice_ce_fwd")
+        ctx.save_for_backward(lg, lab, wt, saved)
+        ctx.meta = (eps, sn, sc, logits.dtype, lab_sn, lab_dt)
+        ctx.split = getattr(logits, "_mednet_split", None) if lg is logits else None
+        if debug.TRACE is not None:
+            debug.trace("dice_ce.fwd", lg, loss, saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lg, lab, wt, saved = ctx.saved_tensors
+        eps, sn, sc, in_dtype, lab_sn, lab_dt = ctx.meta
+        n, c = lg.shape[:2]
+        spatial = lg[0, 0].numel()
+        dl = dloss.to(torch.float32).contiguous()
+        dlogits = _loss_grad_like(lg, ctx.split)
+        L.check(L.lib().mednet_dice_ce_bwd_lt(lg.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt), saved.data_ptr(), dl.data_ptr(),
+                                              dlogits.data_ptr(), n, c, spatial, sn, sc, eps, L.stream()), "dice_ce_bwd")
+        if debug.TRACE is not None:
+            debug.trace("dice_ce.bwd", dlogits)
+        return dlogits.to(in_dtype), None, None, None
+
+
+def dice_ce_loss(logits, labels, weight=None, eps=1e-5):
+    """DiceLoss(weight=weight, epsilon=eps)(logits, labels) + nn.CrossEntropyLoss(weight)(logits, labels), softmax, unit coefficients."""
+    return DiceCELossFn.apply(logits, labels, weight, eps)
 
 
 class HeatmapLossFn(Function):

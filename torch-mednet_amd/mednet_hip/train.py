@@ -395,6 +395,14 @@ def _call_is_hooked(model, final_conv) -> bool:
     return any(bool(getattr(mod, attr, None)) for mod in (model, final_conv) for attr in ("_forward_hooks", "_forward_pre_hooks"))
 
 
+def _class_criterion(loss, w):
+    """The class criterion of a step: "DICE" -> DiceLoss, "DICE_CE" -> DiceCELoss (Dice + cross-entropy, one class-weight vector),
+    anything else the nn.CrossEntropyLoss(weight) of segmentation.py:49 / landmarks.py:49."""
+    if loss == "DICE_CE":
+        return HL.DiceCELoss(weight=w)
+    return HL.DiceLoss(weight=w) if loss == "DICE" else HL.CrossEntropyLoss(weight=w)
+
+
 class SegmentationStep(_GraphedStep):
     """One data-parallel training step of SegmentationNet (segmentation.py:58-65) on the MI355X path."""
 
@@ -402,7 +410,7 @@ class SegmentationStep(_GraphedStep):
         self.model = model
         dev = next(model.parameters()).device
         w = None if loss_weight is None else torch.tensor(loss_weight, dtype=torch.float32, device=dev)
-        self.loss = (HL.DiceLoss(weight=w) if loss == "DICE" else HL.CrossEntropyLoss(weight=w)).to(dev)
+        self.loss = _class_criterion(loss, w).to(dev)
         self.flat = FlatParams(model)
         self.opt = FlatAdam(self.flat, lr=lr)
         self.repack = BatchedRepack(model)
@@ -414,18 +422,28 @@ class SegmentationStep(_GraphedStep):
 
     def _head_loss(self, inputs, label_u8):
         """`outputs = self(inputs); loss = self.loss(outputs, labels)` (segmentation.py:61-62).  When the model is this package's
-        U-Net with a 1x1x1 head of at most 4 classes and the loss is DiceLoss or CrossEntropyLoss, the head and the loss run as one
-        fused node (ops.head_dice / ops.head_ce: logits written once, no logit-gradient tensor, the label volume's uint8 channel
-        consumed where it lies); with 5 to 16 classes on a 32-feature head in a 16-bit storage mode they run as the matrix-core node
+        U-Net with a 1x1x1 head of at most 4 classes and the loss is DiceLoss, CrossEntropyLoss or DiceCELoss, the head and the loss run
+        as one fused node (ops.head_dice / ops.head_ce / ops.head_dice_ce: logits written once, no logit-gradient tensor, the label
+        volume's uint8 channel consumed where it lies); with 5 to 16 classes on a 32-feature head in a 16-bit storage mode they run as the matrix-core node
         ops.head_seg, which writes no logit tensor at all: `outputs` is None in that form (as LandmarkStep has no outputs tensor).
         Anything else takes the two calls as they stand."""
         from .unet.model import _UNetCore
         m, fc = self.model, getattr(self.model, "final_conv", None)
         dice = isinstance(self.loss, HL.DiceLoss)
-        if (isinstance(m, _UNetCore) and not m.testing and (isinstance(self.loss, HL.CrossEntropyLoss) or (dice and not self.loss.skip_last_target))
+        compound = isinstance(self.loss, HL.DiceCELoss)  # (Dice + CE: the same three forms, its one-pass loss in the two-node form)
+        if (isinstance(m, _UNetCore) and not m.testing
+                and (isinstance(self.loss, HL.CrossEntropyLoss) or compound or (dice and not self.loss.skip_last_target))
                 and fc is not None and getattr(fc, "planar_output", False) and fc.kernel_size[0] == 1 and inputs.is_cuda
                 and not _call_is_hooked(m, fc)):
             feats = m.forward_features(inputs)
+            if compound:
+                if ops.head_dice_ce_supported(feats, fc.in_channels, fc.out_channels, label_u8):
+                    return ops.head_dice_ce(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon)
+                if ops.head_seg_supported(feats, fc.in_channels, fc.out_channels, label_u8):
+                    return ops.head_seg(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon,
+                                        class_loss="DICE_CE")
+                outputs = fc(feats)
+                return outputs, self.loss(outputs, label_u8)  # (uint8 labels consumed where they lie)
             if dice and ops.head_dice_supported(feats, fc.in_channels, fc.out_channels, label_u8):
                 return ops.head_dice(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon,
                                      self.loss.sigmoid_normalization, self.loss.ignore_index)
@@ -440,7 +458,7 @@ class SegmentationStep(_GraphedStep):
             outputs = fc(feats)
         else:
             outputs = m(inputs)
-        return outputs, self.loss(outputs, label_u8.long())
+        return outputs, self.loss(outputs, label_u8 if compound else label_u8.long())
 
     def _fwd_bwd(self, batch):
         inputs = batch["data"].float()
@@ -476,7 +494,7 @@ class SegmentationValidation:
         self.model = model
         dev = next(model.parameters()).device
         w = None if loss_weight is None else torch.tensor(loss_weight, dtype=torch.float32, device=dev)
-        self.loss = (HL.DiceLoss(weight=w) if loss == "DICE" else HL.CrossEntropyLoss(weight=w)).to(dev)
+        self.loss = _class_criterion(loss, w).to(dev)
         self.log_interval, self.log_vis_mip, self.on_samples = log_interval, log_vis_mip, on_samples
 
     @torch.no_grad()
@@ -516,12 +534,12 @@ def _class_map(label, labels_long):
 
 
 def _landmark_losses(class_weight, regression_weight, class_loss, regression, dev):
-    """LandmarkNet's two criteria (landmarks.py:43-56): DiceLoss or nn.CrossEntropyLoss(weight) for the class channels, the fused
+    """LandmarkNet's two criteria (landmarks.py:43-56): DiceLoss, nn.CrossEntropyLoss(weight) or their sum for the class channels, the fused
     per-channel heat-map regression for the others."""
-    if class_loss not in ("DICE", "CE"):
-        raise ValueError(f"class_loss must be 'DICE' or 'CE', not {class_loss!r}")
+    if class_loss not in ("DICE", "CE", "DICE_CE"):
+        raise ValueError(f"class_loss must be 'DICE', 'CE' or 'DICE_CE', not {class_loss!r}")
     w = torch.tensor(class_weight, dtype=torch.float32, device=dev)
-    loss_class = (HL.DiceLoss(weight=w) if class_loss == "DICE" else HL.CrossEntropyLoss(weight=w)).to(dev)
+    loss_class = _class_criterion(class_loss, w).to(dev)
     return loss_class, HL.HeatmapRegressionLoss(regression_weight, regression).to(dev)
 
 
@@ -562,6 +580,10 @@ class LandmarkStep(_GraphedStep):
         if _landmark_head_fusable(m, self.loss_class, self.loss_reg, inputs):
             feats = m.forward_features(inputs)
             if ops.head_landmark_supported(feats, fc.in_channels, nh, fc.out_channels - nh, heatmaps, labels):
+                if self.class_loss == "DICE_CE":
+                    return ops.head_landmark(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, self.loss_class.weight,
+                                             self.loss_reg.channel_weights, self.loss_reg.kind, self.loss_class.epsilon,
+                                             class_loss="DICE_CE")
                 if self.class_loss == "CE":
                     return ops.head_landmark(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, self.loss_class.weight,
                                              self.loss_reg.channel_weights, self.loss_reg.kind, ignore_index=self.loss_class.ignore_index,
@@ -632,7 +654,7 @@ class LandmarkValidation:
         m, fc = self.model, getattr(self.model, "final_conv", None)
         lc = self.loss_class
         # (the Dice forward's sums serve dice_metric only when they are its sums: softmax, no ignore mask)
-        metric_ok = self.class_loss == "CE" or (not lc.sigmoid_normalization and lc.ignore_index is None)
+        metric_ok = self.class_loss in ("CE", "DICE_CE") or (not lc.sigmoid_normalization and lc.ignore_index is None)
         if metric_ok and _landmark_head_fusable(m, lc, self.loss_reg, inputs):
             feats = m.forward_features(inputs)
             if ops.head_landmark_supported(feats, fc.in_channels, nh, fc.out_channels - nh, heatmaps, labels):
@@ -640,7 +662,7 @@ class LandmarkValidation:
                     self._log_samples(fc(feats[0:1]), batch, inputs, nh, batch_nb, first=slice(0, 1))
                 return ops.head_landmark_eval(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, lc.weight,
                                               self.loss_reg.channel_weights, self.loss_reg.kind, getattr(lc, "epsilon", 1e-5),
-                                              lc.ignore_index, self.class_loss)
+                                              getattr(lc, "ignore_index", None), self.class_loss)
             outputs = fc(feats)
         else:
             outputs = m(inputs)

@@ -60,6 +60,22 @@ class CrossEntropyLoss(nn.Module):
         return ops.cross_entropy(input, target, self.weight, self.ignore_index)
 
 
+class DiceCELoss(nn.Module):
+    """DiceLoss(epsilon, weight)(input, target) + CrossEntropyLoss(weight)(input, target): the compound class loss with unit
+    coefficients and one class-weight vector, as one fused pass over the logits each way (ops.dice_ce_loss).  Softmax only and no
+    ignore_index: Dice's mask on the one-hot target and cross-entropy's voxel rule do not compose."""
+
+    def __init__(self, epsilon=1e-5, weight=None, sigmoid_normalization=False):
+        super().__init__()
+        if sigmoid_normalization:
+            raise ValueError("DiceCELoss is a softmax form: sigmoid_normalization=True is not supported")
+        self.epsilon = epsilon
+        self.register_buffer("weight", weight)
+
+    def forward(self, input, target):
+        return ops.dice_ce_loss(input, target, self.weight, self.epsilon)
+
+
 class HeatmapRegressionLoss(nn.Module):
     """Fused form of the per-channel loop of LandmarkNet.loss (landmarks.py:129-132)."""
 
