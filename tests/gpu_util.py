@@ -919,3 +919,94 @@ def check_aug_two_channel(got, case, ref, eps, what):
     assert not bad.any(), f"{what}: {int(bad.sum())} of {int((~case.half).sum())} L / H voxels differ; first at {tuple(np.argwhere(bad)[0])}"
     assert bool((ref.sure_lo | ref.sure_hi).all()), what + ": a voxel is not clipped beyond doubt at factor 2^40"
     return check_augment(got, ref, eps, what)
+
+
+# ------------------------------------------------------------------------------- the rounding lattice
+# Inputs of tests/test_gpu_rounding.py keep "every fp32 partial sum is exact" and DROP "the result is a number of the output
+# type": the accumulator holds the exact result, the kernel rounds once, and ref64.to(dtype) is the one correct answer.  The
+# helpers below count, on the reference alone, what such a case needs in order to tell the roundings apart.
+def neighbours(v, dtype):
+    """v (fp64) -> (towards, away): the `dtype` numbers next to v on the side of zero and on the far side, both v itself where
+    v is a number of the type; fp64 tensors, the sign of a zero kept, `away` +-inf beyond the largest finite number."""
+    v = v.detach().double()
+    r = v.to(dtype)
+    bits = r.view(torch.int16)       # sign-magnitude patterns: one less is the next number towards zero, for both signs
+    t_bits = bits - (r.double().abs() > v.abs()).to(torch.int16)
+    towards = t_bits.view(dtype).double()
+    away = (t_bits + (towards != v).to(torch.int16)).view(dtype).double()
+    return towards, away
+
+
+def rounding_census(v, dtype):
+    """What a reference holds: .rne = v.to(dtype) (fp64), the neighbours, and masks .nonrep (no number of the type), .tie_zero /
+    .tie_away (exactly half way; round-to-nearest-even goes towards / away from zero), .sub (stored as a nonzero subnormal),
+    .zeroed (nonzero, stored as a signed zero), .inf (stored as +-inf)."""
+    v = v.detach().double()
+    rne = v.to(dtype).double()
+    towards, away = neighbours(v, dtype)
+    top = 2.0 * 2.0 ** float(np.floor(np.log2(torch.finfo(dtype).max)))       # the number after the largest finite one
+    far = torch.where(torch.isinf(away), torch.sign(away) * top, away)
+    nonrep = towards != v
+    tie = nonrep & ((v - towards).abs() == (far - v).abs())
+    tiny = torch.finfo(dtype).smallest_normal
+    return types.SimpleNamespace(v=v, rne=rne, towards=towards, away=away, nonrep=nonrep, tie_zero=tie & (rne == towards),
+                                 tie_away=tie & (rne == away), sub=(rne != 0) & (rne.abs() < tiny), zeroed=(v != 0) & (rne == 0),
+                                 inf=torch.isinf(rne))
+
+
+def census_counts(cen):
+    n = lambda m: int(m.sum())
+    return dict(elements=cen.v.numel(), nonrep=n(cen.nonrep), tie_zero=n(cen.tie_zero), tie_away=n(cen.tie_away), sub=n(cen.sub),
+                zeroed=n(cen.zeroed), inf=n(cen.inf))
+
+
+def assert_rounding_premises(v, dtype, what, nonrep=0.25, ties=100, sub=0, sub_ties=0, zeroed=0, inf=None):
+    """Conditions under which equality with v.to(dtype) tells the roundings apart -- on the reference alone: at least `nonrep` of
+    the elements are no numbers of the type, at least `ties` exact ties resolve towards zero and as many away from it; at least
+    `sub` elements are stored as nonzero subnormals with `sub_ties` ties among them in each direction; at least `zeroed` nonzero
+    elements lie below half the smallest subnormal (or on that tie) and are stored as a signed zero; inf = None: every element
+    is finite, inf = (lo, hi): the share of +-inf lies in [lo, hi], both signs occur, and the rest is finite.  -> the census."""
+    v = v.detach().double()
+    assert bool(torch.isfinite(v).all()), f"{what}: the fp64 reference is not finite"
+    cen = rounding_census(v, dtype)
+    k = census_counts(cen)
+    assert k["nonrep"] >= nonrep * k["elements"], f"{what}: only {k['nonrep']} of {k['elements']} reference elements are no {dtype} numbers"
+    assert k["tie_zero"] >= ties and k["tie_away"] >= ties, f"{what}: {k['tie_zero']} ties towards zero, {k['tie_away']} away, {ties} wanted of each"
+    assert k["sub"] >= sub, f"{what}: {k['sub']} subnormal results, {sub} wanted"
+    assert k["zeroed"] >= zeroed, f"{what}: {k['zeroed']} nonzero results are stored as a zero, {zeroed} wanted"
+    if sub_ties:
+        tz, ta = int((cen.tie_zero & (cen.sub | cen.zeroed)).sum()), int((cen.tie_away & cen.sub).sum())
+        assert tz >= sub_ties and ta >= sub_ties, f"{what}: {tz} / {ta} subnormal ties towards zero / away, {sub_ties} wanted of each"
+    if inf is None:
+        assert k["inf"] == 0, f"{what}: {k['inf']} reference elements overflow {dtype}"
+    else:
+        share = k["inf"] / k["elements"]
+        assert inf[0] <= share <= inf[1], f"{what}: {share:.3%} of the reference elements overflow, wanted {inf[0]:.0%} .. {inf[1]:.0%}"
+        assert bool((cen.rne == float("inf")).any()) and bool((cen.rne == float("-inf")).any()), f"{what}: one sign of infinity is missing"
+    return cen
+
+
+def assert_rounded(got, v, dtype, what):
+    """Every element of `got` equals v.to(dtype): ONE round-to-nearest-even of the exact value -- subnormals kept, +-inf from
+    65520 on, no NaN -- and a nonzero value that rounds to zero comes out as the zero of ITS sign.  -> elements compared."""
+    v = v.detach().double().cpu()
+    want = v.to(dtype)
+    total = assert_exact(got, want, what)
+    g = got.detach().cpu()
+    flipped = (want == 0) & (v != 0) & (torch.signbit(g.double()) != torch.signbit(want.double()))
+    if bool(flipped.any()):
+        i = tuple(flipped.nonzero()[0].tolist())
+        raise AssertionError(f"{what}: {int(flipped.sum())} zeros carry the wrong sign; first at {i}: exact value {v[i].item()!r}")
+    return total
+
+
+def report_rounding(item, what, kernel, elements, counts):
+    """The `[exact]` line of a rounding comparison: what was compared and what the reference held."""
+    print(f"[exact] item={item} {what} kernel={kernel} elements={elements} nonrep={counts['nonrep']} ties={counts['tie_zero']}/{counts['tie_away']} "
+          f"subnormal={counts['sub']} zeroed={counts['zeroed']} inf={counts['inf']}")
+
+
+def add_counts(total, k):
+    for name, val in k.items():
+        total[name] = total.get(name, 0) + val
+    return total

@@ -77,8 +77,11 @@ struct FwdArgs {
   unsigned rcp_tiles_x, rcp_tiles_y, rcp_tiles_z, rcp_ncb;  // ceil(2^32 / d): x / d == umulhi(x, rcp) for x * d < 2^32
   unsigned bytes_x;  // size of ONE SAMPLE of x for the buffer resource (< 4 GB)
   unsigned bytes_y;  // same for y
-  const elt* add;    // nullable, shape of y: summed into the output in the epilogue (fp32 add, one rounding) -- the residual
-                      // branch's gradient joining the data gradient of ExtResNetBlock's second conv (components.py:170-178)
+  const elt* add;    // nullable, shape of y: summed into the STORED output row in the epilogue -- the convolution is rounded to
+                      // elt, `add` is added to that value in fp32 and the sum rounded again: TWO roundings, bit for bit what
+                      // mednet_add after a stored data gradient gives (tests/test_gpu_rounding.py pins it in all three kernels) --
+                      // the residual branch's gradient joining the data gradient of ExtResNetBlock's second conv
+                      // (components.py:170-178)
   int act;            // MEDNET_ACT_*: applied to the fp32 accumulators before the elt store (conv -> ReLU/LeakyReLU/ELU of the
                       // 'gcr' orders, components.py:36-40); the fused statistics are then those of the ACTIVATED output
   float* gn_partial;  // nullable: [n][stats_rows][cout][2] = {sum y, sum y^2} of the STORED (rounded) outputs, see stats_accum
