@@ -402,6 +402,28 @@ def test_fused_landmark_head_and_first_layer_entry_points_answer_without_a_devic
     assert rc == -1 and "gn_bwd_coefficients" in lib.mednet_last_error().decode()
 
 
+def test_normalisation_entries_refuse_what_they_refused_in_the_same_order(golden_dir):
+    """tools/norm_refusals.py: every extern "C" entry of csrc/norm_act.hip with argument sets that trip each of its checks in turn
+    (null pointers, bad dtype, C % groups, C / vec > 256, a workspace one byte short, two violations at once, the options that
+    switch a fused form off) -- all refused before any launch, no device needed.  tests/golden/norm_refusals.jsonl is the table
+    the library printed BEFORE the entries were put on one host path (GnPlan, launch_gn_*, gn_bwd_coefs): return code and
+    message of every case are frozen, so a reordered or reworded check shows."""
+    import importlib.util
+    import json
+    import os
+    from mednet_hip import _lib as L
+    spec = importlib.util.spec_from_file_location("norm_refusals", os.path.join(os.path.dirname(golden_dir), "..", "tools", "norm_refusals.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(golden_dir, "norm_refusals.jsonl")) as f:
+        want = [json.loads(line) for line in f]
+    got = tool.run(L.lib())
+    assert len(want) == 360 and [(r["entry"], r["case"]) for r in got] == [(r["entry"], r["case"]) for r in want]
+    for g, w in zip(got, want):
+        assert g == w, (g, w)
+    assert all(r["rc"] < 0 for r in want if r["error"])  # (a refusal each: nothing in the table reached a launch)
+
+
 def test_fused_head_nodes_step_aside_for_hooks_on_the_bypassed_calls():
     """The fused head + loss nodes (train.SegmentationStep._head_loss, LandmarkStep._head_losses) call forward_features() and never
     final_conv: a forward hook / pre-hook on the model or on final_conv would not fire, so the steps take the stock model(inputs)

@@ -7,6 +7,8 @@
 // :208-212 (pooling), :277-280 (interpolate + cat).
 #include "common.h"
 
+#include <type_traits>
+
 #ifndef GN_NT
 #define GN_NT 1  // GroupNorm backward's apply pass reads dz and y for the last time: non-temporal loads.  (Non-temporal STORES of
                  // the streaming kernels' outputs were measured too: +0.13 ms per step, profiles/r04_ab.md section 12.)
@@ -1277,31 +1279,142 @@ extern "C" size_t mednet_gn_ws_bytes(int n, int c, size_t spatial) {
   return ((size_t)n * gn_partial_rows_max(c) * c * 2 + (size_t)n * c * 5 + 64) * sizeof(float);
 }
 
+// Storage type (x vector width) -> kernel instance: f(Tag<T>{}, Width<V>{}) of a generic lambda.  Width 4 exists for fp32 only.
+template <typename T>
+struct Tag {
+  using type = T;
+};
+template <int V>
+using Width = std::integral_constant<int, V>;
+template <typename F>
+static inline void by_type(int dtype, F&& f) {
+  if (dtype == MEDNET_F32) f(Tag<float>{});
+  else if (dtype == MEDNET_BF16) f(Tag<bf16>{});
+  else f(Tag<f16>{});
+}
+template <typename F>
+static inline void by_type_vec(int dtype, int vec, F&& f) {
+  by_type(dtype, [&](auto t) {
+    if constexpr (std::is_same<decltype(t), Tag<float>>::value)
+      if (vec == 4) return f(t, Width<4>{});
+    if (vec == 8) f(t, Width<8>{});
+    else f(t, Width<1>{});
+  });
+}
+
+// What a GroupNorm / BatchNorm entry derives from (n, S, C, dtype) and its workspace: the vector width, the chunking of the
+// streaming kernels' grid, the rows per workgroup of the LDS-free backward sums and the three regions of mednet_gn_ws_bytes.
+struct GnPlan {
+  int n, c, dtype, vec;
+  size_t spatial, chunk_vox = 0;
+  unsigned chunks = 0;  // (0: C / vec > 256, no streaming kernel takes this C -- the entries refuse it)
+  dim3 grid;
+  int rpw = 0;
+  float *partial = nullptr, *bcoef = nullptr, *csum = nullptr;  // [n][rows][c][2], [n][c][3], [n][c][2]
+  int rows() const { return (int)chunks * (rpw > 0 ? rpw : 1); }  // partial rows per sample the backward's first pass writes
+};
+static GnPlan gn_plan(int n, size_t spatial, int c, int dtype, void* ws) {
+  GnPlan p;
+  p.n = n, p.c = c, p.dtype = dtype, p.spatial = spatial;
+  p.vec = pick_vec(c, dtype);
+  const int cols = c / p.vec;
+  if (cols >= 1 && cols <= 256) {
+    chunk_plan(spatial, c, p.vec, p.chunk_vox, p.chunks);
+    p.grid = dim3(p.chunks, n);
+    p.rpw = tuning_option("gn_lds_free", 1) ? lds_free_rows_per_wg(cols) : 0;
+  }
+  if (ws) {
+    p.partial = (float*)ws;
+    p.bcoef = p.partial + (size_t)n * gn_partial_rows_max(c) * c * 2;
+    p.csum = p.bcoef + (size_t)n * c * 3;
+  }
+  return p;
+}
+
+// The streaming kernels, one launch function each (GroupNorm and BatchNorm entries alike)
+static int launch_gn_partial(const GnPlan& p, const void* x, hipStream_t s) {
+  by_type_vec(p.dtype, p.vec, [&](auto t, auto v) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((gn_partial_kernel<T, decltype(v)::value>), p.grid, dim3(256), 0, s, (const T*)x, p.partial, p.spatial, p.c,
+                       p.chunk_vox);
+  });
+  return check_launch("gn_partial");
+}
+static int launch_gn_bwd_partial(const GnPlan& p, const void* dz, const void* dz2, const void* x, const void* z, const float* coef,
+                                 const float* stats, int groups, int act, hipStream_t s) {
+  by_type_vec(p.dtype, p.vec, [&](auto t, auto v) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((gn_bwd_partial_kernel<T, decltype(v)::value>), p.grid, dim3(256), 0, s, (const T*)dz, (const T*)dz2,
+                       (const T*)x, (const T*)z, coef, stats, p.partial, p.spatial, p.c, groups, act, p.chunk_vox, p.rpw);
+  });
+  return check_launch("gn_bwd_partial");
+}
+static int launch_gn_bwd_apply(const GnPlan& p, const void* dz, const void* dz2, const void* x, const void* z, const float* coef,
+                               void* dx, void* dres, int act, int in_act, const GnParamGrad& pg, hipStream_t s) {
+  by_type_vec(p.dtype, p.vec, [&](auto t, auto v) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((gn_bwd_apply_kernel<T, decltype(v)::value>), p.grid, dim3(256), 0, s, (const T*)dz, (const T*)dz2,
+                       (const T*)x, (const T*)z, coef, p.bcoef, (T*)dx, (T*)dres, p.spatial, p.c, act, p.chunk_vox, in_act, pg);
+  });
+  return check_launch("gn_bwd_apply");
+}
+static int launch_gn_finalize(const float* partial, int chunks, const float* gamma, const float* beta, float* stats, float* coef,
+                              int n, size_t spatial, int c, int groups, float eps, hipStream_t s) {
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(n * groups), dim3(chunks >= 4096 ? 1024 : 256), 0, s, partial, gamma, beta, stats, coef, c,
+                     groups, chunks, (double)spatial * (c / groups), eps);
+  return check_launch("gn_finalize");
+}
+
+// The backward's middle passes: `nrows` partial rows per sample -> csum[n][c][2] and bcoef[n][c][3], in one launch where the
+// group size allows, else reduce -> finalize.  DUX: the rows are a producer's {sum du, sum du * x} (a data-gradient, head or
+// pooling epilogue), not gn_bwd_partial_kernel's own {sum du, sum du * xhat}.  The parameter gradients: after the one-launch
+// form the apply kernel's first workgroup computes them from *pg; gn_bwd_params_kernel runs otherwise, and always when no
+// apply pass follows (pg == nullptr).  `skip`: timing probes only (tools/probes/stall_probe.py), bit k drops sub-kernel k.
+template <bool DUX>
+static int gn_bwd_coefs(const float* rows, int nrows, const float* stats, const float* gamma, float* csum, float* bcoef,
+                        float* dgamma, float* dbeta, int n, size_t spatial, int c, int groups, int skip, GnParamGrad* pg,
+                        hipStream_t s) {
+  const double count = (double)spatial * (c / groups);
+  int rc;
+  if (gn_bwd_one_launch(c, groups) && !skip) {
+    hipLaunchKernelGGL(gn_bwd_reduce_finalize_kernel<DUX>, dim3(n * groups), dim3(256), 0, s, rows, stats, gamma, csum, bcoef, c,
+                       groups, nrows, count);
+    rc = check_launch("gn_bwd_reduce_finalize");
+    if (rc) return rc;
+    if (pg) {
+      if (dgamma || dbeta) *pg = GnParamGrad{csum, dgamma, dbeta, n};
+      return MEDNET_OK;
+    }
+  } else {
+    if (!(skip & 1)) {
+      if (DUX) hipLaunchKernelGGL(reduce_partials_dux_kernel, dim3(n * c), dim3(64), 0, s, rows, stats, csum, c, groups, nrows);
+      else hipLaunchKernelGGL(reduce_partials_kernel, dim3(n * c), dim3(64), 0, s, rows, csum, c, nrows);
+    }
+    if (!(skip & 2))
+      hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(n * groups), dim3(64), 0, s, csum, stats, gamma, bcoef, c, groups, count);
+    rc = check_launch("gn_bwd_finalize");
+    if (rc) return rc;
+  }
+  if ((dgamma || dbeta) && !(skip & (4 | 8))) {
+    hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((c + 255) / 256), dim3(256), 0, s, csum, dgamma, dbeta, n, c);
+    return check_launch("gn_bwd_params");
+  }
+  return MEDNET_OK;
+}
+
 extern "C" int mednet_gn_stats(const void* x, const float* gamma, const float* beta, float* stats, float* coef,
                                int n, size_t spatial, int c, int groups, float eps, int dtype, void* ws,
                                size_t ws_bytes, mednet_stream stream) {
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "gn_stats: bad dtype %d", dtype);
   MEDNET_REQUIRE(n > 0 && c > 0 && groups > 0 && c % groups == 0 && spatial > 0, MEDNET_E_SHAPE,
                  "gn_stats: bad shape n=%d c=%d groups=%d", n, c, groups);
-  const int vec = pick_vec(c, dtype);
-  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "gn_stats: C=%d unsupported (need C%%8==0 or C<=256)", c);
+  const GnPlan p = gn_plan(n, spatial, c, dtype, ws);
+  MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "gn_stats: C=%d unsupported (need C%%8==0 or C<=256)", c);
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "gn_stats: workspace too small");
-  size_t cv;
-  unsigned chunks;
-  chunk_plan(spatial, c, vec, cv, chunks);
-  float* partial = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(chunks, n);
-#define GO(T, V) hipLaunchKernelGGL((gn_partial_kernel<T, V>), grid, dim3(256), 0, s, (const T*)x, partial, spatial, c, cv)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
-  int rc = check_launch("gn_partial");
+  const int rc = launch_gn_partial(p, x, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(n * groups), dim3(chunks >= 4096 ? 1024 : 256), 0, s, partial, gamma, beta, stats, coef, c, groups,
-                     (int)chunks, (double)spatial * (c / groups), eps);
-  return check_launch("gn_finalize");
+  return launch_gn_finalize(p.partial, (int)p.chunks, gamma, beta, stats, coef, n, spatial, c, groups, eps, s);
 }
 
 extern "C" int mednet_gn_finalize(const float* partial, int chunks, const float* gamma, const float* beta, float* stats,
@@ -1310,28 +1423,21 @@ extern "C" int mednet_gn_finalize(const float* partial, int chunks, const float*
   MEDNET_REQUIRE(n > 0 && c > 0 && groups > 0 && c % groups == 0 && chunks > 0, MEDNET_E_SHAPE, "gn_finalize: bad shape");
   (void)ws;
   (void)ws_bytes;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(n * groups), dim3(chunks >= 4096 ? 1024 : 256), 0, s, partial, gamma, beta, stats, coef, c, groups, chunks,
-                     (double)spatial * (c / groups), eps);
-  return check_launch("gn_finalize");
+  return launch_gn_finalize(partial, chunks, gamma, beta, stats, coef, n, spatial, c, groups, eps, (hipStream_t)stream);
 }
 
 extern "C" int mednet_gn_act_fwd(const void* x, const float* coef, const void* residual, void* z, int n,
                                  size_t spatial, int c, int act, int x_dtype, int z_dtype, mednet_stream stream) {
   MEDNET_REQUIRE(dtype_ok(x_dtype) && dtype_ok(z_dtype), MEDNET_E_DTYPE, "gn_act_fwd: bad dtype");
   MEDNET_REQUIRE(x_dtype == z_dtype, MEDNET_E_UNSUPPORTED, "gn_act_fwd: x and z must share a dtype");
-  const int vec = pick_vec(c, x_dtype);
-  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "gn_act_fwd: C=%d unsupported", c);
-  size_t cv;
-  unsigned chunks;
-  chunk_plan(spatial, c, vec, cv, chunks);
+  const GnPlan p = gn_plan(n, spatial, c, x_dtype, nullptr);
+  MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "gn_act_fwd: C=%d unsupported", c);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(chunks, n);
-#define GO(T, V) hipLaunchKernelGGL((gn_act_fwd_kernel<T, T, V>), grid, dim3(256), 0, s, (const T*)x, coef, (const T*)residual, (T*)z, spatial, c, act, cv)
-  if (x_dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (x_dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
+  by_type_vec(x_dtype, p.vec, [&](auto t, auto v) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((gn_act_fwd_kernel<T, T, decltype(v)::value>), p.grid, dim3(256), 0, s, (const T*)x, coef, (const T*)residual,
+                       (T*)z, spatial, c, act, p.chunk_vox);
+  });
   return check_launch("gn_act_fwd");
 }
 
@@ -1344,50 +1450,16 @@ extern "C" int mednet_gn_act_bwd(const void* dz, const void* dz2, const void* x,
   MEDNET_REQUIRE(c % groups == 0, MEDNET_E_SHAPE, "gn_act_bwd: C %% groups != 0");
   MEDNET_REQUIRE(act == MEDNET_ACT_NONE || z != nullptr || coef != nullptr, MEDNET_E_SHAPE,
                  "gn_act_bwd: act' needs the activated output z or the forward coefficients");
-  const int vec = pick_vec(c, dtype);
-  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "gn_act_bwd: C=%d unsupported", c);
+  const GnPlan p = gn_plan(n, spatial, c, dtype, ws);
+  MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "gn_act_bwd: C=%d unsupported", c);
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "gn_act_bwd: workspace too small");
-  size_t cv;
-  unsigned chunks;
-  chunk_plan(spatial, c, vec, cv, chunks);
-  float* partial = (float*)ws;
-  float* bcoef = partial + (size_t)n * gn_partial_rows_max(c) * c * 2;
-  float* csum = bcoef + (size_t)n * c * 3;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(chunks, n);
-  const int rpw = tuning_option("gn_lds_free", 1) ? lds_free_rows_per_wg(c / vec) : 0;
-#define GO(T, V) hipLaunchKernelGGL((gn_bwd_partial_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dz, (const T*)dz2, (const T*)x, (const T*)z, coef, stats, partial, spatial, c, groups, act, cv, rpw)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
-  int rc = check_launch("gn_bwd_partial");
+  int rc = launch_gn_bwd_partial(p, dz, dz2, x, z, coef, stats, groups, act, s);
   if (rc) return rc;
   GnParamGrad pg;
-  if (gn_bwd_one_launch(c, groups)) {
-    hipLaunchKernelGGL(gn_bwd_reduce_finalize_kernel<false>, dim3(n * groups), dim3(256), 0, s, partial, stats, gamma, csum, bcoef, c,
-                       groups, (int)chunks * (rpw > 0 ? rpw : 1), (double)spatial * (c / groups));
-    rc = check_launch("gn_bwd_reduce_finalize");
-    if (rc) return rc;
-    if (dgamma || dbeta) pg = GnParamGrad{csum, dgamma, dbeta, n};
-  } else {
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(n * c), dim3(64), 0, s, partial, csum, c, (int)chunks * (rpw > 0 ? rpw : 1));
-    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(n * groups), dim3(64), 0, s, csum, stats, gamma, bcoef, c, groups,
-                       (double)spatial * (c / groups));
-    rc = check_launch("gn_bwd_finalize");
-    if (rc) return rc;
-    if (dgamma || dbeta) {
-      hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((c + 255) / 256), dim3(256), 0, s, csum, dgamma, dbeta, n, c);
-      rc = check_launch("gn_bwd_params");
-      if (rc) return rc;
-    }
-  }
-#define GO(T, V) hipLaunchKernelGGL((gn_bwd_apply_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dz, (const T*)dz2, (const T*)x, (const T*)z, coef, bcoef, (T*)dx, (T*)dres, spatial, c, act, cv, in_act, pg)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
-  return check_launch("gn_bwd_apply");
+  rc = gn_bwd_coefs<false>(p.partial, p.rows(), stats, gamma, p.csum, p.bcoef, dgamma, dbeta, n, spatial, c, groups, 0, &pg, s);
+  if (rc) return rc;
+  return launch_gn_bwd_apply(p, dz, dz2, x, z, coef, dx, dres, act, in_act, pg, s);
 }
 
 static int gn_act_bwd_fused_impl(const void* dz, const void* x, const void* z, const float* coef, const float* stats,
@@ -1396,46 +1468,15 @@ static int gn_act_bwd_fused_impl(const void* dz, const void* x, const void* z, c
                                  int dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "gn_act_bwd_fused: bad dtype");
   MEDNET_REQUIRE(c % groups == 0 && rows > 0 && fused_partial && coef, MEDNET_E_SHAPE, "gn_act_bwd_fused: bad arguments");
-  const int vec = pick_vec(c, dtype);
-  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "gn_act_bwd_fused: C=%d unsupported", c);
+  const GnPlan p = gn_plan(n, spatial, c, dtype, ws);
+  MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "gn_act_bwd_fused: C=%d unsupported", c);
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "gn_act_bwd_fused: workspace too small");
-  size_t cv;
-  unsigned chunks;
-  chunk_plan(spatial, c, vec, cv, chunks);
-  float* bcoef = (float*)ws + (size_t)n * gn_partial_rows_max(c) * c * 2;
-  float* csum = bcoef + (size_t)n * c * 3;
   hipStream_t s = (hipStream_t)stream;
-  const int skip = tuning_option("gn_bwd_skip", 0);  // timing probes only (tools/probes/stall_probe.py): bit k drops sub-kernel k
+  const int skip = tuning_option("gn_bwd_skip", 0);  // (acts in this path only; bit 3 also drops the apply pass)
   GnParamGrad pg;
-  int rc;
-  if (gn_bwd_one_launch(c, groups) && !skip) {
-    hipLaunchKernelGGL(gn_bwd_reduce_finalize_kernel<true>, dim3(n * groups), dim3(256), 0, s, fused_partial, stats, gamma, csum, bcoef,
-                       c, groups, rows, (double)spatial * (c / groups));
-    rc = check_launch("gn_bwd_reduce_finalize");
-    if (rc) return rc;
-    if (dgamma || dbeta) pg = GnParamGrad{csum, dgamma, dbeta, n};
-  } else {
-    if (!(skip & 1))
-      hipLaunchKernelGGL(reduce_partials_dux_kernel, dim3(n * c), dim3(64), 0, s, fused_partial, stats, csum, c, groups, rows);
-    if (!(skip & 2))
-      hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(n * groups), dim3(64), 0, s, csum, stats, gamma, bcoef, c, groups,
-                         (double)spatial * (c / groups));
-    rc = check_launch("gn_bwd_finalize");
-    if (rc) return rc;
-    if (skip & 8) return MEDNET_OK;
-    if ((dgamma || dbeta) && !(skip & 4)) {
-      hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((c + 255) / 256), dim3(256), 0, s, csum, dgamma, dbeta, n, c);
-      rc = check_launch("gn_bwd_params");
-      if (rc) return rc;
-    }
-  }
-  const dim3 grid(chunks, n);
-#define GO(T, V) hipLaunchKernelGGL((gn_bwd_apply_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dz, (const T*)nullptr, (const T*)x, (const T*)z, coef, bcoef, (T*)dx, (T*)dres, spatial, c, act, cv, in_act, pg)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
-  return check_launch("gn_bwd_apply");
+  const int rc = gn_bwd_coefs<true>(fused_partial, rows, stats, gamma, p.csum, p.bcoef, dgamma, dbeta, n, spatial, c, groups, skip, &pg, s);
+  if (rc || (skip & 8)) return rc;
+  return launch_gn_bwd_apply(p, dz, nullptr, x, z, coef, dx, dres, act, in_act, pg, s);
 }
 
 extern "C" int mednet_gn_act_bwd_fused(const void* dz, const void* x, const float* coef, const float* stats,
@@ -1456,27 +1497,10 @@ extern "C" int mednet_gn_bwd_coefficients(const float* stats, const float* gamma
   MEDNET_REQUIRE(c % groups == 0 && rows > 0 && fused_partial && bcoef && stats && gamma, MEDNET_E_SHAPE,
                  "gn_bwd_coefficients: bad arguments");
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "gn_bwd_coefficients: workspace too small");
-  float* csum = (float*)ws;  // [n][c][2]
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (gn_bwd_one_launch(c, groups)) {
-    hipLaunchKernelGGL(gn_bwd_reduce_finalize_kernel<true>, dim3(n * groups), dim3(256), 0, s, fused_partial, stats, gamma, csum, bcoef,
-                       c, groups, rows, (double)spatial * (c / groups));
-    rc = check_launch("gn_bwd_reduce_finalize");
-    if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL(reduce_partials_dux_kernel, dim3(n * c), dim3(64), 0, s, fused_partial, stats, csum, c, groups, rows);
-    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(n * groups), dim3(64), 0, s, csum, stats, gamma, bcoef, c, groups,
-                       (double)spatial * (c / groups));
-    rc = check_launch("gn_bwd_finalize");
-    if (rc) return rc;
-  }
-  if (dgamma || dbeta) {
-    hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((c + 255) / 256), dim3(256), 0, s, csum, dgamma, dbeta, n, c);
-    rc = check_launch("gn_bwd_params");
-    if (rc) return rc;
-  }
-  return MEDNET_OK;
+  // csum at the start of the workspace, not at GnPlan's: no partial rows of this entry's own lie there (the rows are the
+  // producer's, bcoef the caller's), and the footprint tests pin the bytes it touches
+  return gn_bwd_coefs<true>(fused_partial, rows, stats, gamma, (float*)ws, bcoef, dgamma, dbeta, n, spatial, c, groups, 0, nullptr,
+                            (hipStream_t)stream);
 }
 
 // ... for the residual layer of an ExtResNetBlock: the activation derivative comes from the block OUTPUT z, and du is also
@@ -1504,37 +1528,18 @@ extern "C" int mednet_gn_act_bwd_fused_res_pool(const void* dy_pool, const void*
                  "gn_act_bwd_fused_res_pool: even extents and C %% 8 == 0 (%dx%dx%d, C=%d)", d, h, w, c);
   const size_t spatial = (size_t)d * h * w;
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "gn_act_bwd_fused_res_pool: workspace too small");
-  float* bcoef = (float*)ws + (size_t)n * gn_partial_rows_max(c) * c * 2;
-  float* csum = bcoef + (size_t)n * c * 3;
+  const GnPlan p = gn_plan(n, spatial, c, dtype, ws);  // (the regions only: the apply pass walks pooling windows, not chunks)
   hipStream_t s = (hipStream_t)stream;
   GnParamGrad pg;
-  int rc;
-  if (gn_bwd_one_launch(c, groups)) {
-    hipLaunchKernelGGL(gn_bwd_reduce_finalize_kernel<true>, dim3(n * groups), dim3(256), 0, s, fused_partial, stats, gamma, csum, bcoef,
-                       c, groups, rows, (double)spatial * (c / groups));
-    rc = check_launch("gn_bwd_reduce_finalize");
-    if (rc) return rc;
-    if (dgamma || dbeta) pg = GnParamGrad{csum, dgamma, dbeta, n};
-  } else {
-    hipLaunchKernelGGL(reduce_partials_dux_kernel, dim3(n * c), dim3(64), 0, s, fused_partial, stats, csum, c, groups, rows);
-    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(n * groups), dim3(64), 0, s, csum, stats, gamma, bcoef, c, groups,
-                       (double)spatial * (c / groups));
-    rc = check_launch("gn_bwd_finalize");
-    if (rc) return rc;
-    if (dgamma || dbeta) {
-      hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((c + 255) / 256), dim3(256), 0, s, csum, dgamma, dbeta, n, c);
-      rc = check_launch("gn_bwd_params");
-      if (rc) return rc;
-    }
-  }
-  const int vec = dtype == MEDNET_F32 ? 4 : 8;
-  const size_t total = (size_t)n * (d / 2) * (h / 2) * (w / 2) * (c / vec);
-  const dim3 grid((unsigned)((total + 255) / 256));
-#define GO(T, V) hipLaunchKernelGGL((gn_bwd_apply_pool_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dy_pool, (const T*)skip_grad, (const T*)x, (const T*)z, bcoef, (T*)dx, (T*)dres, n, d, h, w, c, act, pool_mode, pg)
-  if (dtype == MEDNET_F32) GO(float, 4);
-  else if (dtype == MEDNET_BF16) GO(bf16, 8);
-  else GO(f16, 8);
-#undef GO
+  const int rc = gn_bwd_coefs<true>(fused_partial, rows, stats, gamma, p.csum, p.bcoef, dgamma, dbeta, n, spatial, c, groups, 0, &pg, s);
+  if (rc) return rc;
+  by_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    constexpr int V = std::is_same<T, float>::value ? 4 : 8;
+    const size_t total = (size_t)n * (d / 2) * (h / 2) * (w / 2) * (c / V);
+    hipLaunchKernelGGL((gn_bwd_apply_pool_kernel<T, V>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const T*)dy_pool,
+                       (const T*)skip_grad, (const T*)x, (const T*)z, p.bcoef, (T*)dx, (T*)dres, n, d, h, w, c, act, pool_mode, pg);
+  });
   return check_launch("gn_bwd_apply_pool");
 }
 
@@ -1689,25 +1694,15 @@ extern "C" int mednet_bn_stats(const void* x, const float* gamma, const float* b
   MEDNET_REQUIRE(n > 0 && c > 0 && spatial > 0 && x && stats && coef, MEDNET_E_SHAPE, "bn_stats: bad shape n=%d c=%d", n, c);
   MEDNET_REQUIRE((running_mean == nullptr) == (running_var == nullptr), MEDNET_E_SHAPE,
                  "bn_stats: running_mean and running_var come together");
-  const int vec = pick_vec(c, dtype);
-  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "bn_stats: C=%d unsupported (need C%%8==0 or C<=256)", c);
+  const GnPlan p = gn_plan(n, spatial, c, dtype, ws);
+  MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "bn_stats: C=%d unsupported (need C%%8==0 or C<=256)", c);
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "bn_stats: workspace too small");
-  size_t cv;
-  unsigned chunks;
-  chunk_plan(spatial, c, vec, cv, chunks);
-  float* partial = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(chunks, n);
-#define GO(T, V) hipLaunchKernelGGL((gn_partial_kernel<T, V>), grid, dim3(256), 0, s, (const T*)x, partial, spatial, c, cv)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
-  int rc = check_launch("gn_partial");
+  const int rc = launch_gn_partial(p, x, s);
   if (rc) return rc;
   const int cw = bn_cw(c);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(c / cw), dim3(BN_NT), 0, s, partial, gamma, beta, running_mean, running_var,
-                     num_batches_tracked, stats, coef, n, c, cw, (int)chunks * n, (double)spatial * n, eps, momentum);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(c / cw), dim3(BN_NT), 0, s, p.partial, gamma, beta, running_mean, running_var,
+                     num_batches_tracked, stats, coef, n, c, cw, (int)p.chunks * n, (double)spatial * n, eps, momentum);
   return check_launch("bn_finalize");
 }
 
@@ -1719,19 +1714,15 @@ extern "C" int mednet_bn_eval_coef(const float* running_mean, const float* runni
   return check_launch("bn_eval_coef");
 }
 
-static int bn_bwd_apply(const void* dz, const void* x, const void* z, const float* coef, const float* bcoef, void* dx, void* dres,
-                        int n, size_t spatial, int c, int act, int in_act, int dtype, int vec, hipStream_t s) {
-  size_t cv;
-  unsigned chunks;
-  chunk_plan(spatial, c, vec, cv, chunks);
-  const dim3 grid(chunks, n);
-  const GnParamGrad pg;  // (dgamma / dbeta were written by bn_bwd_coef_kernel)
-#define GO(T, V) hipLaunchKernelGGL((gn_bwd_apply_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dz, (const T*)nullptr, (const T*)x, (const T*)z, coef, bcoef, (T*)dx, (T*)dres, spatial, c, act, cv, in_act, pg)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
-  return check_launch("gn_bwd_apply");
+// BatchNorm's middle pass, `nrows` partial rows over all samples -> bcoef (replicated per sample), dgamma, dbeta: the apply
+// pass gets an empty GnParamGrad
+template <bool DUX>
+static int bn_bwd_coefs(const GnPlan& p, const float* rows, int nrows, const float* stats, const float* gamma, float* dgamma,
+                        float* dbeta, int frozen, hipStream_t s) {
+  const int cw = bn_cw(p.c);
+  hipLaunchKernelGGL(bn_bwd_coef_kernel<DUX>, dim3(p.c / cw), dim3(BN_NT), 0, s, rows, stats, gamma, p.bcoef, dgamma, dbeta, p.n, p.c,
+                     cw, nrows, (double)p.spatial * p.n, frozen);
+  return check_launch("bn_bwd_coef");
 }
 
 extern "C" int mednet_bn_act_bwd(const void* dz, const void* x, const void* z, const float* coef, const float* stats,
@@ -1739,30 +1730,15 @@ extern "C" int mednet_bn_act_bwd(const void* dz, const void* x, const void* z, c
                                  int act, int in_act, int frozen, int dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "bn_act_bwd: bad dtype");
   MEDNET_REQUIRE(n > 0 && c > 0 && spatial > 0 && dz && x && coef && stats && dx, MEDNET_E_SHAPE, "bn_act_bwd: bad arguments");
-  const int vec = pick_vec(c, dtype);
-  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "bn_act_bwd: C=%d unsupported", c);
+  const GnPlan p = gn_plan(n, spatial, c, dtype, ws);
+  MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "bn_act_bwd: C=%d unsupported", c);
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "bn_act_bwd: workspace too small");
-  size_t cv;
-  unsigned chunks;
-  chunk_plan(spatial, c, vec, cv, chunks);
-  float* partial = (float*)ws;
-  float* bcoef = partial + (size_t)n * gn_partial_rows_max(c) * c * 2;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(chunks, n);
-  const int rpw = tuning_option("gn_lds_free", 1) ? lds_free_rows_per_wg(c / vec) : 0;
-#define GO(T, V) hipLaunchKernelGGL((gn_bwd_partial_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dz, (const T*)nullptr, (const T*)x, (const T*)z, coef, stats, partial, spatial, c, c, act, cv, rpw)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
-  int rc = check_launch("gn_bwd_partial");
+  int rc = launch_gn_bwd_partial(p, dz, nullptr, x, z, coef, stats, c, act, s);  // (groups = C)
   if (rc) return rc;
-  const int cw = bn_cw(c);
-  hipLaunchKernelGGL(bn_bwd_coef_kernel<false>, dim3(c / cw), dim3(BN_NT), 0, s, partial, stats, gamma, bcoef, dgamma, dbeta, n, c, cw,
-                     (int)chunks * (rpw > 0 ? rpw : 1) * n, (double)spatial * n, frozen);
-  rc = check_launch("bn_bwd_coef");
+  rc = bn_bwd_coefs<false>(p, p.partial, p.rows() * n, stats, gamma, dgamma, dbeta, frozen, s);
   if (rc) return rc;
-  return bn_bwd_apply(dz, x, z, coef, bcoef, dx, dres, n, spatial, c, act, in_act, dtype, vec, s);
+  return launch_gn_bwd_apply(p, dz, nullptr, x, z, coef, dx, dres, act, in_act, GnParamGrad{}, s);
 }
 
 extern "C" int mednet_bn_act_bwd_fused(const void* dz, const void* x, const float* coef, const float* stats, const float* gamma,
@@ -1772,45 +1748,40 @@ extern "C" int mednet_bn_act_bwd_fused(const void* dz, const void* x, const floa
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "bn_act_bwd_fused: bad dtype");
   MEDNET_REQUIRE(n > 0 && c > 0 && spatial > 0 && rows > 0 && fused_partial && dz && x && coef && stats && dx, MEDNET_E_SHAPE,
                  "bn_act_bwd_fused: bad arguments");
-  const int vec = pick_vec(c, dtype);
-  MEDNET_REQUIRE(c / vec <= 256, MEDNET_E_UNSUPPORTED, "bn_act_bwd_fused: C=%d unsupported", c);
+  const GnPlan p = gn_plan(n, spatial, c, dtype, ws);
+  MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "bn_act_bwd_fused: C=%d unsupported", c);
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "bn_act_bwd_fused: workspace too small");
-  float* bcoef = (float*)ws + (size_t)n * gn_partial_rows_max(c) * c * 2;
   hipStream_t s = (hipStream_t)stream;
-  const int cw = bn_cw(c);
-  hipLaunchKernelGGL(bn_bwd_coef_kernel<true>, dim3(c / cw), dim3(BN_NT), 0, s, fused_partial, stats, gamma, bcoef, dgamma, dbeta, n, c,
-                     cw, rows * n, (double)spatial * n, frozen);
-  int rc = check_launch("bn_bwd_coef");
+  const int rc = bn_bwd_coefs<true>(p, fused_partial, rows * n, stats, gamma, dgamma, dbeta, frozen, s);
   if (rc) return rc;
-  return bn_bwd_apply(dz, x, nullptr, coef, bcoef, dx, nullptr, n, spatial, c, act, in_act, dtype, vec, s);
+  return launch_gn_bwd_apply(p, dz, nullptr, x, nullptr, coef, dx, nullptr, act, in_act, GnParamGrad{}, s);
 }
 
 extern "C" int mednet_act_fwd(const void* x, void* z, size_t count, int act, int dtype, mednet_stream stream) {
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "act_fwd: bad dtype");
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned g = flat_grid(count, 2048);
-  if (dtype == MEDNET_F32) hipLaunchKernelGGL(act_fwd_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)x, (float*)z, count, act);
-  else if (dtype == MEDNET_BF16) hipLaunchKernelGGL(act_fwd_kernel<bf16>, dim3(g), dim3(256), 0, s, (const bf16*)x, (bf16*)z, count, act);
-  else hipLaunchKernelGGL(act_fwd_kernel<f16>, dim3(g), dim3(256), 0, s, (const f16*)x, (f16*)z, count, act);
+  by_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(act_fwd_kernel<T>, dim3(flat_grid(count, 2048)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)z, count, act);
+  });
   return check_launch("act_fwd");
 }
 extern "C" int mednet_act_bwd(const void* dz, const void* z, void* dx, size_t count, int act, int dtype,
                               mednet_stream stream) {
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "act_bwd: bad dtype");
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned g = flat_grid(count, 2048);
-  if (dtype == MEDNET_F32) hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)dz, (const float*)z, (float*)dx, count, act);
-  else if (dtype == MEDNET_BF16) hipLaunchKernelGGL(act_bwd_kernel<bf16>, dim3(g), dim3(256), 0, s, (const bf16*)dz, (const bf16*)z, (bf16*)dx, count, act);
-  else hipLaunchKernelGGL(act_bwd_kernel<f16>, dim3(g), dim3(256), 0, s, (const f16*)dz, (const f16*)z, (f16*)dx, count, act);
+  by_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(flat_grid(count, 2048)), dim3(256), 0, (hipStream_t)stream, (const T*)dz, (const T*)z,
+                       (T*)dx, count, act);
+  });
   return check_launch("act_bwd");
 }
 extern "C" int mednet_add(const void* a, const void* b, void* out, size_t count, int dtype, mednet_stream stream) {
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "add: bad dtype");
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned g = flat_grid(count, 2048);
-  if (dtype == MEDNET_F32) hipLaunchKernelGGL(add_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)a, (const float*)b, (float*)out, count);
-  else if (dtype == MEDNET_BF16) hipLaunchKernelGGL(add_kernel<bf16>, dim3(g), dim3(256), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)out, count);
-  else hipLaunchKernelGGL(add_kernel<f16>, dim3(g), dim3(256), 0, s, (const f16*)a, (const f16*)b, (f16*)out, count);
+  by_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(add_kernel<T>, dim3(flat_grid(count, 2048)), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b,
+                       (T*)out, count);
+  });
   return check_launch("add");
 }
 
@@ -1820,13 +1791,12 @@ extern "C" int mednet_pool2_fwd(const void* x, void* y, int n, int d, int h, int
   MEDNET_REQUIRE(d >= 2 && h >= 2 && w >= 2, MEDNET_E_SHAPE, "pool2_fwd: dims must be >= 2");
   const int vec = c % 8 == 0 ? 8 : 1;
   const size_t total = (size_t)n * (d / 2) * (h / 2) * (w / 2) * (c / vec);
-  hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((total + 255) / 256));
-#define GO(T, V) hipLaunchKernelGGL((pool2_fwd_kernel<T, V>), grid, dim3(256), 0, s, (const T*)x, (T*)y, n, d, h, w, c, mode)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
+  by_type_vec(dtype, vec, [&](auto t, auto v) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((pool2_fwd_kernel<T, decltype(v)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, d, h,
+                       w, c, mode);
+  });
   return check_launch("pool2_fwd");
 }
 extern "C" int mednet_gn_act_pool_supported(int d, int h, int w, int c, int dtype) {
@@ -1837,16 +1807,13 @@ extern "C" int mednet_gn_act_pool_fwd(const void* x, const float* coef, const vo
   MEDNET_REQUIRE(mednet_gn_act_pool_supported(d, h, w, c, dtype), MEDNET_E_UNSUPPORTED,
                  "gn_act_pool_fwd: even dims and C %% 8 == 0 only (%dx%dx%d, C=%d, dtype %d)", d, h, w, c, dtype);
   MEDNET_REQUIRE(n > 0 && x && coef && z && pooled, MEDNET_E_SHAPE, "gn_act_pool_fwd: bad arguments");
-  const int vec = dtype == MEDNET_F32 ? 4 : 8;  // (fp32: one 16-byte access per lane and tensor, as the other fp32 GroupNorm kernels)
-  const size_t total = (size_t)n * (d / 2) * (h / 2) * (w / 2) * (c / vec);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)((total + 255) / 256));
-  if (dtype == MEDNET_BF16)
-    hipLaunchKernelGGL((gn_act_pool_fwd_kernel<bf16, 8>), grid, dim3(256), 0, s, (const bf16*)x, coef, (const bf16*)residual, (bf16*)z, (bf16*)pooled, n, d, h, w, c, act, mode);
-  else if (dtype == MEDNET_F16)
-    hipLaunchKernelGGL((gn_act_pool_fwd_kernel<f16, 8>), grid, dim3(256), 0, s, (const f16*)x, coef, (const f16*)residual, (f16*)z, (f16*)pooled, n, d, h, w, c, act, mode);
-  else
-    hipLaunchKernelGGL((gn_act_pool_fwd_kernel<float, 4>), grid, dim3(256), 0, s, (const float*)x, coef, (const float*)residual, (float*)z, (float*)pooled, n, d, h, w, c, act, mode);
+  by_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    constexpr int V = std::is_same<T, float>::value ? 4 : 8;  // (fp32: one 16-byte access per lane and tensor, as the other fp32 GroupNorm kernels)
+    const size_t total = (size_t)n * (d / 2) * (h / 2) * (w / 2) * (c / V);
+    hipLaunchKernelGGL((gn_act_pool_fwd_kernel<T, V>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const T*)x, coef, (const T*)residual, (T*)z, (T*)pooled, n, d, h, w, c, act, mode);
+  });
   return check_launch("gn_act_pool_fwd");
 }
 
@@ -1867,11 +1834,11 @@ extern "C" int mednet_pool2_bwd_act(const void* dy, const void* x, const void* a
   const int vec = c % 8 == 0 ? 8 : 1;
   const size_t total = (size_t)n * (d / 2) * (h / 2) * (w / 2) * (c / vec);
   const dim3 grid((unsigned)((total + 255) / 256));
-#define GO(T, V) hipLaunchKernelGGL((pool2_bwd_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dy, (const T*)x, (const T*)add, (T*)dx, n, d, h, w, c, mode, in_act, add_channels)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
+  by_type_vec(dtype, vec, [&](auto t, auto v) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((pool2_bwd_kernel<T, decltype(v)::value>), grid, dim3(256), 0, s, (const T*)dy, (const T*)x, (const T*)add,
+                       (T*)dx, n, d, h, w, c, mode, in_act, add_channels);
+  });
   return check_launch("pool2_bwd");
 }
 extern "C" int mednet_pool2_bwd(const void* dy, const void* x, const void* add, void* dx, int n, int d, int h, int w,
@@ -1895,17 +1862,12 @@ extern "C" int mednet_pool2_bwd_gn(const void* dy, const void* x, const void* ad
   const int rows = mednet_pool2_bwd_gn_rows(n, d, h, w, c, dtype);
   MEDNET_REQUIRE(rows > 0, MEDNET_E_UNSUPPORTED, "pool2_bwd_gn: shape %dx%dx%d c=%d dtype=%d not supported", d, h, w, c, dtype);
   MEDNET_REQUIRE(gn_y && gn_partial, MEDNET_E_SHAPE, "pool2_bwd_gn: gn_y and gn_partial are required");
-  hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)(rows / 4), n);
-  if (dtype == MEDNET_F32)
-    hipLaunchKernelGGL(pool2_bwd_gn_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, (const float*)add,
-                       (float*)dx, (const float*)gn_y, gn_partial, d, h, w, c, mode, gn_act);
-  else if (dtype == MEDNET_BF16)
-    hipLaunchKernelGGL(pool2_bwd_gn_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dy, (const bf16*)x, (const bf16*)add, (bf16*)dx,
-                       (const bf16*)gn_y, gn_partial, d, h, w, c, mode, gn_act);
-  else
-    hipLaunchKernelGGL(pool2_bwd_gn_kernel<f16>, grid, dim3(256), 0, s, (const f16*)dy, (const f16*)x, (const f16*)add, (f16*)dx,
-                       (const f16*)gn_y, gn_partial, d, h, w, c, mode, gn_act);
+  by_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(pool2_bwd_gn_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)x, (const T*)add,
+                       (T*)dx, (const T*)gn_y, gn_partial, d, h, w, c, mode, gn_act);
+  });
   return check_launch("pool2_bwd_gn");
 }
 
@@ -1914,13 +1876,12 @@ extern "C" int mednet_upcat_fwd(const void* enc, const void* x, void* out, int n
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "upcat_fwd: bad dtype");
   const int vec = (c_enc % 8 == 0 && c_x % 8 == 0) ? 8 : 1;
   const size_t total = (size_t)n * d * h * w * ((c_enc + c_x) / vec);
-  hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((total + 255) / 256));
-#define GO(T, V) hipLaunchKernelGGL((upcat_fwd_kernel<T, V>), grid, dim3(256), 0, s, (const T*)enc, (const T*)x, (T*)out, n, d, h, w, c_enc, xd, xh, xw, c_x)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
+  by_type_vec(dtype, vec, [&](auto t, auto v) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((upcat_fwd_kernel<T, decltype(v)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)enc, (const T*)x,
+                       (T*)out, n, d, h, w, c_enc, xd, xh, xw, c_x);
+  });
   return check_launch("upcat_fwd");
 }
 // ... with the GroupNorm partial sums of the concatenated tensor: partial[n][mednet_upcat_stats_chunks][c_enc + c_x][2]
@@ -1939,14 +1900,13 @@ extern "C" int mednet_upcat_fwd_stats(const void* enc, const void* x, void* out,
                  "upcat_fwd_stats: %d + %d channels, dtype %d", c_enc, c_x, dtype);
   size_t cv;
   unsigned chunks;
-  chunk_plan((size_t)d * h * w, c_enc + c_x, 8, cv, chunks);
-  hipStream_t s = (hipStream_t)stream;
+  chunk_plan((size_t)d * h * w, c_enc + c_x, 8, cv, chunks);  // (8 wide in every storage type, not GnPlan's width)
   const dim3 grid(chunks, n);
-#define GO(T) hipLaunchKernelGGL((upcat_stats_fwd_kernel<T, 8>), grid, dim3(256), 0, s, (const T*)enc, (const T*)x, (T*)out, partial, d, h, w, c_enc, xd, xh, xw, c_x, cv)
-  if (dtype == MEDNET_F32) GO(float);
-  else if (dtype == MEDNET_BF16) GO(bf16);
-  else GO(f16);
-#undef GO
+  by_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((upcat_stats_fwd_kernel<T, 8>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)enc, (const T*)x, (T*)out,
+                       partial, d, h, w, c_enc, xd, xh, xw, c_x, cv);
+  });
   return check_launch("upcat_fwd_stats");
 }
 extern "C" int mednet_upcat_bwd(const void* dout, void* denc, void* dx, int n, int d, int h, int w, int c_enc, int xd,
@@ -1959,16 +1919,12 @@ extern "C" int mednet_upcat_bwd(const void* dout, void* denc, void* dx, int n, i
   const dim3 g1((unsigned)((nvox * (c_enc / vec) + 255) / 256));
   const size_t tx = (size_t)n * xd * xh * xw * (c_x / vec);
   const dim3 g2((unsigned)((tx + 255) / 256));
-#define GO(T, V)                                                                                                        \
-  do {                                                                                                                  \
-    if (denc) hipLaunchKernelGGL((upcat_bwd_enc_kernel<T, V>), g1, dim3(256), 0, s, (const T*)dout, (T*)denc, nvox, c_enc, ct); \
-    hipLaunchKernelGGL((upcat_bwd_x_kernel<T, V>), g2, dim3(256), 0, s, (const T*)dout, (T*)dx, n, d, h, w, c_enc, xd,  \
-                       xh, xw, c_x);                                                                                    \
-  } while (0)
-  if (dtype == MEDNET_F32) { if (vec == 4) GO(float, 4); else if (vec == 8) GO(float, 8); else GO(float, 1); }
-  else if (dtype == MEDNET_BF16) { if (vec == 8) GO(bf16, 8); else GO(bf16, 1); }
-  else { if (vec == 8) GO(f16, 8); else GO(f16, 1); }
-#undef GO
+  by_type_vec(dtype, vec, [&](auto t, auto v) {
+    using T = typename decltype(t)::type;
+    constexpr int V = decltype(v)::value;
+    if (denc) hipLaunchKernelGGL((upcat_bwd_enc_kernel<T, V>), g1, dim3(256), 0, s, (const T*)dout, (T*)denc, nvox, c_enc, ct);
+    hipLaunchKernelGGL((upcat_bwd_x_kernel<T, V>), g2, dim3(256), 0, s, (const T*)dout, (T*)dx, n, d, h, w, c_enc, xd, xh, xw, c_x);
+  });
   return check_launch("upcat_bwd");
 }
 

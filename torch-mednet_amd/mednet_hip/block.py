@@ -41,73 +41,19 @@ FUSE_POOL = os.environ.get("MEDNET_FUSE_POOL", "1") == "1"  # A/B knob: the next
 
 
 def _gn_fwd(y, partial, gamma, beta, groups, eps, act, residual, pool_mode=None):
-    """-> (z, stats, coef[, pooled]).  `pool_mode`: also write the 2x2x2-pooled z in the same pass (mednet_gn_act_pool_fwd) when the
-    shape allows; the fourth result is then the pooled tensor, else None."""
-    n, c, d, h, w = y.shape
-    spatial = d * h * w
-    lib = L.lib()
-    stats = torch.empty((n, groups, 2), dtype=torch.float32, device=y.device)
-    coef = torch.empty((n, c, 2), dtype=torch.float32, device=y.device)
-    ws = L.workspace(lib.mednet_gn_ws_bytes(n, c, spatial), y.device)
-    if partial is not None:
-        L.check(lib.mednet_gn_finalize(partial.data_ptr(), partial.shape[1], gamma.data_ptr(), beta.data_ptr(), stats.data_ptr(),
-                                       coef.data_ptr(), n, spatial, c, groups, eps, ws.data_ptr(), ws.numel(), L.stream()),
-                "gn_finalize")
-    else:
-        L.check(lib.mednet_gn_stats(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), stats.data_ptr(), coef.data_ptr(), n,
-                                    spatial, c, groups, eps, L.dt(y), ws.data_ptr(), ws.numel(), L.stream()), "gn_stats")
-    z = torch.empty_like(y, memory_format=ops.CL)
-    if pool_mode is not None and FUSE_POOL and lib.mednet_gn_act_pool_supported(d, h, w, c, L.dt(y)):
-        pooled = ops.empty_cl(n, c, d // 2, h // 2, w // 2, y.dtype, y.device)
-        L.check(lib.mednet_gn_act_pool_fwd(y.data_ptr(), coef.data_ptr(), L.ptr(residual), z.data_ptr(), pooled.data_ptr(), n, d, h, w,
-                                           c, act, pool_mode, L.dt(y), L.stream()), "gn_act_pool_fwd")
-        return z, stats, coef, pooled
-    L.check(lib.mednet_gn_act_fwd(y.data_ptr(), coef.data_ptr(), L.ptr(residual), z.data_ptr(), n, spatial, c, act, L.dt(y),
-                                  L.dt(z), L.stream()), "gn_act_fwd")
-    return (z, stats, coef, None) if pool_mode is not None else (z, stats, coef)
+    """-> (z, stats, coef, pooled) on the path of ops.GroupNormActFn.  `pool_mode`: also write the 2x2x2-pooled z in the same pass
+    when the shape allows; `pooled` is None otherwise."""
+    stats, coef = ops.gn_statistics(y, gamma, beta, groups, eps, partial)
+    z, pooled = ops.norm_apply(y, coef, residual, act, pool_mode if FUSE_POOL else None)
+    return z, stats, coef, pooled
 
 
 def _gn_bwd(dz, dz2, y, z, coef, stats, gamma_p, beta_p, groups, act, want_dres, partial=None, lazy=None):
     """Returns (dy, dres, dgamma, dbeta).  `partial`: the first pass ({sum du, sum du*y} per channel) already taken by the
-    data-gradient kernel that produced dz (mednet_conv3d_dgrad_gn)."""
-    n, c, d, h, w = y.shape
-    spatial = d * h * w
-    lib = L.lib()
-    dy = torch.empty_like(y, memory_format=ops.CL)
-    dres = torch.empty_like(y, memory_format=ops.CL) if want_dres else None
-    dgamma, dg_direct = ops._grad_target(gamma_p, (c,))
-    dbeta, db_direct = ops._grad_target(beta_p, (c,))
-    ws = L.workspace(lib.mednet_gn_ws_bytes(n, c, spatial), y.device)
-    if partial is not None and z is not None and lazy is not None:
-        # residual layer of an encoder block; dz = pooling backward + skip join was NOT written (ops.SkipPool2Fn, lazy): the
-        # apply pass rebuilds its rows from the pooled gradient, the arg-max of the block output and the skip gradient
-        dy_pool, dskip, pool_mode = lazy
-        assert dz2 is None and want_dres
-        L.check(lib.mednet_gn_act_bwd_fused_res_pool(dy_pool.data_ptr(), L.ptr(dskip), y.data_ptr(), z.data_ptr(), stats.data_ptr(),
-                                                     gamma_p.data_ptr(), partial.data_ptr(), partial.shape[1], dy.data_ptr(),
-                                                     dres.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), n, d, h, w, c, groups,
-                                                     act, pool_mode, L.dt(y), ws.data_ptr(), ws.numel(), L.stream()),
-                "gn_act_bwd_fused_res_pool")
-        return dy, dres, (None if dg_direct else dgamma), (None if db_direct else dbeta)
-    if partial is not None and z is not None:  # residual layer: sums taken by the producer of dz (ops.GN3Hook)
-        assert dz2 is None and want_dres
-        L.check(lib.mednet_gn_act_bwd_fused_res(dz.data_ptr(), y.data_ptr(), z.data_ptr(), coef.data_ptr(), stats.data_ptr(),
-                                                gamma_p.data_ptr(), partial.data_ptr(), partial.shape[1], dy.data_ptr(),
-                                                dres.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), n, spatial, c, groups, act,
-                                                L.dt(y), ws.data_ptr(), ws.numel(), L.stream()), "gn_act_bwd_fused_res")
-        return dy, dres, (None if dg_direct else dgamma), (None if db_direct else dbeta)
-    if partial is not None:
-        assert dz2 is None and z is None and not want_dres
-        L.check(lib.mednet_gn_act_bwd_fused(dz.data_ptr(), y.data_ptr(), coef.data_ptr(), stats.data_ptr(), gamma_p.data_ptr(),
-                                            partial.data_ptr(), partial.shape[1], dy.data_ptr(), dgamma.data_ptr(),
-                                            dbeta.data_ptr(), n, spatial, c, groups, act, L.ACT_NONE, L.dt(y), ws.data_ptr(),
-                                            ws.numel(), L.stream()), "gn_act_bwd_fused")
-        return dy, None, (None if dg_direct else dgamma), (None if db_direct else dbeta)
-    L.check(lib.mednet_gn_act_bwd(dz.data_ptr(), L.ptr(dz2), y.data_ptr(), L.ptr(z), coef.data_ptr(), stats.data_ptr(),
-                                  gamma_p.data_ptr(), dy.data_ptr(), L.ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), n,
-                                  spatial, c, groups, act, L.ACT_NONE, L.dt(y), ws.data_ptr(), ws.numel(), L.stream()),
-            "gn_act_bwd")
-    return dy, dres, (None if dg_direct else dgamma), (None if db_direct else dbeta)
+    kernel that produced dz; `z`: the residual layer, act' from the block output; `lazy`: dz was not written (ops.gn_backward)."""
+    b = ops._NormBackward(y, gamma_p, beta_p, want_dres)
+    ops.gn_backward(b, dz, y, z, coef, stats, gamma_p, act, L.ACT_NONE, partial, groups, dz2=dz2, lazy=lazy)
+    return (b.dx, b.dres, *b.param_grads())
 
 
 FUSE_C1GN = os.environ.get("MEDNET_FUSE_C1GN", "1") == "1"  # A/B knob: first layer's GroupNorm backward inside its weight gradient
@@ -223,17 +169,15 @@ class ResBlockFn(Function):
         ctx.x_layout = x_layout
         fuse = (cout // groups) % 2 == 0  # fused partials are per channel pair (include/mednet_hip.h)
         y1, p1 = _conv_fwd(xin, pk1, cout, fuse, x_layout)
-        z1, s1, c1 = _gn_fwd(y1, p1, g1, b1, groups, eps, act, None)
+        z1, s1, c1, _ = _gn_fwd(y1, p1, g1, b1, groups, eps, act, None)
         y2, p2 = _conv_fwd(z1, pk2, cout, fuse)
-        z2, s2, c2 = _gn_fwd(y2, p2, g2, b2, groups, eps, act, None)
+        z2, s2, c2, _ = _gn_fwd(y2, p2, g2, b2, groups, eps, act, None)
         y3, p3 = _conv_fwd(z2, pk3, cout, fuse)
         # `pool`: a holder the caller reads the pooled output from (the next encoder level pools this block's output: one pass
         # writes both; ops.SkipPool2Fn uses the stash instead of launching the pooling kernel)
+        out, s3, c3, pooled = _gn_fwd(y3, p3, g3, b3, groups, eps, act, z1, pool_mode=pool.mode if pool is not None else None)
         if pool is not None:
-            out, s3, c3, pooled = _gn_fwd(y3, p3, g3, b3, groups, eps, act, z1, pool_mode=pool.mode)
             pool.pooled = pooled
-        else:
-            out, s3, c3 = _gn_fwd(y3, p3, g3, b3, groups, eps, act, z1)
         if debug.TRACE is not None:
             debug.trace("resblock.fwd", y1, p1, s1, c1, z1, y2, p2, s2, c2, z2, y3, p3, s3, c3, out)
         ctx.save_for_backward(xin, y1, z1, y2, z2, y3, out, s1, c1, s2, c2, s3, c3, pk1, pk2, pk3)

@@ -607,96 +607,188 @@ def conv_transpose3d(x, weight, bias, skip, packed):
     return ConvT3dFn.apply(x, weight, bias, skip, packed)
 
 
-# ------------------------------------------------------------------------------------------------- GroupNorm (+act, +residual)
+# ------------------------------------------------------------------------------------------------- GroupNorm / BatchNorm3d (+act, +residual)
+# One path for ops.GroupNormActFn, ops.BatchNormActFn and the ExtResNetBlock node (block.py): the statistics (gn_statistics; BatchNorm's
+# are its own), the apply pass (norm_apply), the backward's buffers (_NormBackward) and its entries (gn_backward / bn_backward).
+def gn_statistics(x, gamma, beta, groups, eps, partial=None):
+    """-> (stats [n][groups][2], coef [n][c][2]) of GroupNorm over the channels-last x.  `partial`: the sums came out of the
+    producer's epilogue (a convolution, upsample_concat) and only the finalize pass runs."""
+    n, c, d, h, w = x.shape
+    spatial = d * h * w
+    lib = L.lib()
+    stats = torch.empty((n, groups, 2), dtype=torch.float32, device=x.device)
+    coef = torch.empty((n, c, 2), dtype=torch.float32, device=x.device)
+    ws = L.workspace(lib.mednet_gn_ws_bytes(n, c, spatial), x.device)
+    if partial is not None:
+        L.check(lib.mednet_gn_finalize(partial.data_ptr(), partial.shape[1], L.ptr(gamma), L.ptr(beta), stats.data_ptr(),
+                                       coef.data_ptr(), n, spatial, c, groups, eps, ws.data_ptr(), ws.numel(),
+                                       L.stream()), "gn_finalize")
+    else:
+        L.check(lib.mednet_gn_stats(x.data_ptr(), L.ptr(gamma), L.ptr(beta), stats.data_ptr(), coef.data_ptr(), n,
+                                    spatial, c, groups, eps, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "gn_stats")
+    return stats, coef
+
+
+def norm_apply(x, coef, residual, act, pool_mode=None):
+    """z = act(coef_a * x + coef_b [+ residual]) -> (z, pooled).  `pool_mode`: also write the 2x2x2-pooled z in the same pass
+    (mednet_gn_act_pool_fwd) when the shape allows; `pooled` is None otherwise."""
+    n, c, d, h, w = x.shape
+    lib = L.lib()
+    z = torch.empty_like(x, memory_format=CL)
+    if pool_mode is not None and lib.mednet_gn_act_pool_supported(d, h, w, c, L.dt(x)):
+        pooled = empty_cl(n, c, d // 2, h // 2, w // 2, x.dtype, x.device)
+        L.check(lib.mednet_gn_act_pool_fwd(x.data_ptr(), coef.data_ptr(), L.ptr(residual), z.data_ptr(), pooled.data_ptr(), n, d, h, w,
+                                           c, act, pool_mode, L.dt(x), L.stream()), "gn_act_pool_fwd")
+        return z, pooled
+    L.check(lib.mednet_gn_act_fwd(x.data_ptr(), coef.data_ptr(), L.ptr(residual), z.data_ptr(), n, d * h * w, c, act,
+                                  L.dt(x), L.dt(z), L.stream()), "gn_act_fwd")
+    return z, None
+
+
+class _NormBackward:
+    """What the backward of a normalisation (+ activation) layer sets up -- the gradient of its input, of the residual branch when
+    there is one, the targets of the parameter gradients (_grad_target), the workspace -- and what autograd gets for the parameters."""
+
+    def __init__(self, x, gamma_p, beta_p, want_dres):
+        n, c, d, h, w = x.shape
+        self.dx = torch.empty_like(x, memory_format=CL)
+        self.dres = torch.empty_like(x, memory_format=CL) if want_dres else None
+        self.dgamma, self.direct_g = _grad_target(gamma_p, (c,)) if gamma_p is not None else (None, False)
+        self.dbeta, self.direct_b = _grad_target(beta_p, (c,)) if beta_p is not None else (None, False)
+        self.ws = L.workspace(L.lib().mednet_gn_ws_bytes(n, c, d * h * w), x.device)
+
+    def param_grads(self):
+        return (None if self.direct_g else self.dgamma), (None if self.direct_b else self.dbeta)
+
+
+def gn_backward(b, dz, x, z, coef, stats, gamma, act, in_act, partial, groups, dz2=None, lazy=None):
+    """GroupNorm (+ activation, + residual) backward into the buffers of `b`, in one of four forms.  No `partial`: all three
+    passes (mednet_gn_act_bwd; `dz2`: a second gradient stream, read beside dz).  `partial` = the first pass's rows, taken by the
+    producer of dz (GNBHook / GN3Hook): the plain layer (mednet_gn_act_bwd_fused); with the activated output `z`, the residual layer
+    of a block (_fused_res); with `lazy` = (dy_pool, skip gradient, pool mode), the residual layer of an encoder block whose dz was
+    NOT written (SkipPool2Fn, lazy): the apply pass rebuilds its rows per pooling window (_fused_res_pool)."""
+    n, c, d, h, w = x.shape
+    spatial = d * h * w
+    lib = L.lib()
+    grads, tail = (L.ptr(b.dgamma), L.ptr(b.dbeta)), (L.dt(x), b.ws.data_ptr(), b.ws.numel(), L.stream())
+    if partial is None:
+        L.check(lib.mednet_gn_act_bwd(dz.data_ptr(), L.ptr(dz2), x.data_ptr(), L.ptr(z), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
+                                      b.dx.data_ptr(), L.ptr(b.dres), *grads, n, spatial, c, groups, act, in_act, *tail), "gn_act_bwd")
+        return
+    assert dz2 is None and (z is None) == (b.dres is None)
+    if lazy is not None:
+        dy_pool, dskip, pool_mode = lazy
+        L.check(lib.mednet_gn_act_bwd_fused_res_pool(dy_pool.data_ptr(), L.ptr(dskip), x.data_ptr(), z.data_ptr(), stats.data_ptr(),
+                                                     gamma.data_ptr(), partial.data_ptr(), partial.shape[1], b.dx.data_ptr(),
+                                                     b.dres.data_ptr(), *grads, n, d, h, w, c, groups, act, pool_mode, *tail),
+                "gn_act_bwd_fused_res_pool")
+    elif z is not None:
+        assert in_act == L.ACT_NONE
+        L.check(lib.mednet_gn_act_bwd_fused_res(dz.data_ptr(), x.data_ptr(), z.data_ptr(), coef.data_ptr(), stats.data_ptr(),
+                                                gamma.data_ptr(), partial.data_ptr(), partial.shape[1], b.dx.data_ptr(),
+                                                b.dres.data_ptr(), *grads, n, spatial, c, groups, act, *tail), "gn_act_bwd_fused_res")
+    else:
+        L.check(lib.mednet_gn_act_bwd_fused(dz.data_ptr(), x.data_ptr(), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
+                                            partial.data_ptr(), partial.shape[1], b.dx.data_ptr(), *grads, n, spatial, c, groups, act,
+                                            in_act, *tail), "gn_act_bwd_fused")
+
+
+def bn_backward(b, dz, x, z, coef, stats, gamma, act, in_act, partial, frozen):
+    """BatchNorm3d (+ activation, + residual) backward into the buffers of `b`: all three passes (mednet_bn_act_bwd), or the last
+    two over the rows the producer of dz took (BNBHook, mednet_bn_act_bwd_fused).  `frozen`: evaluation mode, constant statistics."""
+    n, c, d, h, w = x.shape
+    lib = L.lib()
+    tail = (n, d * h * w, c, act, in_act, int(frozen), L.dt(x), b.ws.data_ptr(), b.ws.numel(), L.stream())
+    if partial is not None:
+        L.check(lib.mednet_bn_act_bwd_fused(dz.data_ptr(), x.data_ptr(), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
+                                            partial.data_ptr(), partial.shape[1], b.dx.data_ptr(), L.ptr(b.dgamma), L.ptr(b.dbeta),
+                                            *tail), "bn_act_bwd_fused")
+    else:
+        L.check(lib.mednet_bn_act_bwd(dz.data_ptr(), x.data_ptr(), L.ptr(z), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
+                                      b.dx.data_ptr(), L.ptr(b.dres), L.ptr(b.dgamma), L.ptr(b.dbeta), *tail), "bn_act_bwd")
+
+
+def _norm_input(ctx, x, who):
+    """Forward prologue of both nodes: x in channels-last storage, and ctx.inmask = the ActMaskHook x carries, if it is honoured."""
+    L.require_gpu(x, who)
+    x0 = x
+    x = to_cl(_as_act(x))
+    ctx.inmask = getattr(x0, "_mednet_actmask", None) if (x is x0 and FUSE_GN3) else None
+    # The fold multiplies dx by act'(x) HERE; the conv layer skips its own activation backward only if the gradient it
+    # receives is this very tensor (ActMaskHook.take).  If it declines (x has a second consumer, a tensor hook replaced
+    # the gradient) act' is applied twice to this contribution: idempotent for ReLU (a 0/1 mask), wrong for
+    # LeakyReLU / ELU -- so only ReLU layers are folded.
+    if ctx.inmask is not None and ctx.inmask.act != L.ACT_RELU:
+        ctx.inmask = None
+    return x
+
+
+def _norm_output(ctx, x, stats, coef, gamma, beta, residual, act, hook, extra):
+    """The apply pass of both nodes and what they keep for the backward (`extra`: groups / frozen)."""
+    res = None
+    if residual is not None:
+        res = to_cl(residual.to(x.dtype))
+    z, _ = norm_apply(x, coef, res, act)
+    # the activated output is only read back when a residual entered the pre-activation; otherwise the backward
+    # recomputes act' from x and `coef` (one tensor less to read in each of its two passes)
+    keep_z = act != L.ACT_NONE and residual is not None
+    ctx.save_for_backward(x, z if keep_z else None, stats, gamma, coef)
+    ctx.meta = (act, residual is not None, extra)
+    ctx.params = (gamma, beta)
+    ctx.gnb = hook
+    if hook is not None:
+        hook.gn_in, hook.coef, hook.act = x, coef, act
+    return z
+
+
+def _norm_backward(ctx, dz, entries, n_inputs):
+    """Backward of both nodes around `entries` (gn_backward / bn_backward): takes the hook's rows, sets the buffers up, offers dx to
+    the activation mask -> the gradients of (x, gamma, beta, residual), None for every input behind them."""
+    x, z, stats, gamma, coef = ctx.saved_tensors
+    act, has_res, extra = ctx.meta
+    fused = ctx.gnb.take(dz) if ctx.gnb is not None else None  # (before any conversion: identity matters)
+    dz = to_cl(dz.to(x.dtype))
+    b = _NormBackward(x, *ctx.params, has_res)
+    inmask = ctx.inmask  # x is the output of a fused conv -> activation layer: fold act'(x) into dx (ActMaskHook)
+    in_act = inmask.act if inmask is not None else L.ACT_NONE
+    if inmask is not None:
+        inmask.offer(b.dx)
+    # (the rows only without a residual: the first pass was taken by the conv data gradient that produced dz)
+    entries(b, dz, x, z, coef, stats, gamma, act, in_act, None if has_res else fused, extra)
+    return (b.dx, *b.param_grads(), b.dres) + (None,) * (n_inputs - 4)
+
+
+def _norm_hook(kind, gamma, residual):
+    """GNBHook / BNBHook for a layer whose consumer may take its first backward pass, or None."""
+    if FUSE_GN3 and residual is None and config.is_half_mode() and torch.is_grad_enabled() and gamma is not None:
+        return kind()
+    return None
+
+
 class GroupNormActFn(Function):
     """z = act(GroupNorm(x) [+ residual])  -- components.py:57, :36-40, :177-178."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, groups, eps, act, partial=None, hook=None):
-        L.require_gpu(x, "group_norm_act")
-        x0 = x
-        x = to_cl(_as_act(x))
-        ctx.inmask = getattr(x0, "_mednet_actmask", None) if (x is x0 and FUSE_GN3) else None
-        # The fold multiplies dx by act'(x) HERE; the conv layer skips its own activation backward only if the gradient it
-        # receives is this very tensor (ActMaskHook.take).  If it declines (x has a second consumer, a tensor hook replaced
-        # the gradient) act' is applied twice to this contribution: idempotent for ReLU (a 0/1 mask), wrong for
-        # LeakyReLU / ELU -- so only ReLU layers are folded.
-        if ctx.inmask is not None and ctx.inmask.act != L.ACT_RELU:
-            ctx.inmask = None
-        n, c, d, h, w = x.shape
-        if c % groups:
-            raise RuntimeError(f"group_norm: C={c} not divisible by num_groups={groups}")
-        spatial = d * h * w
-        lib = L.lib()
-        stats = torch.empty((n, groups, 2), dtype=torch.float32, device=x.device)
-        coef = torch.empty((n, c, 2), dtype=torch.float32, device=x.device)
-        ws = L.workspace(lib.mednet_gn_ws_bytes(n, c, spatial), x.device)
-        if partial is not None:  # partial sums came out of the producing conv's epilogue
-            L.check(lib.mednet_gn_finalize(partial.data_ptr(), partial.shape[1], L.ptr(gamma), L.ptr(beta), stats.data_ptr(),
-                                           coef.data_ptr(), n, spatial, c, groups, eps, ws.data_ptr(), ws.numel(),
-                                           L.stream()), "gn_finalize")
-        else:
-            L.check(lib.mednet_gn_stats(x.data_ptr(), L.ptr(gamma), L.ptr(beta), stats.data_ptr(), coef.data_ptr(), n,
-                                        spatial, c, groups, eps, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "gn_stats")
-        res = None
-        if residual is not None:
-            res = to_cl(residual.to(x.dtype))
-        z = torch.empty_like(x, memory_format=CL)
-        L.check(lib.mednet_gn_act_fwd(x.data_ptr(), coef.data_ptr(), L.ptr(res), z.data_ptr(), n, spatial, c, act,
-                                      L.dt(x), L.dt(z), L.stream()), "gn_act_fwd")
-        # the activated output is only read back when a residual entered the pre-activation; otherwise the backward
-        # recomputes act' from x and `coef` (one tensor less to read in each of its two passes)
-        keep_z = act != L.ACT_NONE and residual is not None
-        ctx.save_for_backward(x, z if keep_z else None, stats, gamma, coef)
-        ctx.meta = (groups, act, residual is not None, gamma is not None, beta is not None)
-        ctx.params = (gamma, beta)
-        ctx.gnb = hook
-        if hook is not None:
-            hook.gn_in, hook.coef, hook.act = x, coef, act
-        return z
+        x = _norm_input(ctx, x, "group_norm_act")
+        if x.shape[1] % groups:
+            raise RuntimeError(f"group_norm: C={x.shape[1]} not divisible by num_groups={groups}")
+        stats, coef = gn_statistics(x, gamma, beta, groups, eps, partial)
+        return _norm_output(ctx, x, stats, coef, gamma, beta, residual, act, hook, groups)
 
     @staticmethod
     def backward(ctx, dz):
-        x, z, stats, gamma, coef = ctx.saved_tensors
-        groups, act, has_res, has_gamma, has_beta = ctx.meta
-        n, c, d, h, w = x.shape
-        spatial = d * h * w
-        fused = ctx.gnb.take(dz) if ctx.gnb is not None else None  # (before any conversion: identity matters)
-        dz = to_cl(dz.to(x.dtype))
-        lib = L.lib()
-        dx = torch.empty_like(x, memory_format=CL)
-        dres = torch.empty_like(x, memory_format=CL) if has_res else None
-        pg, pb = ctx.params
-        dgamma, direct_g = _grad_target(pg, (c,)) if has_gamma else (None, False)
-        dbeta, direct_b = _grad_target(pb, (c,)) if has_beta else (None, False)
-        ws = L.workspace(lib.mednet_gn_ws_bytes(n, c, spatial), x.device)
-        inmask = ctx.inmask  # x is the output of a fused conv -> activation layer: fold act'(x) into dx (ActMaskHook)
-        in_act = inmask.act if inmask is not None else L.ACT_NONE
-        if inmask is not None:
-            inmask.offer(dx)
-        if fused is not None and not has_res:  # first pass taken by the conv data gradient that produced dz
-            L.check(lib.mednet_gn_act_bwd_fused(dz.data_ptr(), x.data_ptr(), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
-                                                fused.data_ptr(), fused.shape[1], dx.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), n,
-                                                spatial, c, groups, act, in_act, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()),
-                    "gn_act_bwd_fused")
-            return dx, (None if direct_g else dgamma), (None if direct_b else dbeta), dres, None, None, None, None, None
-        L.check(lib.mednet_gn_act_bwd(dz.data_ptr(), None, x.data_ptr(), L.ptr(z), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
-                                      dx.data_ptr(), L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta), n, spatial, c, groups, act, in_act,
-                                      L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "gn_act_bwd")
-        return dx, (None if direct_g else dgamma), (None if direct_b else dbeta), dres, None, None, None, None, None
+        return _norm_backward(ctx, dz, gn_backward, 9)
 
 
 def group_norm_act(x, gamma, beta, groups, eps=1e-5, act=L.ACT_NONE, residual=None, partial=None):
-    hook = None
-    if FUSE_GN3 and residual is None and config.is_half_mode() and torch.is_grad_enabled() and gamma is not None:
-        hook = GNBHook()  # the conv that consumes z may take this GroupNorm's first backward pass (see GNBHook)
+    hook = _norm_hook(GNBHook, gamma, residual)
     z = GroupNormActFn.apply(x, gamma, beta, residual, groups, eps, act, partial, hook)
     if hook is not None:
         z._mednet_gnb = hook
     return z
 
 
-# ------------------------------------------------------------------------------------------------- BatchNorm3d (+act, +residual)
 class BatchNormActFn(Function):
     """z = act(BatchNorm3d(x) [+ residual])  -- components.py:58-63, :36-40, :177-178.  The statistics pass and both backward
     first passes are GroupNorm's kernels over the channels-last batch; the reduction across samples, the running statistics and
@@ -705,12 +797,7 @@ class BatchNormActFn(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running, training, momentum, eps, act, hook=None):
-        L.require_gpu(x, "batch_norm_act")
-        x0 = x
-        x = to_cl(_as_act(x))
-        ctx.inmask = getattr(x0, "_mednet_actmask", None) if (x is x0 and FUSE_GN3) else None
-        if ctx.inmask is not None and ctx.inmask.act != L.ACT_RELU:  # (only ReLU layers are folded: GroupNormActFn.forward says why)
-            ctx.inmask = None
+        x = _norm_input(ctx, x, "batch_norm_act")
         n, c, d, h, w = x.shape
         spatial = d * h * w
         lib = L.lib()
@@ -729,50 +816,11 @@ class BatchNormActFn(Function):
             rm, rv, _ = running
             L.check(lib.mednet_bn_eval_coef(rm.data_ptr(), rv.data_ptr(), L.ptr(gamma), L.ptr(beta), stats.data_ptr(),
                                             coef.data_ptr(), n, c, eps, L.stream()), "bn_eval_coef")
-        res = None
-        if residual is not None:
-            res = to_cl(residual.to(x.dtype))
-        z = torch.empty_like(x, memory_format=CL)
-        L.check(lib.mednet_gn_act_fwd(x.data_ptr(), coef.data_ptr(), L.ptr(res), z.data_ptr(), n, spatial, c, act,
-                                      L.dt(x), L.dt(z), L.stream()), "gn_act_fwd")
-        keep_z = act != L.ACT_NONE and residual is not None  # (as GroupNormActFn: else act' is recomputed from x and coef)
-        ctx.save_for_backward(x, z if keep_z else None, stats, gamma, coef)
-        ctx.meta = (act, residual is not None, gamma is not None, beta is not None, not batch_stats)
-        ctx.params = (gamma, beta)
-        ctx.gnb = hook
-        if hook is not None:
-            hook.gn_in, hook.coef, hook.act = x, coef, act
-        return z
+        return _norm_output(ctx, x, stats, coef, gamma, beta, residual, act, hook, not batch_stats)
 
     @staticmethod
     def backward(ctx, dz):
-        x, z, stats, gamma, coef = ctx.saved_tensors
-        act, has_res, has_gamma, has_beta, frozen = ctx.meta
-        n, c, d, h, w = x.shape
-        spatial = d * h * w
-        fused = ctx.gnb.take(dz) if ctx.gnb is not None else None  # (before any conversion: identity matters)
-        dz = to_cl(dz.to(x.dtype))
-        lib = L.lib()
-        dx = torch.empty_like(x, memory_format=CL)
-        dres = torch.empty_like(x, memory_format=CL) if has_res else None
-        pg, pb = ctx.params
-        dgamma, direct_g = _grad_target(pg, (c,)) if has_gamma else (None, False)
-        dbeta, direct_b = _grad_target(pb, (c,)) if has_beta else (None, False)
-        ws = L.workspace(lib.mednet_gn_ws_bytes(n, c, spatial), x.device)
-        inmask = ctx.inmask  # x is the output of a fused conv -> activation layer: fold act'(x) into dx (ActMaskHook)
-        in_act = inmask.act if inmask is not None else L.ACT_NONE
-        if inmask is not None:
-            inmask.offer(dx)
-        if fused is not None and not has_res:  # first pass taken by the conv data gradient that produced dz
-            L.check(lib.mednet_bn_act_bwd_fused(dz.data_ptr(), x.data_ptr(), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
-                                                fused.data_ptr(), fused.shape[1], dx.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), n,
-                                                spatial, c, act, in_act, int(frozen), L.dt(x), ws.data_ptr(), ws.numel(),
-                                                L.stream()), "bn_act_bwd_fused")
-        else:
-            L.check(lib.mednet_bn_act_bwd(dz.data_ptr(), x.data_ptr(), L.ptr(z), coef.data_ptr(), stats.data_ptr(), L.ptr(gamma),
-                                          dx.data_ptr(), L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta), n, spatial, c, act, in_act,
-                                          int(frozen), L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "bn_act_bwd")
-        return dx, (None if direct_g else dgamma), (None if direct_b else dbeta), dres, None, None, None, None, None, None
+        return _norm_backward(ctx, dz, bn_backward, 10)
 
 
 def batch_norm_act(x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, training=True, momentum=0.1,
@@ -791,9 +839,7 @@ def batch_norm_act(x, gamma, beta, running_mean=None, running_var=None, num_batc
             if t is None or t.dtype != dt or t.device != x.device or not t.is_contiguous():
                 raise RuntimeError(f"batch_norm: {name} must be a contiguous {dt} tensor on {x.device}")
         running = (running_mean, running_var, num_batches_tracked)
-    hook = None
-    if FUSE_GN3 and residual is None and config.is_half_mode() and torch.is_grad_enabled() and gamma is not None:
-        hook = BNBHook()  # the conv that consumes z may take this BatchNorm's first backward pass (see GNBHook)
+    hook = _norm_hook(BNBHook, gamma, residual)
     z = BatchNormActFn.apply(x, gamma, beta, residual, running, bool(training), float(momentum), float(eps), act, hook)
     if hook is not None:
         z._mednet_gnb = hook
