@@ -424,6 +424,35 @@ def test_normalisation_entries_refuse_what_they_refused_in_the_same_order(golden
     assert all(r["rc"] < 0 for r in want if r["error"])  # (a refusal each: nothing in the table reached a launch)
 
 
+def test_convolution_entries_refuse_and_answer_what_they_did_before_their_host_code_was_shared(golden_dir):
+    """tools/conv_routes.py: every conv-family extern "C" entry of csrc/api.hip with argument sets that trip each of its checks in
+    turn (bad dtype, ksize = 2, a zero extent, null gn_* pointers, negative workgroups, a workspace one byte short for the bias
+    gradient, MEDNET_ALGO_MFMA on shapes the matrix-core path does not take, an activation out of range, two at once, the options
+    that switch a fused form off) -- all refused before any launch -- and every entry that answers a number (rows, chunks, plans,
+    workspace and pack sizes, the *_supported predicates) at points of volumes x channel pairs x storage types x algo, with
+    assume_cus = 256, no device needed.  tests/golden/conv_routes.jsonl is the table the library printed BEFORE the family's host code was put
+    on one launch idiom, one variant table and shared route predicates: every code, message and number is frozen."""
+    import importlib.util
+    import json
+    import os
+    from mednet_hip import _lib as L
+    spec = importlib.util.spec_from_file_location("conv_routes", os.path.join(os.path.dirname(golden_dir), "..", "tools", "conv_routes.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(golden_dir, "conv_routes.jsonl")) as f:
+        want = [json.loads(line) for line in f]
+    got = tool.run(L.lib())
+    assert len(want) == 375 and [r["case"] for r in got] == [r["case"] for r in want]
+    for g, w in zip(got, want):
+        assert g == w, (g, w)
+    refused = [r for r in want if "error" in r]
+    assert len(refused) == 231 and all(r["rc"] in (-1, -2, -3, -5) for r in refused)  # (a check's refusal each: nothing reached a launch)
+    plans = [a for r in want if r["case"].startswith("plan") for a in r["answers"].items()]
+    kinds = lambda name: {p[0] for k, v in plans if k.startswith(name) for p in v if isinstance(p, list)}  # noqa: E731
+    assert kinds("stats_plan") == {2, 3, 4, 5, 6, 7}  # (every kind of the forward / data-gradient family's plan occurs)
+    assert kinds("wgrad_plan") == {2, 4}
+
+
 def test_fused_head_nodes_step_aside_for_hooks_on_the_bypassed_calls():
     """The fused head + loss nodes (train.SegmentationStep._head_loss, LandmarkStep._head_losses) call forward_features() and never
     final_conv: a forward hook / pre-hook on the model or on final_conv would not fire, so the steps take the stock model(inputs)

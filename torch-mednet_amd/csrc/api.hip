@@ -62,6 +62,19 @@ static inline int algo_base(int a) { return (a & 3) == MEDNET_ALGO_EXACT ? MEDNE
 // weight images too; the pack must hold them (MEDNET_PACK_LOW for fp16 packs, every bf16 pack).  -> distance of the low image
 static inline size_t algo_lo_delta(int a, int dtype, const PackLayout& L) { return (a & MEDNET_ALGO_SPLITW_BIT) && is16(dtype) ? L.lo_delta : 0; }
 static inline bool algo_split(int a, int dtype) { return (a & MEDNET_ALGO_SPLITW_BIT) && is16(dtype); }
+// fp32 storage on the matrix cores (the 1e-3 parity mode): both tensors fp32, any choice but DIRECT, option f32_mfma on ...
+static inline bool algo_f32_mode(int a, int dt1, int dt2) {
+  return algo_base(a) != MEDNET_ALGO_DIRECT && conv_f32_mfma_enabled() && dt1 == MEDNET_F32 && dt2 == MEDNET_F32;
+}
+// ... by the split-bf16 contraction (conv_x3_mfma.hip) where it takes the shape, not by the fp32 matrix instruction
+static inline bool algo_x3(int a) { return !algo_exact(a) && conv_x3_enabled(); }
+// the image of a pack that a forward (dgrad = 0) or data-gradient call reads: the 16-bit fragment image / the fp32 tap-major one
+static inline const char* pack_mfma(const void* packed, const PackLayout& L, int dgrad) {
+  return (const char*)packed + (dgrad ? L.mfma_bwd : L.mfma_fwd);
+}
+static inline const float* pack_f32(const void* packed, const PackLayout& L, int dgrad) {
+  return (const float*)((const char*)packed + (dgrad ? L.f32_bwd : L.f32_fwd));
+}
 
 extern "C" int mednet_set_option(const char* name, int value) {
   for (int i = 0; i < g_noptions; ++i)
@@ -189,7 +202,7 @@ extern "C" int mednet_conv3d_fused_stats_chunks(int n, int d, int h, int w, int 
                                                 int y_dtype, int algo) {
   if (algo_base(algo) == MEDNET_ALGO_DIRECT || !tuning_option("conv_fuse_stats", 1)) return 0;
   if (x_dtype == MEDNET_F32 && y_dtype == MEDNET_F32) {  // fp32 storage: the split-bf16 forward kernels keep the sums per wave
-    if (!(conv_f32_mfma_enabled() && !algo_exact(algo) && conv_x3_enabled())) return 0;
+    if (!(algo_f32_mode(algo, x_dtype, y_dtype) && algo_x3(algo))) return 0;
     if (conv_c1_x3_supported(cin, cout, ksize)) return tuning_option("x3_stats", 1) ? conv_c1_x3_stats_rows(d, h, w) : 0;
     return conv_x3_supported(cin, cout, ksize) && conv_x3_fits(d, h, w, cin) ? conv_x3_stats_rows(n, d, h, w, cout) : 0;
   }
@@ -218,54 +231,61 @@ extern "C" int mednet_conv3d_fwd(const void* x, const void* packed, const float*
   if (rc) return rc;
   // the pack was built for the layer's (Cin,Cout); a dgrad call swaps the roles
   const PackLayout L = dgrad ? pack_layout(cout, cin, ksize) : pack_layout(cin, cout, ksize);
-  const char* base = (const char*)packed;
   hipStream_t s = (hipStream_t)stream;
   const bool mfma_ok = ELT_CALL(y_dtype, conv_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, x_layout, y_layout, bias != nullptr) &&
                        conv_mfma_fits(n, d, h, w, cin);
   // fp32 storage (the 1e-3 parity mode): 3x3x3 forward / data gradient on the matrix cores -- the split-bf16 contraction (three
   // bf16 MFMAs per product; the pack must hold the low images: mednet_conv3d_pack_elt(MEDNET_F32)) or, for shapes it does not
   // take and under ALGO_EXACT, the fp32 matrix instruction.  Both satisfy MEDNET_ALGO_MFMA ("a matrix-core path is required").
-  const bool f32_mode = algo_base(algo) != MEDNET_ALGO_DIRECT && conv_f32_mfma_enabled() && ksize == 3 && x_dtype == MEDNET_F32 &&
-                        y_dtype == MEDNET_F32 && (x_layout == MEDNET_NDHWC || cin == 1) && y_layout == MEDNET_NDHWC;
+  const bool f32_mode = algo_f32_mode(algo, x_dtype, y_dtype) && ksize == 3 && (x_layout == MEDNET_NDHWC || cin == 1) && y_layout == MEDNET_NDHWC;
   // multi-channel first layer (2-4 input channels, read planar or channels-last where they lie): contraction over Cin x 27 taps
   if (!dgrad && !bias && y_layout == MEDNET_NDHWC && (x_layout == MEDNET_NDHWC || x_layout == MEDNET_NCDHW) &&
       mednet_conv3d_cm_supported(cin, cout, ksize, x_dtype, y_dtype, algo))
-    return ELT_CALL(y_dtype, launch_conv_first_mfma, x, x_layout, x_dtype, (const float*)(base + L.f32_fwd), y, n, d, h, w, cin, cout,
+    return ELT_CALL(y_dtype, launch_conv_first_mfma, x, x_layout, x_dtype, pack_f32(packed, L, 0), y, n, d, h, w, cin, cout,
                     gn_partial, s, algo_split(algo, y_dtype) ? 1 : 0);
   if (algo_base(algo) == MEDNET_ALGO_MFMA && !mfma_ok && !f32_mode)
     return fail(MEDNET_E_UNSUPPORTED, "conv3d_fwd: MFMA path does not take cin=%d cout=%d k=%d dtypes %d->%d", cin, cout,
                 ksize, x_dtype, y_dtype);
   if (mfma_ok && algo_base(algo) != MEDNET_ALGO_DIRECT)
-    return ELT_CALL(y_dtype, launch_conv_mfma, x, base + (dgrad ? L.mfma_bwd : L.mfma_fwd), y, n, d, h, w, cin, cout, x_dtype,
+    return ELT_CALL(y_dtype, launch_conv_mfma, x, pack_mfma(packed, L, dgrad), y, n, d, h, w, cin, cout, x_dtype,
                     y_dtype, gn_partial, s, MEDNET_ACT_NONE, nullptr, algo_lo_delta(algo, y_dtype, L));
   // first layer (one input channel): contraction over the 27 taps on the matrix cores
   if (!dgrad && algo_base(algo) != MEDNET_ALGO_DIRECT && x_layout == MEDNET_NDHWC && cin == 1 &&
       ELT_CALL(y_dtype, conv_first_mfma_supported, cin, cout, ksize, x_dtype, y_dtype, y_layout, bias != nullptr))
-    return ELT_CALL(y_dtype, launch_conv_first_mfma, x, x_layout, x_dtype, (const float*)(base + L.f32_fwd), y, n, d, h, w, cin, cout,
+    return ELT_CALL(y_dtype, launch_conv_first_mfma, x, x_layout, x_dtype, pack_f32(packed, L, 0), y, n, d, h, w, cin, cout,
                     gn_partial, s, algo_split(algo, y_dtype) ? 1 : 0);
   // fp32 storage: the split-bf16 contraction ...
-  if (f32_mode && (!algo_exact(algo) && conv_x3_enabled()) && L.mfma_bytes && conv_x3_supported(cin, cout, ksize) && conv_x3_fits(d, h, w, cin))
-    return launch_conv_x3(x, base + (dgrad ? L.mfma_bwd : L.mfma_fwd), L.lo_delta, bias, y, n, d, h, w, cin, cout, gn_partial, s);
-  if (f32_mode && !dgrad && !algo_exact(algo) && conv_x3_enabled() && conv_c1_x3_supported(cin, cout, ksize))  // first layer
-    return launch_conv_c1_x3(x, (const float*)(base + L.f32_fwd), bias, y, n, d, h, w, cout, gn_partial, s);
+  if (f32_mode && algo_x3(algo) && L.mfma_bytes && conv_x3_supported(cin, cout, ksize) && conv_x3_fits(d, h, w, cin))
+    return launch_conv_x3(x, pack_mfma(packed, L, dgrad), L.lo_delta, bias, y, n, d, h, w, cin, cout, gn_partial, s);
+  if (f32_mode && !dgrad && algo_x3(algo) && conv_c1_x3_supported(cin, cout, ksize))  // first layer
+    return launch_conv_c1_x3(x, pack_f32(packed, L, 0), bias, y, n, d, h, w, cout, gn_partial, s);
   MEDNET_REQUIRE(gn_partial == nullptr, MEDNET_E_UNSUPPORTED,
                  "conv3d_fwd: fused GroupNorm partials are only produced by the MFMA paths (ask mednet_conv3d_fused_stats_chunks)");
   // ... or, for the shapes those kernels do not take (odd channel counts; ALGO_EXACT), on the fp32 matrix-core instruction
   if (f32_mode)
-    return launch_conv_f32_mfma(x, (const float*)(base + (dgrad ? L.f32_bwd : L.f32_fwd)), bias, y, n, d, h, w, cin, cout, s);
+    return launch_conv_f32_mfma(x, pack_f32(packed, L, dgrad), bias, y, n, d, h, w, cin, cout, s);
   // 1x1x1 head forward (channels-last features -> planar fp32 logits): the packed backward image Pb[t=0][co][ci] = W[m][k]
   if (!dgrad && algo_base(algo) != MEDNET_ALGO_DIRECT && ksize == 1 && x_layout == MEDNET_NDHWC && y_layout == MEDNET_NCDHW &&
       y_dtype == MEDNET_F32 && head_vox_supported(cin))
-    return launch_head_fwd_vox(x, (const float*)(base + L.f32_bwd), bias, (float*)y, n, (size_t)d * h * w, cin, cout, x_dtype, s);
+    return launch_head_fwd_vox(x, pack_f32(packed, L, 1), bias, (float*)y, n, (size_t)d * h * w, cin, cout, x_dtype, s);
   // data gradient of the 1x1x1 head: the packed backward image Pb[t=0][co][ci] is exactly W[m][k]
   if (dgrad && !bias && algo_base(algo) != MEDNET_ALGO_DIRECT && head_dgrad_supported(cin, cout, ksize, x_dtype, x_layout, y_layout))
-    return launch_head_dgrad(x, (const float*)(base + L.f32_bwd), y, n, (size_t)d * h * w, cin, cout, y_dtype, s);
+    return launch_head_dgrad(x, pack_f32(packed, L, 1), y, n, (size_t)d * h * w, cin, cout, y_dtype, s);
   ConvGeom g;
   g.n = n; g.od = d; g.oh = h; g.ow = w; g.id = d; g.ih = h; g.iw = w;
   g.k = cin; g.m = cout; g.ks = ksize;
   g.in_planar = x_layout == MEDNET_NCDHW; g.out_planar = y_layout == MEDNET_NCDHW;
-  return launch_direct<MAP_CONV>(x, (const float*)(base + (dgrad ? L.f32_bwd : L.f32_fwd)), bias, nullptr, y, g, x_dtype,
-                                 y_dtype, s);
+  return launch_direct<MAP_CONV>(x, pack_f32(packed, L, dgrad), bias, nullptr, y, g, x_dtype, y_dtype, s);
+}
+
+// The bias gradient of a weight-gradient entry: the channel sums of dy, whose partial rows are carved from the tail of the workspace
+// (ws_bytes becomes what lies in front of them)
+static int bias_gradient(const char* who, const void* dy, float* dbias, int n, size_t spatial, int cout, int planar, int dy_dtype, void* ws,
+                         size_t& ws_bytes, hipStream_t s) {
+  const size_t need = channel_sum_ws_bytes(n, spatial, cout);
+  MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "%s: workspace too small for the bias gradient", who);
+  ws_bytes = (ws_bytes - need) / 256 * 256;
+  return launch_channel_sum(dy, dbias, n, spatial, cout, planar, dy_dtype, (char*)ws + ws_bytes, need, s);
 }
 
 extern "C" size_t mednet_conv3d_wgrad_ws_bytes(int n, int d, int h, int w, int cin, int cout, int ksize, int workgroups) {
@@ -350,25 +370,18 @@ extern "C" int mednet_conv3d_wgrad(const void* x, const void* dy, float* dw, flo
   int rc = conv_common_checks("conv3d_wgrad", n, d, h, w, cin, cout, ksize, x_dtype, dy_dtype);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dbias) {
-    const size_t need = channel_sum_ws_bytes(n, (size_t)d * h * w, cout);
-    MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "conv3d_wgrad: workspace too small for the bias gradient");
-    rc = launch_channel_sum(dy, dbias, n, (size_t)d * h * w, cout, dy_layout == MEDNET_NCDHW, dy_dtype,
-                            (char*)ws + (ws_bytes - need) / 256 * 256, need, s);
-    if (rc) return rc;
-    ws_bytes = (ws_bytes - need) / 256 * 256;
-  }
+  if (dbias && (rc = bias_gradient("conv3d_wgrad", dy, dbias, n, (size_t)d * h * w, cout, dy_layout == MEDNET_NCDHW, dy_dtype, ws, ws_bytes, s)))
+    return rc;
   if (algo_base(algo) != MEDNET_ALGO_DIRECT && wgrad_c1_supported(cin, cout, ksize, x_layout, dy_layout))
-    return launch_wgrad_c1(x, dy, dw, n, d, h, w, cout, x_dtype, dy_dtype, ws, ws_bytes, s, !algo_exact(algo) && conv_x3_enabled());
+    return launch_wgrad_c1(x, dy, dw, n, d, h, w, cout, x_dtype, dy_dtype, ws, ws_bytes, s, algo_x3(algo));
   if (algo_base(algo) != MEDNET_ALGO_DIRECT && (x_layout == MEDNET_NDHWC || x_layout == MEDNET_NCDHW) &&
       wgrad_cm_supported(cin, cout, ksize, x_dtype, dy_dtype, dy_layout))  // multi-channel first layer, plain form
     return launch_wgrad_cm(x, x_layout, dy, nullptr, nullptr, nullptr, 0, dw, n, d, h, w, cin, cout, dy_dtype, ws, ws_bytes, s);
   if (algo_base(algo) != MEDNET_ALGO_DIRECT && wgrad_1x1_supported(cin, cout, ksize, x_layout, dy_layout, dy_dtype))
     return launch_wgrad_1x1(x, dy, dw, n, (size_t)d * h * w, cin, cout, x_dtype, ws, ws_bytes, s);
-  if (algo_base(algo) != MEDNET_ALGO_DIRECT && conv_f32_mfma_enabled() && ksize == 3 && x_dtype == MEDNET_F32 && dy_dtype == MEDNET_F32 &&
-      (x_layout == MEDNET_NDHWC || cin == 1) && dy_layout == MEDNET_NDHWC) {
+  if (algo_f32_mode(algo, x_dtype, dy_dtype) && ksize == 3 && (x_layout == MEDNET_NDHWC || cin == 1) && dy_layout == MEDNET_NDHWC) {
     const int cmax = cin > cout ? cin : cout;
-    if ((!algo_exact(algo) && conv_x3_enabled()) && conv_x3_supported(cin, cout, ksize) && conv_x3_fits(d, h, w, cmax))
+    if (algo_x3(algo) && conv_x3_supported(cin, cout, ksize) && conv_x3_fits(d, h, w, cmax))
       return launch_wgrad_x3(x, dy, dw, n, d, h, w, cin, cout, ws, ws_bytes, s, workgroups);  // split-bf16 contraction over the voxels
     return launch_wgrad_f32_mfma(x, dy, dw, n, d, h, w, cin, cout, ws, ws_bytes, s);
   }
@@ -401,7 +414,7 @@ extern "C" int mednet_conv3d_act_fwd(const void* x, const void* packed, void* y,
   if (!mednet_conv3d_act_supported(n, d, h, w, cin, cout, algo))
     return fail(MEDNET_E_UNSUPPORTED, "conv3d_act_fwd: only the bf16 matrix-core path fuses the activation (cin=%d cout=%d)", cin, cout);
   const PackLayout L = pack_layout(cin, cout, 3);
-  return ELT_CALL(dtype, launch_conv_mfma, x, (const char*)packed + L.mfma_fwd, y, n, d, h, w, cin, cout, dtype, dtype,
+  return ELT_CALL(dtype, launch_conv_mfma, x, pack_mfma(packed, L, 0), y, n, d, h, w, cin, cout, dtype, dtype,
                   gn_partial, (hipStream_t)stream, act, nullptr, algo_lo_delta(algo, dtype, L));
 }
 
@@ -410,8 +423,7 @@ extern "C" int mednet_conv3d_act_fwd(const void* x, const void* packed, void* y,
 // the layer Cin -> Cout?
 static bool x3_dgrad_ok(int n, int d, int h, int w, int cin, int cout, int algo) {
   (void)n;
-  return algo_base(algo) != MEDNET_ALGO_DIRECT && !algo_exact(algo) && conv_f32_mfma_enabled() && conv_x3_enabled() &&
-         conv_x3_supported(cin, cout, 3) && conv_x3_fits(d, h, w, cout);
+  return algo_f32_mode(algo, MEDNET_F32, MEDNET_F32) && algo_x3(algo) && conv_x3_supported(cin, cout, 3) && conv_x3_fits(d, h, w, cout);
 }
 extern "C" int mednet_conv3d_dgrad_add_supported(int n, int d, int h, int w, int cin, int cout, int algo, int dtype) {
   if (dtype == MEDNET_F32) return x3_dgrad_ok(n, d, h, w, cin, cout, algo) ? 1 : 0;
@@ -419,23 +431,21 @@ extern "C" int mednet_conv3d_dgrad_add_supported(int n, int d, int h, int w, int
 }
 extern "C" int mednet_conv3d_dgrad_add(const void* dy, const void* packed, const void* add, void* dx, int n, int d, int h,
                                        int w, int cin, int cout, int algo, int dtype, mednet_stream stream) {
-  if (dtype == MEDNET_F32) {
-    int rc32 = conv_common_checks("conv3d_dgrad_add", n, d, h, w, cin, cout, 3, dtype, dtype);
-    if (rc32) return rc32;
-    MEDNET_REQUIRE(x3_dgrad_ok(n, d, h, w, cin, cout, algo), MEDNET_E_UNSUPPORTED,
-                   "conv3d_dgrad_add: fp32 storage fuses the add only on the split-bf16 path (cin=%d cout=%d)", cin, cout);
-    const PackLayout L32 = pack_layout(cin, cout, 3);
-    return launch_conv_x3_dgrad(dy, (const char*)packed + L32.mfma_bwd, L32.lo_delta, dx, n, d, h, w, cout, cin, add, nullptr, nullptr,
-                                MEDNET_ACT_NONE, nullptr, (hipStream_t)stream);
-  }
-  MEDNET_REQUIRE(is16(dtype), MEDNET_E_DTYPE, "conv3d_dgrad_add: 16-bit storage only (dtype %d)", dtype);
+  const bool f32 = dtype == MEDNET_F32;  // fp32 storage: the split-bf16 data-gradient kernel; 16-bit: the matrix-core family
+  if (!f32) MEDNET_REQUIRE(is16(dtype), MEDNET_E_DTYPE, "conv3d_dgrad_add: 16-bit storage only (dtype %d)", dtype);
   int rc = conv_common_checks("conv3d_dgrad_add", n, d, h, w, cin, cout, 3, dtype, dtype);
   if (rc) return rc;
+  const PackLayout L = pack_layout(cin, cout, 3);
   // (roles swapped as in mednet_conv3d_fwd(dgrad=1): the kernel reads dy with Cout channels and writes Cin channels)
+  if (f32) {
+    MEDNET_REQUIRE(x3_dgrad_ok(n, d, h, w, cin, cout, algo), MEDNET_E_UNSUPPORTED,
+                   "conv3d_dgrad_add: fp32 storage fuses the add only on the split-bf16 path (cin=%d cout=%d)", cin, cout);
+    return launch_conv_x3_dgrad(dy, pack_mfma(packed, L, 1), L.lo_delta, dx, n, d, h, w, cout, cin, add, nullptr, nullptr, MEDNET_ACT_NONE,
+                                nullptr, (hipStream_t)stream);
+  }
   if (!mednet_conv3d_act_supported(n, d, h, w, cout, cin, algo))
     return fail(MEDNET_E_UNSUPPORTED, "conv3d_dgrad_add: only the bf16 matrix-core path fuses the add (cin=%d cout=%d)", cin, cout);
-  const PackLayout L = pack_layout(cin, cout, 3);
-  return ELT_CALL(dtype, launch_conv_mfma, dy, (const char*)packed + L.mfma_bwd, dx, n, d, h, w, cout, cin, dtype, dtype, nullptr,
+  return ELT_CALL(dtype, launch_conv_mfma, dy, pack_mfma(packed, L, 1), dx, n, d, h, w, cout, cin, dtype, dtype, nullptr,
                   (hipStream_t)stream, MEDNET_ACT_NONE, add, algo_lo_delta(algo, dtype, L));
 }
 
@@ -640,27 +650,23 @@ extern "C" int mednet_conv3d_dgrad_gn_rows_dt(int n, int d, int h, int w, int ci
 extern "C" int mednet_conv3d_dgrad_gn(const void* dy, const void* packed, const void* add, void* dx, const void* gn_y,
                                       const float* gn_coef, int gn_act, float* gn_partial, int n, int d, int h, int w,
                                       int cin, int cout, int algo, int dtype, mednet_stream stream) {
-  if (dtype == MEDNET_F32) {
-    int rc32 = conv_common_checks("conv3d_dgrad_gn", n, d, h, w, cin, cout, 3, dtype, dtype);
-    if (rc32) return rc32;
-    MEDNET_REQUIRE(gn_y && gn_coef && gn_partial, MEDNET_E_SHAPE, "conv3d_dgrad_gn: gn_y, gn_coef and gn_partial are required");
-    MEDNET_REQUIRE(gn_act >= MEDNET_ACT_NONE && gn_act <= MEDNET_ACT_ELU, MEDNET_E_UNSUPPORTED, "conv3d_dgrad_gn: activation %d", gn_act);
-    MEDNET_REQUIRE(mednet_conv3d_dgrad_gn_rows_dt(n, d, h, w, cin, cout, algo, dtype) > 0, MEDNET_E_UNSUPPORTED,
-                   "conv3d_dgrad_gn: fp32 storage fuses the GroupNorm sums only on the split-bf16 path (cin=%d cout=%d)", cin, cout);
-    const PackLayout L32 = pack_layout(cin, cout, 3);
-    return launch_conv_x3_dgrad(dy, (const char*)packed + L32.mfma_bwd, L32.lo_delta, dx, n, d, h, w, cout, cin, add, gn_y, gn_coef,
-                                gn_act, gn_partial, (hipStream_t)stream);
-  }
-  MEDNET_REQUIRE(is16(dtype), MEDNET_E_DTYPE, "conv3d_dgrad_gn: 16-bit storage only (dtype %d)", dtype);
+  const bool f32 = dtype == MEDNET_F32;  // fp32 storage: the split-bf16 data-gradient kernel; 16-bit: the matrix-core family
+  if (!f32) MEDNET_REQUIRE(is16(dtype), MEDNET_E_DTYPE, "conv3d_dgrad_gn: 16-bit storage only (dtype %d)", dtype);
   int rc = conv_common_checks("conv3d_dgrad_gn", n, d, h, w, cin, cout, 3, dtype, dtype);
   if (rc) return rc;
   MEDNET_REQUIRE(gn_y && gn_coef && gn_partial, MEDNET_E_SHAPE, "conv3d_dgrad_gn: gn_y, gn_coef and gn_partial are required");
   MEDNET_REQUIRE(gn_act >= MEDNET_ACT_NONE && gn_act <= MEDNET_ACT_ELU, MEDNET_E_UNSUPPORTED, "conv3d_dgrad_gn: activation %d", gn_act);
+  const PackLayout L = pack_layout(cin, cout, 3);
+  if (f32) {
+    MEDNET_REQUIRE(mednet_conv3d_dgrad_gn_rows_dt(n, d, h, w, cin, cout, algo, dtype) > 0, MEDNET_E_UNSUPPORTED,
+                   "conv3d_dgrad_gn: fp32 storage fuses the GroupNorm sums only on the split-bf16 path (cin=%d cout=%d)", cin, cout);
+    return launch_conv_x3_dgrad(dy, pack_mfma(packed, L, 1), L.lo_delta, dx, n, d, h, w, cout, cin, add, gn_y, gn_coef, gn_act, gn_partial,
+                                (hipStream_t)stream);
+  }
   if (mednet_conv3d_dgrad_gn_rows(n, d, h, w, cin, cout, algo) == 0)
     return fail(MEDNET_E_UNSUPPORTED, "conv3d_dgrad_gn: only the bf16 matrix-core path fuses the GroupNorm sums (cin=%d cout=%d)", cin, cout);
-  const PackLayout L = pack_layout(cin, cout, 3);
-  return ELT_CALL(dtype, launch_conv_mfma_gnb, dy, (const char*)packed + L.mfma_bwd, dx, n, d, h, w, cout, cin, add, gn_y,
-                  gn_coef, gn_act, gn_partial, (hipStream_t)stream, algo_lo_delta(algo, dtype, L));
+  return ELT_CALL(dtype, launch_conv_mfma_gnb, dy, pack_mfma(packed, L, 1), dx, n, d, h, w, cout, cin, add, gn_y, gn_coef, gn_act, gn_partial,
+                  (hipStream_t)stream, algo_lo_delta(algo, dtype, L));
 }
 
 // ---- ConvTranspose3d(k3,s2,p1,op1) ------------------------------------------------------------------------------------
@@ -671,24 +677,21 @@ extern "C" int mednet_convt3d_fwd(const void* x, const void* packed, const float
   if (rc) return rc;
   const PackLayout L = pack_layout(cin, cout, 3);
   const bool mfma_ok = L.mfma_bytes && cin % 32 == 0 && cout % 32 == 0 && is16(x_dtype) && y_dtype == x_dtype;
-  const bool f32_mfma = conv_f32_mfma_enabled() && x_dtype == MEDNET_F32 && y_dtype == MEDNET_F32;  // (fp32 storage: see conv3d_fwd)
-  if (algo_base(algo) == MEDNET_ALGO_MFMA && !mfma_ok && !f32_mfma)
+  const bool f32_mode = algo_f32_mode(algo, x_dtype, y_dtype);  // (fp32 storage: see conv3d_fwd)
+  if (algo_base(algo) == MEDNET_ALGO_MFMA && !mfma_ok && !f32_mode)
     return fail(MEDNET_E_UNSUPPORTED, "convt3d_fwd: MFMA path does not take cin=%d cout=%d", cin, cout);
   if (mfma_ok && algo_base(algo) != MEDNET_ALGO_DIRECT)
-    return ELT_CALL(x_dtype, launch_convt_fwd_mfma, x, (const char*)packed + L.mfma_fwd, bias, skip, y, n, d, h, w, cin, cout,
+    return ELT_CALL(x_dtype, launch_convt_fwd_mfma, x, pack_mfma(packed, L, 0), bias, skip, y, n, d, h, w, cin, cout,
                     (hipStream_t)stream, algo_lo_delta(algo, x_dtype, L));
-  if (algo_base(algo) != MEDNET_ALGO_DIRECT && conv_f32_mfma_enabled() && x_dtype == MEDNET_F32 && y_dtype == MEDNET_F32) {
-    if ((!algo_exact(algo) && conv_x3_enabled()) && L.mfma_bytes && conv_x3_supported(cin, cout, 3))
-      return launch_convt_fwd_x3(x, (const char*)packed + L.mfma_fwd, L.lo_delta, bias, skip, y, n, d, h, w, cin, cout,
-                                 (hipStream_t)stream);
-    return launch_convt_fwd_f32_mfma(x, (const float*)((const char*)packed + L.f32_fwd), bias, skip, y, n, d, h, w, cin, cout,
-                                     (hipStream_t)stream);
+  if (f32_mode) {
+    if (algo_x3(algo) && L.mfma_bytes && conv_x3_supported(cin, cout, 3))
+      return launch_convt_fwd_x3(x, pack_mfma(packed, L, 0), L.lo_delta, bias, skip, y, n, d, h, w, cin, cout, (hipStream_t)stream);
+    return launch_convt_fwd_f32_mfma(x, pack_f32(packed, L, 0), bias, skip, y, n, d, h, w, cin, cout, (hipStream_t)stream);
   }
   ConvGeom g;
   g.n = n; g.od = 2 * d; g.oh = 2 * h; g.ow = 2 * w; g.id = d; g.ih = h; g.iw = w;
   g.k = cin; g.m = cout; g.ks = 3; g.in_planar = 0; g.out_planar = 0;
-  return launch_direct<MAP_CT_FWD>(x, (const float*)((const char*)packed + L.f32_fwd), bias, skip, y, g, x_dtype, y_dtype,
-                                   (hipStream_t)stream);
+  return launch_direct<MAP_CT_FWD>(x, pack_f32(packed, L, 0), bias, skip, y, g, x_dtype, y_dtype, (hipStream_t)stream);
 }
 
 extern "C" int mednet_convt3d_dgrad(const void* dy, const void* packed, void* dx, int n, int d, int h, int w, int cin,
@@ -698,23 +701,21 @@ extern "C" int mednet_convt3d_dgrad(const void* dy, const void* packed, void* dx
   const PackLayout L = pack_layout(cin, cout, 3);
   const bool mfma_ok = L.mfma_bytes && cin % 32 == 0 && cout % 32 == 0 && is16(dy_dtype) && dx_dtype == dy_dtype &&
                        conv_mfma_fits(n, 2 * d, 2 * h, 2 * w, cout);
-  const bool f32_mfma = conv_f32_mfma_enabled() && dy_dtype == MEDNET_F32 && dx_dtype == MEDNET_F32;
-  if (algo_base(algo) == MEDNET_ALGO_MFMA && !mfma_ok && !f32_mfma)
+  const bool f32_mode = algo_f32_mode(algo, dy_dtype, dx_dtype);
+  if (algo_base(algo) == MEDNET_ALGO_MFMA && !mfma_ok && !f32_mode)
     return fail(MEDNET_E_UNSUPPORTED, "convt3d_dgrad: MFMA path does not take cin=%d cout=%d", cin, cout);
   if (mfma_ok && algo_base(algo) != MEDNET_ALGO_DIRECT)
-    return ELT_CALL(dy_dtype, launch_convt_dgrad_mfma, dy, (const char*)packed + L.mfma_bwd, dx, n, d, h, w, cin, cout,
+    return ELT_CALL(dy_dtype, launch_convt_dgrad_mfma, dy, pack_mfma(packed, L, 1), dx, n, d, h, w, cin, cout,
                     (hipStream_t)stream, algo_lo_delta(algo, dy_dtype, L));
-  if (algo_base(algo) != MEDNET_ALGO_DIRECT && conv_f32_mfma_enabled() && dy_dtype == MEDNET_F32 && dx_dtype == MEDNET_F32) {
-    if ((!algo_exact(algo) && conv_x3_enabled()) && L.mfma_bytes && conv_x3_supported(cin, cout, 3) && conv_x3_fits(2 * d, 2 * h, 2 * w, cout))
-      return launch_convt_dgrad_x3(dy, (const char*)packed + L.mfma_bwd, L.lo_delta, dx, n, d, h, w, cin, cout, (hipStream_t)stream);
-    return launch_convt_dgrad_f32_mfma(dy, (const float*)((const char*)packed + L.f32_bwd), dx, n, d, h, w, cin, cout,
-                                       (hipStream_t)stream);
+  if (f32_mode) {
+    if (algo_x3(algo) && L.mfma_bytes && conv_x3_supported(cin, cout, 3) && conv_x3_fits(2 * d, 2 * h, 2 * w, cout))
+      return launch_convt_dgrad_x3(dy, pack_mfma(packed, L, 1), L.lo_delta, dx, n, d, h, w, cin, cout, (hipStream_t)stream);
+    return launch_convt_dgrad_f32_mfma(dy, pack_f32(packed, L, 1), dx, n, d, h, w, cin, cout, (hipStream_t)stream);
   }
   ConvGeom g;
   g.n = n; g.od = d; g.oh = h; g.ow = w; g.id = 2 * d; g.ih = 2 * h; g.iw = 2 * w;
   g.k = cout; g.m = cin; g.ks = 3; g.in_planar = 0; g.out_planar = 0;
-  return launch_direct<MAP_CT_DG>(dy, (const float*)((const char*)packed + L.f32_bwd), nullptr, nullptr, dx, g, dy_dtype,
-                                  dx_dtype, (hipStream_t)stream);
+  return launch_direct<MAP_CT_DG>(dy, pack_f32(packed, L, 1), nullptr, nullptr, dx, g, dy_dtype, dx_dtype, (hipStream_t)stream);
 }
 
 static bool convt_dgrad_mfma_ok(int n, int d, int h, int w, int cin, int cout, int dtype) {
@@ -734,7 +735,7 @@ extern "C" int mednet_convt3d_dgrad_gn(const void* dy, const void* packed, void*
   MEDNET_REQUIRE(mednet_convt3d_dgrad_gn_rows(n, d, h, w, cin, cout, dtype, algo) > 0, MEDNET_E_UNSUPPORTED,
                  "convt3d_dgrad_gn: cin=%d cout=%d dtype=%d not on the matrix-core path", cin, cout, dtype);
   const PackLayout L = pack_layout(cin, cout, 3);
-  return ELT_CALL(dtype, launch_convt_dgrad_gn_mfma, dy, (const char*)packed + L.mfma_bwd, dx, gn_y, gn_z, gn_act, gn_partial, n, d,
+  return ELT_CALL(dtype, launch_convt_dgrad_gn_mfma, dy, pack_mfma(packed, L, 1), dx, gn_y, gn_z, gn_act, gn_partial, n, d,
                   h, w, cin, cout, (hipStream_t)stream, algo_lo_delta(algo, dtype, L));
 }
 
@@ -755,16 +756,9 @@ extern "C" int mednet_convt3d_wgrad(const void* x, const void* dy, float* dw, fl
   int rc = conv_common_checks("convt3d_wgrad", n, d, h, w, cin, cout, 3, x_dtype, dy_dtype);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dbias) {
-    const size_t need = channel_sum_ws_bytes(n, (size_t)8 * d * h * w, cout);
-    MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "convt3d_wgrad: workspace too small for the bias gradient");
-    rc = launch_channel_sum(dy, dbias, n, (size_t)8 * d * h * w, cout, 0, dy_dtype,
-                            (char*)ws + (ws_bytes - need) / 256 * 256, need, s);
-    if (rc) return rc;
-    ws_bytes = (ws_bytes - need) / 256 * 256;
-  }
-  if (algo_base(algo) != MEDNET_ALGO_DIRECT && conv_f32_mfma_enabled() && x_dtype == MEDNET_F32 && dy_dtype == MEDNET_F32) {
-    if (!algo_exact(algo) && conv_x3_enabled() && tuning_option("x3_convt_wgrad", 1) && conv_x3_supported(cin, cout, 3) &&
+  if (dbias && (rc = bias_gradient("convt3d_wgrad", dy, dbias, n, (size_t)8 * d * h * w, cout, 0, dy_dtype, ws, ws_bytes, s))) return rc;
+  if (algo_f32_mode(algo, x_dtype, dy_dtype)) {
+    if (algo_x3(algo) && tuning_option("x3_convt_wgrad", 1) && conv_x3_supported(cin, cout, 3) &&
         conv_x3_fits(2 * d, 2 * h, 2 * w, cout) && conv_x3_fits(d, h, w, cin))
       return launch_convt_wgrad_x3(x, dy, dw, n, d, h, w, cin, cout, ws, ws_bytes, s, workgroups);  // split-bf16, output-parity planes
     return launch_convt_wgrad_f32_mfma(x, dy, dw, n, d, h, w, cin, cout, ws, ws_bytes, s);

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
+#include <utility>
+#include <vector>
 #include "../../include/mednet_hip.h"
 
 // ---- error plumbing + tuning knobs (defined once in api.hip, global names: conv_mfma.hip is compiled a second time under
@@ -33,6 +36,28 @@ static inline int tuning_option(const char* name, int default_value) { return ::
   do {                                         \
     if (!(cond)) return fail(code, __VA_ARGS__); \
   } while (0)
+
+// Launch of a kernel that needs more dynamic LDS than the default limit: the limit is raised the first time this (kernel, current
+// device) pair is seen -- on one device once per kernel, during warm-up, before any graph capture; never per launch -- and the
+// launch is checked.  `what` names the launch in check_launch's message; the text in front of any '(' in it names the kernel in
+// "<name>: cannot raise dynamic LDS to <bytes>".
+static inline bool lds_limit_raised(const void* kernel, size_t lds) {
+  static std::vector<std::pair<const void*, int>> seen;  // (a failed attempt is not recorded: the next launch tries again)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) (void)hipGetLastError();
+  for (const auto& k : seen)
+    if (k.first == kernel && k.second == dev) return true;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+  seen.emplace_back(kernel, dev);
+  return true;
+}
+template <typename K, typename... A>
+static inline int launch_lds(const char* what, K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+  if (!lds_limit_raised((const void*)kernel, lds))
+    return fail(MEDNET_E_HIP, "%.*s: cannot raise dynamic LDS to %zu", (int)strcspn(what, "("), what, lds);
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  return check_launch(what);
+}
 
 inline bool dtype_ok(int dt) { return dt == MEDNET_F32 || dt == MEDNET_BF16 || dt == MEDNET_F16; }
 inline size_t dtype_size(int dt) { return dt == MEDNET_F32 ? 4 : 2; }

@@ -211,14 +211,7 @@ static int launch_f32(const void* x, const float* P, const float* bias, void* y,
   a.nkc = (k + 7) / 8;
   a.ncb = (m + 31) / 32;
   MEDNET_REQUIRE((double)a.ntiles * a.ncb < 2147483647.0, MEDNET_E_UNSUPPORTED, "conv_f32_mfma: grid too large");
-  static bool attr_set[3] = {false, false, false};
-  if (!attr_set[STRIDE]) {
-    if (hipFuncSetAttribute((const void*)conv_f32_mfma_kernel<STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "conv_f32_mfma: cannot raise dynamic LDS to %zu", lds);
-    attr_set[STRIDE] = true;
-  }
-  hipLaunchKernelGGL((conv_f32_mfma_kernel<STRIDE>), dim3((unsigned)(a.ntiles * a.ncb)), dim3(256), lds, s, a);
-  return check_launch("conv_f32_mfma");
+  return launch_lds("conv_f32_mfma", conv_f32_mfma_kernel<STRIDE>, dim3((unsigned)(a.ntiles * a.ncb)), dim3(256), lds, s, a);
 }
 
 bool conv_f32_mfma_enabled() { return tuning_option("f32_mfma", 1) != 0; }
@@ -502,14 +495,7 @@ static int launch_wgf32(const void* A, const void* B, float* dw, int n, int ad, 
   wgf32_plan<STRIDE>(n, ad, ah, aw, ka, kb, a);
   const size_t need = (size_t)a.nab * a.nbb * a.splits * 27 * 1024 * sizeof(float);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "wgrad_f32_mfma: workspace %zu < %zu", ws_bytes, need);
-  static bool attr_set[3] = {false, false, false};
-  if (!attr_set[STRIDE]) {
-    if (hipFuncSetAttribute((const void*)wgrad_f32_mfma_kernel<STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "wgrad_f32_mfma: cannot raise dynamic LDS to %zu", lds);
-    attr_set[STRIDE] = true;
-  }
-  hipLaunchKernelGGL((wgrad_f32_mfma_kernel<STRIDE>), dim3(a.nab * a.nbb * a.splits), dim3(256), lds, s, a);
-  int rc = check_launch("wgrad_f32_mfma");
+  int rc = launch_lds("wgrad_f32_mfma", wgrad_f32_mfma_kernel<STRIDE>, dim3(a.nab * a.nbb * a.splits), dim3(256), lds, s, a);
   if (rc) return rc;
   const size_t total = (size_t)a.nab * a.nbb * 1024 * 27;
   hipLaunchKernelGGL(wgrad_f32_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.part, dw, ka, kb, a.nbb, a.splits);

@@ -594,29 +594,12 @@ int launch_wgrad_first_mfma(const void* x, int x_layout, int x_dtype, const void
   wgrad_first_mfma_plan(n, d, h, w, cin, cout, gn, plan);
   const int blocks = plan[0], nb = plan[1];
   const size_t lds = (size_t)plan[3];
-  static bool attr_set[4][2][2] = {};  // (once per process and instantiation)
-#define WFIRST_GO(CIN_, NB_, GN_)                                                                                                 \
-  do {                                                                                                                            \
-    if (lds > 48 * 1024 && !attr_set[CIN_ - 1][NB_ - 1][GN_]) {                                                                   \
-      if (hipFuncSetAttribute((const void*)wgrad_first_mfma_kernel<CIN_, NB_, GN_>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                              (int)lds) != hipSuccess)                                                                            \
-        return fail(MEDNET_E_HIP, "%s: cannot raise dynamic LDS to %zu", who, lds);                                               \
-      attr_set[CIN_ - 1][NB_ - 1][GN_] = true;                                                                                    \
-    }                                                                                                                             \
-    hipLaunchKernelGGL((wgrad_first_mfma_kernel<CIN_, NB_, GN_>), dim3(blocks), dim3(256), lds, s, a);                            \
-  } while (0)
-#define WFIRST_NB(CIN_)                          \
-  do {                                           \
-    if (nb == 1 && gn) WFIRST_GO(CIN_, 1, true); \
-    else if (nb == 1) WFIRST_GO(CIN_, 1, false); \
-    else if (gn) WFIRST_GO(CIN_, 2, true);       \
-    else WFIRST_GO(CIN_, 2, false);              \
-  } while (0)
-  if (cin == 1) WFIRST_NB(1);
-  else if (cin == 2) WFIRST_NB(2);
-  else if (cin == 3) WFIRST_NB(3);
-  else WFIRST_NB(4);
+#define WFIRST_NB(CIN_)                                                                            \
+  (nb == 1 ? (gn ? wgrad_first_mfma_kernel<CIN_, 1, true> : wgrad_first_mfma_kernel<CIN_, 1, false>) \
+           : (gn ? wgrad_first_mfma_kernel<CIN_, 2, true> : wgrad_first_mfma_kernel<CIN_, 2, false>))
+  const auto kernel = cin == 1 ? WFIRST_NB(1) : cin == 2 ? WFIRST_NB(2) : cin == 3 ? WFIRST_NB(3) : WFIRST_NB(4);
 #undef WFIRST_NB
-#undef WFIRST_GO
+  if (lds > 48 * 1024) return launch_lds(who, kernel, dim3(blocks), dim3(256), lds, s, a);  // (below that the default limit serves)
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, s, a);
   return check_launch(who);
 }

@@ -51,6 +51,11 @@ static bool narrow_bricks(int w) {
   const int mode = tuning_option("conv_narrow", 1);
   return mode != 0 && (w <= 8 || (mode == 2 && (w + 7) / 8 < 2 * ((w + 15) / 16)));
 }
+// bricks of kind G, tx wide, that cover n volumes of d x h x w voxels
+template <typename G>
+static int bricks(int n, int d, int h, int w, int tx = G::TX) {
+  return n * ((d + G::TZ - 1) / G::TZ) * ((h + G::TY - 1) / G::TY) * ((w + tx - 1) / tx);
+}
 
 // Order in which the forward / data-gradient kernels of this file visit the 27 taps of a K chunk: position s = (kz, kx, ky) with ky
 // FASTEST, i.e. tap index tap_at(s) = kz * 9 + ky * 3 + kx.  Round 6: conv32_mfma_kernel serves the three ky taps of a (kz, kx)
@@ -1305,14 +1310,7 @@ int launch_convt_fwd_mfma(const void* x, const void* sec, const float* bias, con
   a.lo_delta = (unsigned)lo_delta;
   a.ncb = cout / 32;
   const unsigned grid = (unsigned)((a.ntiles + 7) / 8) * 8 * a.ncb;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)convt_fwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "convt_fwd_mfma: cannot raise dynamic LDS to %zu", lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(convt_fwd_mfma_kernel, dim3(grid), dim3(256), lds, s, a);
-  return check_launch("convt_fwd_mfma");
+  return launch_lds("convt_fwd_mfma", convt_fwd_mfma_kernel, dim3(grid), dim3(256), lds, s, a);
 }
 
 // ================================================================================================== weight packing
@@ -1520,9 +1518,7 @@ static bool conv2b_takes(int ntiles, int cin, int cout, bool split = false) {
 // Brick kind of a stride-1 launch: 3 (8-wide bricks) where that covers the volume with fewer voxel slots, unless the 32 -> 32
 // specialisation (16-wide bricks only) takes the call
 static int conv_fwd_kind(int n, int d, int h, int w, int cin, int cout, bool gnb, bool split = false) {
-  using G = FwdTile<1>;
-  const int ntiles16 = n * ((d + G::TZ - 1) / G::TZ) * ((h + G::TY - 1) / G::TY) * ((w + G::TX - 1) / G::TX);
-  return narrow_bricks(w) && !conv32_takes(ntiles16, cin, cout, gnb, split) ? 3 : 1;
+  return narrow_bricks(w) && !conv32_takes(bricks<FwdTile<1>>(n, d, h, w), cin, cout, gnb, split) ? 3 : 1;
 }
 // workgroups of a conv2b launch: one per CU, fewer (a multiple of 8) when the launch has fewer items
 static int conv2b_grid(int nitems) { return nitems < 256 ? nitems : 256; }
@@ -1534,7 +1530,7 @@ static bool convt_dgrad32_takes(int ntiles, int k_dy, int m_dx, bool split) {
 static void conv_stats_plan(int n, int d, int h, int w, int cin, int cout, int& rows, int& accum, bool gnb = false, bool split = false) {
   const int tx = conv_fwd_kind(n, d, h, w, cin, cout, gnb, split) == 3 ? FwdTile<3>::TX : FwdTile<1>::TX;
   using G = FwdTile<1>;
-  const int tps = ((d + G::TZ - 1) / G::TZ) * ((h + G::TY - 1) / G::TY) * ((w + tx - 1) / tx);
+  const int tps = bricks<G>(1, d, h, w, tx);
   const int ncb = (cout + 31) / 32, ntiles = n * tps;
   if (tx == G::TX && conv32_takes(ntiles, cin, cout, gnb, split)) {  // always accumulating: one row per wave of the 256 workgroups
     accum = 1;
@@ -1572,10 +1568,36 @@ struct GnbSpec {  // fused first pass of a GroupNorm backward (see FwdArgs::gnb_
   const void* z = nullptr;  // residual-layer form (FwdArgs::gnb_z)
 };
 
+// the probe's answer: the arguments the launch would carry, its kernel (`kind`), workgroups and work items
+static int plan_answer(FwdPlanProbe* probe, int kind, int grid, int nitems, const FwdArgs& a) {
+  *probe = FwdPlanProbe{kind, grid, nitems, a.ncb, a.ntiles, a.tiles_z * a.tiles_y * a.tiles_x, a.stats_accum, a.stats_rows, a.xcd_chunk,
+                        a.zslab, a.tiles_x, a.tiles_y, a.tiles_z};
+  return MEDNET_OK;
+}
+
+// Epilogue variants of conv32_mfma_kernel and conv2b_mfma_kernel (the C32_* bits; conv2b has each with C32_SPLIT as well): the
+// data-gradient form with a GroupNorm backward's sums takes `add` only, the others any of `add`, statistics and activation
+static int c32_variant(bool use_gnb, bool add, bool stats, bool act, bool split) {
+  return (use_gnb ? C32_GNB | (add ? C32_ADD : 0) : (add ? C32_ADD : 0) | (stats ? C32_STATS : 0) | (act ? C32_ACT : 0)) | (split ? C32_SPLIT : 0);
+}
+// -> go(std::integral_constant<int, V>()) for the V of the ten that `variant` is, C32_SPLIT aside
+template <typename F, int... V>
+static int c32_dispatch(int variant, F go, std::integer_sequence<int, V...>) {
+  int rc = MEDNET_E_UNSUPPORTED;
+  (void)(((variant & ~C32_SPLIT) == V ? (rc = go(std::integral_constant<int, V>()), true) : false) || ...);
+  return rc;
+}
+template <typename F>
+static int c32_dispatch(int variant, F go) {
+  return c32_dispatch(variant, go,
+                      std::integer_sequence<int, 0, C32_ADD, C32_STATS, C32_STATS | C32_ADD, C32_ACT, C32_ACT | C32_ADD, C32_ACT | C32_STATS,
+                                            C32_ACT | C32_STATS | C32_ADD, C32_GNB, C32_GNB | C32_ADD>());
+}
+
 template <int KIND>
 static int launch_fwd(const void* x, const void* sec, void* y, int n, int od, int oh, int ow, int id, int ih, int iw,
-                      int cin, int cout, float* gn_partial, hipStream_t s, int act = MEDNET_ACT_NONE,
-                      const void* add = nullptr, GnbSpec gnb = GnbSpec(), FwdPlanProbe* probe = nullptr, size_t lo_delta = 0) {
+                      int cin, int cout, float* gn_partial, hipStream_t s, int act, const void* add, GnbSpec gnb,
+                      FwdPlanProbe* probe, size_t lo_delta) {
   using G = FwdTile<KIND>;
   constexpr int STRIDE = G::STRIDE;
   constexpr int HZ = STRIDE * (G::TZ - 1) + 3, HY = STRIDE * (G::TY - 1) + 3, HX = STRIDE * (G::TX - 1) + 3;
@@ -1601,7 +1623,7 @@ static int launch_fwd(const void* x, const void* sec, void* y, int n, int od, in
   a.tiles_z = (od + G::TZ - 1) / G::TZ;
   a.tiles_y = (oh + G::TY - 1) / G::TY;
   a.tiles_x = (ow + G::TX - 1) / G::TX;
-  a.ntiles = n * a.tiles_z * a.tiles_y * a.tiles_x;
+  a.ntiles = bricks<G>(n, od, oh, ow);
   const bool split = lo_delta != 0;  // split weights: the low image lies lo_delta bytes behind `sec` (FwdArgs::lo_delta)
   MEDNET_REQUIRE(lo_delta < 0xFFFFFFFFull, MEDNET_E_UNSUPPORTED, "conv_mfma: weight images too large for split weights");
   a.lo_delta = (unsigned)lo_delta;
@@ -1621,6 +1643,8 @@ static int launch_fwd(const void* x, const void* sec, void* y, int n, int od, in
   a.stats_rows = 4 * a.tiles_z * a.tiles_y * a.tiles_x;
   if (gn_partial && STRIDE == 1) conv_stats_plan(n, od, oh, ow, cin, cout, a.stats_rows, a.stats_accum, use_gnb, split);
   a.xcd_chunk = 0;
+  a.zslab = 0;
+  a.rcp_zslab = 0;
   if constexpr (KIND == 2) {
     if (convt_dgrad32_takes(a.ntiles, cin, cout, split) && !add && act == MEDNET_ACT_NONE) {
       Ct32Args c;
@@ -1631,70 +1655,31 @@ static int launch_fwd(const void* x, const void* sec, void* y, int n, int od, in
       c.rcp_tiles_x = a.rcp_tiles_x; c.rcp_tiles_y = a.rcp_tiles_y; c.rcp_tiles_z = a.rcp_tiles_z;
       c.bytes_dy = a.bytes_x; c.bytes_dx = a.bytes_y;
       const int rows32 = 2 * 256;  // one row per (workgroup, z-plane of its bricks) and sample: see convt_dgrad_gn_rows
-      if (probe) {
-        *probe = FwdPlanProbe{7, 256, a.ntiles, 2, a.ntiles, a.tiles_z * a.tiles_y * a.tiles_x, 1, rows32,
-                              a.ntiles % 8 == 0 ? a.ntiles / 8 : 0, 0, a.tiles_x, a.tiles_y, a.tiles_z};
-        return MEDNET_OK;
+      if (probe) {  // (this kernel's rows and its walk, which Ct32Args does not carry, in FwdArgs' terms; its two channel blocks are a.ncb)
+        a.stats_accum = 1;
+        a.stats_rows = rows32;
+        a.xcd_chunk = a.ntiles % 8 == 0 ? a.ntiles / 8 : 0;
+        return plan_answer(probe, 7, 256, a.ntiles, a);
       }
-      static bool attr_ct32[2] = {false, false};
-      auto go = [&](auto kernel) -> int {
-        if (!attr_ct32[use_gnb]) {
-          if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CT32_LDS) != hipSuccess)
-            return fail(MEDNET_E_HIP, "convt_dgrad32_mfma: cannot raise dynamic LDS to %zu", CT32_LDS);
-          attr_ct32[use_gnb] = true;
-        }
-        hipLaunchKernelGGL(kernel, dim3(256), dim3(256), CT32_LDS, s, c);
-        return MEDNET_OK;
-      };
-      const int rc = use_gnb ? go(convt_dgrad32_mfma_kernel<true>) : go(convt_dgrad32_mfma_kernel<false>);
-      if (rc) return rc;
-      return check_launch("convt_dgrad32_mfma");
+      return launch_lds("convt_dgrad32_mfma", use_gnb ? convt_dgrad32_mfma_kernel<true> : convt_dgrad32_mfma_kernel<false>, dim3(256), dim3(256),
+                        CT32_LDS, s, c);
     }
   }
   if constexpr (KIND == 1) {
+    const int variant = c32_variant(use_gnb, add != nullptr, gn_partial != nullptr, act != MEDNET_ACT_NONE, split);
     if (conv32_takes(a.ntiles, cin, cout, use_gnb, split)) {
       constexpr size_t lds32 = (size_t)2 * 4 * (HZ * HY * HX + 4) * 16 + 4 * 4096 + 256 * 16;
       static_assert(lds32 <= 160 * 1024, "two bricks of whole rows + the waves' epilogue areas + spare slots");
       a.xcd_chunk = a.ntiles % 8 == 0 ? a.ntiles / 8 : 0;
-      a.zslab = 0;
-      a.rcp_zslab = 0;
       if ((n * a.tiles_z) % 8 == 0 && a.tiles_z % (n * a.tiles_z / 8) == 0 && tuning_option("conv32_zslab", 1)) {
         a.zslab = n * a.tiles_z / 8;  // (a slab lies inside ONE sample: the statistics rows of a workgroup need that)
         a.rcp_zslab = fastdiv_rcp(a.zslab);
       }
-      const int variant = use_gnb ? (C32_GNB | (add ? C32_ADD : 0))
-                                  : ((add ? C32_ADD : 0) | (gn_partial ? C32_STATS : 0) | (act != MEDNET_ACT_NONE ? C32_ACT : 0));
       MEDNET_REQUIRE(!use_gnb || act == MEDNET_ACT_NONE, MEDNET_E_UNSUPPORTED, "conv32_mfma: no activation in the data-gradient form");
-      if (probe) {
-        *probe = FwdPlanProbe{4, 256, a.ntiles, a.ncb, a.ntiles, a.tiles_z * a.tiles_y * a.tiles_x, a.stats_accum, a.stats_rows,
-                              a.xcd_chunk, a.zslab, a.tiles_x, a.tiles_y, a.tiles_z};
-        return MEDNET_OK;
-      }
-      static bool attr32[16] = {};
-      auto go = [&](auto kernel) -> int {
-        if (!attr32[variant]) {
-          if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32) != hipSuccess)
-            return fail(MEDNET_E_HIP, "conv32_mfma: cannot raise dynamic LDS to %zu", lds32);
-          attr32[variant] = true;
-        }
-        hipLaunchKernelGGL(kernel, dim3(256), dim3(256), lds32, s, a);
-        return MEDNET_OK;
-      };
-      int rc32 = MEDNET_OK;
-      switch (variant) {
-        case 0: rc32 = go(conv32_mfma_kernel<0>); break;
-        case C32_ADD: rc32 = go(conv32_mfma_kernel<C32_ADD>); break;
-        case C32_STATS: rc32 = go(conv32_mfma_kernel<C32_STATS>); break;
-        case C32_STATS | C32_ADD: rc32 = go(conv32_mfma_kernel<C32_STATS | C32_ADD>); break;
-        case C32_ACT: rc32 = go(conv32_mfma_kernel<C32_ACT>); break;
-        case C32_ACT | C32_ADD: rc32 = go(conv32_mfma_kernel<C32_ACT | C32_ADD>); break;
-        case C32_ACT | C32_STATS: rc32 = go(conv32_mfma_kernel<C32_ACT | C32_STATS>); break;
-        case C32_ACT | C32_STATS | C32_ADD: rc32 = go(conv32_mfma_kernel<C32_ACT | C32_STATS | C32_ADD>); break;
-        case C32_GNB: rc32 = go(conv32_mfma_kernel<C32_GNB>); break;
-        default: rc32 = go(conv32_mfma_kernel<C32_GNB | C32_ADD>); break;
-      }
-      if (rc32) return rc32;
-      return check_launch("conv32_mfma");
+      if (probe) return plan_answer(probe, 4, 256, a.ntiles, a);
+      return c32_dispatch(variant, [&](auto v) {
+        return launch_lds("conv32_mfma", conv32_mfma_kernel<decltype(v)::value>, dim3(256), dim3(256), lds32, s, a);
+      });
     }
     if (conv2b_takes(a.ntiles, cin, cout, split)) {
       FwdArgs b2 = a;
@@ -1704,100 +1689,42 @@ static int launch_fwd(const void* x, const void* sec, void* y, int n, int od, in
       b2.nkc = a.nkc_in;
       b2.xcd_chunk = (a.ntiles % 8 == 0 && tuning_option("conv2b_xcd_walk", 1)) ? a.ntiles / 8 : 0;
       const int grid2 = conv2b_grid(b2.nitems);
-      const int variant = (use_gnb ? (C32_GNB | (add ? C32_ADD : 0))
-                                   : ((add ? C32_ADD : 0) | (gn_partial ? C32_STATS : 0) | (act != MEDNET_ACT_NONE ? C32_ACT : 0))) |
-                          (split ? C32_SPLIT : 0);
       MEDNET_REQUIRE(!use_gnb || act == MEDNET_ACT_NONE, MEDNET_E_UNSUPPORTED, "conv2b_mfma: no activation in the data-gradient form");
-      if (probe) {
-        *probe = FwdPlanProbe{b2.stats_accum ? 6 : 5, grid2, b2.nitems, b2.ncb, a.ntiles, a.tiles_z * a.tiles_y * a.tiles_x, b2.stats_accum,
-                              b2.stats_rows, b2.xcd_chunk, 0, a.tiles_x, a.tiles_y, a.tiles_z};
-        return MEDNET_OK;
-      }
-      static bool attr2b[32] = {};
-      auto go2 = [&](auto kernel) -> int {
-        if (!attr2b[variant]) {
-          if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C2B_LDS) != hipSuccess)
-            return fail(MEDNET_E_HIP, "conv2b_mfma: cannot raise dynamic LDS to %zu", C2B_LDS);
-          attr2b[variant] = true;
-        }
-        hipLaunchKernelGGL(kernel, dim3(grid2), dim3(256), C2B_LDS, s, b2);
-        return MEDNET_OK;
-      };
-      int rc2 = MEDNET_OK;
-      switch (variant) {
-        case C32_SPLIT: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT>); break;
-        case C32_SPLIT | C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_ADD>); break;
-        case C32_SPLIT | C32_STATS: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_STATS>); break;
-        case C32_SPLIT | C32_STATS | C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_STATS | C32_ADD>); break;
-        case C32_SPLIT | C32_ACT: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_ACT>); break;
-        case C32_SPLIT | C32_ACT | C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_ACT | C32_ADD>); break;
-        case C32_SPLIT | C32_ACT | C32_STATS: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_ACT | C32_STATS>); break;
-        case C32_SPLIT | C32_ACT | C32_STATS | C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_ACT | C32_STATS | C32_ADD>); break;
-        case C32_SPLIT | C32_GNB: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_GNB>); break;
-        case C32_SPLIT | C32_GNB | C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_SPLIT | C32_GNB | C32_ADD>); break;
-        case 0: rc2 = go2(conv2b_mfma_kernel<0>); break;
-        case C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_ADD>); break;
-        case C32_STATS: rc2 = go2(conv2b_mfma_kernel<C32_STATS>); break;
-        case C32_STATS | C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_STATS | C32_ADD>); break;
-        case C32_ACT: rc2 = go2(conv2b_mfma_kernel<C32_ACT>); break;
-        case C32_ACT | C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_ACT | C32_ADD>); break;
-        case C32_ACT | C32_STATS: rc2 = go2(conv2b_mfma_kernel<C32_ACT | C32_STATS>); break;
-        case C32_ACT | C32_STATS | C32_ADD: rc2 = go2(conv2b_mfma_kernel<C32_ACT | C32_STATS | C32_ADD>); break;
-        case C32_GNB: rc2 = go2(conv2b_mfma_kernel<C32_GNB>); break;
-        default: rc2 = go2(conv2b_mfma_kernel<C32_GNB | C32_ADD>); break;
-      }
-      if (rc2) return rc2;
-      return check_launch("conv2b_mfma");
+      if (probe) return plan_answer(probe, b2.stats_accum ? 6 : 5, grid2, b2.nitems, b2);
+      return c32_dispatch(variant, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        return launch_lds("conv2b_mfma", split ? conv2b_mfma_kernel<V | C32_SPLIT> : conv2b_mfma_kernel<V>, dim3(grid2), dim3(256), C2B_LDS, s, b2);
+      });
     }
   }
-  if (probe) {
-    *probe = FwdPlanProbe{a.stats_accum ? 3 : 2, (int)grid, a.nitems, a.ncb, a.ntiles, a.tiles_z * a.tiles_y * a.tiles_x,
-                          a.stats_accum, a.stats_rows, 0, 0, a.tiles_x, a.tiles_y, a.tiles_z};
-    return MEDNET_OK;
-  }
-  static bool attr_set[4] = {false, false, false, false};
-  if (!attr_set[KIND]) {
-    if (hipFuncSetAttribute((const void*)conv_mfma_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "conv_mfma: cannot raise dynamic LDS to %zu", lds);
-    attr_set[KIND] = true;
-  }
+  if (probe) return plan_answer(probe, a.stats_accum ? 3 : 2, (int)grid, a.nitems, a);
   if constexpr (STRIDE == 1) {
     if (use_gnb) {
       constexpr size_t lds_gnb = lds + 16 * 256 * sizeof(float);  // + the parked GroupNorm-backward sums (16 per thread)
       static_assert(lds_gnb <= 80 * 1024, "two workgroups must fit one CU");
-      static bool attr_gnb[4] = {false, false, false, false};
-      if (!attr_gnb[KIND]) {
-        if (hipFuncSetAttribute((const void*)conv_mfma_kernel<KIND, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_gnb) != hipSuccess)
-          return fail(MEDNET_E_HIP, "conv_mfma: cannot raise dynamic LDS to %zu", lds_gnb);
-        attr_gnb[KIND] = true;
-      }
-      hipLaunchKernelGGL((conv_mfma_kernel<KIND, true>), dim3(grid), dim3(256), lds_gnb, s, a);
-      return check_launch("conv_mfma(gnb)");
+      return launch_lds("conv_mfma(gnb)", conv_mfma_kernel<KIND, true>, dim3(grid), dim3(256), lds_gnb, s, a);
     }
   }
   if constexpr (STRIDE == 2) {
-    if (use_gnb) {
-      static bool attr_gnb2 = false;
-      if (!attr_gnb2) {
-        if (hipFuncSetAttribute((const void*)conv_mfma_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-          return fail(MEDNET_E_HIP, "conv_mfma: cannot raise dynamic LDS to %zu", lds);
-        attr_gnb2 = true;
-      }
-      hipLaunchKernelGGL((conv_mfma_kernel<2, true>), dim3(grid), dim3(256), lds, s, a);
-      return check_launch("conv_mfma(gnb, stride 2)");
-    }
+    if (use_gnb) return launch_lds("conv_mfma(gnb, stride 2)", conv_mfma_kernel<2, true>, dim3(grid), dim3(256), lds, s, a);
   }
-  hipLaunchKernelGGL((conv_mfma_kernel<KIND>), dim3(grid), dim3(256), lds, s, a);
-  return check_launch("conv_mfma");
+  return launch_lds("conv_mfma", conv_mfma_kernel<KIND>, dim3(grid), dim3(256), lds, s, a);
+}
+
+// A stride-1 launch (input and output grids agree) on the bricks conv_fwd_kind chooses; `gnb.y` says whether it is the
+// data-gradient form with a GroupNorm backward's sums, `lo_delta` whether the weights are split
+static int fwd_by_kind(const void* x, const void* sec, void* y, int n, int d, int h, int w, int cin, int cout, float* gn_partial,
+                       hipStream_t s, int act, const void* add, GnbSpec gnb, FwdPlanProbe* probe, size_t lo_delta) {
+  return conv_fwd_kind(n, d, h, w, cin, cout, gnb.y != nullptr, lo_delta != 0) == 3
+             ? launch_fwd<3>(x, sec, y, n, d, h, w, d, h, w, cin, cout, gn_partial, s, act, add, gnb, probe, lo_delta)
+             : launch_fwd<1>(x, sec, y, n, d, h, w, d, h, w, cin, cout, gn_partial, s, act, add, gnb, probe, lo_delta);
 }
 
 int launch_conv_mfma(const void* x, const void* packed_section, void* y, int n, int d, int h, int w, int cin, int cout,
                      int x_dtype, int y_dtype, float* gn_partial, hipStream_t s, int act, const void* add, size_t lo_delta) {
   (void)x_dtype;
   (void)y_dtype;
-  if (conv_fwd_kind(n, d, h, w, cin, cout, false, lo_delta != 0) == 3)
-    return launch_fwd<3>(x, packed_section, y, n, d, h, w, d, h, w, cin, cout, gn_partial, s, act, add, GnbSpec(), nullptr, lo_delta);
-  return launch_fwd<1>(x, packed_section, y, n, d, h, w, d, h, w, cin, cout, gn_partial, s, act, add, GnbSpec(), nullptr, lo_delta);
+  return fwd_by_kind(x, packed_section, y, n, d, h, w, cin, cout, gn_partial, s, act, add, GnbSpec(), nullptr, lo_delta);
 }
 // data gradient + the first pass of the GroupNorm backward its output feeds (gn_partial: per-channel {sum du, sum du*y})
 int launch_conv_mfma_gnb(const void* dy, const void* packed_section, void* dx, int n, int d, int h, int w, int cin, int cout,
@@ -1807,9 +1734,7 @@ int launch_conv_mfma_gnb(const void* dy, const void* packed_section, void* dx, i
   g.y = gn_y;
   g.coef = gn_coef;
   g.act = gn_act;
-  if (conv_fwd_kind(n, d, h, w, cin, cout, true, lo_delta != 0) == 3)
-    return launch_fwd<3>(dy, packed_section, dx, n, d, h, w, d, h, w, cin, cout, gn_partial, s, MEDNET_ACT_NONE, add, g, nullptr, lo_delta);
-  return launch_fwd<1>(dy, packed_section, dx, n, d, h, w, d, h, w, cin, cout, gn_partial, s, MEDNET_ACT_NONE, add, g, nullptr, lo_delta);
+  return fwd_by_kind(dy, packed_section, dx, n, d, h, w, cin, cout, gn_partial, s, MEDNET_ACT_NONE, add, g, nullptr, lo_delta);
 }
 // plan of launch_conv_mfma / launch_conv_mfma_gnb (stride 1) or launch_convt_dgrad_gn_mfma (stride 2; d, h, w = the LOW-resolution
 // grid the data gradient writes), with fused sums: out[13] = the fields of FwdPlanProbe in order
@@ -1828,9 +1753,7 @@ int conv_mfma_plan(int n, int d, int h, int w, int cin, int cout, bool gnb, int 
       g.y = &dummy_partial;
       g.coef = &dummy_partial;
     }
-    rc = conv_fwd_kind(n, d, h, w, cin, cout, gnb, split) == 3
-             ? launch_fwd<3>(nullptr, nullptr, nullptr, n, d, h, w, d, h, w, cin, cout, &dummy_partial, nullptr, MEDNET_ACT_NONE, nullptr, g, &p, lo)
-             : launch_fwd<1>(nullptr, nullptr, nullptr, n, d, h, w, d, h, w, cin, cout, &dummy_partial, nullptr, MEDNET_ACT_NONE, nullptr, g, &p, lo);
+    rc = fwd_by_kind(nullptr, nullptr, nullptr, n, d, h, w, cin, cout, &dummy_partial, nullptr, MEDNET_ACT_NONE, nullptr, g, &p, lo);
   }
   if (rc) return rc;
   const int v[13] = {p.kind, p.grid, p.nitems, p.ncb, p.ntiles, p.tiles_per_sample, p.accum, p.rows, p.xcd_chunk, p.zslab,
@@ -1843,11 +1766,7 @@ int conv_mfma_stats_chunks(int n, int d, int h, int w, int cin, int cout, bool g
   conv_stats_plan(n, d, h, w, cin, cout, rows, accum, gnb, split);
   // (A/B knob conv_fuse_gnb_general=0: only the 32 -> 32 specialisation takes the GroupNorm-backward sums in its epilogue; the
   //  general kernel's data gradients leave them to the stand-alone pass)
-  if (gnb && !tuning_option("conv_fuse_gnb_general", 1)) {
-    using G = FwdTile<1>;
-    const int ntiles16 = n * ((d + G::TZ - 1) / G::TZ) * ((h + G::TY - 1) / G::TY) * ((w + G::TX - 1) / G::TX);
-    if (!conv32_takes(ntiles16, cin, cout, true, split)) return 0;
-  }
+  if (gnb && !tuning_option("conv_fuse_gnb_general", 1) && !conv32_takes(bricks<FwdTile<1>>(n, d, h, w), cin, cout, true, split)) return 0;
   return rows;
 }
 
@@ -1860,8 +1779,7 @@ int launch_convt_dgrad_mfma(const void* dy, const void* packed_section, void* dx
 // ... + the first pass of the GroupNorm-3 backward of the ExtResNetBlock whose output the ConvTranspose3d upsamples
 // (model.py:202-207): one partial row per wave and brick, gn_partial[n][rows][Cin][2]
 int convt_dgrad_gn_rows(int n, int d, int h, int w, int cin, int cout, bool split) {
-  using G = FwdTile<2>;
-  const int tps = ((d + G::TZ - 1) / G::TZ) * ((h + G::TY - 1) / G::TY) * ((w + G::TX - 1) / G::TX);
+  const int tps = bricks<FwdTile<2>>(1, d, h, w);
   // (cin, cout are the ConvTranspose3d's: its data gradient reads cout channels and writes cin)
   if (convt_dgrad32_takes(n * tps, cout, cin, split)) return 2 * 256;  // convt_dgrad32_mfma_kernel: 2 rows per workgroup and sample
   return 4 * tps;
@@ -2424,67 +2342,50 @@ size_t wgrad_mfma_ws_bytes(int n, int d, int h, int w, int cin, int cout, int ks
   return v2 > v4 ? v2 : v4;
 }
 
+// The operands of a weight-gradient launch (Wg2Args, Wg4Args, Ct2Args): A with ka channels on the (d, h, w) grid, B with kb channels
+// on a grid of scale_b times as many voxels, both addressed per sample; the workgroups' partial sums go to the workspace
+template <typename Args>
+static void wgrad_operands(Args& a, const void* A, int ka, const void* B, int kb, int scale_b, void* ws, int n, int d, int h, int w) {
+  a.A = (const elt*)A;
+  a.B = (const elt*)B;
+  a.part = (float*)ws;
+  a.n = n; a.d = d; a.h = h; a.w = w; a.ka = ka; a.kb = kb;
+  a.bytesA = (unsigned)((size_t)d * h * w * ka * 2);  // per sample
+  a.bytesB = (unsigned)((size_t)scale_b * d * h * w * kb * 2);
+}
+template <typename Args>
+static size_t wgrad_part_bytes(const Args& a) { return (size_t)a.nab * a.nbb * a.splits * 27 * 1024 * sizeof(float); }
+// part[pair][split][27][32][32] -> dw, the splits summed in a fixed order
+static int launch_wgrad_reduce(const float* part, float* dw, int ka, int kb, int nab, int nbb, int splits, hipStream_t s) {
+  const size_t total = (size_t)nab * nbb * 1024 * 27;
+  if (splits < 4) hipLaunchKernelGGL(wgrad_mfma_reduce_kernel_few, dim3((unsigned)(nab * nbb * 4)), dim3(256), 0, s, part, dw, ka, kb, nbb, splits);
+  else hipLaunchKernelGGL(wgrad_mfma_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, part, dw, ka, kb, nbb, splits);
+  return check_launch("wgrad_mfma_reduce");
+}
+
 int launch_wgrad_mfma(const void* x, const void* dy, float* dw, int n, int d, int h, int w, int cin, int cout, int dtype,
                       void* ws, size_t ws_bytes, hipStream_t s, int workgroups) {
   (void)dtype;
   // conv: A = dy (Cout rows), B = x (Cin cols) shifted by tap - 1
   if (wgrad4_applies(d, h, w)) {
     Wg4Args a;
-    a.A = (const elt*)dy;
-    a.B = (const elt*)x;
-    a.part = (float*)ws;
-    a.n = n; a.d = d; a.h = h; a.w = w; a.ka = cout; a.kb = cin;
+    wgrad_operands(a, dy, cout, x, cin, 1, ws, n, d, h, w);
     wgrad4_plan(n, d, h, w, cout, cin, workgroups, a);
-    a.bytesA = (unsigned)((size_t)d * h * w * cout * 2);  // per sample
-    a.bytesB = (unsigned)((size_t)d * h * w * cin * 2);
-    const size_t need = (size_t)a.nab * a.nbb * a.splits * 27 * 1024 * sizeof(float);
+    const size_t need = wgrad_part_bytes(a);
     MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "wgrad_mfma4: workspace %zu < %zu", ws_bytes, need);
-    static bool attr4 = false;
-    if (!attr4) {
-      if (hipFuncSetAttribute((const void*)wgrad_mfma4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG4_LDS) != hipSuccess)
-        return fail(MEDNET_E_HIP, "wgrad_mfma4: cannot raise dynamic LDS to %zu", WG4_LDS);
-      attr4 = true;
-    }
-    hipLaunchKernelGGL(wgrad_mfma4_kernel, dim3(a.nab * a.nbb * a.splits), dim3(256), WG4_LDS, s, a);
-    int rc4 = check_launch("wgrad_mfma4");
-    if (rc4) return rc4;
-    const size_t total4 = (size_t)a.nab * a.nbb * 1024 * 27;
-    if (a.splits < 4) hipLaunchKernelGGL(wgrad_mfma_reduce_kernel_few, dim3((unsigned)(a.nab * a.nbb * 4)), dim3(256), 0, s, a.part, dw, cout, cin,
-                       a.nbb, a.splits);
-    else hipLaunchKernelGGL(wgrad_mfma_reduce_kernel, dim3((unsigned)((total4 + 63) / 64)), dim3(256), 0, s, a.part, dw, cout, cin,
-                       a.nbb, a.splits);
-    return check_launch("wgrad_mfma_reduce");
+    const int rc4 = launch_lds("wgrad_mfma4", wgrad_mfma4_kernel, dim3(a.nab * a.nbb * a.splits), dim3(256), WG4_LDS, s, a);
+    return rc4 ? rc4 : launch_wgrad_reduce(a.part, dw, cout, cin, a.nab, a.nbb, a.splits, s);
   }
   const int tx = wgrad2_tx(w);
   size_t lds = ((size_t)4 * 8 * tx + 6 * 10 * (tx + 2)) * 64;
   if (lds < 65536) lds = 65536;  // (the k-groups' merge area at the end: 4 tap waves x 4 slots x 16 x 64 floats)
   Wg2Args a;
-  a.A = (const elt*)dy;
-  a.B = (const elt*)x;
-  a.part = (float*)ws;
-  a.n = n; a.d = d; a.h = h; a.w = w; a.ka = cout; a.kb = cin;
+  wgrad_operands(a, dy, cout, x, cin, 1, ws, n, d, h, w);
   wgrad2_plan(n, d, h, w, cout, cin, workgroups, a);
-  a.bytesA = (unsigned)((size_t)d * h * w * cout * 2);  // per sample
-  a.bytesB = (unsigned)((size_t)d * h * w * cin * 2);
-  const size_t need = (size_t)a.nab * a.nbb * a.splits * 27 * 1024 * sizeof(float);
+  const size_t need = wgrad_part_bytes(a);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "wgrad_mfma2: workspace %zu < %zu", ws_bytes, need);
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[tx == 8]) {
-    const hipError_t e = tx == 8 ? hipFuncSetAttribute((const void*)wgrad_mfma2_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                 : hipFuncSetAttribute((const void*)wgrad_mfma2_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(MEDNET_E_HIP, "wgrad_mfma2: cannot raise dynamic LDS to %zu", lds);
-    attr_set[tx == 8] = true;
-  }
-  if (tx == 8) hipLaunchKernelGGL(wgrad_mfma2_kernel<8>, dim3(a.nab * a.nbb * a.splits), dim3(512), lds, s, a);
-  else hipLaunchKernelGGL(wgrad_mfma2_kernel<16>, dim3(a.nab * a.nbb * a.splits), dim3(512), lds, s, a);
-  int rc = check_launch("wgrad_mfma2");
-  if (rc) return rc;
-  const size_t total = (size_t)a.nab * a.nbb * 1024 * 27;
-  if (a.splits < 4) hipLaunchKernelGGL(wgrad_mfma_reduce_kernel_few, dim3((unsigned)(a.nab * a.nbb * 4)), dim3(256), 0, s, a.part, dw, cout, cin,
-                     a.nbb, a.splits);
-  else hipLaunchKernelGGL(wgrad_mfma_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, a.part, dw, cout, cin,
-                     a.nbb, a.splits);
-  return check_launch("wgrad_mfma_reduce");
+  const int rc = launch_lds("wgrad_mfma2", tx == 8 ? wgrad_mfma2_kernel<8> : wgrad_mfma2_kernel<16>, dim3(a.nab * a.nbb * a.splits), dim3(512), lds, s, a);
+  return rc ? rc : launch_wgrad_reduce(a.part, dw, cout, cin, a.nab, a.nbb, a.splits, s);
 }
 
 // ---- the first layer (Cin = 1 .. 4): forward with fused GroupNorm sums and weight gradient, contraction over Cin x 27 taps
@@ -2707,30 +2608,12 @@ int launch_convt_wgrad_mfma(const void* x, const void* dy, float* dw, int n, int
   // convT: A = x (Cin rows) on the (d,h,w) grid, B = dy (Cout cols) on the (2d,2h,2w) grid at 2v - 1 + tap
   constexpr size_t lds = 16384 + 8 * 128 * 64;
   Ct2Args a;
-  a.A = (const elt*)x;
-  a.B = (const elt*)dy;
-  a.part = (float*)ws;
-  a.n = n; a.d = d; a.h = h; a.w = w; a.ka = cin; a.kb = cout;
+  wgrad_operands(a, x, cin, dy, cout, 8, ws, n, d, h, w);
   ct2_plan(n, d, h, w, cin, cout, workgroups, a);
-  a.bytesA = (unsigned)((size_t)d * h * w * cin * 2);
-  a.bytesB = (unsigned)((size_t)8 * d * h * w * cout * 2);
-  const size_t need = (size_t)a.nab * a.nbb * a.splits * 27 * 1024 * sizeof(float);
+  const size_t need = wgrad_part_bytes(a);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "convt_wgrad_mfma2: workspace %zu < %zu", ws_bytes, need);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)convt_wgrad_mfma2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "convt_wgrad_mfma2: cannot raise dynamic LDS to %zu", lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(convt_wgrad_mfma2_kernel, dim3(a.nab * a.nbb * a.splits), dim3(512), lds, s, a);
-  int rc = check_launch("convt_wgrad_mfma2");
-  if (rc) return rc;
-  const size_t total = (size_t)a.nab * a.nbb * 1024 * 27;
-  if (a.splits < 4) hipLaunchKernelGGL(wgrad_mfma_reduce_kernel_few, dim3((unsigned)(a.nab * a.nbb * 4)), dim3(256), 0, s, a.part, dw, cin, cout,
-                     a.nbb, a.splits);
-  else hipLaunchKernelGGL(wgrad_mfma_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, a.part, dw, cin, cout,
-                     a.nbb, a.splits);
-  return check_launch("wgrad_mfma_reduce");
+  const int rc = launch_lds("convt_wgrad_mfma2", convt_wgrad_mfma2_kernel, dim3(a.nab * a.nbb * a.splits), dim3(512), lds, s, a);
+  return rc ? rc : launch_wgrad_reduce(a.part, dw, cin, cout, a.nab, a.nbb, a.splits, s);
 }
 
 }  // namespace mednet

@@ -497,14 +497,7 @@ static int launch_x3(const void* x, const void* sec_hi, size_t lo_delta, const f
     const int yb = 32 / a.tiles_x < a.tiles_y ? 32 / a.tiles_x : a.tiles_y;
     if (a.tiles_y % yb == 0) a.yb = yb;
   }
-  static bool attr_set[3] = {false, false, false};
-  if (!attr_set[STRIDE]) {
-    if (hipFuncSetAttribute((const void*)conv_x3_kernel<STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "conv_x3: cannot raise dynamic LDS to %zu", lds);
-    attr_set[STRIDE] = true;
-  }
-  hipLaunchKernelGGL((conv_x3_kernel<STRIDE>), dim3(x3_grid()), dim3(G::NWAVES * 64), lds, s, a);
-  return check_launch("conv_x3");
+  return launch_lds("conv_x3", conv_x3_kernel<STRIDE>, dim3(x3_grid()), dim3(G::NWAVES * 64), lds, s, a);
 }
 
 int launch_conv_x3(const void* x, const void* sec_hi, size_t lo_delta, const float* bias, void* y, int n, int d, int h, int w, int k,
@@ -856,14 +849,7 @@ int launch_convt_fwd_x3(const void* x, const void* sec_hi, size_t lo_delta, cons
   a.nkc = cin / 16;
   a.ncb = (cout + 31) / 32;
   MEDNET_REQUIRE((double)a.ntiles * a.ncb < 2147483647.0, MEDNET_E_UNSUPPORTED, "convt_x3: grid too large");
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)convt_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "convt_x3: cannot raise dynamic LDS to %zu", lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(convt_x3_kernel, dim3((unsigned)(a.ntiles * a.ncb)), dim3(256), lds, s, a);
-  return check_launch("convt_x3");
+  return launch_lds("convt_x3", convt_x3_kernel, dim3((unsigned)(a.ntiles * a.ncb)), dim3(256), lds, s, a);
 }
 
 // ================================================================================================== weight gradient
@@ -1235,14 +1221,7 @@ int launch_wgrad_c1_x3(const void* x, const void* dy, float* part, int n, int d,
   a.bytes_x = (unsigned)((size_t)d * h * w * 4);
   a.bytes_dy = (unsigned)((size_t)d * h * w * 32 * 4);
   constexpr size_t lds = 4352 + (size_t)2 * 512 * 64;  // halo of x + the two planes of dy (> the 16 KB of the final reduction)
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)wgrad_c1_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "wgrad_c1_x3: cannot raise dynamic LDS to %zu", lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(wgrad_c1_x3_kernel, dim3(wgrad_c1_x3_blocks(n, d, h, w)), dim3(256), lds, s, a);
-  return check_launch("wgrad_c1_x3");
+  return launch_lds("wgrad_c1_x3", wgrad_c1_x3_kernel, dim3(wgrad_c1_x3_blocks(n, d, h, w)), dim3(256), lds, s, a);
 }
 
 int launch_wgrad_x3(const void* x, const void* dy, float* dw, int n, int d, int h, int w, int cin, int cout, void* ws,
@@ -1260,14 +1239,7 @@ int launch_wgrad_x3(const void* x, const void* dy, float* dw, int n, int d, int 
   a.bytesB = (unsigned)((size_t)d * h * w * cin * 4);
   const size_t need = (size_t)a.nab * a.nbb * a.splits * 27 * 1024 * sizeof(float);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "wgrad_x3: workspace %zu < %zu", ws_bytes, need);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)wgrad_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(MEDNET_E_HIP, "wgrad_x3: cannot raise dynamic LDS to %zu", lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(wgrad_x3_kernel, dim3(a.nab * a.nbb * a.splits), dim3(512), lds, s, a);
-  int rc = check_launch("wgrad_x3");
+  int rc = launch_lds("wgrad_x3", wgrad_x3_kernel, dim3(a.nab * a.nbb * a.splits), dim3(512), lds, s, a);
   if (rc) return rc;
   const size_t total = (size_t)a.nab * a.nbb * 1024 * 27;
   if (a.splits < 4) hipLaunchKernelGGL(wgrad_x3_reduce_kernel_few, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.part, dw, cout, cin, a.nbb, a.splits);
@@ -1493,17 +1465,7 @@ int launch_convt_wgrad_x3(const void* x, const void* dy, float* dw, int n, int d
   const size_t need = (size_t)a.nab * a.nbb * a.splits * 27 * ca * 1024 * sizeof(float);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "convt_wgrad_x3: workspace %zu < %zu", ws_bytes, need);
   const size_t lds = ((size_t)2 * ca * 153 + 2 * 512) * 64;
-  static bool attr_set[3] = {false, false, false};
-  if (!attr_set[ca]) {
-    const hipError_t e = ca == 2 ? hipFuncSetAttribute((const void*)convt_wgrad_x3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                 : hipFuncSetAttribute((const void*)convt_wgrad_x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(MEDNET_E_HIP, "convt_wgrad_x3: cannot raise dynamic LDS to %zu", lds);
-    attr_set[ca] = true;
-  }
-  const dim3 grid(a.nab * a.nbb * a.splits);
-  if (ca == 2) hipLaunchKernelGGL(convt_wgrad_x3_kernel<2>, grid, dim3(512), lds, s, a);
-  else hipLaunchKernelGGL(convt_wgrad_x3_kernel<1>, grid, dim3(512), lds, s, a);
-  int rc = check_launch("convt_wgrad_x3");
+  int rc = launch_lds("convt_wgrad_x3", ca == 2 ? convt_wgrad_x3_kernel<2> : convt_wgrad_x3_kernel<1>, dim3(a.nab * a.nbb * a.splits), dim3(512), lds, s, a);
   if (rc) return rc;
   const size_t total = (size_t)a.nab * a.nbb * 27 * ca * 1024;
   hipLaunchKernelGGL(convt_wgrad_x3_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.part, dw, cin, cout, a.nbb,

@@ -19,22 +19,11 @@ from . import _lib as L
 from . import config, debug, ops
 
 ENABLED = os.environ.get("MEDNET_BLOCK_NODE", "1") == "1"
-WGRAD_FIRST = os.environ.get("MEDNET_WGRAD_FIRST", "1") == "1"  # A/B knob: launch order of the two gradients
+WGRAD_FIRST = ops.WGRAD_FIRST  # A/B knob: launch order of the two gradients (this module's own switch for the block's layers)
 
 
 def _conv_fwd(x, packed, cout, want_stats, x_layout=L.NDHWC):
-    n, cin, d, h, w = x.shape
-    lib = L.lib()
-    y = ops.empty_cl(n, cout, d, h, w, config.act_dtype(), x.device)
-    partial = None
-    if want_stats:
-        chunks = lib.mednet_conv3d_fused_stats_chunks(n, d, h, w, cin, cout, 3, L.dt(x), L.dt(y), config.conv_algo())
-        if chunks > 0:
-            partial = torch.empty((n, chunks, cout, 2), dtype=torch.float32, device=x.device)
-    with ops.profiled_conv(3, cin, cout, n, d, h, w):
-        L.check(lib.mednet_conv3d_fwd(x.data_ptr(), packed.data_ptr(), None, y.data_ptr(), n, d, h, w, cin, cout, 3, L.dt(x),
-                                      x_layout, L.dt(y), L.NDHWC, 0, config.conv_algo(), L.ptr(partial), L.stream()), "conv3d_fwd")
-    return y, partial
+    return ops.conv_forward(x, x_layout, packed, None, cout, 3, False, config.act_dtype(), want_stats)
 
 
 FUSE_POOL = os.environ.get("MEDNET_FUSE_POOL", "1") == "1"  # A/B knob: the next level's pooling inside the block's last apply pass
@@ -102,59 +91,13 @@ def _c1_gn_bwd(xin, dz, y, coef, stats, gamma_p, beta_p, weight_p, groups, act, 
 FUSE_DRES = os.environ.get("MEDNET_FUSE_DRES", "1") == "1"  # A/B knob: residual gradient summed in conv2's data gradient
 
 
-FUSE_GNB = os.environ.get("MEDNET_FUSE_GNB", "1") == "1"  # A/B knob: GroupNorm-backward sums in the data-gradient epilogue
+FUSE_GNB = ops.FUSE_GNB  # A/B knob: GroupNorm-backward sums in the data-gradient epilogue (this module's own switch, as WGRAD_FIRST)
 
 
 def _conv_bwd(x, dy, packed, weight_p, need_dx, add=None, gnb=None, x_layout=L.NDHWC):
-    """Weight gradient (side stream in trainer mode) + data gradient (+ `add`, a second gradient of x, summed in the
-    data-gradient kernel's epilogue when given).  `gnb` = (y_prev, coef_prev, act): x is act(GroupNorm(y_prev)); when the
-    kernel can, it also takes the first pass of that GroupNorm's backward over the dx it stores.
-    Returns (dx, dw-or-None, partial-or-None)."""
-    n, cin, d, h, w = x.shape
-    cout = dy.shape[1]
-    lib = L.lib()
-    # data gradient first (critical path), THEN the weight gradient on the side stream: queued behind the data gradient it
-    # overlaps the next GroupNorm backward (HBM-bound) instead of fighting the data gradient for the matrix cores
-    dx = None
-    partial = None
-
-    def dgrad():
-        nonlocal dx, partial
-        if need_dx:
-            dx = ops.empty_cl(n, cin, d, h, w, x.dtype if x.dtype in (torch.float32, config.act_dtype()) else config.act_dtype(), dy.device)
-            rows = 0
-            if gnb is not None and FUSE_GNB and dx.dtype == dy.dtype and (add is None or add.dtype == dy.dtype):
-                # (16-bit storage: the bf16 / fp16 matrix-core kernel; fp32 storage: the split-bf16 kernel)
-                rows = lib.mednet_conv3d_dgrad_gn_rows_dt(n, d, h, w, cin, cout, config.conv_algo(), L.dt(dy))
-            variant = ("add+gn" if add is not None else "gn") if rows > 0 else ("add" if add is not None else "plain")
-            with ops.profiled_dgrad(variant, 3, cout, cin, n, d, h, w):
-                if rows > 0:
-                    y_prev, coef_prev, act_prev = gnb
-                    partial = torch.empty((n, rows, cin, 2), dtype=torch.float32, device=dy.device)
-                    L.check(lib.mednet_conv3d_dgrad_gn(dy.data_ptr(), packed.data_ptr(), L.ptr(add), dx.data_ptr(), y_prev.data_ptr(),
-                                                       coef_prev.data_ptr(), act_prev, partial.data_ptr(), n, d, h, w, cin, cout,
-                                                       config.conv_algo(), L.dt(dy), L.stream()), "conv3d_dgrad_gn")
-                elif add is not None:
-                    L.check(lib.mednet_conv3d_dgrad_add(dy.data_ptr(), packed.data_ptr(), add.data_ptr(), dx.data_ptr(), n, d, h, w,
-                                                        cin, cout, config.conv_algo(), L.dt(dy), L.stream()), "conv3d_dgrad_add")
-                else:
-                    L.check(lib.mednet_conv3d_fwd(dy.data_ptr(), packed.data_ptr(), None, dx.data_ptr(), n, d, h, w, cout, cin, 3,
-                                                  L.dt(dy), L.NDHWC, L.dt(dx), L.NDHWC, 1, config.conv_algo(), None, L.stream()),
-                            "conv3d_dgrad")
-
-    if not WGRAD_FIRST:
-        dgrad()
-    dw, direct = ops._grad_target(weight_p, (cout, cin, 3, 3, 3))
-    on_side = ops.SIDE["enabled"] and direct
-    with ops._OnSide(on_side, dy.device, x, dy, coresident=on_side and ops.wgrad_coresident(n, d, h, w, cin, cout, 3, x, dy)) as side:
-        ws = L.workspace(lib.mednet_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout, 3, side.workgroups), dy.device)
-        with ops.profiled_wgrad(3, cin, cout, n, d, h, w):
-            L.check(lib.mednet_conv3d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), None, n, d, h, w, cin, cout, 3, L.dt(x),
-                                            x_layout, L.dt(dy), L.NDHWC, config.conv_algo(), side.workgroups, ws.data_ptr(),
-                                            ws.numel(), L.stream()), "conv3d_wgrad")
-    if WGRAD_FIRST:
-        dgrad()
-    return dx, (None if direct else dw), partial
+    """ops.conv_backward under this module's switches.  Returns (dx, dw-or-None, partial-or-None)."""
+    return ops.conv_backward(x, dy, packed, weight_p, need_dx, ops.block_dx_dtype(x), add=add, gnb=gnb if FUSE_GNB else None,
+                             x_layout=x_layout, wgrad_first=WGRAD_FIRST)
 
 
 class ResBlockFn(Function):

@@ -7,6 +7,7 @@ fragments; the network input (C=1) and the logits (written planar by the 1x1x1 h
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -351,6 +352,133 @@ def _gn3_hook_of(x, dtype):
     return h
 
 
+# One path for Conv3dFn, ConvActFn, ConvT3dFn and the ExtResNetBlock node (block.py): the fused partial rows (fused_partial_rows),
+# the stride-1 forward (conv_forward), the stride-1 data gradient (conv_dgrad), the weight gradient (conv_wgrad) and the two
+# gradients in the trainer's order (conv_backward).  What the call sites do differently comes in as arguments.
+FUSE_GNB = os.environ.get("MEDNET_FUSE_GNB", "1") == "1"  # A/B knob: GroupNorm-backward sums in the data-gradient epilogue
+WGRAD_FIRST = os.environ.get("MEDNET_WGRAD_FIRST", "1") == "1"  # A/B knob: launch order of the two gradients
+
+
+def fused_partial_rows(n, d, h, w, cin, cout, ksize, x_dt, y_dt, device):
+    """-> the rows [n][chunks][cout][2] that the convolution's epilogue fills with the GroupNorm sums of its output (saves a pass
+    over y), or None when no kernel takes this call with them."""
+    chunks = L.lib().mednet_conv3d_fused_stats_chunks(n, d, h, w, cin, cout, ksize, x_dt, y_dt, config.conv_algo())
+    return torch.empty((n, chunks, cout, 2), dtype=torch.float32, device=device) if chunks > 0 else None
+
+
+def _partial_out(ctx, partial, device):
+    """A node's second output: autograd needs a tensor, so "no fused statistics" leaves as an empty one (_partial_in: back)."""
+    if partial is None:
+        partial = torch.empty(0, device=device)
+    ctx.mark_non_differentiable(partial)
+    return partial
+
+
+def _partial_in(partial):
+    return partial if partial.numel() else None
+
+
+def conv_forward(x, x_layout, packed, bias, cout, ksize, out_planar, out_dtype, want_stats):
+    """Stride-1 convolution of x (read in `x_layout`) -> (y, fused partial rows or None)."""
+    n, cin, d, h, w = x.shape
+    if out_planar:
+        y = torch.empty((n, cout, d, h, w), dtype=out_dtype, device=x.device)
+    else:
+        y = empty_cl(n, cout, d, h, w, out_dtype, x.device)
+    partial = fused_partial_rows(n, d, h, w, cin, cout, ksize, L.dt(x), L.dt(y), x.device) if want_stats else None
+    with profiled_conv(ksize, cin, cout, n, d, h, w):
+        L.check(L.lib().mednet_conv3d_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), y.data_ptr(), n, d, h, w, cin, cout, ksize,
+                                          L.dt(x), x_layout, L.dt(y), L.NCDHW if out_planar else L.NDHWC, 0, config.conv_algo(),
+                                          L.ptr(partial), L.stream()), "conv3d_fwd")
+    return y, partial
+
+
+def conv_dgrad(dy, packed, x_shape, cout, ksize, dx_dtype, dy_planar=False, head=None, gnb=None, add=None, profiled=False):
+    """Data gradient of a stride-1 convolution whose input had `x_shape` -> (dx, partial rows or None), by the first form that
+    applies:
+      head = (y3, out, act): the convolution is the 1x1x1 head on an ExtResNetBlock's output `out` -- + the first pass of the block's
+        GroupNorm-3 backward (mednet_head_dgrad_gn);
+      gnb = (y_prev, coef_prev, act): x is act(norm(y_prev)) -- + the first pass of that GroupNorm's / BatchNorm's backward over the
+        dx it stores, with or without `add` (mednet_conv3d_dgrad_gn; 16-bit storage: the bf16 / fp16 matrix-core kernel, fp32
+        storage: the split-bf16 kernel);
+      add: a second gradient of x, summed in the epilogue (mednet_conv3d_dgrad_add);
+      plain.
+    `profiled`: the launch counts for bench.py's data-gradient roofline."""
+    n, cin, d, h, w = x_shape
+    lib, algo = L.lib(), config.conv_algo()
+    dx = empty_cl(n, cin, d, h, w, dx_dtype, dy.device)
+    head_rows = lib.mednet_head_dgrad_gn_rows(n, d, h, w, cin, L.dt(dx)) if head is not None else 0
+    gn_rows = 0
+    if head_rows == 0 and gnb is not None and dx.dtype == dy.dtype and (add is None or add.dtype == dy.dtype):
+        gn_rows = lib.mednet_conv3d_dgrad_gn_rows_dt(n, d, h, w, cin, cout, algo, L.dt(dy))
+    rows = head_rows or gn_rows
+    variant = ("add+gn" if add is not None else "gn") if rows > 0 else ("add" if add is not None else "plain")
+    with profiled_dgrad(variant, ksize, cout, cin, n, d, h, w) if profiled else contextlib.nullcontext():
+        partial = torch.empty((n, rows, cin, 2), dtype=torch.float32, device=dy.device) if rows > 0 else None
+        if head_rows > 0:
+            y3, out, act = head
+            L.check(lib.mednet_head_dgrad_gn(dy.data_ptr(), packed.data_ptr(), dx.data_ptr(), y3.data_ptr(), out.data_ptr(), act,
+                                             partial.data_ptr(), n, d, h, w, cin, cout, L.dt(dx), L.stream()), "head_dgrad_gn")
+        elif gn_rows > 0:
+            y_prev, coef_prev, act_prev = gnb
+            L.check(lib.mednet_conv3d_dgrad_gn(dy.data_ptr(), packed.data_ptr(), L.ptr(add), dx.data_ptr(), y_prev.data_ptr(),
+                                               coef_prev.data_ptr(), act_prev, partial.data_ptr(), n, d, h, w, cin, cout, algo,
+                                               L.dt(dy), L.stream()), "conv3d_dgrad_gn")
+        elif add is not None:
+            L.check(lib.mednet_conv3d_dgrad_add(dy.data_ptr(), packed.data_ptr(), add.data_ptr(), dx.data_ptr(), n, d, h, w, cin, cout,
+                                                algo, L.dt(dy), L.stream()), "conv3d_dgrad_add")
+        else:
+            L.check(lib.mednet_conv3d_fwd(dy.data_ptr(), packed.data_ptr(), None, dx.data_ptr(), n, d, h, w, cout, cin, ksize, L.dt(dy),
+                                          L.NCDHW if dy_planar else L.NDHWC, L.dt(dx), L.NDHWC, 1, algo, None, L.stream()), "conv3d_dgrad")
+    return dx, partial
+
+
+def conv_wgrad(x, dy, weight_p, bias_p, ksize, x_layout=L.NDHWC, dy_planar=False, coresident=False, profiled=False, transposed=False):
+    """Weight (and, with `bias_p`, bias) gradient of a stride-1 convolution or (`transposed`) of ConvTranspose3d -> (dw, db), each None
+    when the kernel wrote it into the trainer's buffer (_grad_target).  With in-place targets for everything it writes, the launch
+    goes to the side stream; `coresident`: the caller wants all CUs for it there when the kernel leaves room beside it
+    (wgrad_coresident).  `profiled`: the launch counts for bench.py's weight-gradient roofline."""
+    n, cin, d, h, w = x.shape
+    cout = dy.shape[1]
+    lib = L.lib()
+    dw, direct_w = _grad_target(weight_p, (cin, cout, 3, 3, 3) if transposed else (cout, cin, ksize, ksize, ksize))
+    db, direct_b = _grad_target(bias_p, (cout,)) if bias_p is not None else (None, False)
+    on_side = SIDE["enabled"] and direct_w and (db is None or direct_b)
+    cores = on_side and coresident and wgrad_coresident(n, d, h, w, cin, cout, ksize, x, dy)
+    with _OnSide(on_side, dy.device, x, dy, coresident=cores) as side:
+        if transposed:
+            ws = L.workspace(lib.mednet_convt3d_wgrad_ws_bytes(n, d, h, w, cin, cout, side.workgroups), dy.device)
+            L.check(lib.mednet_convt3d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), L.ptr(db), n, d, h, w, cin, cout, L.dt(x),
+                                             L.dt(dy), config.conv_algo(), side.workgroups, ws.data_ptr(), ws.numel(), L.stream()),
+                    "convt3d_wgrad")
+        else:
+            ws = L.workspace(lib.mednet_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout, ksize, side.workgroups), dy.device)
+            with profiled_wgrad(ksize, cin, cout, n, d, h, w) if profiled else contextlib.nullcontext():
+                L.check(lib.mednet_conv3d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), L.ptr(db), n, d, h, w, cin, cout, ksize,
+                                                L.dt(x), x_layout, L.dt(dy), L.NCDHW if dy_planar else L.NDHWC, config.conv_algo(),
+                                                side.workgroups, ws.data_ptr(), ws.numel(), L.stream()), "conv3d_wgrad")
+    return (None if direct_w else dw), (None if direct_b else db)
+
+
+def conv_backward(x, dy, packed, weight_p, need_dx, dx_dtype, add=None, gnb=None, x_layout=L.NDHWC, wgrad_first=False):
+    """The two gradients of a 3x3x3 layer inside a block-style node (ExtResNetBlock, ConvActFn), launches counted for bench.py's
+    rooflines: weight gradient (side stream in trainer mode) and data gradient (conv_dgrad's `add` / `gnb` forms), the weight
+    gradient first if `wgrad_first`.  Queued behind the data gradient, the weight gradient overlaps the next GroupNorm backward
+    (HBM-bound) instead of fighting the data gradient for the matrix cores.  -> (dx, dw-or-None, partial-or-None)."""
+    dx = partial = None
+    if need_dx and not wgrad_first:
+        dx, partial = conv_dgrad(dy, packed, x.shape, dy.shape[1], 3, dx_dtype, gnb=gnb, add=add, profiled=True)
+    dw, _ = conv_wgrad(x, dy, weight_p, None, 3, x_layout=x_layout, coresident=True, profiled=True)
+    if need_dx and wgrad_first:
+        dx, partial = conv_dgrad(dy, packed, x.shape, dy.shape[1], 3, dx_dtype, gnb=gnb, add=add, profiled=True)
+    return dx, dw, partial
+
+
+def block_dx_dtype(x):
+    """Type of the data gradient inside a block-style node: x's own if that is fp32 or the storage type, else the storage type."""
+    return x.dtype if x.dtype in (torch.float32, config.act_dtype()) else config.act_dtype()
+
+
 class Conv3dFn(Function):
     """nn.Conv3d(k in {1,3}, stride 1, padding k//2)  -- components.py:8-9,44; model.py:77,179."""
 
@@ -363,20 +491,8 @@ class Conv3dFn(Function):
         cout = weight.shape[0]
         # Cin == 1: NCDHW and NDHWC coincide, so the network input is consumed as it arrives; so are 2-4 fp32 channels
         xin, x_layout = first_layer_input(x, cout, ksize, out_dtype, plain=bias is None and not out_planar)
-        if out_planar:
-            y = torch.empty((n, cout, d, h, w), dtype=out_dtype, device=x.device)
-        else:
-            y = empty_cl(n, cout, d, h, w, out_dtype, x.device)
-        # GroupNorm partial sums from the conv epilogue (when the MFMA kernel takes this call): saves a pass over y
-        partial = None
-        if want_stats and bias is None and not out_planar:
-            chunks = L.lib().mednet_conv3d_fused_stats_chunks(n, d, h, w, cin, cout, ksize, L.dt(xin), L.dt(y), config.conv_algo())
-            if chunks > 0:
-                partial = torch.empty((n, chunks, cout, 2), dtype=torch.float32, device=x.device)
-        with profiled_conv(ksize, cin, cout, n, d, h, w):
-            L.check(L.lib().mednet_conv3d_fwd(xin.data_ptr(), packed.data_ptr(), L.ptr(bias), y.data_ptr(), n, d, h, w, cin,
-                                              cout, ksize, L.dt(xin), x_layout, L.dt(y), L.NCDHW if out_planar else L.NDHWC,
-                                              0, config.conv_algo(), L.ptr(partial), L.stream()), "conv3d_fwd")
+        y, partial = conv_forward(xin, x_layout, packed, bias, cout, ksize, out_planar, out_dtype,
+                                  want_stats and bias is None and not out_planar)
         ctx.save_for_backward(xin, packed)
         ctx.x_layout = x_layout
         ctx.meta = (ksize, out_planar, cin, cout, bias is not None, x.dtype)
@@ -390,64 +506,31 @@ class Conv3dFn(Function):
             ctx.gnb = hook if isinstance(hook, BNBHook) else None
         if debug.TRACE is not None:
             debug.trace(f"conv3d.fwd k{ksize} {cin}->{cout}", y, partial)
-        if not want_stats:
-            return y
-        if partial is None:
-            partial = torch.empty(0, device=x.device)  # "no fused statistics"
-        ctx.mark_non_differentiable(partial)
-        return y, partial
+        return (y, _partial_out(ctx, partial, x.device)) if want_stats else y
 
     @staticmethod
     @_with_algo
     def backward(ctx, dy, _dpartial=None):
         xin, packed = ctx.saved_tensors
         ksize, out_planar, cin, cout, has_bias, x_dtype = ctx.meta
-        n, _, d, h, w = xin.shape
         dy = dy.contiguous() if out_planar else to_cl(dy)
-        lib = L.lib()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = empty_cl(n, cin, d, h, w, x_dtype, dy.device)
-            hook = ctx.gn3
-            rows = 0
-            if hook is not None and dy.dtype == torch.float32 and dx.dtype == xin.dtype and config.conv_algo() != L.ALGO_DIRECT:
-                rows = lib.mednet_head_dgrad_gn_rows(n, d, h, w, cin, L.dt(dx))
-            bnb = ctx.gnb
-            bn_rows = 0
-            if bnb is not None and dx.dtype == dy.dtype:
-                bn_rows = lib.mednet_conv3d_dgrad_gn_rows_dt(n, d, h, w, cin, cout, config.conv_algo(), L.dt(dy))
-            if rows > 0:  # + the first pass of the producing block's GroupNorm-3 backward (xin IS that block's output)
-                partial = torch.empty((n, rows, cin, 2), dtype=torch.float32, device=dy.device)
-                L.check(lib.mednet_head_dgrad_gn(dy.data_ptr(), packed.data_ptr(), dx.data_ptr(), hook.gn_in.data_ptr(),
-                                                 xin.data_ptr(), hook.act, partial.data_ptr(), n, d, h, w, cin, cout, L.dt(dx),
-                                                 L.stream()), "head_dgrad_gn")
-                hook.offer(dx, partial)
-            elif bn_rows > 0:  # + the first pass of the backward of the BatchNorm (+ activation) that produced xin
-                partial = torch.empty((n, bn_rows, cin, 2), dtype=torch.float32, device=dy.device)
-                L.check(lib.mednet_conv3d_dgrad_gn(dy.data_ptr(), packed.data_ptr(), None, dx.data_ptr(), bnb.gn_in.data_ptr(),
-                                                   bnb.coef.data_ptr(), bnb.act, partial.data_ptr(), n, d, h, w, cin, cout,
-                                                   config.conv_algo(), L.dt(dy), L.stream()), "conv3d_dgrad_gn")
-                bnb.offer(dx, partial)
-            else:
-                L.check(lib.mednet_conv3d_fwd(dy.data_ptr(), packed.data_ptr(), None, dx.data_ptr(), n, d, h, w, cout, cin,
-                                              ksize, L.dt(dy), L.NCDHW if out_planar else L.NDHWC, L.dt(dx), L.NDHWC, 1,
-                                              config.conv_algo(), None, L.stream()), "conv3d_dgrad")
-        direct_w = direct_b = False
+            # the 1x1x1 head on a block's output (xin IS that output): + the first pass of the block's GroupNorm-3 backward; the 'c b .'
+            # orders: + the first pass of the backward of the BatchNorm (+ activation) that produced xin
+            hook, bnb = ctx.gn3, ctx.gnb
+            head = None
+            if hook is not None and dy.dtype == torch.float32 and x_dtype == xin.dtype and config.conv_algo() != L.ALGO_DIRECT:
+                head = (hook.gn_in, xin, hook.act)
+            dx, partial = conv_dgrad(dy, packed, xin.shape, cout, ksize, x_dtype, dy_planar=out_planar, head=head,
+                                     gnb=None if bnb is None else (bnb.gn_in, bnb.coef, bnb.act))
+            if partial is not None:
+                (hook if head is not None else bnb).offer(dx, partial)
         if ctx.needs_input_grad[1]:
             weight, bias = ctx.params
-            dw, direct_w = _grad_target(weight, (cout, cin, ksize, ksize, ksize))
-            if has_bias and ctx.needs_input_grad[2]:
-                db, direct_b = _grad_target(bias, (cout,))
-            on_side = SIDE["enabled"] and direct_w and (db is None or direct_b)
-            cores = on_side and not out_planar and wgrad_coresident(n, d, h, w, cin, cout, ksize, xin, dy)
-            with _OnSide(on_side, dy.device, xin, dy, coresident=cores) as side:
-                nbytes = lib.mednet_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout, ksize, side.workgroups)
-                ws = L.workspace(nbytes, dy.device)
-                L.check(lib.mednet_conv3d_wgrad(xin.data_ptr(), dy.data_ptr(), dw.data_ptr(), L.ptr(db), n, d, h, w, cin,
-                                                cout, ksize, L.dt(xin), ctx.x_layout, L.dt(dy),
-                                                L.NCDHW if out_planar else L.NDHWC, config.conv_algo(), side.workgroups,
-                                                ws.data_ptr(), ws.numel(), L.stream()), "conv3d_wgrad")
-        return dx, (None if direct_w else dw), (None if direct_b else db), None, None, None, None, None
+            dw, db = conv_wgrad(xin, dy, weight, bias if has_bias and ctx.needs_input_grad[2] else None, ksize, x_layout=ctx.x_layout,
+                                dy_planar=out_planar, coresident=not out_planar)
+        return dx, dw, db, None, None, None, None, None
 
 
 def conv3d(x, weight, bias, packed, ksize, out_planar=False, out_dtype=None):
@@ -457,7 +540,7 @@ def conv3d(x, weight, bias, packed, ksize, out_planar=False, out_dtype=None):
 def conv3d_with_stats(x, weight, bias, packed, ksize):
     """conv + (when the kernel can) the GroupNorm partial sums of its output; returns (y, partial-or-None)."""
     y, partial = Conv3dFn.apply(x, weight, bias, packed, ksize, False, config.act_dtype(), True)
-    return y, (partial if partial.numel() else None)
+    return y, _partial_in(partial)
 
 
 class ConvActFn(Function):
@@ -476,26 +559,18 @@ class ConvActFn(Function):
         cout = weight.shape[0]
         lib = L.lib()
         z = empty_cl(n, cout, d, h, w, config.act_dtype(), x.device)
-        partial = None
-        if want_stats:
-            chunks = lib.mednet_conv3d_fused_stats_chunks(n, d, h, w, cin, cout, 3, L.dt(xin), L.dt(z), config.conv_algo())
-            if chunks > 0:
-                partial = torch.empty((n, chunks, cout, 2), dtype=torch.float32, device=x.device)
+        partial = fused_partial_rows(n, d, h, w, cin, cout, 3, L.dt(xin), L.dt(z), x.device) if want_stats else None
         with profiled_conv(3, cin, cout, n, d, h, w):
             L.check(lib.mednet_conv3d_act_fwd(xin.data_ptr(), packed.data_ptr(), z.data_ptr(), n, d, h, w, cin, cout, act,
                                               config.conv_algo(), L.ptr(partial), L.dt(z), L.stream()), "conv3d_act_fwd")
         ctx.save_for_backward(xin, packed, z)
         ctx.act = act
         ctx.weight = weight
-        if partial is None:
-            partial = torch.empty(0, device=x.device)
-        ctx.mark_non_differentiable(partial)
-        return z, partial
+        return z, _partial_out(ctx, partial, x.device)
 
     @staticmethod
     @_with_algo
     def backward(ctx, dz, _dpartial=None):
-        from . import block  # (block imports ops)
         xin, packed, z = ctx.saved_tensors
         masked = ctx.mask is not None and ctx.mask.take(dz)  # (before any conversion: identity matters)
         dz = to_cl(dz.to(z.dtype))
@@ -506,8 +581,9 @@ class ConvActFn(Function):
             L.check(L.lib().mednet_act_bwd(dz.data_ptr(), z.data_ptr(), du.data_ptr(), z.numel(), ctx.act, L.dt(z), L.stream()),
                     "act_bwd")
         hook = ctx.gnb
-        dx, dw, partial = block._conv_bwd(xin, du, packed, ctx.weight, ctx.needs_input_grad[0],
-                                          gnb=None if hook is None else (hook.gn_in, hook.coef, hook.act))
+        dx, dw, partial = conv_backward(xin, du, packed, ctx.weight, ctx.needs_input_grad[0], block_dx_dtype(xin),
+                                        gnb=(hook.gn_in, hook.coef, hook.act) if hook is not None and FUSE_GNB else None,
+                                        wgrad_first=WGRAD_FIRST)
         if partial is not None:
             hook.offer(dx, partial)
         return dx, dw, None, None, None, None
@@ -528,7 +604,7 @@ def conv3d_act(x, weight, packed, act, want_stats=False):
     z, partial = ConvActFn.apply(x, weight, packed, act, want_stats, mask)
     if mask is not None:
         z._mednet_actmask = mask
-    return z, (partial if partial.numel() else None)
+    return z, _partial_in(partial)
 
 
 # ------------------------------------------------------------------------------------------------- ConvTranspose3d (+ skip add)
@@ -584,23 +660,14 @@ class ConvT3dFn(Function):
             else:
                 L.check(lib.mednet_convt3d_dgrad(dy.data_ptr(), packed.data_ptr(), dx.data_ptr(), n, d, h, w, cin, cout,
                                                  L.dt(dy), L.dt(dx), config.conv_algo(), L.stream()), "convt3d_dgrad")
-        direct_w = direct_b = False
         if ctx.needs_input_grad[1]:
             weight, bias = ctx.params
-            dw, direct_w = _grad_target(weight, (cin, cout, 3, 3, 3))
-            if has_bias and ctx.needs_input_grad[2]:
-                db, direct_b = _grad_target(bias, (cout,))
-            on_side = SIDE["enabled"] and direct_w and (db is None or direct_b)
-            with _OnSide(on_side, dy.device, x, dy) as side:
-                ws = L.workspace(lib.mednet_convt3d_wgrad_ws_bytes(n, d, h, w, cin, cout, side.workgroups), dy.device)
-                L.check(lib.mednet_convt3d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), L.ptr(db), n, d, h, w, cin, cout,
-                                                 L.dt(x), L.dt(dy), config.conv_algo(), side.workgroups, ws.data_ptr(), ws.numel(),
-                                                 L.stream()), "convt3d_wgrad")
+            dw, db = conv_wgrad(x, dy, weight, bias if has_bias and ctx.needs_input_grad[2] else None, 3, transposed=True)
         if has_skip and ctx.needs_input_grad[3]:
             dskip = dy if dy.dtype == skip_dtype else dy.to(skip_dtype)
         if debug.TRACE is not None:
             debug.trace(f"convt3d.bwd {cin}->{cout}", dx, ctx.gn3.partial if ctx.gn3 is not None else None)
-        return dx, (None if direct_w else dw), (None if direct_b else db), dskip, None
+        return dx, dw, db, dskip, None
 
 
 def conv_transpose3d(x, weight, bias, skip, packed):
