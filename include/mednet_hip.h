@@ -591,6 +591,49 @@ int mednet_predict_assemble(const float* logits, const int* pos, uint8_t* result
                             int num_classes, int d, int h, int w, int pd, int ph, int pw, int crop_start0, int crop_start1,
                             int crop_start2, int crop_d, int crop_h, int crop_w, mednet_stream stream);
 
+/* ---- blended sliding-window inference (additive to ABI 3; the reference has no counterpart: its stitch is the crop above) ------
+ * Overlapping patches are blended with a separable importance window instead of being cropped: every patch adds
+ * window-weighted class probabilities (or logits) and heat maps to fp32 accumulators over the whole volume, and a last pass divides
+ * by the accumulated weight.  No atomics: the same patches in the same order give the same bits, whatever the batch size.
+ *
+ * mednet_grid_gather_mirror: mednet_grid_gather with test-time mirroring.  Bit k of `mirror` (0..7) reverses patch axis k: the patch
+ * voxel (z, y, x) holds what the unmirrored patch holds at (pD - 1 - z, ..) on the flagged axes.  mirror == 0 is mednet_grid_gather
+ * bit for bit (one kernel serves both entries).  Another mask is MEDNET_E_UNSUPPORTED. */
+int mednet_grid_gather_mirror(const float* volume, const int* pos, float* out, int batch, int c, int d, int h, int w, int pd,
+                              int ph, int pw, int ov0, int ov1, int ov2, int pad_mode, int mirror, mednet_stream stream);
+/* logits: batch x (H + classes) x pD x pH x pW planar fp32, as the model returns it; pos: the rows mednet_grid_gather takes (patch b
+ * covers the volume voxels [pos[b] - ov, pos[b] - ov + patch); what lies outside the volume -- the padding in front, the overhang
+ * behind -- is dropped).  win0..2: fp32 tables (device) of pD, pH, pW entries; a voxel's weight is (win0[z] * win1[y]) * win2[x] in
+ * fp32, in that association.  acc ((H + classes) x D x H x W fp32) and wsum (D x H x W fp32) are read-modify-write; zero them before
+ * the first patch.  Heat-map channels add weight * value; class channels add weight * softmax(logits)_c with
+ * MEDNET_BLEND_PROBABILITIES (one softmax per voxel per patch: max-subtracted, expf, one reciprocal) or weight * logit_c with
+ * MEDNET_BLEND_LOGITS; each addition is one fmaf.  Another class_mode is MEDNET_E_UNSUPPORTED.
+ * mirror (0..7): the logits belong to a patch gathered with that mask and are read at the reversed index on the flagged axes -- the
+ * flip back.  The WEIGHT is looked up at the unmirrored patch coordinate, i.e. the window is fixed to the volume, not to the
+ * mirrored patch; this only matters for an asymmetric custom window.
+ * Rows of one launch may overlap: a voxel is owned by the first row of the launch that holds it, whose thread adds the contributions
+ * of all the launch's rows in row order; across launches stream order continues that order.  batch <= 65535. */
+enum { MEDNET_BLEND_PROBABILITIES = 0, MEDNET_BLEND_LOGITS = 1 };
+int mednet_blend_accumulate(const float* logits, const int* pos, float* acc, float* wsum, const float* win0, const float* win1,
+                            const float* win2, int batch, int num_heatmaps, int num_classes, int d, int h, int w, int pd, int ph,
+                            int pw, int ov0, int ov1, int ov2, int mirror, int class_mode, mednet_stream stream);
+/* One pass over the voxels.  Any of the three outputs may be NULL (all three: MEDNET_E_SHAPE).
+ *   heat      H x D x H x W fp32            acc[k] / wsum
+ *   prob      classes x D x H x W           acc[H + c] / wsum (MEDNET_BLEND_PROBABILITIES) or softmax over c of acc[H + c] / wsum
+ *                                           (MEDNET_BLEND_LOGITS); prob_dtype MEDNET_F32 or MEDNET_F16 (rounded once), else MEDNET_E_DTYPE
+ *   result_u8 (H + 1) x D x H x W uint8     mednet_predict_assemble's layout: (uint8)(int)clamp(heat, 0, 255), then the arg-max of the
+ *                                           class accumulators, first maximum on ties
+ * A voxel whose wsum is 0 (none with grid_positions' grid) reads 0 everywhere, not NaN. */
+int mednet_blend_finalize(const float* acc, const float* wsum, uint8_t* result_u8, void* prob, int prob_dtype, float* heat,
+                          int num_heatmaps, int num_classes, int d, int h, int w, int class_mode, mednet_stream stream);
+/* Landmark positions: per channel of heat (H x voxels fp32) the maximum (out_value, fp32 H) and its flat index (out_index, int64 H),
+ * the lowest index on ties.  A NaN never wins; a channel of NaNs only gives index -1 and value -inf.  Two deterministic stages: one
+ * partial per workgroup of 4096 voxels in ws, then one workgroup per channel.  A ws smaller than _ws_bytes is MEDNET_E_WORKSPACE; ws
+ * is 8-byte aligned. */
+size_t mednet_heatmap_peaks_ws_bytes(int num_heatmaps, size_t voxels);
+int mednet_heatmap_peaks(const float* heat, int num_heatmaps, size_t voxels, int64_t* out_index, float* out_value, void* ws,
+                         size_t ws_bytes, mednet_stream stream);
+
 /* ---- training-patch sampler ------------------------------------------------------------------ */
 /* MedDataset.__getitem__'s crop + cast (dataset.py:313-331) from a device-resident volume src (C x D x H x W; f16 / f32
  * images, u8 labels or heat maps): for i < count,

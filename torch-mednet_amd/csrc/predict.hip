@@ -1,5 +1,6 @@
 // Inference path: the data movement around the forward kernels at prediction time, on the device.
-//   grid_gather      midasmednet/dataset.py:349-390 (grid_patch_generator): np.pad + overlapping patch extraction
+//   grid_gather      midasmednet/dataset.py:349-390 (grid_patch_generator): np.pad + overlapping patch extraction; with a mirror
+//                    mask (grid_gather_mirror, for blend.hip's test-time mirroring) the patch comes out reversed on the flagged axes
 //   predict_assemble examples/predict.py:88-95 (argmax of the class logits, heat maps clipped to uint8) fused with
 //                    GridPatchSampler.add_processed_batch (dataset.py:446-474): crop the overlap, clip at the volume
 //                    edge, write into the result volume -- one pass over the logits, nothing intermediate in HBM.
@@ -20,7 +21,7 @@ __device__ __forceinline__ int pad_src(int q, int ov, int n, int mode) {
 
 __global__ __launch_bounds__(256) void grid_gather_kernel(const float* __restrict__ vol, const int* __restrict__ pos,
                                                           float* __restrict__ out, int c, int d, int h, int w, int pd,
-                                                          int ph, int pw, int ov0, int ov1, int ov2, int mode) {
+                                                          int ph, int pw, int ov0, int ov1, int ov2, int mode, int mirror) {
   const size_t per = (size_t)c * pd * ph * pw;
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= per) return;
@@ -31,8 +32,10 @@ __global__ __launch_bounds__(256) void grid_gather_kernel(const float* __restric
   r /= ph;
   const int z = (int)(r % pd);
   const int cc = (int)(r / pd);
-  const int sz = pad_src(pos[b * 3] + z, ov0, d, mode), sy = pad_src(pos[b * 3 + 1] + y, ov1, h, mode),
-            sx = pad_src(pos[b * 3 + 2] + x, ov2, w, mode);
+  // bit k of `mirror` reverses patch axis k: voxel (z, y, x) holds what the unmirrored patch holds at (pd - 1 - z, ..)
+  const int mz = (mirror & 1) ? pd - 1 - z : z, my = (mirror & 2) ? ph - 1 - y : y, mx = (mirror & 4) ? pw - 1 - x : x;
+  const int sz = pad_src(pos[b * 3] + mz, ov0, d, mode), sy = pad_src(pos[b * 3 + 1] + my, ov1, h, mode),
+            sx = pad_src(pos[b * 3 + 2] + mx, ov2, w, mode);
   float v = 0.f;
   if (sz >= 0 && sy >= 0 && sx >= 0) v = vol[(((size_t)cc * d + sz) * h + sy) * w + sx];
   out[(size_t)b * per + i] = v;
@@ -123,15 +126,30 @@ extern "C" int mednet_crop_patches(const void* src, int src_dtype, const int* po
   return check_launch("crop_patches");
 }
 
-extern "C" int mednet_grid_gather(const float* volume, const int* pos, float* out, int batch, int c, int d, int h, int w,
-                                  int pd, int ph, int pw, int ov0, int ov1, int ov2, int pad_mode, mednet_stream stream) {
-  MEDNET_REQUIRE(batch > 0 && c > 0 && d > 0 && h > 0 && w > 0 && pd > 0 && ph > 0 && pw > 0, MEDNET_E_SHAPE, "grid_gather: bad shape");
+// both gather entries: `who` names the entry in the messages
+static int grid_gather_go(const char* who, const float* volume, const int* pos, float* out, int batch, int c, int d, int h, int w,
+                          int pd, int ph, int pw, int ov0, int ov1, int ov2, int pad_mode, int mirror, mednet_stream stream) {
+  MEDNET_REQUIRE(batch > 0 && c > 0 && d > 0 && h > 0 && w > 0 && pd > 0 && ph > 0 && pw > 0, MEDNET_E_SHAPE, "%s: bad shape", who);
   MEDNET_REQUIRE(pad_mode == MEDNET_PAD_CONSTANT || pad_mode == MEDNET_PAD_SYMMETRIC, MEDNET_E_UNSUPPORTED,
-                 "grid_gather: pad mode %d (supported: constant, symmetric)", pad_mode);
+                 "%s: pad mode %d (supported: constant, symmetric)", who, pad_mode);
   const size_t per = (size_t)c * pd * ph * pw;
   hipLaunchKernelGGL(grid_gather_kernel, dim3((unsigned)((per + 255) / 256), batch), dim3(256), 0, (hipStream_t)stream, volume,
-                     pos, out, c, d, h, w, pd, ph, pw, ov0, ov1, ov2, pad_mode);
-  return check_launch("grid_gather");
+                     pos, out, c, d, h, w, pd, ph, pw, ov0, ov1, ov2, pad_mode, mirror);
+  return check_launch(who);
+}
+
+extern "C" int mednet_grid_gather(const float* volume, const int* pos, float* out, int batch, int c, int d, int h, int w,
+                                  int pd, int ph, int pw, int ov0, int ov1, int ov2, int pad_mode, mednet_stream stream) {
+  return grid_gather_go("grid_gather", volume, pos, out, batch, c, d, h, w, pd, ph, pw, ov0, ov1, ov2, pad_mode, 0, stream);
+}
+
+extern "C" int mednet_grid_gather_mirror(const float* volume, const int* pos, float* out, int batch, int c, int d, int h, int w,
+                                         int pd, int ph, int pw, int ov0, int ov1, int ov2, int pad_mode, int mirror,
+                                         mednet_stream stream) {
+  MEDNET_REQUIRE(volume && pos && out, MEDNET_E_SHAPE, "grid_gather_mirror: null pointer");
+  MEDNET_REQUIRE(mirror >= 0 && mirror <= 7, MEDNET_E_UNSUPPORTED, "grid_gather_mirror: mirror mask %d (supported: 0..7, bit k reverses axis k)",
+                 mirror);
+  return grid_gather_go("grid_gather_mirror", volume, pos, out, batch, c, d, h, w, pd, ph, pw, ov0, ov1, ov2, pad_mode, mirror, stream);
 }
 
 extern "C" int mednet_predict_assemble(const float* logits, const int* pos, uint8_t* result, int batch, int num_heatmaps,

@@ -27,6 +27,7 @@ REG_L2, REG_L1 = 0, 1
 CLASS_DICE, CLASS_CE, CLASS_DICE_CE = 0, 1, 2
 PAD_CONSTANT, PAD_SYMMETRIC = 0, 1
 MIP_MEAN, MIP_MAX = 0, 1
+BLEND_PROBABILITIES, BLEND_LOGITS = 0, 1
 F16, U8, I64 = 2, 3, 4  # F16: fp16 storage / resident volumes; U8, I64: label types
 NO_IGNORE = -(2 ** 31)
 
@@ -150,6 +151,11 @@ SIGNATURES = {
     "mednet_adam_step_scaled": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _f, _vp, _f, _f, _i, _vp]),
     "mednet_grid_gather": (_i, [_vp, _vp, _vp] + [_i] * 12 + [_vp]),
     "mednet_predict_assemble": (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
+    "mednet_grid_gather_mirror": (_i, [_vp, _vp, _vp] + [_i] * 13 + [_vp]),
+    "mednet_blend_accumulate": (_i, [_vp] * 7 + [_i] * 14 + [_vp]),
+    "mednet_blend_finalize": (_i, [_vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp]),
+    "mednet_heatmap_peaks_ws_bytes": (_sz, [_i, _sz]),
+    "mednet_heatmap_peaks": (_i, [_vp, _i, _sz, _vp, _vp, _vp, _sz, _vp]),
     "mednet_crop_patches": (_i, [_vp, _i, _vp, _vp, _i, _vp] + [_i] * 10 + [_vp]),
     "mednet_augment_ws_bytes": (_sz, [_i, _i, _sz]),
     "mednet_augment_patches": (_i, [_vp, _vp, _i, _i, _sz, _vp, _sz, _vp]),

@@ -8,7 +8,11 @@ The volume is uploaded once; the overlapping grid patches are gathered on the de
 symmetric), run through the network in batches (forward kernels only, `torch.no_grad`), and the logits are turned into
 the uint8 result -- arg-max class, heat maps clipped to 0..255 -- and stitched into the result volume by ONE kernel that
 applies the reference's crop rule (including its asymmetric first-axis window, dataset.py:453).  Bit-identical to the
-reference's procedure for identical logits (tests/test_gpu_predict.py)."""
+reference's procedure for identical logits (tests/test_gpu_predict.py).
+
+Beyond the reference (csrc/blend.hip): GridPredictor(..., blend="gaussian", mirror_axes=(0, 1, 2)) blends
+overlapping windows with an importance map instead of cropping them, averages over flips, and `predict(volume)` returns a
+BlendedPrediction with .result() (the uint8 layout above), .probabilities(), .heatmaps() and .peaks()."""
 from __future__ import annotations
 
 import numpy as np
@@ -38,8 +42,9 @@ def crop_window(patch_size, patch_overlap):
     return [r.start if len(r) else 0 for r in idx], [len(r) for r in idx]
 
 
-def gather_patches(volume: torch.Tensor, pos: torch.Tensor, patch_size, patch_overlap, pad_mode="symmetric"):
-    """volume C x D x H x W fp32 (device), pos B x 3 int32 (device) -> B x C x pD x pH x pW fp32."""
+def gather_patches(volume: torch.Tensor, pos: torch.Tensor, patch_size, patch_overlap, pad_mode="symmetric", mirror=0):
+    """volume C x D x H x W fp32 (device), pos B x 3 int32 (device) -> B x C x pD x pH x pW fp32.  Bit k of `mirror` reverses
+    patch axis k (test-time mirroring; 0: the reference's patches)."""
     L.require_gpu(volume, "grid_gather")
     if pad_mode not in _PAD:
         raise NotImplementedError(f"pad mode {pad_mode!r} (supported: constant, symmetric)")
@@ -47,6 +52,10 @@ def gather_patches(volume: torch.Tensor, pos: torch.Tensor, patch_size, patch_ov
     pd, ph, pw = (int(v) for v in patch_size)
     out = torch.empty((pos.shape[0], c, pd, ph, pw), dtype=torch.float32, device=volume.device)
     o = [int(v) for v in patch_overlap]
+    if mirror:
+        L.check(L.lib().mednet_grid_gather_mirror(volume.data_ptr(), pos.data_ptr(), out.data_ptr(), pos.shape[0], c, d, h, w, pd, ph,
+                                                  pw, o[0], o[1], o[2], _PAD[pad_mode], int(mirror), L.stream()), "grid_gather_mirror")
+        return out
     L.check(L.lib().mednet_grid_gather(volume.data_ptr(), pos.data_ptr(), out.data_ptr(), pos.shape[0], c, d, h, w, pd, ph, pw,
                                        o[0], o[1], o[2], _PAD[pad_mode], L.stream()), "grid_gather")
     return out
@@ -65,14 +74,180 @@ def assemble(logits: torch.Tensor, pos: torch.Tensor, result: torch.Tensor, num_
     return result
 
 
+# ---------------------------------------------------------------------------------------------- blended inference
+_BLEND_OF = {"probabilities": L.BLEND_PROBABILITIES, "logits": L.BLEND_LOGITS}
+
+
+def blend_window(patch_size, kind="gaussian", sigma_scale=0.125):
+    """Three fp32 vectors (one per patch axis) whose outer product is the patch's importance map.  "gaussian":
+    exp(-0.5 * ((i - (p - 1) / 2) / (sigma_scale * p)) ** 2), computed in fp64 (nnU-Net's map up to its normalisation, which the
+    division by the weight sum removes; the smallest product at p = 128 is about 5.5e-11: no clamp needed in fp32); "constant": ones."""
+    if kind not in ("gaussian", "constant"):
+        raise ValueError(f"blend window {kind!r} (supported: gaussian, constant)")
+    out = []
+    for p in (int(v) for v in patch_size):
+        i = np.arange(p, dtype=np.float64)
+        v = np.exp(-0.5 * ((i - (p - 1) / 2.0) / (sigma_scale * p)) ** 2) if kind == "gaussian" else np.ones(p)
+        out.append(v.astype(np.float32))
+    return tuple(out)
+
+
+def mirror_mask(axes):
+    """Patch axes (0, 1, 2) -> the kernels' mask (bit k reverses axis k)."""
+    mask = 0
+    for a in axes:
+        if int(a) not in (0, 1, 2):
+            raise ValueError(f"mirror axis {a!r} (patch axes are 0, 1, 2)")
+        mask |= 1 << int(a)
+    return mask
+
+
+def accumulate(logits: torch.Tensor, pos: torch.Tensor, acc: torch.Tensor, wsum: torch.Tensor, windows, num_heatmaps, patch_overlap,
+               mirror=0, blend_of="probabilities"):
+    """logits B x (H + classes) x pD x pH x pW -> adds the window-weighted heat maps and class probabilities (or logits) of every
+    patch to acc ((H + classes) x D x H x W fp32) and the weights to wsum (D x H x W fp32), in place.  windows: three fp32 device
+    vectors (blend_window); mirror: the mask the patches were gathered with (the logits are flipped back).  Bit-reproducible and
+    independent of how the rows are split into calls."""
+    L.require_gpu(logits, "blend_accumulate")
+    lg = logits.float().contiguous()
+    b, ch, pd, ph, pw = lg.shape
+    _, d, h, w = acc.shape
+    if acc.shape[0] != ch or tuple(wsum.shape) != (d, h, w) or acc.dtype != torch.float32 or wsum.dtype != torch.float32 \
+            or not (acc.is_contiguous() and wsum.is_contiguous()):
+        raise ValueError(f"blend_accumulate: acc {tuple(acc.shape)} {acc.dtype} / wsum {tuple(wsum.shape)} {wsum.dtype} do not fit {ch} channels (contiguous fp32)")
+    if [int(t.numel()) for t in windows] != [pd, ph, pw] or any(t.dtype != torch.float32 or not t.is_contiguous() for t in windows):
+        raise ValueError(f"blend_accumulate: windows must be three contiguous fp32 vectors of {pd}, {ph}, {pw} entries")
+    o = [int(v) for v in patch_overlap]
+    L.check(L.lib().mednet_blend_accumulate(lg.data_ptr(), pos.data_ptr(), acc.data_ptr(), wsum.data_ptr(), windows[0].data_ptr(),
+                                            windows[1].data_ptr(), windows[2].data_ptr(), b, num_heatmaps, ch - num_heatmaps, d, h, w,
+                                            pd, ph, pw, o[0], o[1], o[2], int(mirror), _BLEND_OF[blend_of], L.stream()),
+            "blend_accumulate")
+    return acc, wsum
+
+
+def finalize(acc: torch.Tensor, wsum: torch.Tensor, num_heatmaps, blend_of="probabilities", result=False, probabilities=None,
+             heatmaps=False):
+    """One pass over the accumulators -> (result, probabilities, heatmaps), None for what was not asked for.  result=True: uint8
+    (H + 1) x D x H x W in `assemble`'s layout; probabilities=torch.float32 / torch.float16: classes x D x H x W; heatmaps=True:
+    H x D x H x W fp32."""
+    L.require_gpu(acc, "blend_finalize")
+    ch, d, h, w = acc.shape
+    ncls = ch - num_heatmaps
+    if tuple(wsum.shape) != (d, h, w) or acc.dtype != torch.float32 or wsum.dtype != torch.float32 \
+            or not (acc.is_contiguous() and wsum.is_contiguous()):
+        raise ValueError(f"blend_finalize: acc {tuple(acc.shape)} {acc.dtype} / wsum {tuple(wsum.shape)} {wsum.dtype}: contiguous fp32 expected")
+    res = torch.empty((num_heatmaps + 1, d, h, w), dtype=torch.uint8, device=acc.device) if result else None
+    prob = torch.empty((ncls, d, h, w), dtype=probabilities, device=acc.device) if probabilities is not None else None
+    heat = torch.empty((num_heatmaps, d, h, w), dtype=torch.float32, device=acc.device) if heatmaps else None
+    if prob is not None and prob.dtype not in (torch.float32, torch.float16):
+        raise RuntimeError(f"blend_finalize: probabilities as {prob.dtype} (supported: float32, float16)")
+    if res is None and prob is None and heat is not None and num_heatmaps == 0:
+        return res, prob, heat  # (the heat maps of a network without any: nothing to compute)
+    L.check(L.lib().mednet_blend_finalize(acc.data_ptr(), wsum.data_ptr(), L.ptr(res), L.ptr(prob), L.dt(prob) if prob is not None else L.F32,
+                                          L.ptr(heat) if num_heatmaps else None, num_heatmaps, ncls, d, h, w, _BLEND_OF[blend_of],
+                                          L.stream()), "blend_finalize")
+    return res, prob, heat
+
+
+def heatmap_peaks(heat: torch.Tensor):
+    """heat H x D x H x W fp32 (device) -> (positions H x 3 int64 as (z, y, x), values H fp32): every channel's maximum, the lowest
+    flat index on ties; a NaN never wins."""
+    L.require_gpu(heat, "heatmap_peaks")
+    ht = heat.float().contiguous()
+    nh, d, h, w = ht.shape
+    vox = d * h * w
+    index = torch.empty((nh,), dtype=torch.int64, device=ht.device)
+    value = torch.empty((nh,), dtype=torch.float32, device=ht.device)
+    if nh == 0:
+        return index.reshape(0, 3), value
+    ws = L.workspace(L.lib().mednet_heatmap_peaks_ws_bytes(nh, vox), ht.device)
+    L.check(L.lib().mednet_heatmap_peaks(ht.data_ptr(), nh, vox, index.data_ptr(), value.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()),
+            "heatmap_peaks")
+    zyx = torch.stack((torch.div(index, h * w, rounding_mode="floor"), torch.div(index, w, rounding_mode="floor") % h, index % w), dim=1)
+    return zyx, value
+
+
+class BlendedPrediction:
+    """What GridPredictor.predict leaves on the device: the accumulators, the weight sum and how to read them."""
+
+    def __init__(self, acc, wsum, num_heatmaps, blend_of):
+        self.acc, self.wsum, self.num_heatmaps, self.blend_of = acc, wsum, num_heatmaps, blend_of
+
+    def result(self):
+        """uint8 (H + 1) x D x H x W: the crop-stitch predictor's layout (heat maps clipped to 0..255, then the arg-max class)."""
+        return finalize(self.acc, self.wsum, self.num_heatmaps, self.blend_of, result=True)[0]
+
+    def probabilities(self, dtype=torch.float32):
+        return finalize(self.acc, self.wsum, self.num_heatmaps, self.blend_of, probabilities=dtype)[1]
+
+    def heatmaps(self):
+        return finalize(self.acc, self.wsum, self.num_heatmaps, self.blend_of, heatmaps=True)[2]
+
+    def peaks(self):
+        """(positions H x 3 int64 as (z, y, x), values H fp32) of the blended heat maps."""
+        return heatmap_peaks(self.heatmaps())
+
+
 class GridPredictor:
     def __init__(self, model, patch_size, patch_overlap, num_heatmaps=0, pad_mode="constant", batch_size=4,
-                 channel_selection=None):
+                 channel_selection=None, blend=None, sigma_scale=0.125, mirror_axes=(), blend_of="probabilities"):
+        """blend=None: the reference's crop-stitch (the default).  blend="gaussian" / "constant" / three per-axis weight vectors:
+        overlapping windows are blended (`predict`); mirror_axes: patch axes averaged over their flips (2^k passes per patch);
+        blend_of: what the class channels accumulate, "probabilities" (softmax per patch) or "logits" (softmax once, at the end)."""
         self.model, self.patch_size, self.patch_overlap = model, list(patch_size), list(patch_overlap)
         self.num_heatmaps, self.pad_mode, self.batch_size, self.channel_selection = num_heatmaps, pad_mode, batch_size, channel_selection
+        self.blend, self.blend_of = blend, blend_of
+        self.mirror_bits = mirror_mask(mirror_axes)
+        if blend is None:
+            if self.mirror_bits:
+                raise ValueError("mirror_axes needs blend: averaging over flips is an accumulate-style stitch")
+            return
+        if blend_of not in _BLEND_OF:
+            raise ValueError(f"blend_of {blend_of!r} (supported: probabilities, logits)")
+        if isinstance(blend, str):
+            self.windows = blend_window(self.patch_size, blend, sigma_scale)
+        else:
+            self.windows = tuple(np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for v in blend)
+            if [v.shape for v in self.windows] != [(int(p),) for p in self.patch_size]:
+                raise ValueError(f"blend: three weight vectors of {self.patch_size} entries expected")
+        # the passes of a patch: every subset of the mirror axes, ascending mask
+        self.mirror_passes = [m for m in range(8) if m & ~self.mirror_bits == 0]
+
+    @torch.no_grad()
+    def predict(self, volume) -> BlendedPrediction:
+        """Blended sliding-window inference.  For every mirror pass (ascending mask) and every batch of grid positions:
+        gather(mirror) -> model -> accumulate(mirror).  A voxel's sums are taken pass by pass in patch order, so the result does not
+        depend on batch_size.  An overlap of 0 is legal here (nothing is cropped)."""
+        if self.blend is None:
+            raise ValueError("predict() needs blend (the crop-stitch path is __call__)")
+        dev = next(self.model.parameters()).device
+        vol = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
+        if self.channel_selection is not None:
+            vol = vol[self.channel_selection]
+        vol = vol.to(dev, non_blocking=True).float().contiguous()
+        pos_all = torch.from_numpy(grid_positions(vol.shape[1:], self.patch_size, self.patch_overlap)).to(dev)
+        windows = tuple(torch.from_numpy(v).to(dev) for v in self.windows)
+        acc = wsum = None
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            for m in self.mirror_passes:
+                for b0 in range(0, pos_all.shape[0], self.batch_size):
+                    pos = pos_all[b0:b0 + self.batch_size].contiguous()
+                    inputs = gather_patches(vol, pos, self.patch_size, self.patch_overlap, self.pad_mode, mirror=m)
+                    logits = self.model(inputs)
+                    if acc is None:
+                        acc = torch.zeros((logits.shape[1],) + tuple(vol.shape[1:]), dtype=torch.float32, device=dev)
+                        wsum = torch.zeros(tuple(vol.shape[1:]), dtype=torch.float32, device=dev)
+                    accumulate(logits, pos, acc, wsum, windows, self.num_heatmaps, self.patch_overlap, m, self.blend_of)
+        finally:
+            self.model.train(was_training)
+        return BlendedPrediction(acc, wsum, self.num_heatmaps, self.blend_of)
 
     @torch.no_grad()
     def __call__(self, volume):
+        if self.blend is not None:
+            return self.predict(volume).result()
         dev = next(self.model.parameters()).device
         vol = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
         if self.channel_selection is not None:
