@@ -652,6 +652,38 @@ size_t mednet_augment_ws_bytes(int batch, int channels, size_t spatial);
 int mednet_augment_patches(float* data, const float* params, int batch, int channels, size_t spatial, void* ws,
                            size_t ws_bytes, mednet_stream stream);
 
+/* ---- spatial augmentation of training patches (additive to ABI 3): crop + rotation / scale / mirror + elastic deformation in one
+ * pass over a device-resident volume, the `transform=` slot of the reference (midasmednet/dataset.py:223,340-341) for the spatial
+ * transforms.  One call per source volume, as mednet_crop_patches: src is C x D x H x W, out is B x c_total x pD x pH x pW and row
+ * i < count writes channels [c_off, c_off + c) of sample slot[i].  Pairs: f16 -> f32 and f32 -> f32 (images), u8 -> u8 (heat maps:
+ * MEDNET_INTERP_LINEAR, rounded once to nearest-even; labels: MEDNET_INTERP_NEAREST); every pair takes either interpolation, another
+ * pair is MEDNET_E_DTYPE.
+ *   affine  count x 12 fp32 (device): row-major 3 x 4 [A | t] per row, built by the host.
+ *   disp    NULL, or count x 3 x gd x gh x gw fp32 (device): a coarse control lattice of displacements in PATCH voxels (component 0
+ *           along z, 1 along y, 2 along x) whose corner points sit on the patch's corner voxels.
+ * For output voxel (z, y, x) -- all fp32, in exactly this association:
+ *   1. u = (z - (pD - 1)/2, y - (pH - 1)/2, x - (pW - 1)/2)                 (half-integer centres: exact)
+ *   2. with disp: lattice coordinate g_k = fl(idx_k * r_k), r_k = fl((extent_k - 1) / (p_k - 1)) (0 if p_k == 1), cell
+ *      min(floor(g_k), extent_k - 2), weight g_k - cell; each component is lerped over x, then y, then z as fmaf(q, b - a, a) and
+ *      added: u_j = fl(u_j + D_j)
+ *   3. s_k = fmaf(A[k][0], u_0, fmaf(A[k][1], u_1, fmaf(A[k][2], u_2, t[k])))    (source coordinate, volume voxels)
+ *   4. linear: cell f = floor(s), weights s - f, lerp over x, then y, then z as fmaf(w, b - a, a) (weight 0 returns a bit for bit);
+ *      nearest: index floor(s + 0.5f)
+ *   5. border, per call: MEDNET_BORDER_CONSTANT -- a tap outside the volume reads cval and the result is still interpolated towards it
+ *      (scipy.ndimage 'grid-constant'); MEDNET_BORDER_EDGE -- tap indices are clamped (scipy.ndimage 'nearest').  cval is converted
+ *      to the output type as a value of the source would be.
+ * Any coordinate is safe -- NaN, +-inf, |s| >= 2^31: it is clamped in float to [-2, n + 1] before the conversion and NaN counts as
+ * outside (csrc/warp_index.h).  Unlike the crop, the patch may be larger than the volume: the border rule covers it.
+ * Refused before anything is launched: a null src / affine / slot / out, count <= 0, a non-positive extent, c_off + c > c_total, disp
+ * with a lattice extent < 2, count > 65535, a volume, patch or lattice extent above 2^24 - 2 (MEDNET_E_SHAPE); an unknown interp or border, and
+ * for the u8 pair a cval outside [0, 255] or NaN -- it could not be converted to a byte -- (MEDNET_E_UNSUPPORTED); another dtype pair
+ * (MEDNET_E_DTYPE). */
+enum { MEDNET_INTERP_LINEAR = 0, MEDNET_INTERP_NEAREST = 1 };
+enum { MEDNET_BORDER_CONSTANT = 0, MEDNET_BORDER_EDGE = 1 };
+int mednet_warp_patches(const void* src, int src_dtype, const float* affine, const float* disp, int gd, int gh, int gw,
+                        const int* slot, int count, void* out, int dst_dtype, int c, int d, int h, int w, int c_total, int c_off,
+                        int pd, int ph, int pw, int interp, int border, float cval, mednet_stream stream);
+
 /* ---- validation sample logging: the arrays `log_samples` (segmentation.py:67-92, landmarks.py:85-123) hands
  * to imshow through vis_loglabels / vis_logheatmaps (utils/plots.py:45-127), from ONE sample where its tensors lie.  Additive to
  * ABI 3.  All pointers address that sample: logits = channel 0 of its network output (planar fp32, plane k at + k * stride_c

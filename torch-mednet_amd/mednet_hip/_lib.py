@@ -28,6 +28,8 @@ CLASS_DICE, CLASS_CE, CLASS_DICE_CE = 0, 1, 2
 PAD_CONSTANT, PAD_SYMMETRIC = 0, 1
 MIP_MEAN, MIP_MAX = 0, 1
 BLEND_PROBABILITIES, BLEND_LOGITS = 0, 1
+INTERP_LINEAR, INTERP_NEAREST = 0, 1
+BORDER_CONSTANT, BORDER_EDGE = 0, 1
 F16, U8, I64 = 2, 3, 4  # F16: fp16 storage / resident volumes; U8, I64: label types
 NO_IGNORE = -(2 ** 31)
 
@@ -159,6 +161,7 @@ SIGNATURES = {
     "mednet_crop_patches": (_i, [_vp, _i, _vp, _vp, _i, _vp] + [_i] * 10 + [_vp]),
     "mednet_augment_ws_bytes": (_sz, [_i, _i, _sz]),
     "mednet_augment_patches": (_i, [_vp, _vp, _i, _i, _sz, _vp, _sz, _vp]),
+    "mednet_warp_patches": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp] + [_i] * 12 + [_f, _vp]),
     "mednet_sample_panels_ws_bytes": (_sz, [_i] * 5),
     "mednet_sample_panels": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _i, _vp] + [_vp] * 5 + [_i] * 5 + [_vp, _sz, _vp]),
 }
