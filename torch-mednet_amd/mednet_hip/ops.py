@@ -433,15 +433,21 @@ def conv_dgrad(dy, packed, x_shape, cout, ksize, dx_dtype, dy_planar=False, head
     return dx, partial
 
 
-def conv_wgrad(x, dy, weight_p, bias_p, ksize, x_layout=L.NDHWC, dy_planar=False, coresident=False, profiled=False, transposed=False):
+def conv_wgrad(x, dy, weight_p, bias_p, ksize, x_layout=L.NDHWC, dy_planar=False, coresident=False, profiled=False, transposed=False,
+               want_dw=True):
     """Weight (and, with `bias_p`, bias) gradient of a stride-1 convolution or (`transposed`) of ConvTranspose3d -> (dw, db), each None
     when the kernel wrote it into the trainer's buffer (_grad_target).  With in-place targets for everything it writes, the launch
     goes to the side stream; `coresident`: the caller wants all CUs for it there when the kernel leaves room beside it
-    (wgrad_coresident).  `profiled`: the launch counts for bench.py's weight-gradient roofline."""
+    (wgrad_coresident).  `profiled`: the launch counts for bench.py's weight-gradient roofline.  `want_dw=False`: a trainable bias
+    behind a frozen weight -- the bias sum comes out of this entry, so it runs with a scratch dw that nobody gets (a rare path)."""
     n, cin, d, h, w = x.shape
     cout = dy.shape[1]
     lib = L.lib()
-    dw, direct_w = _grad_target(weight_p, (cin, cout, 3, 3, 3) if transposed else (cout, cin, ksize, ksize, ksize))
+    w_shape = (cin, cout, 3, 3, 3) if transposed else (cout, cin, ksize, ksize, ksize)
+    if want_dw:
+        dw, direct_w = _grad_target(weight_p, w_shape)
+    else:
+        dw, direct_w = torch.empty(w_shape, dtype=torch.float32, device=dy.device), False
     db, direct_b = _grad_target(bias_p, (cout,)) if bias_p is not None else (None, False)
     on_side = SIDE["enabled"] and direct_w and (db is None or direct_b)
     cores = on_side and coresident and wgrad_coresident(n, d, h, w, cin, cout, ksize, x, dy)
@@ -457,7 +463,7 @@ def conv_wgrad(x, dy, weight_p, bias_p, ksize, x_layout=L.NDHWC, dy_planar=False
                 L.check(lib.mednet_conv3d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), L.ptr(db), n, d, h, w, cin, cout, ksize,
                                                 L.dt(x), x_layout, L.dt(dy), L.NCDHW if dy_planar else L.NDHWC, config.conv_algo(),
                                                 side.workgroups, ws.data_ptr(), ws.numel(), L.stream()), "conv3d_wgrad")
-    return (None if direct_w else dw), (None if direct_b else db)
+    return (None if (direct_w or not want_dw) else dw), (None if direct_b else db)
 
 
 def conv_backward(x, dy, packed, weight_p, need_dx, dx_dtype, add=None, gnb=None, x_layout=L.NDHWC, wgrad_first=False):
@@ -526,10 +532,11 @@ class Conv3dFn(Function):
                                      gnb=None if bnb is None else (bnb.gn_in, bnb.coef, bnb.act))
             if partial is not None:
                 (hook if head is not None else bnb).offer(dx, partial)
-        if ctx.needs_input_grad[1]:
+        want_db = has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_db:  # (a trainable bias behind a frozen weight still gets its gradient)
             weight, bias = ctx.params
-            dw, db = conv_wgrad(xin, dy, weight, bias if has_bias and ctx.needs_input_grad[2] else None, ksize, x_layout=ctx.x_layout,
-                                dy_planar=out_planar, coresident=not out_planar)
+            dw, db = conv_wgrad(xin, dy, weight, bias if want_db else None, ksize, x_layout=ctx.x_layout,
+                                dy_planar=out_planar, coresident=not out_planar, want_dw=ctx.needs_input_grad[1])
         return dx, dw, db, None, None, None, None, None
 
 
@@ -660,9 +667,10 @@ class ConvT3dFn(Function):
             else:
                 L.check(lib.mednet_convt3d_dgrad(dy.data_ptr(), packed.data_ptr(), dx.data_ptr(), n, d, h, w, cin, cout,
                                                  L.dt(dy), L.dt(dx), config.conv_algo(), L.stream()), "convt3d_dgrad")
-        if ctx.needs_input_grad[1]:
+        want_db = has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_db:  # (a trainable bias behind a frozen weight still gets its gradient)
             weight, bias = ctx.params
-            dw, db = conv_wgrad(x, dy, weight, bias if has_bias and ctx.needs_input_grad[2] else None, 3, transposed=True)
+            dw, db = conv_wgrad(x, dy, weight, bias if want_db else None, 3, transposed=True, want_dw=ctx.needs_input_grad[1])
         if has_skip and ctx.needs_input_grad[3]:
             dskip = dy if dy.dtype == skip_dtype else dy.to(skip_dtype)
         if debug.TRACE is not None:

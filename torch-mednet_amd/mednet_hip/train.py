@@ -22,7 +22,12 @@ class FlatParams:
     """Re-homes a module's parameters into one flat fp32 buffer (+ a flat gradient buffer the kernels write into)."""
 
     def __init__(self, module: torch.nn.Module):
+        # (name, parameter, requires_grad) of EVERY parameter as the buffers were laid out: a flag changed later is an error
+        # (verify), not a silently trained "frozen" parameter or a silently untrained thawed one
+        self.flags = [(k, p, p.requires_grad) for k, p in module.named_parameters()]
         self.params = [p for p in module.parameters() if p.requires_grad]
+        if not self.params:
+            raise RuntimeError("FlatParams: the module has no trainable parameter")
         dev = self.params[0].device
         self.offsets = []
         total = 0
@@ -37,6 +42,15 @@ class FlatParams:
             view.copy_(p.data)
             p.data = view
             p._mednet_grad = self.grad[off:off + p.numel()].view_as(p)
+
+    def verify(self):
+        """The gradient slices are handed out once, here at construction: a parameter frozen afterwards would still be written by
+        the kernels and moved by Adam, one thawed afterwards would never train.  Called by the step classes on every call (a loop
+        over the recorded flags: no device work, nothing to capture)."""
+        for name, p, flag in self.flags:
+            if p.requires_grad != flag:
+                raise RuntimeError(f"mednet_hip: requires_grad of parameter '{name}' changed from {flag} to {p.requires_grad} after the "
+                                   f"training step was built; freeze or unfreeze first, then rebuild the step")
 
     def grads_as_attr(self):
         """Expose the flat slices as .grad (for inspection / torch optimizers)."""
@@ -359,6 +373,7 @@ class _GraphedStep:
 
     def _run(self, batch):
         """-> tuple of detached loss tensors of this step's forward/backward (gradients are in self.flat.grad)."""
+        self.flat.verify()  # (every call, capture and replay included: requires_grad must be what the flat buffers were built for)
         if not self.use_graph:
             return self._fwd_bwd(batch)
         self._calls += 1
