@@ -575,6 +575,47 @@ int mednet_adam_step_scaled(float* p, const float* g, float* m, float* v, size_t
                             float eps, float weight_decay, float inv_world, float* scaler_state, float growth_factor,
                             float backoff_factor, int growth_interval, mednet_stream stream);
 
+/* ---- optimisers behind a global gradient norm (additive to ABI 3; the reference trains with plain Adam only) ---------------------
+ * Optimiser state opt_state (device, 8 floats): {sumsq, norm, coef, nonfinite, steps taken, steps skipped, -, -}; a fresh one is
+ * {0, 0, 1, 0, 0, 0, 0, 0}.  scaler_state is mednet_adam_step_scaled's loss-scaler state or NULL.  In every entry
+ *   gscale = scaler_state ? inv_world / scaler_state[0] : inv_world                                       (fp32, on the device)
+ *
+ * mednet_grad_norm: two launches, no atomics, bitwise reproducible (the grid is a function of count alone).
+ *   partial[row] = sum over the row's elements of (g * gscale)^2     fp32, fmaf(s, s, acc), s = g * gscale: scaled BEFORE squaring
+ *   sum          = the partials added in a fixed order in fp64
+ *   sumsq = (float)sum;  norm = (float)sqrt(sum);  coef = max_norm > 0 ? (float)min(1, max_norm / (sqrt(sum) + 1e-6)) : 1
+ *   nonfinite = sumsq is NaN or inf          every NaN / +-inf gradient, and a finite one whose scaled square overflows fp32: that
+ *                                            step is skipped as well.  With a scaler state, found_inf (entry 3) is raised too, so this
+ *                                            pass replaces the overflow sweep of mednet_adam_step_scaled.
+ * coef is torch.nn.utils.clip_grad_norm_'s clip coefficient; max_norm == 0 turns clipping off.  g: any 4-byte aligned pointer, any
+ * count >= 1.  ws holds one float per row: mednet_grad_norm_ws_bytes(count) / 4 rows (0 for count == 0). */
+size_t mednet_grad_norm_ws_bytes(size_t count);
+int mednet_grad_norm(const float* g, size_t count, float inv_world, float* scaler_state, float max_norm, float* opt_state, void* ws,
+                     size_t ws_bytes, mednet_stream stream);
+/* torch.optim.SGD(lr, momentum, dampening 0, weight_decay, nesterov) on flat fp32 buffers, per element, fp32:
+ *   skipped entirely when nonfinite (or the scaler's found_inf) is set: p, buf and the step count stay bit-unchanged
+ *   gr  = (g * gscale) * coef
+ *   gr  = fma(wd, p, gr)                        when wd != 0
+ *   buf = fma(mu, buf, gr)                      when mu != 0 (a zero-initialised buffer reproduces torch's first step)
+ *   d   = nesterov ? fma(mu, buf, gr) : buf     (d = gr when mu == 0: buf may be NULL and is not touched)
+ *   p   = fma(-lr, d, p)
+ * then one thread applies the loss scaler's update rule (scaler_state given) or counts the step in opt_state[4] / a skipped one in
+ * opt_state[5], and clears nonfinite.  opt_state == NULL (only without a scaler state): coef = 1, no guard, one launch. */
+int mednet_sgd_step(float* p, const float* g, float* buf, size_t count, float lr, float momentum, int nesterov, float weight_decay,
+                    float inv_world, float* opt_state, float* scaler_state, float growth_factor, float backoff_factor,
+                    int growth_interval, mednet_stream stream);
+/* torch.optim.Adam (decoupled == 0) / torch.optim.AdamW (decoupled != 0) behind the norm pass, per element, fp32:
+ *   skipped entirely when nonfinite (or found_inf) is set: p, m, v and the step count stay bit-unchanged
+ *   t   = (scaler_state ? scaler_state[2] : opt_state[4]) + 1;  bc1 = 1 - beta1^t;  bc2s = sqrt(1 - beta2^t)
+ *   gr  = (g * gscale) * coef
+ *   Adam:  gr = fma(wd, p, gr)                  AdamW:  p = p * (1 - lr * wd)                   (each when wd != 0)
+ *   m   = beta1 * m + (1 - beta1) * gr;  v = beta2 * v + (1 - beta2) * gr * gr
+ *   p   = p - (lr / bc1) * (m / (sqrt(v) / bc2s + eps))
+ * (the lines of mednet_adam_step_scaled: with coef == 1 and decoupled == 0 the two give the same bits), then the state update as above. */
+int mednet_adamw_step(float* p, const float* g, float* m, float* v, size_t count, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, int decoupled, float inv_world, float* opt_state, float* scaler_state, float growth_factor,
+                      float backoff_factor, int growth_interval, mednet_stream stream);
+
 /* ---- inference path ------------------------------------------------------------------------ */
 enum { MEDNET_PAD_CONSTANT = 0, MEDNET_PAD_SYMMETRIC = 1 };
 /* midasmednet/dataset.py:349-390 (grid_patch_generator): patch b = padded(volume)[:, pos[b] : pos[b] + patch] where the

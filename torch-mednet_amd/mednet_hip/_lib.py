@@ -151,6 +151,10 @@ SIGNATURES = {
     "mednet_heatmap_loss_bwd": (_i, [_vp] * 5 + [_i, _i, _sz, _i64, _i64, _i, _i, _vp]),
     "mednet_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _f, _vp]),
     "mednet_adam_step_scaled": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _f, _vp, _f, _f, _i, _vp]),
+    "mednet_grad_norm_ws_bytes": (_sz, [_sz]),
+    "mednet_grad_norm": (_i, [_vp, _sz, _f, _vp, _f, _vp, _vp, _sz, _vp]),
+    "mednet_sgd_step": (_i, [_vp, _vp, _vp, _sz, _f, _f, _i, _f, _f, _vp, _vp, _f, _f, _i, _vp]),
+    "mednet_adamw_step": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _f, _f, _i, _vp]),
     "mednet_grid_gather": (_i, [_vp, _vp, _vp] + [_i] * 12 + [_vp]),
     "mednet_predict_assemble": (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
     "mednet_grid_gather_mirror": (_i, [_vp, _vp, _vp] + [_i] * 13 + [_vp]),

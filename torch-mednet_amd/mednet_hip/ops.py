@@ -1856,3 +1856,55 @@ def adam_step_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale
     L.require_gpu(p, "adam_step")
     L.check(L.lib().mednet_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2,
                                      eps, weight_decay, step, grad_scale, L.stream()), "adam_step")
+
+
+OPT_STATE_FRESH = (0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0)  # {sumsq, norm, coef, nonfinite, steps taken, steps skipped, -, -}
+
+
+def new_opt_state(device):
+    """The 8-float device state the norm pass writes and the update kernels read (include/mednet_hip.h)."""
+    return torch.tensor(OPT_STATE_FRESH, dtype=torch.float32, device=device)
+
+
+def grad_norm_rows(count: int) -> int:
+    """Partial rows (workgroups) of the norm pass over `count` elements; needs no GPU."""
+    return L.lib().mednet_grad_norm_ws_bytes(count) // 4
+
+
+def grad_norm_(g, opt_state, max_norm=None, inv_world=1.0, scaler_state=None, ws=None):
+    """Global L2 norm of g * gscale (gscale = inv_world, over the loss scale when scaler_state is given) into opt_state:
+    {sumsq, norm, coef = min(1, max_norm / (norm + 1e-6)), nonfinite}.  Two launches, no host synchronisation, bitwise
+    reproducible.  max_norm None: coef = 1.  ws: a workspace of the caller's (at least mednet_grad_norm_ws_bytes bytes)."""
+    L.require_gpu(g, "grad_norm")
+    need = L.lib().mednet_grad_norm_ws_bytes(g.numel())
+    if ws is None:
+        ws = L.workspace(need, g.device)
+    L.check(L.lib().mednet_grad_norm(g.data_ptr(), g.numel(), inv_world, L.ptr(scaler_state), 0.0 if max_norm is None else max_norm,
+                                     opt_state.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), L.stream()), "grad_norm")
+    return opt_state
+
+
+def _scaler_args(scaler):
+    """(state pointer, growth, backoff, interval) of a train.LossScaler, or the null form."""
+    if scaler is None:
+        return None, 2.0, 0.5, 1
+    return scaler.state.data_ptr(), scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval
+
+
+def sgd_step_(p, g, buf, lr, momentum=0.0, nesterov=False, weight_decay=0.0, inv_world=1.0, opt_state=None, scaler=None):
+    """In-place torch.optim.SGD (dampening 0) on flat fp32 buffers behind grad_norm_: the clip coefficient and the skip rule are
+    read from opt_state on the device.  buf is None when momentum == 0.  opt_state None (no scaler): the plain update, one launch."""
+    L.require_gpu(p, "sgd_step")
+    sc, growth, backoff, interval = _scaler_args(scaler)
+    L.check(L.lib().mednet_sgd_step(p.data_ptr(), g.data_ptr(), L.ptr(buf), p.numel(), lr, momentum, int(bool(nesterov)), weight_decay,
+                                    inv_world, L.ptr(opt_state), sc, growth, backoff, interval, L.stream()), "sgd_step")
+
+
+def adamw_step_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, opt_state, decoupled=True, inv_world=1.0, scaler=None):
+    """In-place torch.optim.AdamW (decoupled) or torch.optim.Adam (not) on flat fp32 buffers behind grad_norm_; the bias correction
+    uses the device-side count of steps actually taken (opt_state[4], or the scaler's)."""
+    L.require_gpu(p, "adamw_step")
+    sc, growth, backoff, interval = _scaler_args(scaler)
+    L.check(L.lib().mednet_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,
+                                      weight_decay, int(bool(decoupled)), inv_world, opt_state.data_ptr(), sc, growth, backoff, interval,
+                                      L.stream()), "adamw_step")

@@ -19,7 +19,11 @@ from .unet import loss as HL
 
 
 class FlatParams:
-    """Re-homes a module's parameters into one flat fp32 buffer (+ a flat gradient buffer the kernels write into)."""
+    """Re-homes a module's parameters into one flat fp32 buffer (+ a flat gradient buffer the kernels write into).
+
+    Slices are 64-element aligned; the padding elements between them are zero in both buffers from construction on and must STAY
+    zero: no kernel writes them, and the global gradient norm (ops.grad_norm_) runs over the whole buffer, padding included, and
+    relies on it."""
 
     def __init__(self, module: torch.nn.Module):
         # (name, parameter, requires_grad) of EVERY parameter as the buffers were laid out: a flag changed later is an error
@@ -63,11 +67,29 @@ class FlatParams:
                 del p._mednet_grad
 
 
-class FlatAdam:
-    """torch.optim.Adam(lr) semantics (betas .9/.999, eps 1e-8, weight_decay 0) as one kernel over FlatParams."""
+def _check_guard_args(who, clip_grad_norm, lr, weight_decay):
+    if clip_grad_norm is not None and not clip_grad_norm > 0:
+        raise ValueError(f"{who}: clip_grad_norm must be a positive number or None, got {clip_grad_norm!r}")
+    if lr < 0 or weight_decay < 0:
+        raise ValueError(f"{who}: negative lr {lr} or weight_decay {weight_decay}")
 
-    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+
+class FlatAdam:
+    """torch.optim.Adam(lr) semantics (betas .9/.999, eps 1e-8, weight_decay 0) as one kernel over FlatParams.
+
+    decoupled_weight_decay=True is torch.optim.AdamW's rule (p *= 1 - lr wd, no L2 term).  clip_grad_norm (a float: clip the mean
+    gradient to that global L2 norm, torch.nn.utils.clip_grad_norm_'s rule) and skip_nonfinite (skip the whole update when a gradient
+    is NaN / inf, in every storage mode) route the step through the norm pass and the guarded update kernel (ops.grad_norm_ +
+    ops.adamw_step_), as does the decoupled decay; the bias correction then uses the device-side count `opt_state[4]` of steps actually
+    taken.  With all three off the launches are the ones this class always made."""
+
+    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
+                 clip_grad_norm=None, skip_nonfinite=False):
+        _check_guard_args("FlatAdam", clip_grad_norm, lr, weight_decay)
         self.flat, self.lr, self.betas, self.eps, self.wd = flat, lr, betas, eps, weight_decay
+        self.decoupled, self.clip, self.skip_nonfinite = bool(decoupled_weight_decay), clip_grad_norm, bool(skip_nonfinite)
+        self.guarded = self.decoupled or self.clip is not None or self.skip_nonfinite
+        self.opt_state = ops.new_opt_state(flat.flat.device) if self.guarded else None
         self.m = torch.zeros_like(flat.flat)
         self.v = torch.zeros_like(flat.flat)
         self.t = 0  # calls so far.  Plain mode: = optimizer steps taken (bias correction uses it).  Behind a LossScaler the
@@ -77,11 +99,15 @@ class FlatAdam:
 
     def steps_taken(self, scaler: "LossScaler | None" = None) -> int:
         """Optimizer steps actually applied (synchronises when a scaler holds the count)."""
-        return self.t if scaler is None else int(scaler.state[2].item())
+        if scaler is not None:
+            return int(scaler.state[2].item())
+        return int(self.opt_state[4].item()) if self.guarded else self.t
 
     def state_dict(self, scaler: "LossScaler | None" = None):
         sd = {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(), "t": self.steps_taken(scaler),
               "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd}
+        if self.guarded:
+            sd["opt_state"] = self.opt_state.detach().cpu().clone()
         if scaler is not None:
             sd["scaler"] = scaler.state_dict()
         return sd
@@ -98,6 +124,8 @@ class FlatAdam:
         self.betas = tuple(sd.get("betas", self.betas))
         self.eps = sd.get("eps", self.eps)
         self.wd = sd.get("weight_decay", self.wd)
+        if self.guarded:  # (a state saved by the plain form has no device state: its host count becomes the device count)
+            _load_opt_state(self.opt_state, sd, self.t)
         if scaler is not None:
             if "scaler" not in sd:
                 raise KeyError("FlatAdam.load_state_dict: a LossScaler was passed but the saved state has no 'scaler' entry "
@@ -111,11 +139,20 @@ class FlatAdam:
             raise RuntimeError("FlatAdam: step() and step_scaled() keep different step counts (host / device) and cannot "
                                "be mixed on one optimizer")
 
+    def _guarded_step(self, inv_world, scaler):
+        f = self.flat
+        ops.grad_norm_(f.grad, self.opt_state, self.clip, inv_world, None if scaler is None else scaler.state)
+        ops.adamw_step_(f.flat, f.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.opt_state,
+                        self.decoupled, inv_world, scaler)
+
     def step(self, grad_scale=1.0):
         self._form(False)
         self.t += 1
-        ops.adam_step_(self.flat.flat, self.flat.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
-                       self.wd, self.t, grad_scale)
+        if self.guarded:
+            self._guarded_step(grad_scale, None)
+        else:
+            ops.adam_step_(self.flat.flat, self.flat.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+                           self.wd, self.t, grad_scale)
         self._bump()
 
     def step_scaled(self, scaler: "LossScaler", inv_world=1.0):
@@ -123,6 +160,10 @@ class FlatAdam:
         from . import _lib as L
         self._form(True)
         self.t += 1
+        if self.guarded:  # (the norm is taken of the UNSCALED gradient and its pass replaces the overflow sweep)
+            self._guarded_step(inv_world, scaler)
+            self._bump()
+            return
         f = self.flat
         L.check(L.lib().mednet_adam_step_scaled(f.flat.data_ptr(), f.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
                                                 f.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
@@ -135,6 +176,137 @@ class FlatAdam:
         # reach the views' counters, so packed-weight caches are keyed on this step counter as well.
         for p in self.flat.params:
             p._mednet_step = self.t
+
+
+def _load_opt_state(opt_state, sd, steps):
+    """Restore the device state of the guarded update forms; a saved state without one starts from `steps` steps taken."""
+    if "opt_state" in sd:
+        opt_state.copy_(sd["opt_state"].to(opt_state.device))
+    else:
+        opt_state.copy_(torch.tensor(ops.OPT_STATE_FRESH, dtype=torch.float32))
+        opt_state[4] = float(steps)
+    opt_state[3] = 0.0
+
+
+class FlatSGD:
+    """torch.optim.SGD(lr, momentum, dampening 0, weight_decay, nesterov) as one kernel over FlatParams, with FlatAdam's surface.
+
+    clip_grad_norm / skip_nonfinite put the norm pass (ops.grad_norm_) in front: clip coefficient and skip rule are read by the update
+    kernel on the device.  Behind a LossScaler (step_scaled) the norm pass always runs: it is what finds the overflow.  With
+    momentum 0 there is no buffer and no buffer traffic.  Weight decay applies to the whole flat buffer (no parameter groups)."""
+
+    def __init__(self, flat: FlatParams, lr, momentum=0.0, nesterov=False, weight_decay=0.0, clip_grad_norm=None, skip_nonfinite=False):
+        _check_guard_args("FlatSGD", clip_grad_norm, lr, weight_decay)
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError(f"FlatSGD: momentum {momentum} outside [0, 1)")
+        if nesterov and momentum == 0.0:
+            raise ValueError("FlatSGD: nesterov needs momentum > 0 (torch.optim.SGD's rule)")
+        self.flat, self.lr, self.momentum, self.nesterov, self.wd = flat, lr, momentum, bool(nesterov), weight_decay
+        self.clip, self.skip_nonfinite = clip_grad_norm, bool(skip_nonfinite)
+        self.guarded = self.clip is not None or self.skip_nonfinite
+        self.opt_state = ops.new_opt_state(flat.flat.device)
+        self.buf = torch.zeros_like(flat.flat) if momentum != 0.0 else None
+        self.t = 0  # calls so far; versions the parameters (_bump).  Steps actually taken: steps_taken()
+        self._scaled = None
+
+    def steps_taken(self, scaler: "LossScaler | None" = None) -> int:
+        """Optimizer steps actually applied (synchronises when the count lives on the device)."""
+        if scaler is not None:
+            return int(scaler.state[2].item())
+        return int(self.opt_state[4].item()) if self.guarded else self.t
+
+    def state_dict(self, scaler: "LossScaler | None" = None):
+        sd = {"buf": None if self.buf is None else self.buf.detach().cpu().clone(), "t": self.steps_taken(scaler), "lr": self.lr,
+              "momentum": self.momentum, "nesterov": self.nesterov, "weight_decay": self.wd,
+              "opt_state": self.opt_state.detach().cpu().clone()}
+        if scaler is not None:
+            sd["scaler"] = scaler.state_dict()
+        return sd
+
+    def load_state_dict(self, sd, scaler: "LossScaler | None" = None):
+        """Restores the momentum buffer, the counts and the hyper-parameters.  As FlatAdam's: a run behind a loss scaler must find the
+        scaler's state in `sd`."""
+        if (self.buf is None) != (sd["buf"] is None):
+            raise ValueError("FlatSGD.load_state_dict: the saved state and this optimizer disagree about a momentum buffer")
+        if self.buf is not None:
+            self.buf.copy_(sd["buf"].to(self.buf.device))
+        self.t = int(sd["t"])
+        self.lr = sd.get("lr", self.lr)
+        self.momentum, self.nesterov = sd.get("momentum", self.momentum), sd.get("nesterov", self.nesterov)
+        self.wd = sd.get("weight_decay", self.wd)
+        _load_opt_state(self.opt_state, sd, self.t)
+        if scaler is not None:
+            if "scaler" not in sd:
+                raise KeyError("FlatSGD.load_state_dict: a LossScaler was passed but the saved state has no 'scaler' entry "
+                               "(it was saved by a run without loss scaling)")
+            scaler.load_state_dict(sd["scaler"])
+
+    def _form(self, scaled: bool):
+        if self._scaled is None:
+            self._scaled = scaled
+        elif self._scaled != scaled:
+            raise RuntimeError("FlatSGD: step() and step_scaled() keep different step counts and cannot be mixed on one optimizer")
+
+    def _update(self, inv_world, opt_state, scaler):
+        f = self.flat
+        ops.sgd_step_(f.flat, f.grad, self.buf, self.lr, self.momentum, self.nesterov, self.wd, inv_world, opt_state, scaler)
+
+    def step(self, grad_scale=1.0):
+        self._form(False)
+        self.t += 1
+        if self.guarded:
+            ops.grad_norm_(self.flat.grad, self.opt_state, self.clip, grad_scale)
+            self._update(grad_scale, self.opt_state, None)
+        else:
+            self._update(grad_scale, None, None)
+        self._bump()
+
+    def step_scaled(self, scaler: "LossScaler", inv_world=1.0):
+        """The same update behind the loss scaler: the norm of the unscaled gradient, skip on overflow, scale update -- on the device."""
+        self._form(True)
+        self.t += 1
+        ops.grad_norm_(self.flat.grad, self.opt_state, self.clip, inv_world, scaler.state)
+        self._update(inv_world, self.opt_state, scaler)
+        self._bump()
+
+    def _bump(self):
+        for p in self.flat.params:
+            p._mednet_step = self.t
+
+
+class PolyLR:
+    """lr(call_index) = base_lr * (1 - call_index / total_steps) ** power, 0 from total_steps on: the polynomial decay of the common 3D
+    segmentation recipe.  A step class evaluates it on the host once per call, as a scheduler stepped once per iteration is; the index
+    counts CALLS, skipped steps included.  The optimiser launch lies outside the captured graph and takes lr as a kernel argument, so
+    a changing lr is graph-safe as it stands."""
+
+    def __init__(self, base_lr, total_steps, power=0.9):
+        if total_steps < 1:
+            raise ValueError(f"PolyLR: total_steps {total_steps} < 1")
+        self.base_lr, self.total_steps, self.power = float(base_lr), int(total_steps), float(power)
+
+    def __call__(self, call_index):
+        left = 1.0 - min(max(int(call_index), 0), self.total_steps) / self.total_steps
+        return self.base_lr * left ** self.power
+
+
+def make_optimizer(flat, optimizer="adam", optimizer_args=None, lr=1e-3, clip_grad_norm=None, skip_nonfinite=False):
+    """-> (optimizer, lr callable or None) for the step classes.  optimizer: "adam" | "adamw" | "sgd"; optimizer_args go to FlatAdam /
+    FlatSGD as they are and may not repeat what the step's own arguments set."""
+    args = dict(optimizer_args or {})
+    for k in ("lr", "clip_grad_norm", "skip_nonfinite", "flat"):
+        if k in args:
+            raise ValueError(f"optimizer_args: '{k}' is an argument of the step itself")
+    lr_fn = lr if callable(lr) else None
+    args.update(lr=0.0 if lr_fn is not None else lr, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+    if optimizer in ("adam", "adamw"):
+        if "decoupled_weight_decay" in args and bool(args["decoupled_weight_decay"]) != (optimizer == "adamw"):
+            raise ValueError(f"optimizer='{optimizer}' conflicts with decoupled_weight_decay={args['decoupled_weight_decay']}")
+        args["decoupled_weight_decay"] = optimizer == "adamw"
+        return FlatAdam(flat, **args), lr_fn
+    if optimizer == "sgd":
+        return FlatSGD(flat, **args), lr_fn
+    raise ValueError(f"optimizer must be 'adam', 'adamw' or 'sgd', got {optimizer!r}")
 
 
 class BatchedRepack:
@@ -392,6 +564,37 @@ class _GraphedStep:
         self._graph.replay()
         return self._out
 
+    # ---- the optimiser of a step (outside the graph: lr and the step count are kernel arguments / device state)
+    def _init_optimizer(self, optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite):
+        self.opt, self._lr_fn = make_optimizer(self.flat, optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
+        self._opt_calls = 0
+
+    def _optimizer_step(self, scale):
+        if self._lr_fn is not None:
+            self.opt.lr = float(self._lr_fn(self._opt_calls))  # (host arithmetic, once per call)
+        self._opt_calls += 1
+        if self.scaler is None:
+            self.opt.step(grad_scale=scale)
+        else:
+            self.opt.step_scaled(self.scaler, inv_world=scale)
+
+    def _norm_runs(self) -> bool:
+        return self.opt.guarded or (isinstance(self.opt, FlatSGD) and self.scaler is not None)
+
+    @property
+    def grad_norm(self):
+        """Device scalar: the last step's global L2 norm of the mean gradient (unscaled, after the exchange's 1/world) BEFORE
+        clipping.  Reading the attribute synchronises nothing; float() / .item() of it does."""
+        if not self._norm_runs():
+            raise RuntimeError("grad_norm: this step takes no gradient norm (pass clip_grad_norm=... or skip_nonfinite=True)")
+        return self.opt.opt_state[1]
+
+    def skipped_steps(self) -> int:
+        """Updates skipped for non-finite gradients so far (synchronises)."""
+        if self.scaler is not None:
+            return self.scaler.skipped_steps()
+        return int(self.opt.opt_state[5].item()) if self._norm_runs() else 0
+
 
 def use_side_stream():
     """Weight gradients on their own stream (ops.SIDE) for every step class: MEDNET_SIDE_STREAM=0 turns it off."""
@@ -419,15 +622,24 @@ def _class_criterion(loss, w):
 
 
 class SegmentationStep(_GraphedStep):
-    """One data-parallel training step of SegmentationNet (segmentation.py:58-65) on the MI355X path."""
+    """One data-parallel training step of SegmentationNet (segmentation.py:58-65) on the MI355X path.
 
-    def __init__(self, model, loss_weight=None, lr=1e-3, loss="DICE", world_size=1, graph=None):
+    optimizer: "adam" (the reference's rule and the default), "adamw" or "sgd"; optimizer_args: a dict for FlatAdam / FlatSGD
+    (betas, eps, weight_decay / momentum, nesterov, weight_decay; weight decay defaults to 0 for all three).  lr: a float, or a callable
+    lr(call_index) -> float such as PolyLR, evaluated on the host once per call -- the optimiser launch is outside the captured graph,
+    so a changing lr is graph-safe.  clip_grad_norm: clip the mean gradient to this global L2 norm (taken after the gradient exchange
+    with 1/world folded in, so every rank clips by the same number; of the UNSCALED gradient in fp16 storage).  skip_nonfinite: skip
+    the update when a gradient is NaN / inf, in any storage mode.  Neither makes the step wait for the host: `grad_norm` is a device
+    scalar, `skipped_steps()` synchronises.  With the defaults the step launches exactly what it always launched."""
+
+    def __init__(self, model, loss_weight=None, lr=1e-3, loss="DICE", world_size=1, graph=None, optimizer="adam", optimizer_args=None,
+                 clip_grad_norm=None, skip_nonfinite=False):
         self.model = model
         dev = next(model.parameters()).device
         w = None if loss_weight is None else torch.tensor(loss_weight, dtype=torch.float32, device=dev)
         self.loss = _class_criterion(loss, w).to(dev)
         self.flat = FlatParams(model)
-        self.opt = FlatAdam(self.flat, lr=lr)
+        self._init_optimizer(optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
         self.repack = BatchedRepack(model)
         self.world = world_size
         use_side_stream()
@@ -487,11 +699,8 @@ class SegmentationStep(_GraphedStep):
         if self._exchange is None:  # (built lazily: bench.py sets force_allreduce after construction)
             self._exchange = BucketedExchange(self.model, self.flat, self.world, force)
         (loss,) = self._run(batch)
-        scale = self._exchange.finish()  # 1/world is folded into Adam
-        if self.scaler is None:
-            self.opt.step(grad_scale=scale)
-        else:
-            self.opt.step_scaled(self.scaler, inv_world=scale)
+        scale = self._exchange.finish()  # 1/world is folded into the optimiser (and into the gradient norm in front of it)
+        self._optimizer_step(scale)
         self.repack.run()
         return loss
 
@@ -571,15 +780,17 @@ def _landmark_head_fusable(model, loss_class, loss_reg, inputs) -> bool:
 
 class LandmarkStep(_GraphedStep):
     """LandmarkNet.training_step (landmarks.py:66-83, loss :125-134) with the per-channel regression loop fused.  class_loss:
-    the hparams' `loss_class`, "DICE" (DiceLoss) or "CE" (nn.CrossEntropyLoss(weight=class_weight))."""
+    the hparams' `loss_class`, "DICE" (DiceLoss) or "CE" (nn.CrossEntropyLoss(weight=class_weight)).  optimizer, optimizer_args, lr as
+    a callable, clip_grad_norm and skip_nonfinite: as SegmentationStep's."""
 
-    def __init__(self, model, class_weight, regression_weight, regression="L2", lr=1e-3, world_size=1, graph=None, class_loss="DICE"):
+    def __init__(self, model, class_weight, regression_weight, regression="L2", lr=1e-3, world_size=1, graph=None, class_loss="DICE",
+                 optimizer="adam", optimizer_args=None, clip_grad_norm=None, skip_nonfinite=False):
         self.model = model
         dev = next(model.parameters()).device
         self.class_loss = class_loss
         self.loss_class, self.loss_reg = _landmark_losses(class_weight, regression_weight, class_loss, regression, dev)
         self.flat = FlatParams(model)
-        self.opt = FlatAdam(self.flat, lr=lr)
+        self._init_optimizer(optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
         self.repack = BatchedRepack(model)
         self.world = world_size
         use_side_stream()
@@ -628,10 +839,7 @@ class LandmarkStep(_GraphedStep):
     def __call__(self, batch):
         out = self._run(batch)
         scale = self._exchange.finish()
-        if self.scaler is None:
-            self.opt.step(grad_scale=scale)
-        else:
-            self.opt.step_scaled(self.scaler, inv_world=scale)
+        self._optimizer_step(scale)
         self.repack.run()
         return out
 
