@@ -245,12 +245,14 @@ int mednet_convt3d_wgrad(const void* x, const void* dy, float* dw, float* dbias,
 /* ---- nn.GroupNorm(G,C,eps) fused with the following activation and the residual add
  *      components.py:57 (GroupNorm), :36-40 (ReLU/LeakyReLU(0.1)/ELU), :177-178 (out += residual; non_linearity) */
 size_t mednet_gn_ws_bytes(int n, int c, size_t spatial);
-/* stats[n][g] = {mean, rstd}; coef[n][c] = {gamma*rstd, beta - mean*gamma*rstd} (both outputs, fp32). */
+/* stats[n][g] = {mean, rstd}; coef[n][c] = {gamma*rstd, beta - mean*gamma*rstd} (both outputs, fp32).  The sums are taken of
+ * x - p, p one element of the group itself (mednet_bn_stats: of the channel): the variance does not degrade with mean / std. */
 int mednet_gn_stats(const void* x, const float* gamma, const float* beta, float* stats, float* coef, int n,
                     size_t spatial, int c, int groups, float eps, int dtype, void* ws, size_t ws_bytes,
                     mednet_stream stream);
 /* the second half of mednet_gn_stats for partial sums produced elsewhere (fused conv epilogue):
- * partial is [n][chunks][c][2]; ws needs n*c*2 floats. */
+ * partial is [n][chunks][c][2] = {sum x, sum x^2}; ws needs n*c*2 floats.  var = sum x^2 / N - mean^2: its error grows as
+ * (mean / std)^2 -- for data far from zero use mednet_gn_stats on the tensor. */
 int mednet_gn_finalize(const float* partial, int chunks, const float* gamma, const float* beta, float* stats,
                        float* coef, int n, size_t spatial, int c, int groups, float eps, void* ws, size_t ws_bytes,
                        mednet_stream stream);

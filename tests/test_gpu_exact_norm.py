@@ -346,6 +346,10 @@ def run_stats(lt, beta, mode, item="h"):
     assert_representable(lt.x, dt, "x")
     assert_sums_exact(channel_sums(lt.x.abs()), "sum |x|")
     assert_sums_exact(channel_sums(lt.x.double() ** 2), "sum x^2")
+    # the statistics pass sums x - p, p the first channel of the unit at voxel 0 (of sample 0 for BatchNorm): exact as well
+    p = (lt.x[:1] if lt.batch else lt.x)[:, ::lt.cg, :1, :1, :1].double().repeat_interleave(lt.cg, dim=1)
+    assert_sums_exact(channel_sums((lt.x.double() - p).abs()), "sum |x - pivot|")
+    assert_sums_exact(channel_sums((lt.x.double() - p) ** 2), "sum (x - pivot)^2")
     xg, gam, bet = vol(lt.x, dt), f32(lt.gamma), f32(beta)
     stats, coef, y = nan_f32(lt.n, lt.groups, 2), nan_f32(lt.n, lt.c, 2), nan_vol(lt, dt)
     ws, wsb = workspace(lt.n, lt.c, lt.spatial)

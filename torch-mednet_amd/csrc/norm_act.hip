@@ -149,10 +149,21 @@ __device__ __forceinline__ void column_reduce_lds_free(float* vals, int cols, in
 }
 
 // ---------------------------------------------------------------------------------------------- GN statistics
-// partial[n][chunk][c][2] = {sum x, sum x^2}
+// The stand-alone statistics pass is PIVOTED: a variance taken as sum x^2 / N - mean^2 from fp32 sums loses (mean / std)^2 ulps
+// (an image at -1000 +- 5: everything).  The pivot of a statistics unit -- a GroupNorm group of a sample (cg channels), a
+// BatchNorm channel over all samples (cg = 1, per_sample = 0) -- is one element of the unit itself, its first channel at voxel 0:
+// it lies within the unit's spread of the mean, so the sums of x - pivot are as well conditioned as those of centred data.
+// pivot_x: the tensor (nullptr: rows that someone else produced, pivot 0); i: the element's index.
+__device__ __forceinline__ float pivot_of(const void* pivot_x, size_t i, int dtype) {
+  if (!pivot_x) return 0.f;
+  if (dtype == MEDNET_F32) return ld((const float*)pivot_x, i);
+  return dtype == MEDNET_BF16 ? ld((const bf16*)pivot_x, i) : ld((const f16*)pivot_x, i);
+}
+
+// partial[n][chunk][c][2] = {sum (x - p), sum (x - p)^2}, p the pivot of the channel's unit
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, float* __restrict__ partial,
-                                                         size_t spatial, int c, size_t chunk_vox) {
+                                                         size_t spatial, int c, size_t chunk_vox, int cg, int per_sample) {
   __shared__ float lds[256 * 2 * VEC];
   const Cols<VEC> L(c);
   const int n = blockIdx.y;
@@ -163,6 +174,10 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
   for (int k = 0; k < 2 * VEC; ++k) acc[k] = 0.f;
   if (L.active) {
     const T* base = x + (size_t)n * spatial * c + (size_t)L.col * VEC;
+    const T* first = x + (per_sample ? (size_t)n * spatial * c : 0);  // voxel 0 of the sample the pivots come from
+    float piv[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) piv[k] = ld(first, (size_t)((L.col * VEC + k) / cg * cg));
     size_t v = v0 + L.row;
     for (; v + 3 * (size_t)L.rows < v1; v += 4 * (size_t)L.rows) {  // 4 independent 16-byte loads in flight per lane
       F8 xv[4];
@@ -172,16 +187,18 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
       for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-          acc[2 * k] += xv[u].v[k];
-          acc[2 * k + 1] = fmaf(xv[u].v[k], xv[u].v[k], acc[2 * k + 1]);
+          const float dv = xv[u].v[k] - piv[k];
+          acc[2 * k] += dv;
+          acc[2 * k + 1] = fmaf(dv, dv, acc[2 * k + 1]);
         }
     }
     for (; v < v1; v += L.rows) {
       const F8 xv = VecIO<T, VEC>::load(base, v * c);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        acc[2 * k] += xv.v[k];
-        acc[2 * k + 1] = fmaf(xv.v[k], xv.v[k], acc[2 * k + 1]);
+        const float dv = xv.v[k] - piv[k];
+        acc[2 * k] += dv;
+        acc[2 * k + 1] = fmaf(dv, dv, acc[2 * k + 1]);
       }
     }
   }
@@ -248,12 +265,16 @@ __global__ __launch_bounds__(64) void reduce_partials_dux_kernel(const float* __
 // one workgroup per (n, g) -- 256 threads, or 1024 when there are thousands of rows (the first layer writes 16 384 per sample: a
 // thread's chain of dependent round trips, four rows in flight, was 46 us of exposed latency) --: a thread walks rows t, t + NT,
 // ... and adds the group's cg {sum, sumsq} pairs of each row (32 contiguous bytes when cg = 4); fp64, fixed order => bitwise
-// reproducible; then mean, rstd and the per-channel affine the apply kernel uses.
+// reproducible; then mean, rstd and the per-channel affine the apply kernel uses.  The rows are sums of x - p, p = pivot_of(pivot_x,
+// n * sample_stride + g * cg, dtype) (gn_partial_kernel's; 0 for rows from elsewhere): mean = p + s / N, var = q / N - (s / N)^2.
+// var < 0 -> 0: with a pivot only rounding noise of a constant group (its sums are exactly 0: var = 0, rstd = 1 / sqrt(eps)); in
+// unpivoted rows also the total cancellation of data whose mean / std exceeds a few thousand.
 __global__ __launch_bounds__(1024) void gn_finalize_kernel(const float* __restrict__ partial,
                                                            const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float* __restrict__ stats,
                                                            float* __restrict__ coef, int c, int groups, int chunks,
-                                                           double count, float eps) {
+                                                           double count, float eps, const void* __restrict__ pivot_x,
+                                                           size_t sample_stride, int dtype) {
   __shared__ double sh[2][16];
   const int n = blockIdx.x / groups, g = blockIdx.x % groups;
   const int cg = c / groups, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -301,8 +322,9 @@ __global__ __launch_bounds__(1024) void gn_finalize_kernel(const float* __restri
     s += sh[0][k];
     q += sh[1][k];
   }
-  const double mean = s / count;
-  double var = q / count - mean * mean;
+  const double ms = s / count;
+  const double mean = (double)pivot_of(pivot_x, (size_t)n * sample_stride + (size_t)g * cg, dtype) + ms;
+  double var = q / count - ms * ms;
   if (var < 0.0) var = 0.0;
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   if (threadIdx.x == 0) {
@@ -1332,11 +1354,11 @@ static GnPlan gn_plan(int n, size_t spatial, int c, int dtype, void* ws) {
 }
 
 // The streaming kernels, one launch function each (GroupNorm and BatchNorm entries alike)
-static int launch_gn_partial(const GnPlan& p, const void* x, hipStream_t s) {
+static int launch_gn_partial(const GnPlan& p, const void* x, int cg, int per_sample, hipStream_t s) {  // (pivots: gn_partial_kernel)
   by_type_vec(p.dtype, p.vec, [&](auto t, auto v) {
     using T = typename decltype(t)::type;
     hipLaunchKernelGGL((gn_partial_kernel<T, decltype(v)::value>), p.grid, dim3(256), 0, s, (const T*)x, p.partial, p.spatial, p.c,
-                       p.chunk_vox);
+                       p.chunk_vox, cg, per_sample);
   });
   return check_launch("gn_partial");
 }
@@ -1359,9 +1381,10 @@ static int launch_gn_bwd_apply(const GnPlan& p, const void* dz, const void* dz2,
   return check_launch("gn_bwd_apply");
 }
 static int launch_gn_finalize(const float* partial, int chunks, const float* gamma, const float* beta, float* stats, float* coef,
-                              int n, size_t spatial, int c, int groups, float eps, hipStream_t s) {
+                              int n, size_t spatial, int c, int groups, float eps, hipStream_t s, const void* pivot_x = nullptr,
+                              int dtype = MEDNET_F32) {
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(n * groups), dim3(chunks >= 4096 ? 1024 : 256), 0, s, partial, gamma, beta, stats, coef, c,
-                     groups, chunks, (double)spatial * (c / groups), eps);
+                     groups, chunks, (double)spatial * (c / groups), eps, pivot_x, spatial * (size_t)c, dtype);
   return check_launch("gn_finalize");
 }
 
@@ -1412,9 +1435,9 @@ extern "C" int mednet_gn_stats(const void* x, const float* gamma, const float* b
   MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "gn_stats: C=%d unsupported (need C%%8==0 or C<=256)", c);
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "gn_stats: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int rc = launch_gn_partial(p, x, s);
+  const int rc = launch_gn_partial(p, x, c / groups, 1, s);
   if (rc) return rc;
-  return launch_gn_finalize(p.partial, (int)p.chunks, gamma, beta, stats, coef, n, spatial, c, groups, eps, s);
+  return launch_gn_finalize(p.partial, (int)p.chunks, gamma, beta, stats, coef, n, spatial, c, groups, eps, s, x, dtype);
 }
 
 extern "C" int mednet_gn_finalize(const float* partial, int chunks, const float* gamma, const float* beta, float* stats,
@@ -1602,22 +1625,25 @@ __device__ __forceinline__ void bn_column_sums(const float* __restrict__ partial
 // channels per workgroup of the two kernels below: 4 (32 contiguous bytes of a row per row class) when C allows
 static inline int bn_cw(int c) { return c % 4 == 0 ? 4 : 1; }
 
-// training statistics: partial rows {sum x, sum x^2} of all samples -> stats, coef (replicated per sample), running statistics
-// (momentum blend, unbiased variance) and the batch counter.  All on the device: nothing here is read by the host.
+// training statistics: partial rows {sum (x - p), sum (x - p)^2} of all samples, p = x[0][voxel 0][channel] the channel's pivot
+// (gn_partial_kernel) -> stats, coef (replicated per sample), running statistics (momentum blend, unbiased variance) and the
+// batch counter.  All on the device: nothing here is read by the host.
 __global__ __launch_bounds__(BN_NT) void bn_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ running_mean,
                                                             float* __restrict__ running_var, long long* __restrict__ num_batches,
                                                             float* __restrict__ stats, float* __restrict__ coef, int n, int c,
-                                                            int cw, int rows, double count, float eps, float momentum) {
+                                                            int cw, int rows, double count, float eps, float momentum,
+                                                            const void* __restrict__ pivot_x, int dtype) {
   __shared__ double sha[BN_NT], shb[BN_NT];
   const int c0 = blockIdx.x * cw, t = threadIdx.x;
   double s, q;
   bn_column_sums(partial, rows, c, c0, cw, sha, shb, s, q);
   if (t < cw) {
     const int cc = c0 + t;
-    const double mean = s / count;
-    double var = q / count - mean * mean;
-    if (var < 0.0) var = 0.0;
+    const double ms = s / count;
+    const double mean = (double)pivot_of(pivot_x, (size_t)cc, dtype) + ms;
+    double var = q / count - ms * ms;
+    if (var < 0.0) var = 0.0;  // (rounding noise of a constant channel)
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     const float ga = gamma ? gamma[cc] : 1.f, be = beta ? beta[cc] : 0.f;
     const float a = ga * rstd, b = be - (float)mean * a;
@@ -1698,11 +1724,11 @@ extern "C" int mednet_bn_stats(const void* x, const float* gamma, const float* b
   MEDNET_REQUIRE(c / p.vec <= 256, MEDNET_E_UNSUPPORTED, "bn_stats: C=%d unsupported (need C%%8==0 or C<=256)", c);
   MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "bn_stats: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int rc = launch_gn_partial(p, x, s);
+  const int rc = launch_gn_partial(p, x, 1, 0, s);
   if (rc) return rc;
   const int cw = bn_cw(c);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(c / cw), dim3(BN_NT), 0, s, p.partial, gamma, beta, running_mean, running_var,
-                     num_batches_tracked, stats, coef, n, c, cw, (int)p.chunks * n, (double)spatial * n, eps, momentum);
+                     num_batches_tracked, stats, coef, n, c, cw, (int)p.chunks * n, (double)spatial * n, eps, momentum, x, dtype);
   return check_launch("bn_finalize");
 }
 
