@@ -538,6 +538,30 @@ int mednet_head_seg_bwd(const void* z, const void* packed, const float* bias, co
                         const float* class_weight, const float* saved, const float* dloss, void* dz, const void* gn_y, int gn_act,
                         float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int ncls, int class_kind,
                         float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+/* Deep supervision: the auxiliary 1x1x1 head on a coarser decoder level fused with its class loss and with the junction "block
+ * output -> {next decoder, auxiliary head}".  Additive to ABI 3.  z: N x (d h w) x cin (NDHWC), the level's block output; labels: the
+ * FULL-resolution MEDNET_U8 volume N x D x H x W (sample stride label_stride_n, any alignment), of which voxel (z, y, x) of the level
+ * reads [z << shift][y << shift][x << shift] -- F.interpolate(mode="nearest") for the scale 2^-shift; d == D >> shift (h, w alike,
+ * else MEDNET_E_SHAPE), shift in 1 .. 3.  class_kind, eps, sigmoid, ignore_index, class_weight, packed, loss and saved as
+ * mednet_head_seg_*.  _bwd writes dz = round(W^T dl + d_pass) -- d_pass (nullable, N x (d h w) x cin, storage type) is the gradient
+ * the level's other consumer sent, added in fp32 before the one rounding --, dw [ncls][cin] and dbias (nullable).  gn_y / gn_partial go
+ * together (else MEDNET_E_SHAPE) and are accepted only when mednet_ds_head_gn_rows(...) > 0; it answers 0 in this version (the
+ * GroupNorm-3 sums of the producing block are not taken here), so both must be NULL (else MEDNET_E_UNSUPPORTED).
+ * _supported: cin in 64, 96, .., 256, 1 <= ncls <= 16, dtype MEDNET_BF16 | MEDNET_F16, label_dtype MEDNET_U8, d h w % 4 == 0,
+ * shift in 1 .. 3, tuning option ds_head_fuse != 0.  Workspace: mednet_ds_head_ws_bytes for both calls.  Every sum is made in a fixed
+ * order (no atomics): results are bitwise repeatable. */
+int mednet_ds_head_supported(int cin, int ncls, int dtype, int label_dtype, int d, int h, int w, int shift);
+size_t mednet_ds_head_ws_bytes(int n, int d, int h, int w, int cin, int ncls);
+int mednet_ds_head_gn_rows(int d, int h, int w, int cin, int dtype);
+int mednet_ds_head_fwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                       int64_t label_stride_n, const float* class_weight, float* loss, float* saved, int n, int d, int h, int w, int D,
+                       int H, int W, int shift, int cin, int ncls, int class_kind, float eps, int sigmoid, int ignore_index, int z_dtype,
+                       void* ws, size_t ws_bytes, mednet_stream stream);
+int mednet_ds_head_bwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                       int64_t label_stride_n, const float* class_weight, const float* saved, const float* dloss, const void* d_pass,
+                       void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* dbias, int n, int d, int h, int w,
+                       int D, int H, int W, int shift, int cin, int ncls, int class_kind, float eps, int sigmoid, int ignore_index,
+                       int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
 /* nn.CrossEntropyLoss(weight)  segmentation.py:49: sum w_y * -log softmax_y / sum w_y.  saved[0] = sum w_y. */
 int mednet_ce_fwd(const float* logits, const int64_t* labels, const float* weight, float* loss, float* saved,
                   int n, int c, size_t spatial, int64_t stride_n, int64_t stride_c, int ignore_index, void* ws,

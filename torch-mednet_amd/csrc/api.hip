@@ -637,6 +637,70 @@ extern "C" int mednet_head_seg_bwd(const void* z, const void* packed, const floa
                   ignore_index, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- deep supervision: the auxiliary head of a coarser decoder level fused with its loss and the junction (ds_head.hip) ----------
+extern "C" int mednet_ds_head_supported(int cin, int ncls, int dtype, int label_dtype, int d, int h, int w, int shift) {
+  if (!is16(dtype) || label_dtype != MEDNET_U8 || d <= 0 || h <= 0 || w <= 0 || shift < 1 || shift > 3) return 0;
+  return ELT_CALL(dtype, ds_head_supported, cin, ncls, dtype, (size_t)d * h * w) ? 1 : 0;
+}
+extern "C" size_t mednet_ds_head_ws_bytes(int n, int d, int h, int w, int cin, int ncls) {
+  return ds_head_ws_bytes(n, (size_t)d * h * w, cin, ncls);
+}
+// (the producing block's GroupNorm-3 sums are not taken by this node: 0 rows, the block runs its stand-alone first pass)
+extern "C" int mednet_ds_head_gn_rows(int d, int h, int w, int cin, int dtype) {
+  (void)d; (void)h; (void)w; (void)cin; (void)dtype;
+  return 0;
+}
+// the checks both directions share; `ok` = the direction's own pointers
+static int ds_head_checks(const char* what, bool ok, const void* z, const void* packed, const void* labels, int label_dtype,
+                          const void* saved, const void* ws, int n, int d, int h, int w, int D, int H, int W, int shift, int cin, int ncls,
+                          int class_kind, int sigmoid, int ignore_index, int z_dtype) {
+  const int rc = class_kind_checks(what, class_kind, sigmoid, ignore_index);
+  if (rc) return rc;
+  MEDNET_REQUIRE(n > 0 && d > 0 && h > 0 && w > 0 && z && packed && labels && saved && ws && ok, MEDNET_E_SHAPE, "%s: bad arguments", what);
+  MEDNET_REQUIRE(shift >= 1 && shift <= 3, MEDNET_E_UNSUPPORTED, "%s: shift %d (1 .. 3)", what, shift);
+  MEDNET_REQUIRE(D > 0 && H > 0 && W > 0 && (D >> shift) == d && (H >> shift) == h && (W >> shift) == w, MEDNET_E_SHAPE,
+                 "%s: level %d x %d x %d is not the label volume %d x %d x %d >> %d", what, d, h, w, D, H, W, shift);
+  MEDNET_REQUIRE(mednet_ds_head_supported(cin, ncls, z_dtype, label_dtype, d, h, w, shift), MEDNET_E_UNSUPPORTED,
+                 "%s: %d -> %d classes, dtype %d, label dtype %d, %d x %d x %d voxels", what, cin, ncls, z_dtype, label_dtype, d, h, w);
+  return 0;
+}
+extern "C" int mednet_ds_head_fwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                                  int64_t label_stride_n, const float* class_weight, float* loss, float* saved, int n, int d, int h, int w,
+                                  int D, int H, int W, int shift, int cin, int ncls, int class_kind, float eps, int sigmoid,
+                                  int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  int rc = ds_head_checks("ds_head_fwd", loss != nullptr, z, packed, labels, label_dtype, saved, ws, n, d, h, w, D, H, W, shift, cin, ncls,
+                          class_kind, sigmoid, ignore_index, z_dtype);
+  if (rc) return rc;
+  const size_t spatial = (size_t)d * h * w;
+  MEDNET_REQUIRE(ws_bytes >= ds_head_ws_bytes(n, spatial, cin, ncls), MEDNET_E_WORKSPACE, "ds_head_fwd: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = ds_head_chunks(spatial);
+  float* partial = (float*)ws;
+  rc = ELT_CALL(z_dtype, launch_ds_head_fwd, z, head_weights_f32(packed, cin, ncls), bias, labels, label_stride_n, class_weight, partial,
+                n, d, h, w, H, W, shift, cin, ncls, class_kind, sigmoid, ignore_index, s);
+  if (rc) return rc;
+  if (class_kind == MEDNET_CLASS_DICE_CE)  // (the Dice rows, behind all of them the CE rows)
+    return launch_dice_ce_finalize(partial, partial + (size_t)n * chunks * ncls * 2, class_weight, loss, saved, ncls, n * chunks, eps, s);
+  if (class_kind == MEDNET_CLASS_CE) return launch_ce_finalize(partial, loss, saved, n * chunks, s);
+  return launch_dice_finalize(partial, class_weight, loss, saved, ncls, n * chunks, eps, s);
+}
+extern "C" int mednet_ds_head_bwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
+                                  int64_t label_stride_n, const float* class_weight, const float* saved, const float* dloss,
+                                  const void* d_pass, void* dz, const void* gn_y, int gn_act, float* gn_partial, float* dw, float* dbias,
+                                  int n, int d, int h, int w, int D, int H, int W, int shift, int cin, int ncls, int class_kind, float eps,
+                                  int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  const int rc = ds_head_checks("ds_head_bwd", dloss && dz && dw, z, packed, labels, label_dtype, saved, ws, n, d, h, w, D, H, W, shift, cin,
+                                ncls, class_kind, sigmoid, ignore_index, z_dtype);
+  if (rc) return rc;
+  (void)gn_act;
+  MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "ds_head_bwd: gn_y and gn_partial go together");
+  MEDNET_REQUIRE(!gn_y || mednet_ds_head_gn_rows(d, h, w, cin, z_dtype) > 0, MEDNET_E_UNSUPPORTED,
+                 "ds_head_bwd: no GroupNorm rows are taken here (mednet_ds_head_gn_rows is 0)");
+  return ELT_CALL(z_dtype, launch_ds_head_bwd, z, head_weights_f32(packed, cin, ncls), bias, labels, label_stride_n, saved, class_weight,
+                  dloss, eps, d_pass, dz, dw, dbias, n, d, h, w, H, W, shift, cin, ncls, class_kind, sigmoid, ignore_index, ws, ws_bytes,
+                  (hipStream_t)stream);
+}
+
 extern "C" int mednet_conv3d_dgrad_gn_rows(int n, int d, int h, int w, int cin, int cout, int algo) {
   if (!tuning_option("conv_fuse_gnb", 1) || !mednet_conv3d_act_supported(n, d, h, w, cout, cin, algo)) return 0;
   // (the kernel reads the layer's Cout channels, writes its Cin; 16-bit storage only, so the split-weight request counts as given)

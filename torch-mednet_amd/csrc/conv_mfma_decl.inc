@@ -97,3 +97,17 @@ int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const 
                         const float* cls_weight, const float* dloss, float eps, void* dz, const void* gn_y, int gn_act,
                         float* gn_partial, float* dw, float* db, int n, size_t spatial, int ncls, int ce, int sigmoid, int ignore,
                         void* ws, size_t ws_bytes, hipStream_t s);
+
+// ds_head.hip: the auxiliary head of a coarser decoder level (cin = 64 .. 256 in steps of 32 -> 1 .. 16 classes) fused with its class
+// loss against the full-resolution uint8 labels (extents . x H x Wf) read at stride 2^shift; level extents d x h x w.  `partial` and `ce`
+// as launch_head_seg_fwd's; the backward adds `d_pass` (nullable) in fp32 before the one rounding of dz.
+bool ds_head_supported(int cin, int ncls, int dtype, size_t spatial);
+int ds_head_chunks(size_t spatial);  // workgroups per sample = rows per sample of every partial
+size_t ds_head_ws_bytes(int n, size_t spatial, int cin, int ncls);
+int launch_ds_head_fwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* cls_weight,
+                       float* partial, int n, int d, int h, int w, int H, int Wf, int shift, int cin, int ncls, int ce, int sigmoid,
+                       int ignore, hipStream_t s);
+int launch_ds_head_bwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* saved,
+                       const float* cls_weight, const float* dloss, float eps, const void* d_pass, void* dz, float* dw, float* db, int n,
+                       int d, int h, int w, int H, int Wf, int shift, int cin, int ncls, int ce, int sigmoid, int ignore, void* ws,
+                       size_t ws_bytes, hipStream_t s);

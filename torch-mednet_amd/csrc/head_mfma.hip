@@ -280,6 +280,9 @@ __device__ __forceinline__ void hlm_dw_db_writeout(const float* scr, int tid, fl
   }
 }
 
+// (ds_head.hip includes this file for everything above and xor32_max below, with MEDNET_HEAD_BLOCKS_ONLY set: the kernels and the
+//  host side of this file are compiled in head_mfma.o alone)
+#ifndef MEDNET_HEAD_BLOCKS_ONLY
 // CE: the class term is nn.CrossEntropyLoss(weight, ignore_index) (landmarks.py:49) instead of Dice: the forward accumulates
 // ce_fwd_kernel's {sum w_y nll, sum w_y} and, for dice_metric (loss.py:51-55), the unweighted, unmasked softmax sums {I, D} into
 // dice_partial; the backward's class gradient is ce_bwd_kernel's closed form (dcls / sum w) w_y (p_k - [k == y]).  Softmax only.
@@ -623,6 +626,7 @@ __global__ __launch_bounds__(256) void head_lm_wfinal_kernel(const float* __rest
     else if (db) db[o - m * 32] = (float)t;
   }
 }
+#endif  // MEDNET_HEAD_BLOCKS_ONLY
 
 // ---- the segmentation head: 32 features -> ncls classes, 5 <= ncls <= 16, fused with DiceLoss (loss.py:114-130) or
 // nn.CrossEntropyLoss (segmentation.py:49) ---------------------------------------------------------------------------------
@@ -641,6 +645,7 @@ __device__ __forceinline__ float xor32_max(float v) {  // max(v(l), v(l ^ 32)) i
   MEDNET_SWAP_PAIR("v_permlane32_swap_b32", a, b);
   return fmaxf(a, b);
 }
+#ifndef MEDNET_HEAD_BLOCKS_ONLY
 
 // Dice + CE (HLM_DICE_CE, softmax, no ignore_index): the forward keeps the Dice accumulators in registers and the CE sums in the idle
 // LDS slot; the backward adds the two closed forms, with w_k dloss / sum w in eight more constants of the lane half.
@@ -1010,5 +1015,6 @@ int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const 
   hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((ncls * 33 + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, ncls, 0, dw, db);
   return check_launch("head_seg_wfinal");
 }
+#endif  // MEDNET_HEAD_BLOCKS_ONLY
 
 }  // namespace mednet

@@ -123,6 +123,12 @@ SIGNATURES = {
     "mednet_head_seg_fwd": (_i, [_vp, _vp, _vp, _vp, _i64] + [_vp] * 4 + [_i, _sz, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
     "mednet_head_seg_bwd": (_i, [_vp, _vp, _vp, _vp, _i64] + [_vp] * 5 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _i, _f, _i, _i, _i,
                                  _vp, _sz, _vp]),
+    "mednet_ds_head_supported": (_i, [_i] * 8),
+    "mednet_ds_head_ws_bytes": (_sz, [_i] * 6),
+    "mednet_ds_head_gn_rows": (_i, [_i] * 5),
+    "mednet_ds_head_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp] + [_i] * 11 + [_f, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_ds_head_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i64] + [_vp] * 6 + [_i, _vp, _vp, _vp] + [_i] * 11 + [_f, _i, _i, _i,
+                                _vp, _sz, _vp]),
     "mednet_head_ce_supported": (_i, [_i] * 4),
     "mednet_head_ce_ws_bytes": (_sz, [_i, _sz, _i, _i]),
     "mednet_head_ce_gn_rows": (_i, [_i, _sz, _i]),

@@ -109,6 +109,8 @@ def exact_products(on: bool = True):
     linear: their gradient is a discontinuous function of every pre-activation, so a 2^-16 perturbation of a convolution
     output flips a few activation masks and moves first-layer gradients by more than the 1e-3 budget (measured: UNet3D 'gcr'
     at 32^3, 1.4e-3).  Such layers therefore ask for exact fp32 products; the smooth default order 'cge' (ELU) does not.
+    A deep-supervised training step asks for them as well (train.SegmentationStep): a coarse level's loss reaches the encoders above
+    it through the max-pooling arg-max alone, and one window that takes its other entry moved a first-block gradient by 1.5e-3.
     A scope only turns the request ON (an inner smooth layer inside a kinked network stays exact)."""
     sc = _scope()
     old = sc.exact

@@ -1580,6 +1580,80 @@ def head_seg(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5, sigmoi
                            want_logits)
 
 
+def ds_head_supported(x: torch.Tensor, cin: int, ncls: int, labels: torch.Tensor, shift: int) -> bool:
+    """Does the deep-supervision node take this level?  x: the level's block output (16-bit storage, channels-last), labels: the
+    FULL-resolution N x D x H x W uint8 labels, of which the level is the nearest-neighbour pick at stride 2^shift."""
+    if not _head_supported(x, labels, mfma=True) or labels.dim() != 4 or getattr(x, "_mednet_actmask", None) is not None:
+        return False
+    d, h, w = x.shape[2:]
+    if tuple(s >> shift for s in labels.shape[1:]) != (d, h, w) or labels.shape[0] != x.shape[0]:
+        return False
+    return bool(L.lib().mednet_ds_head_supported(cin, ncls, L.dt(x), L.U8, d, h, w, shift))
+
+
+class DsHeadFn(Function):
+    """Deep supervision on a coarser decoder level as ONE autograd node at the junction "block output -> {next decoder, auxiliary
+    head}": (x_pass, loss) = (x, criterion(head(x), labels[..., ::2^shift, ::2^shift, ::2^shift])).  The forward is one matrix-core
+    pass that writes loss partials only and reads the full-resolution uint8 labels at a stride (mednet_ds_head_fwd); the backward
+    receives BOTH gradients -- d_pass from the next decoder, dloss -- and in one launch rebuilds the logits, adds W^T dl to d_pass in
+    fp32, rounds once and writes the block's output gradient, plus the head's weight / bias gradients (mednet_ds_head_bwd).  No
+    down-sampled label tensor, logit tensor, logit-gradient tensor or autograd add exists.  As with SkipPool2Fn the caller uses
+    `x_pass` in place of x from here on.  The producing block's GroupNorm-3 sums are taken when mednet_ds_head_gn_rows says so (0 rows
+    in this version: the block runs its stand-alone pass, and nothing is offered that it could decline)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, packed, labels, shift, loss_weight, eps, sigmoid, ignore_index, class_kind):
+        L.require_gpu(x, "ds_head")
+        n, cin, d, h, w = x.shape
+        ncls = weight.shape[0]
+        if labels.dtype != torch.uint8 or labels.dim() != 4:
+            raise RuntimeError(f"ds_head: labels must be a uint8 N x D x H x W volume, not {labels.dtype} (see ds_head_supported)")
+        full = tuple(labels.shape[1:])
+        lab, lab_sn = _label_view(labels, n, full)[:2]  # (byte loads: no alignment rule)
+        wt = _loss_weight(loss_weight, x.device)
+        nsaved, ii = _class_operands(class_kind, ncls, sigmoid, ignore_index, "ds_head")
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        saved = torch.empty((ncls, 2) if nsaved == 2 * ncls else (nsaved,), dtype=torch.float32, device=x.device)
+        lib = L.lib()
+        ws = L.workspace(lib.mednet_ds_head_ws_bytes(n, d, h, w, cin, ncls), x.device)
+        L.check(lib.mednet_ds_head_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), L.U8, lab_sn, L.ptr(wt),
+                                       loss.data_ptr(), saved.data_ptr(), n, d, h, w, *full, shift, cin, ncls, class_kind, eps,
+                                       int(sigmoid), ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "ds_head_fwd")
+        ctx.save_for_backward(x, packed, lab, wt, saved)
+        ctx.meta = (eps, int(sigmoid), ii, lab_sn, ncls, class_kind, full, shift)
+        ctx.params = (weight, bias)
+        rows = lib.mednet_ds_head_gn_rows(d, h, w, cin, L.dt(x))
+        ctx.gn3 = _gn3_hook_of(x, x.dtype) if rows > 0 else None
+        ctx.gn_rows = rows
+        if debug.TRACE is not None:
+            debug.trace("ds_head.fwd", loss, saved)
+        return x.view_as(x), loss
+
+    @staticmethod
+    def backward(ctx, d_pass, dloss):
+        x, packed, lab, wt, saved = ctx.saved_tensors
+        eps, sigmoid, ii, lab_sn, ncls, class_kind, full, shift = ctx.meta
+        if dloss is None:  # (the loss went nowhere: the node is the identity on x)
+            return (d_pass,) + (None,) * 10
+        n, cin, d, h, w = x.shape
+        lib = L.lib()
+        dl = dloss.to(torch.float32).contiguous()
+        if d_pass is not None:
+            d_pass = to_cl(d_pass.to(x.dtype))
+        b = _HeadBackward(ctx, x, ncls, lambda: ctx.gn_rows, lib.mednet_ds_head_ws_bytes(n, d, h, w, cin, ncls))
+        L.check(lib.mednet_ds_head_bwd(x.data_ptr(), packed.data_ptr(), L.ptr(b.bias), lab.data_ptr(), L.U8, lab_sn, L.ptr(wt),
+                                       saved.data_ptr(), dl.data_ptr(), L.ptr(d_pass), b.dx.data_ptr(), b.gn_in, b.act, L.ptr(b.partial),
+                                       b.dw.data_ptr(), L.ptr(b.db), n, d, h, w, *full, shift, cin, ncls, class_kind, eps, sigmoid, ii,
+                                       L.dt(x), b.ws.data_ptr(), b.ws.numel(), L.stream()), "ds_head_bwd")
+        return b.finish("ds_head", 11)
+
+
+def ds_head(x, weight, bias, packed, labels, shift, loss_weight=None, eps=1e-5, sigmoid=False, ignore_index=None, class_loss="DICE"):
+    """-> (x_pass, loss): the deep-supervision loss of level `shift` (class_loss "DICE", "CE" or "DICE_CE" as ops.head_seg) on
+    head(x) against the full-resolution uint8 `labels` picked at stride 2^shift, and x handed through for the next decoder."""
+    return DsHeadFn.apply(x, weight, bias, packed, labels, shift, loss_weight, eps, sigmoid, ignore_index, _class_kind(class_loss))
+
+
 def head_landmark_supported(x: torch.Tensor, cin: int, nh: int, ncls: int, heatmaps: torch.Tensor, labels: torch.Tensor) -> bool:
     return (_head_supported(x, labels, heatmaps, mfma=True)
             and bool(L.lib().mednet_head_landmark_supported(cin, nh, ncls, L.dt(x), x[0, 0].numel())))

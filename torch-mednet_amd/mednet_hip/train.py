@@ -621,6 +621,20 @@ def _class_criterion(loss, w):
     return HL.DiceLoss(weight=w) if loss == "DICE" else HL.CrossEntropyLoss(weight=w)
 
 
+def deep_supervision_weights(k, ds_weights=None):
+    """The level weights w_0 .. w_k of a deep-supervision loss: 2^-s / sum_t 2^-t by default, or `ds_weights` (k + 1 non-negative
+    numbers, used as given)."""
+    if ds_weights is None:
+        total = sum(2.0 ** -t for t in range(k + 1))
+        return [2.0 ** -s / total for s in range(k + 1)]
+    ws = [float(v) for v in ds_weights]
+    if len(ws) != k + 1:
+        raise ValueError(f"ds_weights: {k + 1} weights expected (levels 0 .. {k}), got {len(ws)}")
+    if any(not v >= 0.0 for v in ws):
+        raise ValueError(f"ds_weights must be non-negative, got {ws}")
+    return ws
+
+
 class SegmentationStep(_GraphedStep):
     """One data-parallel training step of SegmentationNet (segmentation.py:58-65) on the MI355X path.
 
@@ -633,11 +647,15 @@ class SegmentationStep(_GraphedStep):
     scalar, `skipped_steps()` synchronises.  With the defaults the step launches exactly what it always launched."""
 
     def __init__(self, model, loss_weight=None, lr=1e-3, loss="DICE", world_size=1, graph=None, optimizer="adam", optimizer_args=None,
-                 clip_grad_norm=None, skip_nonfinite=False):
+                 clip_grad_norm=None, skip_nonfinite=False, ds_weights=None):
         self.model = model
         dev = next(model.parameters()).device
         w = None if loss_weight is None else torch.tensor(loss_weight, dtype=torch.float32, device=dev)
         self.loss = _class_criterion(loss, w).to(dev)
+        # deep supervision (a model built with deep_supervision=k): loss = sum_s w_s L_s over the levels 0 .. k, w_s = 2^-s / sum_t 2^-t
+        # unless `ds_weights` gives them; scale_losses = the detached, unweighted L_0 .. L_k of the last step (device scalars)
+        self.ds_weights = deep_supervision_weights(len(getattr(model, "ds_heads", ())), ds_weights)
+        self.scale_losses = []
         self.flat = FlatParams(model)
         self._init_optimizer(optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
         self.repack = BatchedRepack(model)
@@ -687,9 +705,57 @@ class SegmentationStep(_GraphedStep):
             outputs = m(inputs)
         return outputs, self.loss(outputs, label_u8 if compound else label_u8.long())
 
+    def _ds_level(self, s, feats, label_u8, inputs, aux):
+        """Level s >= 1 of deep supervision, called from the model's decoder loop on that level's block output: L_s = the step's
+        criterion on ds_heads[s-1](feats) against the labels picked at stride 2^s -> aux[s]; returns the tensor that goes on to the
+        next decoder.  Fused (ops.ds_head: one node at the junction, the full-resolution uint8 labels read where they lie) when
+        ops.ds_head_supported says yes; otherwise -- fp32 storage, other label types, the ds_head_fuse knob at 0, hooked modules -- the
+        composed form: the head, then the existing loss on a contiguous strided label slice."""
+        head = self.model.ds_heads[s - 1]
+        crit = self.loss
+        dice, compound = isinstance(crit, HL.DiceLoss), isinstance(crit, HL.DiceCELoss)
+        if (inputs.is_cuda and label_u8.dtype == torch.uint8 and not _call_is_hooked(self.model, head)
+                and (compound or not dice or not crit.skip_last_target)
+                and ops.ds_head_supported(feats, head.in_channels, head.out_channels, label_u8, s)):
+            if compound:
+                feats, aux[s] = ops.ds_head(feats, head.weight, head.bias, head._packed(), label_u8, s, crit.weight, crit.epsilon,
+                                            class_loss="DICE_CE")
+            elif dice:
+                feats, aux[s] = ops.ds_head(feats, head.weight, head.bias, head._packed(), label_u8, s, crit.weight, crit.epsilon,
+                                            crit.sigmoid_normalization, crit.ignore_index, "DICE")
+            else:
+                feats, aux[s] = ops.ds_head(feats, head.weight, head.bias, head._packed(), label_u8, s, crit.weight,
+                                            ignore_index=crit.ignore_index, class_loss="CE")
+            return feats
+        d, h, w = feats.shape[2:]
+        lab = label_u8[:, :d << s:1 << s, :h << s:1 << s, :w << s:1 << s].contiguous()
+        aux[s] = crit(head(feats), lab if compound else lab.long())
+        return feats
+
     def _fwd_bwd(self, batch):
         inputs = batch["data"].float()
-        _, loss = self._head_loss(inputs, batch["label"][:, -1, ...])
+        label_u8 = batch["label"][:, -1, ...]
+        k = len(self.ds_weights) - 1
+        if k == 0:
+            _, loss = self._head_loss(inputs, label_u8)
+            self.scale_losses = [loss.detach()]
+        else:
+            from . import config
+            aux = {}
+            self.model._ds_tap = lambda s, feats: self._ds_level(s, feats, label_u8, inputs, aux)
+            try:
+                # fp32 storage asks for exact fp32 products under deep supervision (config.exact_products): a coarse level's loss
+                # reaches the encoders above it through the max-pooling arg-max alone, one window entry in eight, and a window
+                # whose two largest entries lie within the split-bf16 contraction's 2^-16 takes the other one; a single such
+                # window of 2.6e5 moves the first block's gradients by sqrt(2 / 2.6e5) = 2.8e-3.  Nothing changes in 16-bit storage.
+                with config.exact_products(not config.is_half_mode()):
+                    _, aux[0] = self._head_loss(inputs, label_u8)
+            finally:
+                del self.model._ds_tap
+            loss = aux[0] * self.ds_weights[0]
+            for s in range(1, k + 1):
+                loss = loss + aux[s] * self.ds_weights[s]
+            self.scale_losses = [aux[s].detach() for s in range(k + 1)]
         (loss if self.scaler is None else self.scaler.scale_loss(loss)).backward()
         finish_backward()
         return (loss.detach(),)

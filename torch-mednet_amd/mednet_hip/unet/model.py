@@ -79,7 +79,7 @@ class _CheckpointCompat:
 
 
 class _UNetCore(*((_Base,) if _Base is not nn.Module else (_CheckpointCompat, nn.Module))):
-    def _assemble(self, in_channels, out_channels, f_maps, order, num_groups, block, default_levels):
+    def _assemble(self, in_channels, out_channels, f_maps, order, num_groups, block, default_levels, deep_supervision=0):
         if isinstance(f_maps, int):
             f_maps = create_feature_maps(f_maps, number_of_fmaps=default_levels)
         f_maps = list(f_maps)
@@ -92,6 +92,33 @@ class _UNetCore(*((_Base,) if _Base is not nn.Module else (_CheckpointCompat, nn
             Decoder(rev[i] + rev[i + 1] if concat else rev[i], rev[i + 1], basic_module=block, conv_layer_order=order,
                     num_groups=num_groups) for i in range(len(rev) - 1))
         self.final_conv = hnn.Conv3d(f_maps[0], out_channels, 1, planar_output=True)
+        # deep supervision (the `deep_supervision=k` keyword): an auxiliary 1x1x1 head on each of the k decoder outputs above the
+        # finest, level s having f_maps[s] features at 1 / 2^s of the resolution.  Training only: forward() never runs them, and with
+        # k = 0 the module tree and the state_dict keys are the reference's.
+        k = int(deep_supervision)
+        if not 0 <= k <= max(0, len(f_maps) - 2):
+            raise ValueError(f"deep_supervision must be in 0 .. {max(0, len(f_maps) - 2)} for {len(f_maps)} feature levels, not {deep_supervision}")
+        if k > 0:
+            self.ds_heads = nn.ModuleList(hnn.Conv3d(f_maps[s], out_channels, 1, planar_output=True) for s in range(1, k + 1))
+
+    @property
+    def deep_supervision(self) -> int:
+        return len(self.ds_heads) if hasattr(self, "ds_heads") else 0
+
+    def forward_pyramid(self, x):
+        """-> [features_0, .., features_k]: the decoder outputs the heads sit on, finest first (features_0 is forward_features(x)),
+        channels-last."""
+        kinked = any(getattr(m, "_kinked", False) for m in self.modules())
+        taps = {}
+        with config.exact_products(kinked):
+            taps[0] = self._features(x, tap=lambda s, f: taps.setdefault(s, f))
+        return [taps[s] for s in range(self.deep_supervision + 1)]
+
+    def forward_deep(self, x):
+        """-> [logits_0, .., logits_k], fp32 planar, finest first: final_conv and the auxiliary heads on forward_pyramid(x) -- the
+        composed form of deep supervision (train.SegmentationStep runs the fused one)."""
+        feats = self.forward_pyramid(x)
+        return [self.final_conv(feats[0])] + [head(f) for head, f in zip(getattr(self, "ds_heads", ()), feats[1:])]
 
     def forward(self, x):
         # ReLU / LeakyReLU anywhere in the order string: the whole network asks for exact fp32 products in the fp32 storage
@@ -113,7 +140,12 @@ class _UNetCore(*((_Base,) if _Base is not nn.Module else (_CheckpointCompat, nn
             x = self.final_activation(x)
         return x
 
-    def _features(self, x):
+    def _features(self, x, tap=None):
+        """`tap(s, features_s) -> features_s` (deep supervision; also read from `self._ds_tap`, which train.SegmentationStep sets for
+        the duration of its forward) is called on the output of the decoder of every supervised level s >= 1, coarsest first, and
+        what it returns goes on to the next decoder.  Without a tap, and always with deep_supervision = 0, the launches are unchanged."""
+        tap = tap if tap is not None else getattr(self, "_ds_tap", None)
+        k = self.deep_supervision if tap is not None else 0
         skips = []
         for i, enc in enumerate(self.encoders):
             # the next level pools this level's output (model.py:194-199): tell the block, it writes the pooled tensor as well
@@ -128,8 +160,11 @@ class _UNetCore(*((_Base,) if _Base is not nn.Module else (_CheckpointCompat, nn
                 # hook) may have handed it to an auxiliary / deep-supervision loss, and then its gradient must be materialised
                 skips[0], x = enc(x, with_skip=True, pool_next=pool_next, sole_consumer=not _has_forward_hooks(self.encoders[i - 1]))
             skips.insert(0, x)
-        for dec, skip in zip(self.decoders, skips[1:]):
+        top = len(self.decoders) - 1  # decoder i writes level top - i
+        for i, (dec, skip) in enumerate(zip(self.decoders, skips[1:])):
             x = dec(skip, x)
+            if 1 <= top - i <= k:
+                x = tap(top - i, x)
         return x
 
 
@@ -145,7 +180,8 @@ class UNet3D(_UNetCore):
     def __init__(self, in_channels, out_channels, final_sigmoid, f_maps=64, layer_order="gcr", num_groups=8, **kwargs):
         super().__init__()
         self.testing = kwargs.get("testing", False)
-        self._assemble(in_channels, out_channels, f_maps, layer_order, num_groups, DoubleConv, default_levels=4)
+        self._assemble(in_channels, out_channels, f_maps, layer_order, num_groups, DoubleConv, default_levels=4,
+                       deep_supervision=kwargs.get("deep_supervision", 0))
         self.final_activation = nn.Sigmoid() if final_sigmoid else _Softmax1()
 
 
@@ -155,7 +191,7 @@ class ResidualUNet3D(_UNetCore):
         super().__init__()
         self.testing = kwargs.get("testing", False)
         self._assemble(in_channels, out_channels, f_maps, conv_layer_order, num_groups, ExtResNetBlock,
-                       default_levels=5)
+                       default_levels=5, deep_supervision=kwargs.get("deep_supervision", 0))
         if skip_final_activation:
             self.final_activation = None
         else:
