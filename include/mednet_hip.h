@@ -776,6 +776,45 @@ int mednet_sample_panels(const float* logits, int64_t stride_c, int num_heatmaps
                          uint8_t* label_mip, float* input_mip, float* heatmap_mip, float* output_heatmap_mip, int d, int h, int w,
                          int axis, int image_mode, void* ws, size_t ws_bytes, mednet_stream stream);
 
+/* ---- case-level evaluation of a whole-volume prediction (additive to ABI 3; the reference has no evaluation code) -----------------
+ * Volumes are dense d x h x w, every extent in 1 .. 2048 (else MEDNET_E_SHAPE).  No float atomics: partial rows per workgroup in the
+ * caller's workspace, then a finalize launch; every grid is a function of the extents alone, so the same inputs give the same bits.
+ * Every refusal -- a null pointer, an extent outside 1 .. 2048, ncls outside 1 .. 32, a spacing that is not finite and positive, a
+ * negative or NaN tolerance, an undersized workspace -- returns its code before anything is launched.
+ *
+ * mednet_confusion: pred, label uint8 (any address); counts int64 [ncls * ncls + 1] (8-byte aligned):
+ *   counts[l * ncls + p]  voxels with label l predicted as p
+ *   counts[ncls * ncls]   voxels left out because label or prediction is >= ncls
+ * A voxel whose label equals ignore_index is counted nowhere (MEDNET_NO_IGNORE: none).  ncls > 32 is MEDNET_E_UNSUPPORTED.  Workspace:
+ * one row of ncls * ncls + 1 uint32 per workgroup, ceil(voxels / 4096) workgroups up to 2048 (4-byte aligned). */
+size_t mednet_confusion_ws_bytes(int d, int h, int w, int ncls);
+int mednet_confusion(const uint8_t* pred, const uint8_t* label, int d, int h, int w, int ncls, int ignore_index, int64_t* counts,
+                     void* ws, size_t ws_bytes, mednet_stream stream);
+/* out[v] = 1 where vol[v] == cls and one of the six face neighbours is != cls or lies outside the volume, else 0: mask & ~erosion
+ * with the 6-connected structuring element and background outside (scipy.ndimage.binary_erosion's default border).  vol2 / out2: a
+ * second volume of the same extents in the same launch (prediction and label together), or both NULL.  cls in 0 .. 255. */
+int mednet_surface_mask(const uint8_t* vol, uint8_t* out, const uint8_t* vol2, uint8_t* out2, int cls, int d, int h, int w,
+                        mednet_stream stream);
+/* Exact squared Euclidean distance transform: seed uint8 (nonzero = seed), out fp32,
+ *   out[v] = min over seeds s of  sum over the axes a of (spacing_a * (v_a - s_a))^2        (+inf everywhere without a seed)
+ * Separable, three launches (x, y, z) in place on `out`, no workspace.  The arithmetic, fixed so that a test can be exact:
+ *   T_a(k)    = fl32((spacing_a * k)^2)           formed in fp64 from the fp32 spacing, k an integer index difference: ONE rounding
+ *   a pass    : out[i] = min over ALL j of the line of  fl32(g[j] + T_a(i - j)),  g = 0 / +inf from the seeds in the x pass, the
+ *               previous pass's output after it; nothing is reassociated across axes
+ * With unit or dyadic spacing every operand is a multiple of a power of two below 2^24 (3 * 2047^2 < 2^24) and the result is exact.
+ * In general every term is non-negative and the x term sees three roundings, the y term three, the z term two: the result is within
+ * (1 + 2^-24)^3 - 1 of the real minimum.  A workgroup stages a bundle of 64 / 32 / 16 neighbouring lines in LDS (extent up to 240 /
+ * 464 / 2048; at most 152 KiB), so the y and z passes read and write whole runs of x. */
+int mednet_edt_sq(const uint8_t* seed, float* out, int d, int h, int w, float sz, float sy, float sx, mednet_stream stream);
+/* Over the voxels with surf != 0 (surf uint8, d2 fp32, as mednet_surface_mask and mednet_edt_sq write them):
+ *   counts[0] = their number;  counts[1] = those with d2 <= tol_sq                                               (int64, 8-byte aligned)
+ *   *max_d2   = the largest d2, -inf for an empty surface                                                        (fp32)
+ *   *sum_sqrt = sum of the correctly rounded fp32 roots sqrtf(d2), added in fp64 from the first add on, fixed order   (fp64)
+ * A +inf in d2 reaches max and sum and is not within any tolerance.  Workspace: 28 bytes per workgroup (8-byte aligned). */
+size_t mednet_surface_stats_ws_bytes(int d, int h, int w);
+int mednet_surface_stats(const uint8_t* surf, const float* d2, int d, int h, int w, float tol_sq, int64_t* counts, float* max_d2,
+                         double* sum_sqrt, void* ws, size_t ws_bytes, mednet_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

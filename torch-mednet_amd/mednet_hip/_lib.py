@@ -174,6 +174,12 @@ SIGNATURES = {
     "mednet_warp_patches": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp] + [_i] * 12 + [_f, _vp]),
     "mednet_sample_panels_ws_bytes": (_sz, [_i] * 5),
     "mednet_sample_panels": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _i, _vp] + [_vp] * 5 + [_i] * 5 + [_vp, _sz, _vp]),
+    "mednet_confusion_ws_bytes": (_sz, [_i] * 4),
+    "mednet_confusion": (_i, [_vp, _vp] + [_i] * 5 + [_vp, _vp, _sz, _vp]),
+    "mednet_surface_mask": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
+    "mednet_edt_sq": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _vp]),
+    "mednet_surface_stats_ws_bytes": (_sz, [_i] * 3),
+    "mednet_surface_stats": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,272 @@
+"""Case-level evaluation of a whole-volume prediction on the device (csrc/metrics.hip): what a segmentation
+model is judged by after inference, without the volumes leaving HBM.
+
+    m = evaluate_case(pred, label, num_classes, spacing=(3.0, 0.7, 0.7))      # uint8 D x H x W each, e.g. GridPredictor(...)(vol)[-1]
+    m.to_host()                                                                # one small table: the only transfer
+
+Overlap, per class, from the confusion counts in fp64: Dice 2 TP / (|P| + |G|), IoU TP / (|P| + |G| - TP), sensitivity TP / |G|,
+precision TP / |P|; a zero denominator gives NaN (a class absent from both volumes has Dice NaN, as nnU-Net reports it).
+
+Surface distances, per class.  The surface S of a mask is `mask & ~erosion(mask)` with the 6-connected structuring element and
+background outside the volume; d(a, S) is the Euclidean distance, in units of `spacing`, from voxel a to the nearest voxel of S.
+With S_p, S_g the surfaces of the class in prediction and label, n_p, n_g their sizes:
+
+    hd            = max(max_{p in S_p} d(p, S_g), max_{g in S_g} d(g, S_p))                   (MONAI compute_hausdorff_distance)
+    hd_percentile = max of the two directed numpy.percentile(d, q) values, linear interpolation  (.. with percentile=q)
+    assd          = (sum_p d(p, S_g) + sum_g d(g, S_p)) / (n_p + n_g)       (MONAI compute_average_surface_distance, symmetric)
+    nsd           = (#{p : d(p, S_g) <= tol} + #{g : d(g, S_p) <= tol}) / (n_p + n_g)           (DeepMind's surface Dice)
+
+If either surface is empty all four are NaN and n_pred / n_label say why.  Distances come from the exact squared Euclidean distance
+transform `edt_squared`, two per class (one per direction, one after the other in ONE fp32 volume of scratch).  Neither MONAI nor
+scipy is needed."""
+from __future__ import annotations
+
+import dataclasses
+import math
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+MAX_CLASSES = 32
+_PAD_LABEL, _PAD_IGNORE = 255, 254     # uint8 codes of a converted label outside 0 .. 255 / of an ignore_index outside 0 .. 255
+
+
+def _volume_u8(t: torch.Tensor, who: str) -> torch.Tensor:
+    """uint8 D x H x W, dense: a view such as the last channel of a uint8 C x D x H x W volume is read where it lies; another layout
+    is copied once."""
+    L.require_gpu(t, who)
+    if t.dim() != 3:
+        raise ValueError(f"{who}: a D x H x W volume expected, got shape {tuple(t.shape)}")
+    if t.dtype == torch.bool:
+        t = t.to(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{who}: a uint8 volume expected, got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _label_u8(label: torch.Tensor, ignore_index, who: str):
+    """-> (uint8 volume, the ignore code for the kernel).  A label of another integer type is converted: values outside 0 .. 255
+    become 255 (out of range for every class count the kernel takes), an ignore_index outside 0 .. 255 becomes 254."""
+    L.require_gpu(label, who)
+    ign = L.NO_IGNORE if ignore_index is None else int(ignore_index)
+    if label.dtype in (torch.uint8, torch.bool):
+        return _volume_u8(label, who), (ign if 0 <= ign <= 255 else L.NO_IGNORE)
+    lab = label.long()
+    out = torch.where((lab < 0) | (lab > 255), torch.full_like(lab, _PAD_LABEL), lab)
+    if ignore_index is not None and not 0 <= ign <= 255:
+        out = torch.where(lab == ign, torch.full_like(lab, _PAD_IGNORE), out)
+        ign = _PAD_IGNORE
+    return _volume_u8(out.to(torch.uint8), who), ign
+
+
+def _same_shape(a, b, who):
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"{who}: prediction {tuple(a.shape)} on {a.device} and label {tuple(b.shape)} on {b.device} differ")
+
+
+def _spacing(spacing):
+    sz, sy, sx = (float(np.float32(s)) for s in spacing)
+    return sz, sy, sx
+
+
+# ------------------------------------------------------------------------------------------------------- overlap
+def confusion(pred: torch.Tensor, label: torch.Tensor, num_classes: int, ignore_index=None):
+    """-> (int64 [C, C] with entry [l, p] = voxels of label l predicted as p, int64 scalar = voxels left out because label or
+    prediction is >= C), both on the device.  Voxels whose label equals ignore_index are counted nowhere."""
+    p = _volume_u8(pred, "confusion")
+    lab, ign = _label_u8(label, ignore_index, "confusion")
+    _same_shape(p, lab, "confusion")
+    c = int(num_classes)
+    d, h, w = p.shape
+    out = torch.empty((max(c, 0) * max(c, 0) + 1,), dtype=torch.int64, device=p.device)
+    ws = L.workspace(L.lib().mednet_confusion_ws_bytes(d, h, w, c), p.device)
+    L.check(L.lib().mednet_confusion(p.data_ptr(), lab.data_ptr(), d, h, w, c, ign, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     L.stream()), "confusion")
+    return out[:c * c].view(c, c), out[c * c]
+
+
+def overlap(cm: torch.Tensor):
+    """cm int64 [C, C] (rows: label) -> dice, iou, sensitivity, precision, volume_pred, volume_label, each [C] on cm's device; the
+    ratios in fp64 from the integer counts, NaN where the denominator is 0."""
+    tp = cm.diagonal()
+    vol_label, vol_pred = cm.sum(1), cm.sum(0)
+    tpd, vl, vp = tp.double(), vol_label.double(), vol_pred.double()
+    return 2.0 * tpd / (vp + vl), tpd / (vp + vl - tpd), tpd / vl, tpd / vp, vol_pred, vol_label
+
+
+# ------------------------------------------------------------------------------------------------------- building blocks
+def _surface_masks(a: torch.Tensor, b, cls: int):
+    d, h, w = a.shape
+    out_a = torch.empty_like(a)
+    out_b = None if b is None else torch.empty_like(b)
+    L.check(L.lib().mednet_surface_mask(a.data_ptr(), out_a.data_ptr(), L.ptr(b), L.ptr(out_b), int(cls), d, h, w, L.stream()),
+            "surface_mask")
+    return out_a, out_b
+
+
+def surface_mask(volume: torch.Tensor, cls: int) -> torch.Tensor:
+    """uint8 D x H x W: 1 where volume == cls and a face neighbour differs or lies outside the volume."""
+    return _surface_masks(_volume_u8(volume, "surface_mask"), None, cls)[0]
+
+
+def edt_squared(seed: torch.Tensor, spacing=(1, 1, 1), out=None) -> torch.Tensor:
+    """fp32 D x H x W: the squared Euclidean distance, in units of `spacing` = (z, y, x), to the nearest voxel with seed != 0; +inf
+    everywhere without a seed.  Exact for unit and dyadic spacing (include/mednet_hip.h gives the arithmetic).  out: an fp32 volume
+    to write into."""
+    s = _volume_u8(seed, "edt_squared")
+    d, h, w = s.shape
+    if out is None:
+        out = torch.empty((d, h, w), dtype=torch.float32, device=s.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (d, h, w) or not out.is_contiguous() or out.device != s.device:
+        raise ValueError("edt_squared: out must be a contiguous fp32 volume of the seed's shape on its device")
+    sz, sy, sx = _spacing(spacing)
+    L.check(L.lib().mednet_edt_sq(s.data_ptr(), out.data_ptr(), d, h, w, sz, sy, sx, L.stream()), "edt_squared")
+    return out
+
+
+def surface_stats(surf: torch.Tensor, d2: torch.Tensor, tol_sq: float, counts=None, max_d2=None, sum_sqrt=None):
+    """Over the voxels with surf != 0 -> (int64 [2] = {their number, those with d2 <= tol_sq}, fp32 scalar max d2 (-inf for none),
+    fp64 scalar sum of sqrt(d2)), written into the given tensors where given."""
+    s = _volume_u8(surf, "surface_stats")
+    d, h, w = s.shape
+    if d2.dtype != torch.float32 or tuple(d2.shape) != (d, h, w) or not d2.is_contiguous():
+        raise ValueError("surface_stats: d2 must be a contiguous fp32 volume of the mask's shape")
+    counts = torch.empty((2,), dtype=torch.int64, device=s.device) if counts is None else counts
+    max_d2 = torch.empty((), dtype=torch.float32, device=s.device) if max_d2 is None else max_d2
+    sum_sqrt = torch.empty((), dtype=torch.float64, device=s.device) if sum_sqrt is None else sum_sqrt
+    ws = L.workspace(L.lib().mednet_surface_stats_ws_bytes(d, h, w), s.device)
+    L.check(L.lib().mednet_surface_stats(s.data_ptr(), d2.data_ptr(), d, h, w, float(tol_sq), counts.data_ptr(), max_d2.data_ptr(),
+                                         sum_sqrt.data_ptr(), ws.data_ptr(), ws.numel(), L.stream()), "surface_stats")
+    return counts, max_d2, sum_sqrt
+
+
+def _root32(x: torch.Tensor) -> torch.Tensor:
+    """The correctly rounded fp32 square root (an fp64 root rounded to fp32 is that: 53 >= 2 * 24 + 2 bits)."""
+    return torch.sqrt(x.double()).float()
+
+
+def _directed_percentile(d2: torch.Tensor, surf: torch.Tensor, q: float) -> torch.Tensor:
+    """numpy.percentile(sqrt(d2[surf]), q) with linear interpolation, fp32 on the device: the two order statistics are selected on
+    d2 (exact), rooted, and interpolated as a + (b - a) * t.  NaN for an empty surface."""
+    v = d2[surf.bool()]
+    n = v.numel()
+    if n == 0:
+        return torch.full((), float("nan"), dtype=torch.float32, device=d2.device)
+    v = torch.sort(v).values
+    pos = q / 100.0 * (n - 1)
+    lo = min(int(math.floor(pos)), n - 1)
+    hi = min(lo + 1, n - 1)
+    a, b = _root32(v[lo]), _root32(v[hi])
+    t = pos - lo
+    return a if t == 0.0 else a + (b - a) * t
+
+
+# ------------------------------------------------------------------------------------------------------- surface distances
+def surface_distances(pred: torch.Tensor, label: torch.Tensor, classes, spacing=(1, 1, 1), percentile=95.0, tolerance=1.0):
+    """-> hd (fp32), hd_percentile (fp32), assd (fp64), nsd (fp64), n_pred, n_label (int64), each [len(classes)] on the device; the
+    module docstring gives the definitions.  tolerance is in units of `spacing`; a voxel counts as within it when its squared
+    distance is <= fp32(tolerance)^2."""
+    p = _volume_u8(pred, "surface_distances")
+    g, _ = _label_u8(label, None, "surface_distances")
+    _same_shape(p, g, "surface_distances")
+    if not (float(tolerance) >= 0.0):
+        raise ValueError(f"surface_distances: tolerance {tolerance} is negative or NaN")
+    if not 0.0 <= float(percentile) <= 100.0:
+        raise ValueError(f"surface_distances: percentile {percentile} outside [0, 100]")
+    classes = [int(c) for c in classes]
+    k, dev = len(classes), p.device
+    tol_sq = float(np.float32(tolerance) * np.float32(tolerance))
+    counts = torch.empty((max(k, 1), 2, 2), dtype=torch.int64, device=dev)       # [class][direction][n, within]
+    mx = torch.empty((max(k, 1), 2), dtype=torch.float32, device=dev)
+    sm = torch.empty((max(k, 1), 2), dtype=torch.float64, device=dev)
+    pct = []
+    d2 = torch.empty(tuple(p.shape), dtype=torch.float32, device=dev)            # the one volume of scratch, both directions
+    for i, cls in enumerate(classes):
+        sp, sg = _surface_masks(p, g, cls)
+        row = []
+        for j, (seed, surf) in enumerate(((sg, sp), (sp, sg))):                  # prediction -> label surface, then label -> prediction
+            edt_squared(seed, spacing, out=d2)
+            surface_stats(surf, d2, tol_sq, counts[i, j], mx[i, j], sm[i, j])
+            row.append(_directed_percentile(d2, surf, float(percentile)))
+        pct.append(torch.maximum(row[0], row[1]))
+    counts, mx, sm = counts[:k], mx[:k], sm[:k]
+    n_pred, n_label = counts[:, 0, 0], counts[:, 1, 0]
+    valid = (n_pred > 0) & (n_label > 0)
+    total = (n_pred + n_label).double()
+    nan32 = torch.full((k,), float("nan"), dtype=torch.float32, device=dev)
+    nan64 = nan32.double()
+    hd = torch.where(valid, _root32(torch.maximum(mx[:, 0], mx[:, 1])), nan32)
+    hdp = torch.where(valid, torch.stack(pct) if k else nan32, nan32)
+    assd = torch.where(valid, (sm[:, 0] + sm[:, 1]) / total, nan64)
+    nsd = torch.where(valid, (counts[:, 0, 1] + counts[:, 1, 1]).double() / total, nan64)
+    return hd, hdp, assd, nsd, n_pred, n_label
+
+
+_PER_CLASS = ("dice", "iou", "sensitivity", "precision", "volume_pred", "volume_label")
+_PER_SURFACE = ("hd", "hd_percentile", "assd", "nsd", "n_pred", "n_label")
+_COUNTS = ("volume_pred", "volume_label", "n_pred", "n_label")
+
+
+@dataclasses.dataclass
+class CaseMetrics:
+    """Everything evaluate_case measured, on the device.  confusion [C, C] (rows: label) and out_of_range; the overlap fields [C];
+    the surface fields [len(classes)], in the order of `classes`."""
+    confusion: torch.Tensor
+    out_of_range: torch.Tensor
+    dice: torch.Tensor
+    iou: torch.Tensor
+    sensitivity: torch.Tensor
+    precision: torch.Tensor
+    volume_pred: torch.Tensor
+    volume_label: torch.Tensor
+    classes: tuple
+    hd: torch.Tensor
+    hd_percentile: torch.Tensor
+    assd: torch.Tensor
+    nsd: torch.Tensor
+    n_pred: torch.Tensor
+    n_label: torch.Tensor
+    spacing: tuple
+    percentile: float
+    tolerance: float
+
+    def to_host(self) -> dict:
+        """One transfer: every field packed into one fp64 vector (the counts are exact in it, the fp32 fields widen exactly) -> a
+        dict of numpy arrays, counts as int64, plus `classes`, `spacing`, `percentile`, `tolerance`."""
+        names = ("confusion", "out_of_range") + _PER_CLASS + _PER_SURFACE
+        parts = [getattr(self, n).reshape(-1).double() for n in names]
+        flat = torch.cat(parts).cpu().numpy()
+        out, at = {}, 0
+        for n, part in zip(names, parts):
+            a = flat[at:at + part.numel()]
+            at += part.numel()
+            out[n] = a.astype(np.int64) if n in _COUNTS or n in ("confusion", "out_of_range") else a.copy()
+        c = self.confusion.shape[0]
+        out["confusion"] = out["confusion"].reshape(c, c)
+        out["out_of_range"] = int(out["out_of_range"][0])
+        out.update(classes=tuple(self.classes), spacing=tuple(self.spacing), percentile=self.percentile, tolerance=self.tolerance)
+        return out
+
+
+def evaluate_case(pred: torch.Tensor, label: torch.Tensor, num_classes: int, spacing=(1, 1, 1), classes=None, percentile=95.0,
+                  tolerance=1.0, ignore_index=None) -> CaseMetrics:
+    """Overlap for every class and surface distances for `classes` (default 1 .. C - 1) of one case.  pred, label: D x H x W on the
+    device (uint8; a label of another integer type is converted).  ignore_index applies to the confusion counts.  Synchronises with
+    the host (the percentile selects the surface voxels); not for a captured step."""
+    cm, oor = confusion(pred, label, num_classes, ignore_index)
+    dice, iou, sens, prec, vp, vl = overlap(cm)
+    classes = tuple(range(1, int(num_classes))) if classes is None else tuple(int(c) for c in classes)
+    hd, hdp, assd, nsd, n_pred, n_label = surface_distances(pred, label, classes, spacing, percentile, tolerance)
+    return CaseMetrics(cm, oor, dice, iou, sens, prec, vp, vl, classes, hd, hdp, assd, nsd, n_pred, n_label,
+                       tuple(float(s) for s in spacing), float(percentile), float(tolerance))
+
+
+def landmark_errors(positions: torch.Tensor, targets, spacing=(1, 1, 1)) -> torch.Tensor:
+    """Euclidean error per landmark in units of `spacing`: positions H x 3 as (z, y, x) voxel indices (what peaks() returns),
+    targets likewise (a tensor or anything torch.as_tensor takes) -> fp64 [H] on positions' device."""
+    pos = positions.double()
+    tgt = torch.as_tensor(targets, dtype=torch.float64, device=pos.device)
+    sp = torch.as_tensor([float(s) for s in spacing], dtype=torch.float64, device=pos.device)
+    return torch.linalg.vector_norm((pos - tgt) * sp, dim=-1)

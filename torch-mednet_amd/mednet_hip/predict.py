@@ -187,6 +187,13 @@ class BlendedPrediction:
         """(positions H x 3 int64 as (z, y, x), values H fp32) of the blended heat maps."""
         return heatmap_peaks(self.heatmaps())
 
+    def evaluate(self, label, spacing=(1, 1, 1), **kw):
+        """mednet_hip.metrics.evaluate_case on the class channel of result() against `label` (D x H x W on the device): overlap and
+        surface distances per class as a CaseMetrics; num_classes defaults to the number of class channels."""
+        from .metrics import evaluate_case
+        num_classes = kw.pop("num_classes", self.acc.shape[0] - self.num_heatmaps)
+        return evaluate_case(self.result()[-1], label, num_classes, spacing=spacing, **kw)
+
 
 class GridPredictor:
     def __init__(self, model, patch_size, patch_overlap, num_heatmaps=0, pad_mode="constant", batch_size=4,
