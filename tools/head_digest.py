@@ -17,8 +17,12 @@ Cases.  landmark (bf16, fp16): (nh, ncls, regression) in {(16, 2, L2), (5, 3, L1
 sigmoid / CE x class and regression weights on / off, one ignore_index case per class loss; head_landmark_eval on the same inputs is
 part of every softmax case without a Dice mask.  seg (bf16, fp16): C in {5, 8, 9, 16} x the three losses x want_logits x weights,
 one ignore_index case per loss, labels at an odd byte offset once per loss.  valu (fp32, bf16, fp16): head_dice / head_ce x cin in
-{16, 32, 64} x C in {1, 4} x uint8 / int64 labels.
-Usage: python tools/head_digest.py [heads, default landmark,seg,valu] > digest.jsonl"""
+{16, 32, 64} x C in {1, 4} x uint8 / int64 labels.  ds (bf16, fp16; the deep-supervision node ops.ds_head, which has its own runs:
+n = 2, with and without the next decoder's gradient d_pass, tensors loss, dx, dw, db): (level, shift, cin, C) as
+tests/test_gpu_ds_head.py's CASES -- one run of 128 voxels, a ragged run, five workgroups, 2 / 4 / 8 tiles, C in {1, 2, 4, 5, 8, 16} --
+and C = 9 at (6, 6, 6), shift 1, cin 128, x Dice softmax / Dice sigmoid / CE / Dice + CE x weights, one ignore_index case for Dice
+and for CE.
+Usage: python tools/head_digest.py [heads, default landmark,seg,valu; all: landmark,seg,valu,ds] > digest.jsonl"""
 import hashlib
 import json
 import os
@@ -186,18 +190,53 @@ def valu(mode, form, n, shape, cl, cin, c, u8):
     return finish({"loss": digest(loss), "logits": digest(lg)}, loss, leaf, blk, fc, mode)
 
 
-RUN = {"landmark": (landmark_cases, landmark, ("bf16", "fp16")), "seg": (seg_cases, seg, ("bf16", "fp16")),
-       "valu": (valu_cases, valu, ("fp32", "bf16", "fp16"))}
+DS_LEVELS = [((4, 4, 8), 1, 64, 1), ((4, 4, 8), 2, 128, 2), ((4, 4, 8), 3, 256, 4), ((6, 6, 6), 1, 64, 5), ((6, 6, 6), 1, 256, 8),
+             ((6, 6, 6), 1, 128, 16), ((24, 24, 16), 1, 64, 16), ((4, 4, 8), 1, 256, 16), ((4, 4, 8), 2, 64, 8), ((6, 6, 6), 1, 128, 9)]
+
+
+def ds_cases():
+    for lev, s, cin, c in DS_LEVELS:
+        cases = [(cl, sig, wtd, None) for cl, sig in (("DICE", False), ("DICE", True), ("CE", False), ("DICE_CE", False))
+                 for wtd in (True, False)]
+        if c == 9:
+            cases += [("DICE", False, True, 2), ("CE", False, True, 3)]
+        for cl, sig, wtd, ign in cases:
+            yield f"ds lev={sh(lev)} shift={s} cin={cin} C={c} {cl} sig={int(sig)} w={int(wtd)} ign={ign}", (lev, s, cin, c, cl, sig, wtd, ign)
+
+
+def ds(mode, with_pass, lev, s, cin, c, cl, sig, wtd, ign):
+    n = 2
+    lab = labels(f"dslab{c}", c, n, *(v << s for v in lev)).to(DEV)
+    wt = weights(c).to(DEV) if wtd else None
+    xg = ops.to_cl(rnd(f"x{cin}", n, cin, *lev).to(DEV).to(mednet_hip.config.act_dtype())).requires_grad_(True)
+    fc = head_conv(cin, c)
+    if not ops.ds_head_supported(xg, cin, c, lab, s):
+        raise RuntimeError("ds_head does not take this case")
+    xp, loss = ops.ds_head(xg, fc.weight, fc.bias, fc._packed(), lab, s, wt, 1e-5, sig, ign, cl)
+    scale = 3.0 * 16384.0 if mode == "fp16" else 3.0  # (finish's)
+    outs, grads = [loss], [torch.tensor(scale, device=DEV)]
+    if with_pass:  # the gradient from the next decoder, in the storage type
+        d_pass = ops.to_cl((rnd(f"p{cin}", n, cin, *lev) * (1e-3 * scale)).to(DEV).to(xg.dtype))
+        outs, grads = [xp] + outs, [d_pass] + grads
+    torch.autograd.backward(outs, grads)
+    torch.cuda.synchronize()
+    return {"loss": digest(loss), "dx": digest(xg.grad), "dw": digest(fc.weight.grad), "db": digest(fc.bias.grad)}
+
+
+# per head: its cases, its function, its storage modes and its runs of a case (key, the function's arguments in front of the axes)
+FORMS = [(f"{form}/{sh(shape)}", (form, n, shape)) for form in ("op", "block") for n, shape in SHAPES]
+RUN = {"landmark": (landmark_cases, landmark, ("bf16", "fp16"), FORMS), "seg": (seg_cases, seg, ("bf16", "fp16"), FORMS),
+       "valu": (valu_cases, valu, ("fp32", "bf16", "fp16"), FORMS),
+       "ds": (ds_cases, ds, ("bf16", "fp16"), [("d_pass=0", (False,)), ("d_pass=1", (True,))])}
 for head in HEADS:
-    cases, fn, modes = RUN[head]
+    cases, fn, modes, runs = RUN[head]
     for name, axes in cases():
         res = {}
         for mode in modes:
-            for form in ("op", "block"):
-                for n, shape in SHAPES:
-                    with mednet_hip.precision(mode):
-                        for k, v in fn(mode, form, n, shape, *axes).items():
-                            res[f"{mode}/{form}/{sh(shape)}/{k}"] = v
+            for key, args in runs:
+                with mednet_hip.precision(mode):
+                    for k, v in fn(mode, *args, *axes).items():
+                        res[f"{mode}/{key}/{k}"] = v
         line = {"case": name, "sha256": hashlib.sha256("".join(f"{k}={v};" for k, v in res.items()).encode()).hexdigest()}
         print(json.dumps({**line, **res} if FULL else line), flush=True)
         torch.cuda.empty_cache()

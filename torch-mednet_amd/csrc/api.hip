@@ -513,10 +513,7 @@ static int head_landmark_fwd(const char* what, const void* z, const void* packed
   if (rc) return rc;
   rc = launch_hm_finalize(hm_partial, reg_weight, reg_loss, n, nh, chunks, spatial, s);
   if (rc) return rc;
-  rc = class_kind == MEDNET_CLASS_DICE_CE
-           ? launch_dice_ce_finalize(dice_partial, ce_partial, class_weight, class_loss, saved, ncls, n * chunks, eps, s)
-           : ce ? launch_ce_finalize(ce_partial, class_loss, saved, n * chunks, s)
-                : launch_dice_finalize(dice_partial, class_weight, class_loss, saved, ncls, n * chunks, eps, s);
+  rc = launch_class_finalize(class_kind, dice_partial, ce_partial, class_weight, class_loss, saved, ncls, n * chunks, eps, s);
   if (rc || !dice_metric) return rc;
   return launch_dice_finalize(dice_partial, nullptr, nullptr, metric_saved, ncls, n * chunks, 1e-5f, s, dice_metric);
 }
@@ -613,16 +610,11 @@ extern "C" int mednet_head_seg_fwd(const void* z, const void* packed, const floa
   if (rc) return rc;
   MEDNET_REQUIRE(ws_bytes >= head_seg_ws_bytes(n, spatial, ncls), MEDNET_E_WORKSPACE, "head_seg_fwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int chunks = head_lm_chunks(spatial);
-  const int ce = class_kind == MEDNET_CLASS_CE;
   float* partial = (float*)ws;
   rc = ELT_CALL(z_dtype, launch_head_seg_fwd, z, head_weights_f32(packed, cin, ncls), bias, labels, label_stride_n, class_weight, logits,
                 partial, n, spatial, ncls, class_kind, sigmoid, ignore_index, s);
   if (rc) return rc;
-  if (class_kind == MEDNET_CLASS_DICE_CE)  // (the Dice rows, behind all of them the CE rows: launch_head_seg_fwd)
-    return launch_dice_ce_finalize(partial, partial + (size_t)n * chunks * ncls * 2, class_weight, loss, saved, ncls, n * chunks, eps, s);
-  if (ce) return launch_ce_finalize(partial, loss, saved, n * chunks, s);
-  return launch_dice_finalize(partial, class_weight, loss, saved, ncls, n * chunks, eps, s);
+  return launch_class_finalize(class_kind, partial, class_weight, loss, saved, ncls, n * head_lm_chunks(spatial), eps, s);
 }
 extern "C" int mednet_head_seg_bwd(const void* z, const void* packed, const float* bias, const void* labels, int64_t label_stride_n,
                                    const float* class_weight, const float* saved, const float* dloss, void* dz, const void* gn_y,
@@ -674,15 +666,11 @@ extern "C" int mednet_ds_head_fwd(const void* z, const void* packed, const float
   const size_t spatial = (size_t)d * h * w;
   MEDNET_REQUIRE(ws_bytes >= ds_head_ws_bytes(n, spatial, cin, ncls), MEDNET_E_WORKSPACE, "ds_head_fwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int chunks = ds_head_chunks(spatial);
   float* partial = (float*)ws;
   rc = ELT_CALL(z_dtype, launch_ds_head_fwd, z, head_weights_f32(packed, cin, ncls), bias, labels, label_stride_n, class_weight, partial,
                 n, d, h, w, H, W, shift, cin, ncls, class_kind, sigmoid, ignore_index, s);
   if (rc) return rc;
-  if (class_kind == MEDNET_CLASS_DICE_CE)  // (the Dice rows, behind all of them the CE rows)
-    return launch_dice_ce_finalize(partial, partial + (size_t)n * chunks * ncls * 2, class_weight, loss, saved, ncls, n * chunks, eps, s);
-  if (class_kind == MEDNET_CLASS_CE) return launch_ce_finalize(partial, loss, saved, n * chunks, s);
-  return launch_dice_finalize(partial, class_weight, loss, saved, ncls, n * chunks, eps, s);
+  return launch_class_finalize(class_kind, partial, class_weight, loss, saved, ncls, n * ds_head_chunks(spatial), eps, s);
 }
 extern "C" int mednet_ds_head_bwd(const void* z, const void* packed, const float* bias, const void* labels, int label_dtype,
                                   int64_t label_stride_n, const float* class_weight, const float* saved, const float* dloss,

@@ -1,5 +1,7 @@
 // Internal declarations shared by the convolution translation units.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace mednet {
@@ -71,6 +73,25 @@ int launch_ce_finalize(const float* partial, float* loss, float* saved, int nblo
 // Dice rows + CE rows -> *loss = fl(dice + ce), saved = [c][2] {I, D} then sum w_y (dice_ce_finalize_kernel)
 int launch_dice_ce_finalize(const float* partial, const float* partial_ce, const float* weight, float* loss, float* saved, int c,
                             int nblocks, float eps, hipStream_t s, float* dice_out = nullptr);
+// the one of the three that class loss `kind` (MEDNET_CLASS_*) takes; a fused head's rows: [rows][c][2] (Dice), [rows][2] (CE)
+int launch_class_finalize(int kind, const float* dice_partial, const float* ce_partial, const float* weight, float* loss, float* saved,
+                          int c, int rows, float eps, hipStream_t s);
+// one workspace for both: all the Dice rows first, then all the CE rows (a CE head has its rows at the front)
+inline int launch_class_finalize(int kind, const float* partial, const float* weight, float* loss, float* saved, int c, int rows,
+                                 float eps, hipStream_t s) {
+  const float* ce_partial = kind == MEDNET_CLASS_DICE_CE ? partial + (size_t)rows * c * 2 : partial;
+  return launch_class_finalize(kind, partial, ce_partial, weight, loss, saved, c, rows, eps, s);
+}
+
+// The fused class heads' launches: the run-time class loss `ce` (MEDNET_CLASS_*) as the compile-time KIND of a kernel instantiation,
+// f(std::integral_constant<int, KIND>), and the launch's name for check_launch, STEM + {"", "_ce", "_dice_ce"} + DIR
+template <class F>
+inline void for_class_kind(int ce, F&& f) {
+  if (ce == MEDNET_CLASS_DICE_CE) f(std::integral_constant<int, MEDNET_CLASS_DICE_CE>{});
+  else if (ce) f(std::integral_constant<int, MEDNET_CLASS_CE>{});
+  else f(std::integral_constant<int, MEDNET_CLASS_DICE>{});
+}
+#define MEDNET_CLASS_KIND_NAME(ce, STEM, DIR) ((ce) == MEDNET_CLASS_DICE_CE ? STEM "_dice_ce" DIR : (ce) ? STEM "_ce" DIR : STEM DIR)
 
 // 16-bit matrix-core kernels, conv_mfma.hip (namespace mednet: bf16; api.hip declares the same set in namespace mednet_f16
 // for the fp16 build of that file)

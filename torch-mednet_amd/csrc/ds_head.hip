@@ -5,13 +5,12 @@
 // W^T dl before the one rounding to the storage type.  No down-sampled label tensor, no logit tensor, no logit-gradient tensor and
 // no autograd add of two feature gradients exist.
 //
-// The kernel is head_seg_kernel (head_mfma.hip) with the 32-feature row made a loop over 32-channel tiles; it shares that file's
-// building blocks (the hi + lo split, the weight-row permutation HlmRow, the wave-private dW tiles HlmTiles, the end-of-kernel sums),
-// which this translation unit takes by including head_mfma.hip with MEDNET_HEAD_BLOCKS_ONLY set.
+// The kernel is head_seg_kernel (head_mfma.hip) with the 32-feature row made a loop over 32-channel tiles.  Both are built from
+// head_blocks.inc: the hi + lo split, the permuted weight operands (here at row stride cin, column offset 32 t), the wave-private dW
+// tiles HlmTiles, the end-of-kernel sums, and the hsg_* class-loss arithmetic of the wide-class layout, of which there is one copy.
 //   forward   logits^T = W z^T on v_mfma_f32_32x32x16, accumulated over the tiles (4 MFMAs per tile and 32 voxels: 2 k-steps x hi / lo
-//             of the fp32 weights); lane (g, h) then holds classes 8h .. 8h+7 of its voxels 4g .. 4g+3 exactly as in head_seg_kernel,
-//             and the softmax / sigmoid, the Dice and the cross-entropy terms are that kernel's.  Only loss partial rows are written
-//             (dice_finalize_kernel's / ce_finalize_kernel's layouts).
+//             of the fp32 weights); lane (g, h) then holds classes 8h .. 8h+7 of its voxels 4g .. 4g+3 exactly as in head_seg_kernel
+//             (hsg_probs, hsg_fwd_terms).  Only loss partial rows are written (dice_finalize_kernel's / ce_finalize_kernel's layouts).
 //   backward  the same MFMAs rebuild the logits bit for bit; dl from the closed forms; per tile dz^T = W_t^T dl^T (3 MFMAs), + d_pass,
 //             rounded once, stored; dW_t += dl^T z_t through the transposing LDS tiles; db by lane sums.  The tile's z rows are read a
 //             second time for dW (the run's 128 rows were read a moment ago by the same wave: they come from the cache).
@@ -19,8 +18,9 @@
 // The register budget does not grow with cin except for the dW accumulators (16 per tile): the backward is instantiated for up to 4
 // and up to 8 tiles.  The producing block's GroupNorm-3 sums are NOT taken here (mednet_ds_head_gn_rows answers 0): the block runs
 // its stand-alone first pass.
-#define MEDNET_HEAD_BLOCKS_ONLY
-#include "head_mfma.hip"
+#include "conv.h"
+#include "elt16.inc"
+#include "head_blocks.inc"
 
 namespace mednet {
 
@@ -68,10 +68,8 @@ __device__ __forceinline__ unsigned ds_pick4(const DsArgs& a, const uint8_t* lb8
 
 template <bool BWD, int KIND, int TMAX>
 __global__ __launch_bounds__(256, (BWD && TMAX > 4) ? 1 : 2) void ds_head_kernel(DsArgs a) {
-  constexpr bool CE = KIND == HLM_CE;
-  constexpr int NCST = (BWD && KIND == HLM_DICE_CE) ? 32 : 24;
   __shared__ __attribute__((aligned(16))) char smem[256 * HLM_SCR * 4];
-  __shared__ float cst[2][NCST];
+  __shared__ float cst[2][HSG_NCST<BWD, KIND>];
   __shared__ u32x4 wlog[TMAX][4][64];             // per tile: logits hi (k-steps 0, 1), lo (k-steps 0, 1)
   __shared__ u32x4 wdz[BWD ? TMAX : 1][2][64];    // per tile: dz hi, lo
   const int tid = threadIdx.x, lane = tid & 63;
@@ -79,48 +77,17 @@ __global__ __launch_bounds__(256, (BWD && TMAX > 4) ? 1 : 2) void ds_head_kernel
   const int g = lane & 31, h = lane >> 5;
   const int n = blockIdx.y, chunk = blockIdx.x;
   const int nv = min(8, max(0, a.ncls - 8 * h));  // classes of this lane half
+  const HsgLoss c = {a.bias, a.cls_weight, a.saved, a.dloss, a.eps, a.ncls, a.sigmoid, a.ignore};
 
-  // ---- weight operands of every tile (head_seg_kernel's, rows of W at stride cin), the waves taking tiles in turn ------------
+  // ---- weight operands of every tile (head_seg_kernel's, columns 32 t .. of W at row stride cin), the waves taking tiles in turn,
+  // and the constants of a lane half
   const HlmRow r(lane);
   const int lrow = (r.q < 2 && r.out() < a.ncls) ? r.out() : -1;
   for (int t = wv; t < a.tiles; t += 4) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      float w[8];
-      eltx8 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) w[e] = lrow >= 0 ? a.W[(size_t)lrow * a.cin + 32 * t + 16 * s + 8 * h + e] : 0.f;
-      hlm_split(w, hi, lo);
-      wlog[t][s][lane] = __builtin_bit_cast(u32x4, hi);
-      wlog[t][2 + s][lane] = __builtin_bit_cast(u32x4, lo);
-    }
-    if constexpr (BWD) {  // k-slot 8h + e = class 8h + e, this lane's channel of the tile
-      float w[8];
-      eltx8 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) w[e] = 8 * h + e < a.ncls ? a.W[(size_t)(8 * h + e) * a.cin + 32 * t + r.channel()] : 0.f;
-      hlm_split(w, hi, lo);
-      wdz[t][0][lane] = __builtin_bit_cast(u32x4, hi);
-      wdz[t][1][lane] = __builtin_bit_cast(u32x4, lo);
-    }
+    hlm_logit_operands(wlog[t], a.W, lrow, lane, a.cin, 32 * t);
+    if constexpr (BWD) hlm_dz_operand(wdz[t][0][lane], wdz[t][1][lane], a.W, 8 * h, a.ncls - 8 * h, r.channel(), a.cin, 32 * t);
   }
-  // ---- constants of a lane half: head_seg_kernel's table
-  if (wv == 2 && (lane & 31) < NCST) {
-    const int hh = lane >> 5, i = lane & 31, k = 8 * hh + (i & 7);
-    float v = 0.f;
-    if (k < a.ncls) {
-      const float w = a.cls_weight ? a.cls_weight[k] : 1.f;
-      if (i < 8) v = a.bias ? a.bias[k] : 0.f;
-      else if (KIND == HLM_DICE_CE && !BWD) v = i < 16 ? w : 0.f;
-      else if (KIND == HLM_DICE_CE && i >= 24) v = w * (*a.dloss / a.saved[2 * a.ncls]);
-      else if (CE) v = i < 16 ? (BWD ? w * (*a.dloss / a.saved[0]) : w) : 0.f;
-      else if (BWD) {
-        const float I = a.saved[2 * k], D = a.saved[2 * k + 1];
-        v = i < 16 ? hlm_dice_gI(w, I, D, a.eps, a.ncls, *a.dloss) : hlm_dice_gD(w, I, D, a.eps, a.ncls, *a.dloss);
-      }
-    }
-    cst[hh][i] = v;
-  }
+  if (wv == 2) hsg_constants<BWD, KIND>(cst, lane, c);
   __syncthreads();
   // (made opaque inside the loops: left alone, the compiler hoists the loop-invariant fragments into registers for the whole kernel)
   const u32x4* wlbase = &wlog[0][0][lane];
@@ -191,111 +158,14 @@ __global__ __launch_bounds__(256, (BWD && TMAX > 4) ? 1 : 2) void ds_head_kernel
       for (int e = 0; e < 8; ++e) lc[e] = lg[j][e] + cbase[e];
       const int yl = (int)((lb >> (8 * j)) & 0xFFu);
       const int yk = yl - 8 * h;  // the label's slot in this half, if in 0 .. nv-1
-      float lse = 0.f;
-      if (a.sigmoid) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) p[e] = e < nv ? 1.f / (1.f + expf(-lc[e])) : 0.f;
-      } else {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (e < nv) mx = fmaxf(mx, lc[e]);
-        mx = xor32_max(mx);
-        float den = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          p[e] = e < nv ? expf(lc[e] - mx) : 0.f;
-          den += p[e];
-        }
-        den = xor32_sum(den);
-        const float inv = 1.f / den;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) p[e] *= inv;
-        if (KIND != HLM_DICE) lse = mx + logf(den);
-      }
-      if constexpr (!BWD) {
-        if constexpr (KIND != HLM_DICE) {
-          // ce_fwd_kernel; the half that owns the label's class takes the voxel's term
-          if (live && h == 0 && yl != a.ignore && yl >= a.ncls) ce_acc[0] = __builtin_nanf("");
-          if (live && yl != a.ignore && yk >= 0 && yk < nv) {
-            float zy = 0.f, w = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-              if (e == yk) {
-                zy = lc[e];
-                w = cbase[8 + e];
-              }
-            ce_acc[0] = fmaf(w, lse - zy, ce_acc[0]);
-            ce_acc[1] += w;
-          }
-        }
-        if constexpr (!CE) {
-          bad |= live && yl >= a.ncls;
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (e < nv) {
-              const float t = (e == yk) ? 1.f : 0.f;
-              const float mk = (!live || (a.ignore != MEDNET_NO_IGNORE && t == (float)a.ignore)) ? 0.f : 1.f;
-              dI[e] = fmaf(p[e] * mk, t * mk, dI[e]);
-              dD[e] += (p[e] + t) * mk;
-            }
-        }
-      } else {
-        float dc[8];
-        if constexpr (CE) {
-          float wy = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (e == yk) wy = cbase[8 + e];  // (0 for classes >= ncls)
-          wy = xor32_sum(wy);                // (the other half's lane has 0)
-          wy = (live && yl != a.ignore && yl < a.ncls) ? wy : 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            dc[e] = e < nv ? wy * (p[e] - (e == yk ? 1.f : 0.f)) : 0.f;
-            dbc[e] += dc[e];
-          }
-        } else if constexpr (KIND == HLM_DICE_CE) {
-          float gg[8], dot = 0.f, wy = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float t = (e == yk) ? 1.f : 0.f;
-            gg[e] = e < nv ? cbase[8 + e] * t + cbase[16 + e] : 0.f;
-            dot = fmaf(p[e], gg[e], dot);
-            if (e == yk) wy = cbase[24 + e];  // (0 for classes >= ncls)
-          }
-          dot = xor32_sum(dot);
-          wy = xor32_sum(wy);  // (the other half's lane has 0)
-          wy = (live && yl < a.ncls) ? wy : 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float dl_dice = p[e] * (gg[e] - dot);
-            const float dl_ce = wy * (p[e] - (e == yk ? 1.f : 0.f));
-            dc[e] = (live && e < nv) ? dl_dice + dl_ce : 0.f;
-            dbc[e] += dc[e];
-          }
-        } else {
-          float gg[8], dot = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float t = (e == yk) ? 1.f : 0.f;
-            const float mk = (a.ignore != MEDNET_NO_IGNORE && t == (float)a.ignore) ? 0.f : 1.f;
-            gg[e] = e < nv ? mk * (cbase[8 + e] * t * mk + cbase[16 + e]) : 0.f;
-            dot = fmaf(p[e], gg[e], dot);
-          }
-          if (!a.sigmoid) dot = xor32_sum(dot);  // (uniform)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float v = a.sigmoid ? gg[e] * p[e] * (1.f - p[e]) : p[e] * (gg[e] - dot);
-            dc[e] = (live && e < nv) ? v : 0.f;
-            dbc[e] += dc[e];
-          }
-        }
-        hlm_split(dc, dch[j], dcl[j]);
-      }
+      float lse;
+      hsg_probs<KIND>(lc, nv, a.sigmoid, p, lse);
+      if constexpr (!BWD) hsg_fwd_terms<KIND>(c, p, lc, lse, yl, yk, nv, live, h, cbase, ce_acc, dI, dD, bad);
+      else hsg_logit_grad<KIND>(c, p, yl, yk, nv, live, cbase, dbc, dch[j], dcl[j]);
     }
 
     if constexpr (BWD) {
-      // ---- per channel tile: dz^T = W_t^T dl^T (hi hi, lo hi, hi lo) + d_pass, rounded once and stored; dW_t += dl^T z_t
+      // ---- per channel tile: dz^T = W_t^T dl^T + d_pass, rounded once and stored; dW_t += dl^T z_t
       elt* dzrow = dzs + vb * a.cin + 8 * h;
       const elt* prow = ps ? ps + vb * a.cin + 8 * h : nullptr;
 #pragma unroll
@@ -312,12 +182,7 @@ __global__ __launch_bounds__(256, (BWD && TMAX > 4) ? 1 : 2) void ds_head_kernel
               zp[s] = live ? *reinterpret_cast<const u32x4*>(zrow + at) : zero4;
               pp[s] = (live && prow) ? *reinterpret_cast<const u32x4*>(prow + at) : zero4;
             }
-            f32x16 dzv;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) dzv[i] = 0.f;
-            dzv = MEDNET_MFMA_32x32x16(hlm_wop(wt, 0), dch[j], dzv, 0, 0, 0);
-            dzv = MEDNET_MFMA_32x32x16(hlm_wop(wt, 1), dch[j], dzv, 0, 0, 0);
-            dzv = MEDNET_MFMA_32x32x16(hlm_wop(wt, 0), dcl[j], dzv, 0, 0, 0);
+            const f32x16 dzv = hlm_dz(hlm_wop(wt, 0), hlm_wop(wt, 1), dch[j], dcl[j]);
             const eltx8 p0 = __builtin_bit_cast(eltx8, pp[0]), p1 = __builtin_bit_cast(eltx8, pp[1]);
             eltx8 o0, o1;
 #pragma unroll
@@ -339,32 +204,12 @@ __global__ __launch_bounds__(256, (BWD && TMAX > 4) ? 1 : 2) void ds_head_kernel
 
   // ---- end of kernel: lane and wave sums through LDS in a fixed order (head_seg_kernel's) ---------------------------------
   float* scr = reinterpret_cast<float*>(smem);
-  float* mine = scr + tid * HLM_SCR;
   __syncthreads();
   if constexpr (!BWD) {
-    if constexpr (KIND != HLM_DICE) {  // values 16 / 17 of every thread are its ce_acc
-      if (tid < 2) {
-        float s = 0.f;
-        for (int t = 0; t < 256; ++t) s += scr[t * HLM_SCR + 16 + tid];
-        a.ce_partial[((size_t)n * a.chunks + chunk) * 2 + tid] = s;
-      }
-    }
-    if constexpr (!CE) {
-      if (bad) dI[0] = dD[0] = __builtin_nanf("");
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        mine[e] = dI[e];
-        mine[8 + e] = dD[e];
-      }
-      __syncthreads();
-      if (tid < 2 * HSG_MAXC) {  // class k = 8hh + e: lanes of half hh, value e (I) / 8 + e (D)
-        const int k = tid >> 1, which = tid & 1;
-        const float s = hlm_lane_sum(scr, k >> 3, 8 * which + (k & 7));
-        if (k < a.ncls) a.dice_partial[(((size_t)n * a.chunks + chunk) * a.ncls + k) * 2 + which] = s;
-      }
-    }
+    hsg_fwd_writeout<KIND>(scr, tid, dI, dD, bad, a.ce_partial, a.dice_partial, (size_t)n * a.chunks + chunk, a.ncls);
   } else {
     // per tile a row of head_lm_kernel's shape: dW row k' = class k' (accumulator values 0 .. 7 of a lane), db at 1024 + k'
+    float* mine = scr + tid * HLM_SCR;
     float* wp = a.wpart + ((size_t)n * a.chunks + chunk) * a.tiles * HLM_WIDTH;
 #pragma unroll
     for (int t = 0; t < TMAX; ++t) {
@@ -380,6 +225,7 @@ __global__ __launch_bounds__(256, (BWD && TMAX > 4) ? 1 : 2) void ds_head_kernel
     }
   }
 }
+
 
 // dw[co][32 t + c] = sum over the workgroups' rows of wpart[.][t][co * 32 + c], db[co] of wpart[.][0][1024 + co]: one thread per
 // output, the rows in order, in fp64 (deterministic)
@@ -437,23 +283,11 @@ int launch_ds_head_fwd(const void* z, const float* W, const float* bias, const v
   DsArgs a = {};
   ds_args(a, z, W, bias, lab, lab_sn, cls_weight, d, h, w, H, Wf, shift, cin, ncls, sigmoid, ignore);
   (ce == HLM_CE ? a.ce_partial : a.dice_partial) = partial;
-  const dim3 grid(a.chunks, n);
-  if (ce == HLM_DICE_CE) {
-    a.ce_partial = partial + (size_t)n * a.chunks * ncls * 2;
-    hipLaunchKernelGGL((ds_head_kernel<false, HLM_DICE_CE, DSH_MAXT>), grid, dim3(256), 0, s, a);
-    return check_launch("ds_head_dice_ce_fwd");
-  }
-  if (ce) hipLaunchKernelGGL((ds_head_kernel<false, HLM_CE, DSH_MAXT>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((ds_head_kernel<false, HLM_DICE, DSH_MAXT>), grid, dim3(256), 0, s, a);
-  return check_launch(ce ? "ds_head_ce_fwd" : "ds_head_fwd");
-}
-
-template <int TMAX>
-static void ds_launch_bwd(const DsArgs& a, int n, int ce, hipStream_t s) {
-  const dim3 grid(a.chunks, n);
-  if (ce == HLM_DICE_CE) hipLaunchKernelGGL((ds_head_kernel<true, HLM_DICE_CE, TMAX>), grid, dim3(256), 0, s, a);
-  else if (ce) hipLaunchKernelGGL((ds_head_kernel<true, HLM_CE, TMAX>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((ds_head_kernel<true, HLM_DICE, TMAX>), grid, dim3(256), 0, s, a);
+  if (ce == HLM_DICE_CE) a.ce_partial = partial + (size_t)n * a.chunks * ncls * 2;
+  for_class_kind(ce, [&](auto kind) {
+    hipLaunchKernelGGL((ds_head_kernel<false, decltype(kind)::value, DSH_MAXT>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  });
+  return check_launch(MEDNET_CLASS_KIND_NAME(ce, "ds_head", "_fwd"));
 }
 
 int launch_ds_head_bwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* saved,
@@ -464,9 +298,12 @@ int launch_ds_head_bwd(const void* z, const float* W, const float* bias, const v
   ds_args(a, z, W, bias, lab, lab_sn, cls_weight, d, h, w, H, Wf, shift, cin, ncls, sigmoid, ignore);
   MEDNET_REQUIRE(ws_bytes >= ds_head_ws_bytes(n, a.spatial, cin, ncls), MEDNET_E_WORKSPACE, "ds_head_bwd: workspace too small");
   a.saved = saved; a.dloss = dloss; a.eps = eps; a.d_pass = (const elt*)d_pass; a.dz = (elt*)dz; a.wpart = (float*)ws;
-  if (a.tiles <= 4) ds_launch_bwd<4>(a, n, ce, s);
-  else ds_launch_bwd<DSH_MAXT>(a, n, ce, s);
-  int rc = check_launch(ce == HLM_DICE_CE ? "ds_head_dice_ce_bwd" : ce ? "ds_head_ce_bwd" : "ds_head_bwd");
+  for_class_kind(ce, [&](auto kind) {
+    constexpr int KIND = decltype(kind)::value;
+    if (a.tiles <= 4) hipLaunchKernelGGL((ds_head_kernel<true, KIND, 4>), dim3(a.chunks, n), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((ds_head_kernel<true, KIND, DSH_MAXT>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  });
+  int rc = check_launch(MEDNET_CLASS_KIND_NAME(ce, "ds_head", "_bwd"));
   if (rc) return rc;
   const int total = ncls * cin + ncls;
   hipLaunchKernelGGL(ds_head_wfinal_kernel, dim3((total + 255) / 256), dim3(256), 0, s, a.wpart, n * a.chunks, a.tiles, ncls, dw, db);

@@ -518,10 +518,6 @@ __global__ __launch_bounds__(192) void head_dice_wfinal2_kernel(const double* __
   }
 }
 
-// (defined in loss.hip)
-__global__ void dice_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ weight, float* __restrict__ loss,
-                                     float* __restrict__ saved, float* __restrict__ dice_out, int c, int nblocks, float eps);
-
 static inline unsigned hl_fwd_blocks(size_t spatial) { return (unsigned)((spatial + HL_BLOCK_VOX - 1) / HL_BLOCK_VOX); }
 static inline unsigned hl_bwd_blocks(size_t spatial, int k) {
   const size_t per_wg = (size_t)(256 / (k / 8)) * HL_VPT;
@@ -563,7 +559,6 @@ static int head_loss_fwd(const char* what, const void* z, const void* packed, co
   MEDNET_REQUIRE(mednet_head_dice_supported(cin, cout, z_dtype, label_dtype), MEDNET_E_UNSUPPORTED,
                  "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
   MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && logits && loss && saved, MEDNET_E_SHAPE, "%s: bad arguments", what);
-  constexpr bool CE = KIND == HL_CE;
   const size_t need = KIND == HL_DICE_CE ? mednet_head_dice_ce_ws_bytes(n, spatial, cin, cout) : mednet_head_dice_ws_bytes(n, spatial, cin, cout);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "%s: workspace too small", what);
   const float* Pb = head_weights_f32(packed, cin, cout);
@@ -582,12 +577,7 @@ static int head_loss_fwd(const char* what, const void* z, const void* packed, co
 #undef HF
   int rc = check_launch(what);
   if (rc) return rc;
-  if (CE) return launch_ce_finalize(partial, loss, saved, (int)(nb * n), s);
-  if (KIND == HL_DICE_CE) {
-    return launch_dice_ce_finalize(partial, partial + (size_t)n * nb * cout * 2, weight, loss, saved, cout, (int)(nb * n), eps, s);
-  }
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, s, partial, weight, loss, saved, (float*)nullptr, cout, (int)(nb * n), eps);
-  return check_launch("dice_finalize");
+  return launch_class_finalize(KIND, partial, weight, loss, saved, cout, (int)(nb * n), eps, s);
 }
 
 template <int KIND>

@@ -21,22 +21,16 @@
 // are built once per wave from the fp32 weights) so that every MFMA result lands in the lane that owns those bytes.
 //
 // The file holds two kernels of this shape -- head_lm_kernel (nh heat maps + up to 4 classes in the lanes of half 0) and, further down,
-// head_seg_kernel (5 .. 16 classes spread over both lane halves, softmax through v_permlane32_swap) -- and ONE copy of everything they
-// do alike: the hlm_* / Hlm* building blocks below HlmArgs (weight operands, row loads, logit MFMAs, dz store + GroupNorm pass, the dW
-// tiles, the end-of-kernel sums), head_lm_wfinal_kernel, and on the host one HlmArgs filler behind launch_head_lm_{fwd,bwd} and
-// launch_head_seg_{fwd,bwd}, which take the class loss as `int ce`.
+// head_seg_kernel (5 .. 16 classes spread over both lane halves, softmax through v_permlane32_swap).  Everything they do alike, and
+// everything head_seg_kernel does alike with ds_head.hip's kernel, is in head_blocks.inc: the hlm_* / Hlm* skeleton (weight operands,
+// row loads, logit MFMAs, dz store + GroupNorm pass, the dW tiles, the end-of-kernel sums) and the hsg_* class-loss arithmetic of
+// the wide-class layout.  Here: the two kernels, head_lm_wfinal_kernel, and on the host one HlmArgs filler behind
+// launch_head_lm_{fwd,bwd} and launch_head_seg_{fwd,bwd}, which take the class loss as `int ce` (for_class_kind, conv.h).
 #include "conv.h"
 #include "elt16.inc"
+#include "head_blocks.inc"
 
 namespace mednet {
-
-constexpr int HLM_RUN = 128;       // voxels per wave and trip
-constexpr int HLM_MAXH = 16;       // heat maps (one MFMA k-block)
-constexpr int HLM_MAXC = 4;        // classes (second k-block, lanes 0..31)
-constexpr int HLM_WIDTH = 32 * 33; // per-workgroup partial of (dW [32 k'][32 ci], db [32 k']); k' = heat map c, or 16 + class
-constexpr int HLM_SCR = 33;        // floats per thread of the end-of-kernel LDS scratch
-// the class loss of an instantiation (= MEDNET_CLASS_*; the launches take it as `int ce`): DiceLoss, nn.CrossEntropyLoss, or their sum
-constexpr int HLM_DICE = 0, HLM_CE = 1, HLM_DICE_CE = 2;
 
 struct HlmArgs {
   const elt* z;          // [n][spatial][32]: head input (the last block's output)
@@ -68,221 +62,6 @@ struct HlmArgs {
   float* ce_partial;     // CE forward: [n][chunk][2] = {sum w_y nll, sum w_y}  (ce_finalize_kernel's layout)
 };
 
-// ---- building blocks of head_lm_kernel and head_seg_kernel -------------------------------------------------------------------
-// Everything the two kernels do alike, written once; what differs between them is where the classes live (below).
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-__device__ __forceinline__ void hlm_split(const float (&v)[8], eltx8& hi, eltx8& lo) {  // v = hi + lo in the storage type
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    hi[e] = (elt)v[e];
-    lo[e] = (elt)(v[e] - (float)hi[e]);
-  }
-}
-
-// Row i = 8q + 4hh + t of a 32-row weight operand, as lane i (and i + 32) builds it
-struct HlmRow {
-  int q, hh, t;
-  __device__ __forceinline__ explicit HlmRow(int lane) : q((lane & 31) >> 3), hh((lane & 7) >> 2), t(lane & 3) {}
-  __device__ __forceinline__ int out() const { return 8 * hh + 4 * q + t; }                          // logits: q 0/1 -> output 8hh + 4q + t
-  __device__ __forceinline__ int channel() const { return (q >> 1) * 16 + 8 * hh + (q & 1) * 4 + t; }  // dz: the channel this row stands for
-};
-
-// logits^T [output row][voxel]: wops[0,1] = hi, [2,3] = lo parts of row `lrow` of W (-1: a zero row), k-steps of 16 channels
-__device__ __forceinline__ void hlm_logit_operands(u32x4 (*wops)[64], const float* W, int lrow, int lane) {
-  const int h = lane >> 5;
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    float w[8];
-    eltx8 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) w[e] = lrow >= 0 ? W[lrow * 32 + 16 * s + 8 * h + e] : 0.f;
-    hlm_split(w, hi, lo);
-    wops[s][lane] = __builtin_bit_cast(u32x4, hi);
-    wops[2 + s][lane] = __builtin_bit_cast(u32x4, lo);
-  }
-}
-// dz^T [channel row][voxel], one k-block: k-slot 8h + e = row `row0 + e` of W for e < cnt (the others zero), this lane's channel
-__device__ __forceinline__ void hlm_dz_operand(u32x4& hi_out, u32x4& lo_out, const float* W, int row0, int cnt, int ch) {
-  float w[8];
-  eltx8 hi, lo;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) w[e] = e < cnt ? W[(row0 + e) * 32 + ch] : 0.f;
-  hlm_split(w, hi, lo);
-  hi_out = __builtin_bit_cast(u32x4, hi);
-  lo_out = __builtin_bit_cast(u32x4, lo);
-}
-__device__ __forceinline__ eltx8 hlm_wop(const u32x4* wbase, int i) { return __builtin_bit_cast(eltx8, wbase[i * 64]); }
-
-// loss.hip dice_bwd_kernel's per-class terms: gI (the factor of the one-hot target) and gD
-__device__ __forceinline__ float hlm_dice_gI(float w, float I, float D, float eps, int ncls, float gc) {
-  return -2.f * w / ((float)ncls * fmaxf(D, eps)) * gc + ((I != I || D != D) ? __builtin_nanf("") : 0.f);
-}
-__device__ __forceinline__ float hlm_dice_gD(float w, float I, float D, float eps, int ncls, float gc) {
-  const float Dc = fmaxf(D, eps);
-  return (D >= eps ? 2.f * w * I / ((float)ncls * Dc * Dc) : 0.f) * gc;
-}
-
-// The lane's 4 voxel rows (2 pieces of 16 bytes each) of z for a run, and of the GroupNorm input two sub-tiles at a time: sub-tile j
-// in yp[j & 1], sub-tile j + 1 fetched at the top of trip j
-struct HlmRows {
-  u32x4 zp[4][2], yp[2][2];
-  __device__ __forceinline__ void load_z(const elt* zs, size_t vb, int h, bool live) {
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) zp[j][s] = live ? *reinterpret_cast<const u32x4*>(zs + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
-  }
-  __device__ __forceinline__ void fetch_y(const elt* ys, size_t vb, int h, bool live, int j) {
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-      yp[j & 1][s] = (live && ys) ? *reinterpret_cast<const u32x4*>(ys + (vb + j) * 32 + 16 * s + 8 * h) : zero4;
-  }
-};
-
-// logits of the 32 voxels of a sub-tile: 4 MFMAs (2 k-steps x hi / lo)
-__device__ __forceinline__ f32x16 hlm_logits(const u32x4* wbase, const u32x4 (&zp)[2]) {
-  f32x16 lg;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) lg[i] = 0.f;
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const eltx8 zb = __builtin_bit_cast(eltx8, zp[s]);
-    lg = MEDNET_MFMA_32x32x16(hlm_wop(wbase, s), zb, lg, 0, 0, 0);
-    lg = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 2 + s), zb, lg, 0, 0, 0);
-  }
-  return lg;
-}
-
-// dz of a voxel row: converted, stored (`dzrow`: the lane's first piece), and the first pass of the GroupNorm backward in front taken
-// from the STORED values (head_dgrad_gn_kernel): du = dz * act'(z), ss += du, sq += du * gn_y.  `gn` is workgroup-uniform.
-__device__ __forceinline__ void hlm_store_dz(const f32x16& dzv, elt* dzrow, bool live, bool gn, const u32x4 (&zp)[2], const u32x4 (&yp)[2],
-                                             int gn_act, float (&ss)[16], float (&sq)[16]) {
-  eltx8 o0, o1;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    o0[e] = (elt)dzv[e];
-    o1[e] = (elt)dzv[8 + e];
-  }
-  if (live) {
-    *reinterpret_cast<u32x4*>(dzrow) = __builtin_bit_cast(u32x4, o0);
-    *reinterpret_cast<u32x4*>(dzrow + 16) = __builtin_bit_cast(u32x4, o1);
-  }
-  if (gn) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const eltx8 zv = __builtin_bit_cast(eltx8, zp[s]), yv = __builtin_bit_cast(eltx8, yp[s]);
-      const eltx8 ov = s ? o1 : o0;
-      float du[8], zz[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        du[e] = (float)ov[e];
-        zz[e] = (float)zv[e];
-      }
-      act_grad_n<8>(du, zz, gn_act);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        ss[8 * s + e] += du[e];
-        sq[8 * s + e] = fmaf(du[e], (float)yv[e], sq[8 * s + e]);
-      }
-    }
-  }
-}
-
-// Wave-private LDS tiles of the backward, 32 voxel rows x 64 B each: z, dl (hi) and dl (lo).  dW += dl^T z over a sub-tile goes through
-// them: every lane writes its voxel row, the operands are read back transposed (contraction over the 32 voxels).
-struct HlmTiles {
-  char *zt, *dlh, *dll;
-  int troff;  // tr_operand: voxel rows 8h + tq (+ 4), 4 columns
-  __device__ __forceinline__ HlmTiles(char* smem, int wv, int lane) : zt(smem + wv * 6144), dlh(zt + 2048), dll(zt + 4096) {
-    const int tq = (lane & 15) >> 2, tp = lane & 3, tg = lane >> 4, h = lane >> 5;
-    troff = (8 * h + tq) * 64 + (16 * (tg & 1) + 4 * tp) * 2;
-  }
-  // the dl columns that no step writes are zeroed once (rows of dW that nobody reads, but no NaNs)
-  __device__ __forceinline__ void zero_dl(int lane) const {
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-    *reinterpret_cast<u32x4*>(dlh + lane * 32) = zero;
-    *reinterpret_cast<u32x4*>(dlh + lane * 32 + 16) = zero;
-    *reinterpret_cast<u32x4*>(dll + lane * 32) = zero;
-    *reinterpret_cast<u32x4*>(dll + lane * 32 + 16) = zero;
-    wave_lds_fence();
-  }
-  // d_hi / d_lo: the lane's 8 dl columns 8h .. 8h+7; x_hi / x_lo (nullable, lanes of h = 0): 4 more columns at 16 .. 19
-  __device__ __forceinline__ void dw_step(int g, int h, const u32x4 (&zp)[2], const eltx8& d_hi, const eltx8& d_lo, const eltx8* x_hi,
-                                          const eltx8* x_lo, f32x16& accw) const {
-    wave_lds_fence();  // (the reads of the previous sub-tile are above these writes)
-    *reinterpret_cast<u32x4*>(zt + g * 64 + 16 * h) = zp[0];
-    *reinterpret_cast<u32x4*>(zt + g * 64 + 32 + 16 * h) = zp[1];
-    *reinterpret_cast<u32x4*>(dlh + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, d_hi);
-    *reinterpret_cast<u32x4*>(dll + g * 64 + 16 * h) = __builtin_bit_cast(u32x4, d_lo);
-    if (x_hi && h == 0) {
-      typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-      const u32x4 ch4 = __builtin_bit_cast(u32x4, *x_hi), cl4 = __builtin_bit_cast(u32x4, *x_lo);
-      const u32x2 ch2 = {ch4[0], ch4[1]}, cl2 = {cl4[0], cl4[1]};
-      *reinterpret_cast<u32x2*>(dlh + g * 64 + 32) = ch2;
-      *reinterpret_cast<u32x2*>(dll + g * 64 + 32) = cl2;
-    }
-    wave_lds_fence();  // the rows below were written by OTHER lanes of this wave
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const eltx8 fz = tr_operand(zt + ks * 1024 + troff, 256);
-      const eltx8 fh = tr_operand(dlh + ks * 1024 + troff, 256);
-      const eltx8 fl = tr_operand(dll + ks * 1024 + troff, 256);
-      accw = MEDNET_MFMA_32x32x16(fh, fz, accw, 0, 0, 0);
-      accw = MEDNET_MFMA_32x32x16(fl, fz, accw, 0, 0, 0);
-    }
-  }
-};
-
-// ---- end of kernel: every thread has put its values at scr[tid * HLM_SCR + .]; sums in a fixed order -----------------------------
-// value `idx` summed over the 4 waves x 32 lanes of lane half hh
-__device__ __forceinline__ float hlm_lane_sum(const float* scr, int hh, int idx) {
-  float s = 0.f;
-  for (int w = 0; w < 4; ++w)
-    for (int gg = 0; gg < 32; ++gg) s += scr[(w * 64 + hh * 32 + gg) * HLM_SCR + idx];
-  return s;
-}
-// GroupNorm sums: 16 channels x {ss, sq} per lane -> out[32][2] (this workgroup's row of gn_partial)
-__device__ __forceinline__ void hlm_gn_writeout(float* scr, int tid, const float (&ss)[16], const float (&sq)[16], float* out) {
-  float* mine = scr + tid * HLM_SCR;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    mine[i] = ss[i];
-    mine[16 + i] = sq[i];
-  }
-  __syncthreads();
-  if (tid < 64) {
-    const int which = tid & 1, idx = (tid >> 1) & 15, hh = tid >> 5;
-    const float s = hlm_lane_sum(scr, hh, which * 16 + idx);
-    const int ch = (idx >> 3) * 16 + 8 * hh + (idx & 7);
-    out[ch * 2 + which] = s;
-  }
-  __syncthreads();
-}
-// dW and db of the workgroup -> wp[HLM_WIDTH].  Staged by the caller: the first NV accumulator values of every lane (dW rows k' =
-// 8 (i / 4) + 4h + i % 4; NV = 8: rows 0 .. 15 only), behind them 8 db values per lane half (k' = 8h + e) and, for NDB > 16, NDB - 16
-// more in the lanes of half 0 (k' = 16 + e)
-template <int NV, int NDB>
-__device__ __forceinline__ void hlm_dw_db_writeout(const float* scr, int tid, float* wp) {
-  __syncthreads();
-  for (int o = tid; o < 64 * NV; o += 256) {
-    const int L = o & 63, i = o >> 6;
-    const float s = (scr[(0 * 64 + L) * HLM_SCR + i] + scr[(1 * 64 + L) * HLM_SCR + i]) +
-                    (scr[(2 * 64 + L) * HLM_SCR + i] + scr[(3 * 64 + L) * HLM_SCR + i]);
-    const int kp = 8 * (i >> 2) + 4 * (L >> 5) + (i & 3);  // row k' of dW, column (input channel) L % 32
-    wp[kp * 32 + (L & 31)] = s;
-  }
-  if (tid < NDB) {
-    const int hh = tid < 16 ? tid >> 3 : 0, idx = tid < 16 ? NV + (tid & 7) : NV + 8 + (tid - 16);
-    wp[1024 + tid] = hlm_lane_sum(scr, hh, idx);
-  }
-}
-
-// (ds_head.hip includes this file for everything above and xor32_max below, with MEDNET_HEAD_BLOCKS_ONLY set: the kernels and the
-//  host side of this file are compiled in head_mfma.o alone)
-#ifndef MEDNET_HEAD_BLOCKS_ONLY
 // CE: the class term is nn.CrossEntropyLoss(weight, ignore_index) (landmarks.py:49) instead of Dice: the forward accumulates
 // ce_fwd_kernel's {sum w_y nll, sum w_y} and, for dice_metric (loss.py:51-55), the unweighted, unmasked softmax sums {I, D} into
 // dice_partial; the backward's class gradient is ce_bwd_kernel's closed form (dcls / sum w) w_y (p_k - [k == y]).  Softmax only.
@@ -307,13 +86,13 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
   // the classes in acc[8..11]: row i = 8q + 4hh + t -> q 0/1: heat map 8hh + 4q + t; q 2, hh 0: class t
   const HlmRow r(lane);
   const int lrow = r.q < 2 ? (r.out() < a.nh ? r.out() : -1) : ((r.q == 2 && r.hh == 0 && r.t < a.ncls) ? a.nh + r.t : -1);
-  if (wv == 0) hlm_logit_operands(wops, a.W, lrow, lane);
+  if (wv == 0) hlm_logit_operands(wops, a.W, lrow, lane, 32, 0);
   // dz^T [channel row i][voxel]: row i = 8q + 4hh + t stands for channel (q / 2) * 16 + 8hh + (q % 2) * 4 + t, so that lane
   // (g, h) receives channels 8h .. 8h+7 in acc[0..7] and 16+8h .. in acc[8..15]; k-slots 8h + e: block 0 = heat map 8h + e,
   // block 1 = class e (lanes of h = 0)
   if (BWD && wv == 1) {
-    hlm_dz_operand(wops[4][lane], wops[6][lane], a.W, 8 * h, a.nh - 8 * h, r.channel());
-    hlm_dz_operand(wops[5][lane], wops[7][lane], a.W, a.nh, h == 0 ? a.ncls : 0, r.channel());
+    hlm_dz_operand(wops[4][lane], wops[6][lane], a.W, 8 * h, a.nh - 8 * h, r.channel(), 32, 0);
+    hlm_dz_operand(wops[5][lane], wops[7][lane], a.W, a.nh, h == 0 ? a.ncls : 0, r.channel(), 32, 0);
   }
   // ---- constants of a lane half, in LDS (they would hold 36 registers for the whole kernel): per h the biases of its 8 heat maps
   // [0..7] and of the classes [8..11], the heat maps' gradient scales [12..19] and the Dice gradient terms gI [20..23], gD [24..27]
@@ -626,65 +405,33 @@ __global__ __launch_bounds__(256) void head_lm_wfinal_kernel(const float* __rest
     else if (db) db[o - m * 32] = (float)t;
   }
 }
-#endif  // MEDNET_HEAD_BLOCKS_ONLY
 
 // ---- the segmentation head: 32 features -> ncls classes, 5 <= ncls <= 16, fused with DiceLoss (loss.py:114-130) or
 // nn.CrossEntropyLoss (segmentation.py:49) ---------------------------------------------------------------------------------
-// head_lm_kernel's heat-map rows carrying the classes: lane (g, h) holds, of its voxels 4g .. 4g+3, the logits of classes 8h .. 8h+7
-// in acc[0..7] (weight rows of classes >= ncls are zero), so a voxel's classes live in the two lanes l and l ^ 32.  The softmax
-// exchanges the half maximum and the half sum of those two lanes with v_permlane32_swap (common.h: plain VALU, no LDS queue); the
-// Dice backward exchanges sum_k p_k g_k, the CE backward the label's weight, the same way.  Every exchange runs with all 64 lanes
-// active, on predicated values (a dead lane's logits are the biases: finite).  HlmArgs with nh = 0: `ncls` classes, no targets.
+// head_lm_kernel's heat-map rows carrying the classes in the wide-class layout of head_blocks.inc (classes 8h .. 8h+7 in lane half h;
+// the hsg_* blocks are the per-voxel loss arithmetic).  HlmArgs with nh = 0: `ncls` classes, no targets.
 //   forward   {I, D} per class (dice_finalize_kernel's rows) or {sum w_y nll, sum w_y} (ce_finalize_kernel's rows)
 //   backward  logits rebuilt, dl from dice_bwd_kernel's / ce_bwd_kernel's closed form, dz^T = W^T dl^T stored once, dW through the
 //             wave-private tiles (dl columns 0 .. 15; 16 .. 31 stay zero), db by lane sums, GroupNorm-3's first pass from the stored rows.
-constexpr int HSG_MAXC = 16;
-
-__device__ __forceinline__ float xor32_max(float v) {  // max(v(l), v(l ^ 32)) in every lane: xor32_sum's idiom
-  float a = v, b = v;
-  MEDNET_SWAP_PAIR("v_permlane32_swap_b32", a, b);
-  return fmaxf(a, b);
-}
-#ifndef MEDNET_HEAD_BLOCKS_ONLY
-
 // Dice + CE (HLM_DICE_CE, softmax, no ignore_index): the forward keeps the Dice accumulators in registers and the CE sums in the idle
 // LDS slot; the backward adds the two closed forms, with w_k dloss / sum w in eight more constants of the lane half.
 template <bool BWD, int KIND>
 __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
-  constexpr bool CE = KIND == HLM_CE;
-  constexpr int NCST = (BWD && KIND == HLM_DICE_CE) ? 32 : 24;
   __shared__ __attribute__((aligned(16))) char smem[256 * HLM_SCR * 4];
-  __shared__ float cst[2][NCST];
+  __shared__ float cst[2][HSG_NCST<BWD, KIND>];
   __shared__ u32x4 wops[6][64];  // 0,1: logits hi (k-steps); 2,3: lo; 4: dz hi; 5: dz lo
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane & 31, h = lane >> 5;
   const int n = blockIdx.y, chunk = blockIdx.x;
   const int nv = min(8, max(0, a.ncls - 8 * h));  // classes of this lane half
+  const HsgLoss c = {a.bias, a.cls_weight, a.saved, a.dcls, a.eps, a.ncls, a.sigmoid, a.ignore};
 
-  // ---- weight operands (head_lm_kernel's, the classes in the heat maps' place) ----------------------------------------------
+  // ---- weight operands (head_lm_kernel's, the classes in the heat maps' place) and the constants of a lane half ---------------
   const HlmRow r(lane);
-  if (wv == 0) hlm_logit_operands(wops, a.W, (r.q < 2 && r.out() < a.ncls) ? r.out() : -1, lane);
-  if (BWD && wv == 1) hlm_dz_operand(wops[4][lane], wops[5][lane], a.W, 8 * h, a.ncls - 8 * h, r.channel());
-  // ---- constants of a lane half: the biases of its 8 classes [0..7]; CE forward: the class weights [8..15]; CE backward:
-  // w_k dloss / sum w [8..15]; Dice backward: gI [8..15], gD [16..23] (dice_bwd_kernel); Dice + CE: the forward as CE, the backward as
-  // Dice and w_k dloss / sum w [24..31]
-  if (wv == 2 && (lane & 31) < NCST) {
-    const int hh = lane >> 5, i = lane & 31, k = 8 * hh + (i & 7);
-    float v = 0.f;
-    if (k < a.ncls) {
-      const float w = a.cls_weight ? a.cls_weight[k] : 1.f;
-      if (i < 8) v = a.bias ? a.bias[k] : 0.f;
-      else if (KIND == HLM_DICE_CE && !BWD) v = i < 16 ? w : 0.f;
-      else if (KIND == HLM_DICE_CE && i >= 24) v = w * (*a.dcls / a.saved[2 * a.ncls]);
-      else if (CE) v = i < 16 ? (BWD ? w * (*a.dcls / a.saved[0]) : w) : 0.f;
-      else if (BWD) {
-        const float I = a.saved[2 * k], D = a.saved[2 * k + 1];
-        v = i < 16 ? hlm_dice_gI(w, I, D, a.eps, a.ncls, *a.dcls) : hlm_dice_gD(w, I, D, a.eps, a.ncls, *a.dcls);
-      }
-    }
-    cst[hh][i] = v;
-  }
+  if (wv == 0) hlm_logit_operands(wops, a.W, (r.q < 2 && r.out() < a.ncls) ? r.out() : -1, lane, 32, 0);
+  if (BWD && wv == 1) hlm_dz_operand(wops[4][lane], wops[5][lane], a.W, 8 * h, a.ncls - 8 * h, r.channel(), 32, 0);
+  if (wv == 2) hsg_constants<BWD, KIND>(cst, lane, c);
   __syncthreads();
   const u32x4* wbase = &wops[0][lane];
   const float* cbase = &cst[h][0];
@@ -735,114 +482,14 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
       }
       const int yl = (int)((lb >> (8 * j)) & 0xFFu);
       const int yk = yl - 8 * h;  // the label's slot in this half, if in 0 .. nv-1
-      float lse = 0.f;
-      if (a.sigmoid) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) p[e] = e < nv ? 1.f / (1.f + expf(-lc[e])) : 0.f;
-      } else {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (e < nv) mx = fmaxf(mx, lc[e]);
-        mx = xor32_max(mx);
-        float den = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          p[e] = e < nv ? expf(lc[e] - mx) : 0.f;
-          den += p[e];
-        }
-        den = xor32_sum(den);
-        const float inv = 1.f / den;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) p[e] *= inv;
-        if (KIND != HLM_DICE) lse = mx + logf(den);
-      }
+      float lse;
+      hsg_probs<KIND>(lc, nv, a.sigmoid, p, lse);
       if constexpr (!BWD) {
-        if constexpr (KIND != HLM_DICE) {
-          // ce_fwd_kernel; the half that owns the label's class takes the voxel's term
-          if (live && h == 0 && yl != a.ignore && yl >= a.ncls) ce_acc[0] = __builtin_nanf("");
-          if (live && yl != a.ignore && yk >= 0 && yk < nv) {
-            float zy = 0.f, w = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-              if (e == yk) {
-                zy = lc[e];
-                w = cbase[8 + e];
-              }
-            ce_acc[0] = fmaf(w, lse - zy, ce_acc[0]);
-            ce_acc[1] += w;
-          }
-        }
-        if constexpr (!CE) {
-          bad |= live && yl >= a.ncls;
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (e < nv) {
-              const float t = (e == yk) ? 1.f : 0.f;
-              const float mk = (!live || (a.ignore != MEDNET_NO_IGNORE && t == (float)a.ignore)) ? 0.f : 1.f;
-              dI[e] = fmaf(p[e] * mk, t * mk, dI[e]);
-              dD[e] += (p[e] + t) * mk;
-            }
-        }
+        hsg_fwd_terms<KIND>(c, p, lc, lse, yl, yk, nv, live, h, cbase, ce_acc, dI, dD, bad);
       } else {
-        float dc[8];
-        if constexpr (CE) {
-          float wy = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (e == yk) wy = cbase[8 + e];  // (0 for classes >= ncls)
-          wy = xor32_sum(wy);                // (the other half's lane has 0)
-          wy = (live && yl != a.ignore && yl < a.ncls) ? wy : 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            dc[e] = e < nv ? wy * (p[e] - (e == yk ? 1.f : 0.f)) : 0.f;
-            dbc[e] += dc[e];
-          }
-        } else if constexpr (KIND == HLM_DICE_CE) {
-          float gg[8], dot = 0.f, wy = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float t = (e == yk) ? 1.f : 0.f;
-            gg[e] = e < nv ? cbase[8 + e] * t + cbase[16 + e] : 0.f;
-            dot = fmaf(p[e], gg[e], dot);
-            if (e == yk) wy = cbase[24 + e];  // (0 for classes >= ncls)
-          }
-          dot = xor32_sum(dot);
-          wy = xor32_sum(wy);  // (the other half's lane has 0)
-          wy = (live && yl < a.ncls) ? wy : 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float dl_dice = p[e] * (gg[e] - dot);
-            const float dl_ce = wy * (p[e] - (e == yk ? 1.f : 0.f));
-            dc[e] = (live && e < nv) ? dl_dice + dl_ce : 0.f;
-            dbc[e] += dc[e];
-          }
-        } else {
-          float gg[8], dot = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float t = (e == yk) ? 1.f : 0.f;
-            const float mk = (a.ignore != MEDNET_NO_IGNORE && t == (float)a.ignore) ? 0.f : 1.f;
-            gg[e] = e < nv ? mk * (cbase[8 + e] * t * mk + cbase[16 + e]) : 0.f;
-            dot = fmaf(p[e], gg[e], dot);
-          }
-          if (!a.sigmoid) dot = xor32_sum(dot);  // (uniform)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float v = a.sigmoid ? gg[e] * p[e] * (1.f - p[e]) : p[e] * (gg[e] - dot);
-            dc[e] = (live && e < nv) ? v : 0.f;
-            dbc[e] += dc[e];
-          }
-        }
         eltx8 dc_hi, dc_lo;
-        hlm_split(dc, dc_hi, dc_lo);
-        // ---- dz^T = W^T dl^T: hi hi, lo hi, hi lo
-        f32x16 dzv;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dzv[i] = 0.f;
-        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 4), dc_hi, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 5), dc_hi, dzv, 0, 0, 0);
-        dzv = MEDNET_MFMA_32x32x16(hlm_wop(wbase, 4), dc_lo, dzv, 0, 0, 0);
+        hsg_logit_grad<KIND>(c, p, yl, yk, nv, live, cbase, dbc, dc_hi, dc_lo);
+        const f32x16 dzv = hlm_dz(hlm_wop(wbase, 4), hlm_wop(wbase, 5), dc_hi, dc_lo);
         hlm_store_dz(dzv, dzs + (vb + j) * 32 + 8 * h, live, ys != nullptr, rows.zp[j], rows.yp[j & 1], a.gn_act, ss, sq);
         tiles.dw_step(g, h, rows.zp[j], dc_hi, dc_lo, nullptr, nullptr, accw);  // dW += dl^T z over these 32 voxels
       }
@@ -851,31 +498,11 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
 
   // ---- end of kernel: lane and wave sums through LDS in a fixed order -----------------------------------------------
   float* scr = reinterpret_cast<float*>(smem);
-  float* mine = scr + tid * HLM_SCR;
   __syncthreads();
   if constexpr (!BWD) {
-    if constexpr (KIND != HLM_DICE) {  // values 16 / 17 of every thread are its ce_acc
-      if (tid < 2) {
-        float s = 0.f;
-        for (int t = 0; t < 256; ++t) s += scr[t * HLM_SCR + 16 + tid];
-        a.ce_partial[((size_t)n * a.chunks + chunk) * 2 + tid] = s;
-      }
-    }
-    if constexpr (!CE) {
-      if (bad) dI[0] = dD[0] = __builtin_nanf("");
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        mine[e] = dI[e];
-        mine[8 + e] = dD[e];
-      }
-      __syncthreads();
-      if (tid < 2 * HSG_MAXC) {  // class k = 8hh + e: lanes of half hh, value e (I) / 8 + e (D)
-        const int k = tid >> 1, which = tid & 1;
-        const float s = hlm_lane_sum(scr, k >> 3, 8 * which + (k & 7));
-        if (k < a.ncls) a.dice_partial[(((size_t)n * a.chunks + chunk) * a.ncls + k) * 2 + which] = s;
-      }
-    }
+    hsg_fwd_writeout<KIND>(scr, tid, dI, dD, bad, a.ce_partial, a.dice_partial, (size_t)n * a.chunks + chunk, a.ncls);
   } else {
+    float* mine = scr + tid * HLM_SCR;
     if (a.gn_partial) hlm_gn_writeout(scr, tid, ss, sq, a.gn_partial + ((size_t)n * a.chunks + chunk) * 64);
     // head_lm_kernel's rows: dW row k' = class k' (accumulator values 0 .. 7 of a lane; 8 .. 15 are the zero rows 16 .. 31, which
     // head_lm_wfinal_kernel never reads with ncls = 0), db at 1024 + k'
@@ -887,6 +514,7 @@ __global__ __launch_bounds__(256, 2) void head_seg_kernel(HlmArgs a) {
     hlm_dw_db_writeout<8, HSG_MAXC>(scr, tid, a.wpart + ((size_t)n * a.chunks + chunk) * HLM_WIDTH);
   }
 }
+
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 bool head_lm_supported(int cin, int nh, int ncls, int dtype, size_t spatial) {
@@ -962,10 +590,10 @@ int launch_head_lm_bwd(const void* z, const float* W, const float* bias, const v
                     head_lm_ws_bytes(n, spatial, nh, ncls));
   if (rc) return rc;
   a.reg_weight = reg_weight; a.dreg = dreg; a.inv_count = (float)(1.0 / ((double)n * (double)spatial));
-  if (ce == HLM_DICE_CE) hipLaunchKernelGGL((head_lm_kernel<true, HLM_DICE_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else if (ce) hipLaunchKernelGGL((head_lm_kernel<true, HLM_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((head_lm_kernel<true, HLM_DICE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  rc = check_launch(ce == HLM_DICE_CE ? "head_lm_dice_ce_bwd" : ce ? "head_lm_ce_bwd" : "head_lm_bwd");
+  for_class_kind(ce, [&](auto kind) {
+    hipLaunchKernelGGL((head_lm_kernel<true, decltype(kind)::value>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  });
+  rc = check_launch(MEDNET_CLASS_KIND_NAME(ce, "head_lm", "_bwd"));
   if (rc) return rc;
   const int total = (nh + ncls) * 33;
   hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((total + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, nh, ncls, dw, db);
@@ -989,14 +617,11 @@ int launch_head_seg_fwd(const void* z, const float* W, const float* bias, const 
   if (rc) return rc;
   a.logits = logits;
   (ce == HLM_CE ? a.ce_partial : a.dice_partial) = partial;
-  if (ce == HLM_DICE_CE) {  // the Dice rows, behind all of them the CE rows
-    a.ce_partial = partial + (size_t)n * a.chunks * ncls * 2;
-    hipLaunchKernelGGL((head_seg_kernel<false, HLM_DICE_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-    return check_launch("head_seg_dice_ce_fwd");
-  }
-  if (ce) hipLaunchKernelGGL((head_seg_kernel<false, HLM_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((head_seg_kernel<false, HLM_DICE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  return check_launch(ce ? "head_seg_ce_fwd" : "head_seg_fwd");
+  if (ce == HLM_DICE_CE) a.ce_partial = partial + (size_t)n * a.chunks * ncls * 2;  // the Dice rows, behind all of them the CE rows
+  for_class_kind(ce, [&](auto kind) {
+    hipLaunchKernelGGL((head_seg_kernel<false, decltype(kind)::value>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  });
+  return check_launch(MEDNET_CLASS_KIND_NAME(ce, "head_seg", "_fwd"));
 }
 int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const void* lab, int64_t lab_sn, const float* saved,
                         const float* cls_weight, const float* dloss, float eps, void* dz, const void* gn_y, int gn_act,
@@ -1007,14 +632,13 @@ int launch_head_seg_bwd(const void* z, const float* W, const float* bias, const 
   if (rc) return rc;
   rc = hlm_bwd_args(a, "head_seg_bwd", saved, dloss, eps, dz, gn_y, gn_act, gn_partial, ws, ws_bytes, head_seg_ws_bytes(n, spatial, ncls));
   if (rc) return rc;
-  if (ce == HLM_DICE_CE) hipLaunchKernelGGL((head_seg_kernel<true, HLM_DICE_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else if (ce) hipLaunchKernelGGL((head_seg_kernel<true, HLM_CE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((head_seg_kernel<true, HLM_DICE>), dim3(a.chunks, n), dim3(256), 0, s, a);
-  rc = check_launch(ce == HLM_DICE_CE ? "head_seg_dice_ce_bwd" : ce ? "head_seg_ce_bwd" : "head_seg_bwd");
+  for_class_kind(ce, [&](auto kind) {
+    hipLaunchKernelGGL((head_seg_kernel<true, decltype(kind)::value>), dim3(a.chunks, n), dim3(256), 0, s, a);
+  });
+  rc = check_launch(MEDNET_CLASS_KIND_NAME(ce, "head_seg", "_bwd"));
   if (rc) return rc;
   hipLaunchKernelGGL(head_lm_wfinal_kernel, dim3((ncls * 33 + 15) / 16), dim3(256), 0, s, a.wpart, n * a.chunks, ncls, 0, dw, db);
   return check_launch("head_seg_wfinal");
 }
-#endif  // MEDNET_HEAD_BLOCKS_ONLY
 
 }  // namespace mednet

@@ -517,6 +517,12 @@ int launch_dice_ce_finalize(const float* partial, const float* partial_ce, const
   hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(256), 0, s, partial, partial_ce, weight, loss, saved, dice_out, c, nblocks, eps);
   return check_launch("dice_ce_finalize");
 }
+int launch_class_finalize(int kind, const float* dice_partial, const float* ce_partial, const float* weight, float* loss, float* saved,
+                          int c, int rows, float eps, hipStream_t s) {
+  if (kind == MEDNET_CLASS_DICE_CE) return launch_dice_ce_finalize(dice_partial, ce_partial, weight, loss, saved, c, rows, eps, s, nullptr);
+  if (kind == MEDNET_CLASS_CE) return launch_ce_finalize(ce_partial, loss, saved, rows, s);
+  return launch_dice_finalize(dice_partial, weight, loss, saved, c, rows, eps, s, nullptr);
+}
 
 }  // namespace mednet
 

@@ -1513,6 +1513,27 @@ def head_dice_ce(x, weight, bias, packed, labels, loss_weight=None, eps=1e-5):
     return HeadDiceCEFn.apply(x, weight, bias, packed, labels, loss_weight, eps)
 
 
+def _class_head_fwd(ctx, name, what, x, weight, bias, packed, labels, loss_weight, eps, sigmoid, ignore_index, class_kind, launch):
+    """What the forwards of the matrix-core class heads (HeadSegFn, DsHeadFn) do alike: the label check, the loss operands, the
+    outputs, and what the backward (_HeadBackward) finds on ctx.  `what`: None, or what is wrong with the labels' shape;
+    `launch(wt, ii, loss, saved)` runs the node's forward entry -> (labels as passed to it, their sample stride, the node's own
+    entries of ctx.meta).  -> loss."""
+    if labels.dtype != torch.uint8 or what is not None:
+        raise RuntimeError(f"{name}: labels must be {what or 'uint8'}, not {labels.dtype} (see {name}_supported)")
+    ncls = weight.shape[0]
+    wt = _loss_weight(loss_weight, x.device)
+    nsaved, ii = _class_operands(class_kind, ncls, sigmoid, ignore_index, name)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    saved = torch.empty((ncls, 2) if nsaved == 2 * ncls else (nsaved,), dtype=torch.float32, device=x.device)
+    lab, lab_sn, extra = launch(wt, ii, loss, saved)
+    ctx.save_for_backward(x, packed, lab, wt, saved)
+    ctx.meta = (eps, int(sigmoid), ii, lab_sn, ncls, class_kind) + extra
+    ctx.params = (weight, bias)
+    if debug.TRACE is not None:
+        debug.trace(name + ".fwd", loss, saved)
+    return loss
+
+
 def head_seg_supported(x: torch.Tensor, cin: int, ncls: int, labels: torch.Tensor) -> bool:
     """Does the matrix-core segmentation head (5 .. 16 classes, 16-bit storage, uint8 labels) take this head?"""
     return _head_supported(x, labels, mfma=True) and bool(L.lib().mednet_head_seg_supported(cin, ncls, L.dt(x), L.U8, x[0, 0].numel()))
@@ -1532,27 +1553,22 @@ class HeadSegFn(Function):
         n, cin, d, h, w = x.shape
         ncls = weight.shape[0]
         spatial = d * h * w
-        if labels.dtype != torch.uint8:
-            raise RuntimeError(f"head_seg: labels must be uint8, not {labels.dtype} (see head_seg_supported)")
-        lab, lab_sn = _aligned4(*_label_view(labels, n, (d, h, w))[:2])
-        wt = _loss_weight(loss_weight, x.device)
-        nsaved, ii = _class_operands(class_kind, ncls, sigmoid, ignore_index, "head_seg")
         logits = torch.empty((n, ncls, d, h, w), dtype=torch.float32, device=x.device) if want_logits else None
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        saved = torch.empty((ncls, 2) if nsaved == 2 * ncls else (nsaved,), dtype=torch.float32, device=x.device)
         lib = L.lib()
         ws = L.workspace(lib.mednet_head_seg_ws_bytes(n, spatial, ncls), x.device)
-        L.check(lib.mednet_head_seg_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_sn, L.ptr(wt), L.ptr(logits),
-                                        loss.data_ptr(), saved.data_ptr(), n, spatial, cin, ncls, class_kind, eps, int(sigmoid), ii,
-                                        L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_seg_fwd")
-        ctx.save_for_backward(x, packed, lab, wt, saved)
-        ctx.meta = (eps, int(sigmoid), ii, lab_sn, ncls, class_kind)
-        ctx.params = (weight, bias)
+
+        def launch(wt, ii, loss, saved):
+            lab, lab_sn = _aligned4(*_label_view(labels, n, (d, h, w))[:2])
+            L.check(lib.mednet_head_seg_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), lab_sn, L.ptr(wt), L.ptr(logits),
+                                            loss.data_ptr(), saved.data_ptr(), n, spatial, cin, ncls, class_kind, eps, int(sigmoid), ii,
+                                            L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "head_seg_fwd")
+            return lab, lab_sn, ()
+
+        loss = _class_head_fwd(ctx, "head_seg", None, x, weight, bias, packed, labels, loss_weight, eps, sigmoid, ignore_index,
+                               class_kind, launch)
         ctx.gn3 = _gn3_hook_of(x, x.dtype)
         if logits is not None:
             ctx.mark_non_differentiable(logits)
-        if debug.TRACE is not None:
-            debug.trace("head_seg.fwd", loss, saved)
         return logits, loss
 
     @staticmethod
@@ -1606,27 +1622,22 @@ class DsHeadFn(Function):
         L.require_gpu(x, "ds_head")
         n, cin, d, h, w = x.shape
         ncls = weight.shape[0]
-        if labels.dtype != torch.uint8 or labels.dim() != 4:
-            raise RuntimeError(f"ds_head: labels must be a uint8 N x D x H x W volume, not {labels.dtype} (see ds_head_supported)")
         full = tuple(labels.shape[1:])
-        lab, lab_sn = _label_view(labels, n, full)[:2]  # (byte loads: no alignment rule)
-        wt = _loss_weight(loss_weight, x.device)
-        nsaved, ii = _class_operands(class_kind, ncls, sigmoid, ignore_index, "ds_head")
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        saved = torch.empty((ncls, 2) if nsaved == 2 * ncls else (nsaved,), dtype=torch.float32, device=x.device)
         lib = L.lib()
         ws = L.workspace(lib.mednet_ds_head_ws_bytes(n, d, h, w, cin, ncls), x.device)
-        L.check(lib.mednet_ds_head_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), L.U8, lab_sn, L.ptr(wt),
-                                       loss.data_ptr(), saved.data_ptr(), n, d, h, w, *full, shift, cin, ncls, class_kind, eps,
-                                       int(sigmoid), ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "ds_head_fwd")
-        ctx.save_for_backward(x, packed, lab, wt, saved)
-        ctx.meta = (eps, int(sigmoid), ii, lab_sn, ncls, class_kind, full, shift)
-        ctx.params = (weight, bias)
+
+        def launch(wt, ii, loss, saved):
+            lab, lab_sn = _label_view(labels, n, full)[:2]  # (byte loads: no alignment rule)
+            L.check(lib.mednet_ds_head_fwd(x.data_ptr(), packed.data_ptr(), L.ptr(bias), lab.data_ptr(), L.U8, lab_sn, L.ptr(wt),
+                                           loss.data_ptr(), saved.data_ptr(), n, d, h, w, *full, shift, cin, ncls, class_kind, eps,
+                                           int(sigmoid), ii, L.dt(x), ws.data_ptr(), ws.numel(), L.stream()), "ds_head_fwd")
+            return lab, lab_sn, (full, shift)
+
+        loss = _class_head_fwd(ctx, "ds_head", None if labels.dim() == 4 else "a uint8 N x D x H x W volume", x, weight, bias, packed,
+                               labels, loss_weight, eps, sigmoid, ignore_index, class_kind, launch)
         rows = lib.mednet_ds_head_gn_rows(d, h, w, cin, L.dt(x))
         ctx.gn3 = _gn3_hook_of(x, x.dtype) if rows > 0 else None
         ctx.gn_rows = rows
-        if debug.TRACE is not None:
-            debug.trace("ds_head.fwd", loss, saved)
         return x.view_as(x), loss
 
     @staticmethod
