@@ -77,7 +77,7 @@ def test_fused_head_ce_against_the_unfused_launches(mode, cin, cout, shape, n, l
 
 
 def test_fused_head_ce_out_of_range_label_poisons_the_loss():
-    """A label outside [0, C) that is not ignore_index: NaN loss (ce_fwd_kernel's rule), an ignored one changes nothing."""
+    """A label outside [0, C) that is not ignore_index: NaN loss (class_loss_fwd_kernel<CE>'s rule), an ignored one changes nothing."""
     with mednet_hip.precision("bf16"):
         conv = hnn.Conv3d(32, 2, 1, planar_output=True).to(DEV)
         x = ops.to_cl(rnd("hce-bad", 2, 32, 8, 8, 8).to(DEV).bfloat16())
@@ -310,7 +310,7 @@ def test_landmark_ce_step_repeats_bit_for_bit_at_the_timed_shape():
 def test_landmark_ce_head_honours_ignore_index_and_poisons_bad_labels(mode):
     """ops.head_landmark(class_loss="CE") with an ignore_index that occurs (class 1 of the uint8 labels) against the unfused launches
     (ops.cross_entropy with the same ignore_index): the same loss, ignored voxels contribute no gradient; a label outside [0, ncls)
-    that is not ignore_index makes the class loss NaN (ce_fwd_kernel's rule)."""
+    that is not ignore_index makes the class loss NaN (class_loss_fwd_kernel<CE>'s rule)."""
     from mednet_hip.unet import loss as HL
     nh, ncls = 3, 2
     net_kw = dict(in_channels=1, out_channels=nh + ncls, final_sigmoid=False, f_maps=[32, 64])

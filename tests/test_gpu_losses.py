@@ -191,7 +191,7 @@ def test_cross_entropy_on_exact_terms_is_exact(key, n, c, ignore, ignored):
         P = Placed(case.lg, layout)
         loss, saved, _ = run_ce(P, case.lab, case.w, ignore, 1.0, bwd=False)
         U.check_ce_exact(ref, loss, saved[0], f"CE {key} n={n} C={c} ignore={ignore} ({ignored}) {layout}")
-    print(f"[exact] item=loss CE exact {key} n={n} C={c} ignore={ignore} ({ignored}) kernel=ce_fwd_kernel,ce_finalize_kernel "
+    print(f"[exact] item=loss CE exact {key} n={n} C={c} ignore={ignore} ({ignored}) kernel=class_loss_fwd_kernel<CE>,ce_finalize_kernel "
           f"saved[0]: bit-exact loss: bit-exact ({ref.loss32!r})")
 
 
@@ -215,7 +215,7 @@ def test_dice_on_dyadic_probabilities_is_exact(key, n, c, sigmoid):
             loss, saved, dice, _ = run_dice(P, lab, lab_dt, lab_sn, case.w, case.eps, sigmoid, ignore, 1.0, bwd=False)
             what = f"Dice exact {key} n={n} C={c} sigmoid={int(sigmoid)} ignore={ignore} {layout} labels={LABEL_LAYOUTS[(i - 1) % 3]}"
             worst = max(worst, U.check_dice_exact(case, ref, saved, dice, loss, what))
-    print(f"[exact] item=loss Dice exact {key} n={n} C={c} sigmoid={int(sigmoid)} kernel=dice_fwd_kernel,dice_finalize_kernel saved: bit-exact "
+    print(f"[exact] item=loss Dice exact {key} n={n} C={c} sigmoid={int(sigmoid)} kernel=class_loss_fwd_kernel<DICE>,dice_finalize_kernel saved: bit-exact "
           f"loss: bound {c + 4} roundings seen {worst:.2f}")
 
 
@@ -254,7 +254,7 @@ def test_dice_against_fp64_per_element(key, n, c, edge):
         loss, saved, _, dlg = run_dice(P, lab, lab_dt, lab_sn, case.w, case.eps, sigmoid, ignore, case.dloss)
         seen = U.check_dice_random(case, r64, norm, eps_case, saved, loss, dlg, what + " " + layout)
         assert P.outside_is_untouched(), what + ": the gradient buffer was written outside the channel slice"
-        print(f"[exact] item=loss {what} {layout} kernel=dice_fwd_kernel,dice_finalize_kernel,dice_bwd_kernel saved: bound {U.LOSS_SUM_BOUND:.2e} "
+        print(f"[exact] item=loss {what} {layout} kernel=class_loss_fwd_kernel<DICE>,dice_finalize_kernel,class_loss_bwd_kernel<DICE> saved: bound {U.LOSS_SUM_BOUND:.2e} "
               f"seen {seen['saved']:.2e} loss: seen {seen['loss']:.2e} dlogits: r32 {e32:.2e} eps {eps_case:.2e} seen {seen['dlg']:.2e}")
 
 
@@ -271,7 +271,7 @@ def test_cross_entropy_against_fp64_per_element(key, n, c, edge):
         loss, saved, dlg = run_ce(P, U.ce_labels(case, ignore), case.w, ignore, case.dloss)
         seen = U.check_ce_random(case, r64, eps_case, saved[0], loss, dlg, what + " " + layout)
         assert P.outside_is_untouched(), what + ": the gradient buffer was written outside the channel slice"
-        print(f"[exact] item=loss {what} {layout} kernel=ce_fwd_kernel,ce_finalize_kernel,ce_bwd_kernel saved: bound {U.LOSS_SUM_BOUND:.2e} "
+        print(f"[exact] item=loss {what} {layout} kernel=class_loss_fwd_kernel<CE>,ce_finalize_kernel,class_loss_bwd_kernel<CE> saved: bound {U.LOSS_SUM_BOUND:.2e} "
               f"seen {seen['saved']:.2e} loss: seen {seen['loss']:.2e} dlogits: r32 {e32:.2e} eps {eps_case:.2e} seen {seen['dlg']:.2e}")
 
 

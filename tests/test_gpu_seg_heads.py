@@ -181,7 +181,7 @@ def test_seg_head_logits_are_exact_on_lattice_inputs(mode, c):
 
 @pytest.mark.parametrize("kind", ["DICE", "CE"])
 def test_seg_head_out_of_range_label_poisons_the_loss(kind):
-    """A uint8 label of 200 with 14 classes: NaN loss (dice_fwd_kernel's / ce_fwd_kernel's rule), nothing indexed out of range, the
+    """A uint8 label of 200 with 14 classes: NaN loss (class_loss_fwd_kernel<DICE>'s / class_loss_fwd_kernel<CE>'s rule), nothing indexed out of range, the
     backward still runs and fills gradients of the right shapes."""
     with mednet_hip.precision("bf16"):
         conv = hnn.Conv3d(32, 14, 1, planar_output=True).to(DEV)

@@ -1,5 +1,6 @@
 """SHA-256 digests of what the fused head + loss nodes compute -- the matrix-core landmark head (ops.head_landmark / _eval), the
-matrix-core segmentation head for 5-16 classes (ops.head_seg) and the VALU heads for <= 4 classes (ops.head_dice / ops.head_ce) -- on
+matrix-core segmentation head for 5-16 classes (ops.head_seg), the VALU heads for <= 4 classes (ops.head_dice / ops.head_ce /
+ops.head_dice_ce) and the stand-alone class losses (ops.dice_loss / cross_entropy / dice_ce_loss / per_channel_dice) -- on
 seeded random fp32 inputs that are NOT numbers of the storage type: two commits whose kernels run the same arithmetic in the same
 order print the same lines.  Only the package's public surface is used, so the tool runs against any commit's package and library:
 HD_PKG=<directory that holds that commit's mednet_hip/> MEDNET_LIB_PATH=<its libmednet_hip.so> python tools/head_digest.py
@@ -16,13 +17,19 @@ n = 2 (10080 voxels: two chunks, the second short with a ragged last run).
 Cases.  landmark (bf16, fp16): (nh, ncls, regression) in {(16, 2, L2), (5, 3, L1), (1, 4, L2)} x class loss Dice softmax / Dice
 sigmoid / CE x class and regression weights on / off, one ignore_index case per class loss; head_landmark_eval on the same inputs is
 part of every softmax case without a Dice mask.  seg (bf16, fp16): C in {5, 8, 9, 16} x the three losses x want_logits x weights,
-one ignore_index case per loss, labels at an odd byte offset once per loss.  valu (fp32, bf16, fp16): head_dice / head_ce x cin in
-{16, 32, 64} x C in {1, 4} x uint8 / int64 labels.  ds (bf16, fp16; the deep-supervision node ops.ds_head, which has its own runs:
+one ignore_index case per loss, labels at an odd byte offset once per loss.  valu (fp32, bf16, fp16): head_dice / head_ce /
+head_dice_ce x cin in {16, 32, 64} x C in {1, 2, 4} x uint8 / int64 labels, and once per loss the features out of a fused conv ->
+ReLU layer (SingleConv 'gcr', the end of UNet3D's last block: the backward that folds the activation's derivative in).  loss (planar
+fp32 logits, the two shapes; tensors: the loss, the gradient of the logits, the metric): dice_loss / cross_entropy / dice_ce_loss /
+per_channel_dice x C in {1, 2, 3, 4, 5, 8, 9, 16, 17, 32} (every class bucket of the kernels at its top and just past its bottom) x
+class weights on / off x uint8 / int64 labels; Dice sigmoid at C in {1, 4}; one ignore_index case for Dice and for CE; once per
+function the logits as a channel slice of a wider tensor, the uint8 labels as the last channel of a label volume, and an
+out-of-range label (the NaN pattern is hashed like anything else).  ds (bf16, fp16; the deep-supervision node ops.ds_head, which has its own runs:
 n = 2, with and without the next decoder's gradient d_pass, tensors loss, dx, dw, db): (level, shift, cin, C) as
 tests/test_gpu_ds_head.py's CASES -- one run of 128 voxels, a ragged run, five workgroups, 2 / 4 / 8 tiles, C in {1, 2, 4, 5, 8, 16} --
 and C = 9 at (6, 6, 6), shift 1, cin 128, x Dice softmax / Dice sigmoid / CE / Dice + CE x weights, one ignore_index case for Dice
 and for CE.
-Usage: python tools/head_digest.py [heads, default landmark,seg,valu; all: landmark,seg,valu,ds] > digest.jsonl"""
+Usage: python tools/head_digest.py [heads, default landmark,seg,valu; all: landmark,seg,valu,ds,loss] > digest.jsonl"""
 import hashlib
 import json
 import os
@@ -86,7 +93,10 @@ def features(form, cin, n, shape):
     if form == "op":
         xg = ops.to_cl(x.to(mednet_hip.config.act_dtype())).requires_grad_(True)
         return xg, xg, None
-    blk = O.keyed_init_(HC.ExtResNetBlock(cin, cin, order="cge", num_groups=8)).to(DEV)
+    if form == "fold":  # GroupNorm -> conv -> ReLU, the conv and the ReLU in one kernel where the mode has it
+        blk = O.keyed_init_(HC.SingleConv(cin, cin, order="gcr", num_groups=8)).to(DEV)
+    else:
+        blk = O.keyed_init_(HC.ExtResNetBlock(cin, cin, order="cge", num_groups=8)).to(DEV)
     return blk(x), None, blk
 
 
@@ -168,26 +178,74 @@ def seg(mode, form, n, shape, c, cl, sig, wtd, ign, wl, odd):
 
 
 def valu_cases():
-    for cl in ("DICE", "CE"):
+    for cl in ("DICE", "CE", "DICE_CE"):
         for cin in (16, 32, 64):
-            for c in (1, 4):
+            for c in (1, 2, 4):
                 for u8 in (True, False):
-                    yield f"valu {cl} cin={cin} C={c} labels={'u8' if u8 else 'i64'}", (cl, cin, c, u8)
+                    yield f"valu {cl} cin={cin} C={c} labels={'u8' if u8 else 'i64'}", (cl, cin, c, u8, False)
+        yield f"valu {cl} cin=32 C=4 labels=u8 fold", (cl, 32, 4, True, True)
 
 
-def valu(mode, form, n, shape, cl, cin, c, u8):
+def valu(mode, form, n, shape, cl, cin, c, u8, fold):
     lab = labels(f"lab{c}", c, n, *shape).to(DEV)
     lab = lab if u8 else lab.long()
-    x, leaf, blk = features(form, cin, n, shape)
+    x, leaf, blk = features("fold" if fold else form, cin, n, shape)
     fc = head_conv(cin, c)
     wt = weights(c).to(DEV)
-    if not (ops.head_dice_supported if cl == "DICE" else ops.head_ce_supported)(x, cin, c, lab):
+    if not getattr(ops, f"head_{cl.lower()}_supported")(x, cin, c, lab):
         raise RuntimeError(f"head_{cl.lower()} does not take this case")
     if cl == "DICE":
         lg, loss = ops.head_dice(x, fc.weight, fc.bias, fc._packed(), lab, wt, 1e-5, c == 1, None)
-    else:
+    elif cl == "CE":
         lg, loss = ops.head_ce(x, fc.weight, fc.bias, fc._packed(), lab, wt, -100)
+    else:
+        lg, loss = ops.head_dice_ce(x, fc.weight, fc.bias, fc._packed(), lab, wt, 1e-5)
     return finish({"loss": digest(loss), "logits": digest(lg)}, loss, leaf, blk, fc, mode)
+
+
+LOSS_C = (1, 2, 3, 4, 5, 8, 9, 16, 17, 32)
+
+
+def loss_cases():
+    for fn in ("dice", "ce", "dice_ce", "metric"):
+        cases = [(c, wtd, u8, False, None, None) for c in LOSS_C for wtd in (True, False) for u8 in (True, False)]
+        if fn in ("dice", "metric"):
+            cases += [(c, True, True, True, None, None) for c in (1, 4)] + [(9, True, True, False, 1, None)]
+        if fn == "ce":
+            cases += [(9, True, True, False, 3, None)]
+        cases += [(5, True, True, False, None, var) for var in ("slice", "labvol", "oor")]
+        for c, wtd, u8, sig, ign, var in cases:
+            yield f"loss {fn} C={c} w={int(wtd)} labels={'u8' if u8 else 'i64'} sig={int(sig)} ign={ign} {var or 'plain'}", (fn, c, wtd, u8, sig, ign, var)
+
+
+def loss(mode, n, shape, fn, c, wtd, u8, sig, ign, var):
+    if var == "slice":  # channels 2 .. 2 + c of a wider tensor: stride_n != c * spatial
+        leaf = (rnd(f"lgw{c}", n, c + 3, *shape) * 3.0).to(DEV).requires_grad_(True)
+        z = leaf[:, 2:2 + c]
+    else:
+        leaf = z = (rnd(f"lg{c}", n, c, *shape) * 3.0).to(DEV).requires_grad_(True)
+    if var == "labvol":  # the last channel of a uint8 label volume: sample stride != spatial
+        lab = labels(f"vol{c}", c, n, 3, *shape).to(DEV)[:, -1]
+    else:
+        lab = labels(f"lab{c}", c, n, *shape).to(DEV)
+    if var == "oor":
+        lab = lab.clone()
+        lab[0, 0, 0, 1] = c
+    lab = lab if u8 else lab.long()
+    wt = weights(c).to(DEV) if wtd else None
+    if fn == "metric":
+        out = {"dice": digest(ops.per_channel_dice(z, lab, wt, 1e-5, sig, ign))}
+        torch.cuda.synchronize()
+        return out
+    if fn == "dice":
+        val = ops.dice_loss(z, lab, wt, 1e-5, sig, ign)
+    elif fn == "ce":
+        val = ops.cross_entropy(z, lab, wt, -100 if ign is None else ign)
+    else:
+        val = ops.dice_ce_loss(z, lab, wt, 1e-5)
+    (val * 3.0).backward()
+    torch.cuda.synchronize()
+    return {"loss": digest(val), "dlogits": digest(leaf.grad)}
 
 
 DS_LEVELS = [((4, 4, 8), 1, 64, 1), ((4, 4, 8), 2, 128, 2), ((4, 4, 8), 3, 256, 4), ((6, 6, 6), 1, 64, 5), ((6, 6, 6), 1, 256, 8),
@@ -227,7 +285,8 @@ def ds(mode, with_pass, lev, s, cin, c, cl, sig, wtd, ign):
 FORMS = [(f"{form}/{sh(shape)}", (form, n, shape)) for form in ("op", "block") for n, shape in SHAPES]
 RUN = {"landmark": (landmark_cases, landmark, ("bf16", "fp16"), FORMS), "seg": (seg_cases, seg, ("bf16", "fp16"), FORMS),
        "valu": (valu_cases, valu, ("fp32", "bf16", "fp16"), FORMS),
-       "ds": (ds_cases, ds, ("bf16", "fp16"), [("d_pass=0", (False,)), ("d_pass=1", (True,))])}
+       "ds": (ds_cases, ds, ("bf16", "fp16"), [("d_pass=0", (False,)), ("d_pass=1", (True,))]),
+       "loss": (loss_cases, loss, ("fp32",), [(sh(shape), (n, shape)) for n, shape in SHAPES])}
 for head in HEADS:
     cases, fn, modes, runs = RUN[head]
     for name, axes in cases():

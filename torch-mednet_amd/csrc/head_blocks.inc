@@ -66,7 +66,7 @@ __device__ __forceinline__ void hlm_dz_operand(u32x4& hi_out, u32x4& lo_out, con
 }
 __device__ __forceinline__ eltx8 hlm_wop(const u32x4* wbase, int i) { return __builtin_bit_cast(eltx8, wbase[i * 64]); }
 
-// loss.hip dice_bwd_kernel's per-class terms: gI (the factor of the one-hot target) and gD
+// loss.hip class_loss_bwd_kernel<DICE>'s per-class terms: gI (the factor of the one-hot target) and gD
 __device__ __forceinline__ float hlm_dice_gI(float w, float I, float D, float eps, int ncls, float gc) {
   return -2.f * w / ((float)ncls * fmaxf(D, eps)) * gc + ((I != I || D != D) ? __builtin_nanf("") : 0.f);
 }
@@ -267,7 +267,7 @@ struct HsgLoss {
 };
 
 // Constants of a lane half, cst[hh][i]: the biases of its 8 classes [0..7]; CE forward: the class weights [8..15]; CE backward:
-// w_k dloss / sum w [8..15]; Dice backward: gI [8..15], gD [16..23] (dice_bwd_kernel); Dice + CE: the forward as CE, the backward as
+// w_k dloss / sum w [8..15]; Dice backward: gI [8..15], gD [16..23] (class_loss_bwd_kernel<DICE>); Dice + CE: the forward as CE, the backward as
 // Dice and w_k dloss / sum w [24..31].  Called by one whole wave.
 template <bool BWD, int KIND>
 constexpr int HSG_NCST = (BWD && KIND == HLM_DICE_CE) ? 32 : 24;
@@ -293,7 +293,7 @@ __device__ __forceinline__ void hsg_constants(float (&cst)[2][NCST], int lane, c
   }
 }
 
-// sigmoid / softmax of a voxel's class logits (loss.hip probs_of on registers), the softmax over both lane halves; `lse` (CE terms):
+// sigmoid / softmax of a voxel's class logits (loss.hip cl_probs on registers), the softmax over both lane halves; `lse` (CE terms):
 // max + log of the softmax's denominator
 template <int KIND>
 __device__ __forceinline__ void hsg_probs(const float (&lc)[8], int nv, int sigmoid, float (&p)[8], float& lse) {
@@ -321,15 +321,15 @@ __device__ __forceinline__ void hsg_probs(const float (&lc)[8], int nv, int sigm
   }
 }
 
-// Forward terms of a voxel with label yl (slot yk = yl - 8h of this half, if in 0 .. nv-1): ce_fwd_kernel's {sum w_y nll, sum w_y} into
-// ce_acc[0..1] (an out-of-range label that is not ignore_index poisons the loss), dice_fwd_kernel's {I, D} into dI / dD (`bad`: an
+// Forward terms of a voxel with label yl (slot yk = yl - 8h of this half, if in 0 .. nv-1): class_loss_fwd_kernel<CE>'s {sum w_y nll, sum w_y} into
+// ce_acc[0..1] (an out-of-range label that is not ignore_index poisons the loss), class_loss_fwd_kernel<DICE>'s {I, D} into dI / dD (`bad`: an
 // out-of-range label, NaN at the end of the kernel)
 template <int KIND>
 __device__ __forceinline__ void hsg_fwd_terms(const HsgLoss& c, const float (&p)[8], const float (&lc)[8], float lse, int yl, int yk,
                                               int nv, bool live, int h, const float* cbase, float* ce_acc, float (&dI)[8],
                                               float (&dD)[8], bool& bad) {
   if constexpr (KIND != HLM_DICE) {
-    // ce_fwd_kernel; the half that owns the label's class takes the voxel's term
+    // class_loss_fwd_kernel<CE>; the half that owns the label's class takes the voxel's term
     if (live && h == 0 && yl != c.ignore && yl >= c.ncls) ce_acc[0] = __builtin_nanf("");
     if (live && yl != c.ignore && yk >= 0 && yk < nv) {
       float zy = 0.f, w = 0.f;
@@ -356,7 +356,7 @@ __device__ __forceinline__ void hsg_fwd_terms(const HsgLoss& c, const float (&p)
   }
 }
 
-// Logit gradient of a voxel, dc = ce_bwd_kernel's / dice_bwd_kernel's closed form or their sum: added into dbc (db by lane sums) and
+// Logit gradient of a voxel, dc = class_loss_bwd_kernel<CE>'s / class_loss_bwd_kernel<DICE>'s closed form or their sum: added into dbc (db by lane sums) and
 // split hi + lo for the MFMAs
 template <int KIND>
 __device__ __forceinline__ void hsg_logit_grad(const HsgLoss& c, const float (&p)[8], int yl, int yk, int nv, bool live,

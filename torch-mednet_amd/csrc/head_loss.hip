@@ -4,25 +4,24 @@
 // Dice forward, read again by the Dice backward, which writes their gradient, which the head's data gradient and the head's
 // weight gradient each read: five passes over planes that carry 4 floats per voxel, next to the 32-channel feature rows
 // every one of these kernels streams anyway.  Here
-//   forward   head_dice_fwd_kernel   = head_fwd_vox_kernel + dice_fwd_kernel: the logits are written once (the caller's
+//   forward   head_dice_fwd_kernel   = head_fwd_vox_kernel + class_loss_fwd_kernel: the logits are written once (the caller's
 //             `outputs`) and the softmax terms of the Dice sums are taken from the registers that hold them;
-//   backward  head_dice_bwd_kernel   = dice_bwd_kernel + head_dgrad_gn_kernel + wgrad_1x1_kernel + the bias sums: the logit
+//   backward  head_dice_bwd_kernel   = class_loss_bwd_kernel + head_dgrad_gn_kernel + wgrad_1x1_kernel + the bias sums: the logit
 //             gradient of a voxel lives in registers between its closed form (from the stored logits, the label and the
 //             per-channel Dice sums) and its three uses -- dz = W^T dl (stored, with the first pass of the producing block's
 //             GroupNorm-3 backward taken from the stored row as before), dW += dl (x) z, db += dl.  No dlogits tensor exists.
-// Every per-voxel expression is the one of the kernel it replaces, in the same order, so logits, loss, dz and the
-// GroupNorm sums are BIT-IDENTICAL to the unfused launches (tests/test_gpu_ops.py); dW / db are summed in another (fixed)
-// order.
+// The per-voxel loss arithmetic is loss_blocks.inc's, the text loss.hip's stand-alone kernels run, and every other expression is
+// the one of the kernel it replaces, in the same order, so logits, loss, dz and the GroupNorm sums are BIT-IDENTICAL to the
+// unfused launches (tests/test_gpu_ops.py); dW / db are summed in another (fixed) order.
 #include "common.h"
 #include "conv.h"
+#include "loss_blocks.inc"
 
 namespace mednet {
 
 constexpr int HL_BLOCK_VOX = 256 * 8;  // = LOSS_BLOCK_VOX of loss.hip: the partial rows are dice_finalize_kernel's
 constexpr int HL_MAXC = 4;              // classes kept in registers (the segmentation heads of the callers: 2 and 4)
 constexpr int HL_VPT = 32;              // = HEAD_GN_VPT of conv_direct.hip: the GroupNorm rows are head_dgrad_gn_kernel's
-// the class loss of an instantiation (= MEDNET_CLASS_*): DiceLoss, nn.CrossEntropyLoss, or their sum
-constexpr int HL_DICE = 0, HL_CE = 1, HL_DICE_CE = 2;
 
 // a voxel's 8-channel piece as it lies in memory (4 registers for the 16-bit types): converted where it is used, so rows in
 // flight do not hold 8 registers each
@@ -50,63 +49,21 @@ struct Raw8<float> {
   __device__ __forceinline__ float at(int j) const { return j < 4 ? a[j] : b[j - 4]; }
 };
 
-// A label as an int.  An int64 label that does not fit an int (2^32 + 1) must not narrow to a class: it becomes a negative value
-// that is not ignore_index, so the range tests below see it as out of range.  Every label that fits is returned as it is.
-template <typename TL>
-__device__ __forceinline__ int label_at(const TL* __restrict__ lab, size_t i, int ignore) {
-  const int64_t y = (int64_t)lab[i];
-  if (y == (int64_t)(int)y) return (int)y;
-  return ignore == -1 ? -2 : -1;
-}
-
-// softmax / sigmoid of the class logits of one voxel (loss.hip probs_of, on registers)
-__device__ __forceinline__ void probs_reg(const float* lg, int c, int sigmoid, float* p) {
-  if (sigmoid) {
-#pragma unroll
-    for (int k = 0; k < HL_MAXC; ++k)
-      if (k < c) p[k] = 1.f / (1.f + expf(-lg[k]));
-  } else {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < HL_MAXC; ++k)
-      if (k < c) {
-        p[k] = lg[k];
-        mx = fmaxf(mx, p[k]);
-      }
-    float den = 0.f;
-#pragma unroll
-    for (int k = 0; k < HL_MAXC; ++k)
-      if (k < c) {
-        p[k] = expf(p[k] - mx);
-        den += p[k];
-      }
-    const float inv = 1.f / den;
-#pragma unroll
-    for (int k = 0; k < HL_MAXC; ++k)
-      if (k < c) p[k] *= inv;
-  }
-}
-
 // ---- forward: one voxel per lane, weights wave-uniform (SGPR operands), 8 voxels per thread ------------------------------
 // logits[n][i][v] = bias[i] + sum_k z[n][v][k] W[i][k];  partial[n][block][c][2] = {sum p t mask, sum (p + t) mask}
-// CE (head_ce): partial[n][block][2] = {sum w_y nll, sum w_y} instead (loss.hip ce_fwd_kernel's rows, for ce_finalize_kernel);
+// CE (head_ce): partial[n][block][2] = {sum w_y nll, sum w_y} instead (for ce_finalize_kernel);
 // cw = the class weights (nullable; read by the CE terms only), `sigmoid` unused
-// Dice + CE (head_dice_ce): both, the Dice rows first and behind all of them the CE rows; loss.hip dice_ce_fwd_kernel on registers
-// (one softmax per voxel; softmax only, `ignore` is MEDNET_NO_IGNORE)
-template <typename TI, int K, typename TL, int KIND = HL_DICE>
+// Dice + CE (head_dice_ce): both, the Dice rows first and behind all of them the CE rows (one softmax per voxel; softmax only,
+// `ignore` is MEDNET_NO_IGNORE).  The rows are loss.hip class_loss_fwd_kernel's: both call class_fwd_voxel / class_fwd_writeout.
+template <typename TI, int K, typename TL, int KIND = MEDNET_CLASS_DICE>
 __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict__ z, const float* __restrict__ Pb /*[m][K]*/,
                                                             const float* __restrict__ bias, const TL* __restrict__ lab,
                                                             int64_t lab_sn, float* __restrict__ y, float* __restrict__ partial,
                                                             size_t spatial, int m, int sigmoid, int ignore,
                                                             const float* __restrict__ cw = nullptr) {
-  constexpr bool CE = KIND == HL_CE;
   __shared__ float scratch[4];
   const int n = blockIdx.y;
-  float I[HL_MAXC], D[HL_MAXC];
-  float num = 0.f, den = 0.f;  // (CE)
-  bool bad = false;
-#pragma unroll
-  for (int k = 0; k < HL_MAXC; ++k) I[k] = D[k] = 0.f;
+  ClassSums<HL_MAXC> sums;
   const size_t v0 = (size_t)blockIdx.x * HL_BLOCK_VOX;
   for (int it = 0; it < 8; ++it) {
     const size_t v = v0 + (size_t)it * 256 + threadIdx.x;
@@ -119,7 +76,7 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
         for (int j = 0; j < 8; ++j) zv[q * 8 + j] = t.v[j];
       }
       const int yl = label_at(lab, (size_t)n * lab_sn + v, ignore);
-      float lg[HL_MAXC], p[HL_MAXC];
+      float lg[HL_MAXC];
 #pragma unroll
       for (int i = 0; i < HL_MAXC; ++i) {
         lg[i] = 0.f;
@@ -134,115 +91,19 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
           y[((size_t)n * m + i) * spatial + v] = lg[i];
         }
       }
-      if constexpr (CE) {
-        // loss.hip ce_fwd_kernel on registers: an out-of-range label that is not ignore_index poisons the loss
-        if (yl != ignore && (unsigned)yl >= (unsigned)m) num = __builtin_nanf("");
-        if (yl != ignore && yl >= 0 && yl < m) {
-          float mx = -INFINITY, zy = 0.f;
-#pragma unroll
-          for (int k = 0; k < HL_MAXC; ++k)
-            if (k < m) {
-              mx = fmaxf(mx, lg[k]);
-              if (k == yl) zy = lg[k];
-            }
-          float s = 0.f;
-#pragma unroll
-          for (int k = 0; k < HL_MAXC; ++k)
-            if (k < m) s += expf(lg[k] - mx);
-          const float w = cw ? cw[yl] : 1.f;
-          num = fmaf(w, (mx + logf(s)) - zy, num);
-          den += w;
-        }
-        continue;
-      }
-      if constexpr (KIND == HL_DICE_CE) {
-        const bool ok = (unsigned)yl < (unsigned)m;
-        float mx = -INFINITY, zy = 0.f;
-#pragma unroll
-        for (int k = 0; k < HL_MAXC; ++k)
-          if (k < m) {
-            mx = fmaxf(mx, lg[k]);
-            if (k == yl) zy = lg[k];
-          }
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < HL_MAXC; ++k)
-          if (k < m) {
-            p[k] = expf(lg[k] - mx);
-            s += p[k];
-          }
-        const float inv = 1.f / s;
-        bad |= !ok;
-#pragma unroll
-        for (int k = 0; k < HL_MAXC; ++k)
-          if (k < m) {
-            p[k] *= inv;
-            const float t = (k == yl) ? 1.f : 0.f;
-            I[k] = fmaf(p[k], t, I[k]);
-            D[k] += p[k] + t;
-          }
-        if (ok) {
-          const float w = cw ? cw[yl] : 1.f;
-          num = fmaf(w, (mx + logf(s)) - zy, num);
-          den += w;
-        }
-        continue;
-      }
-      probs_reg(lg, m, sigmoid, p);
-      bad |= (unsigned)yl >= (unsigned)m;  // (loss.hip dice_fwd_kernel: an out-of-range label poisons the loss)
-#pragma unroll
-      for (int k = 0; k < HL_MAXC; ++k)
-        if (k < m) {
-          const float t = (k == yl) ? 1.f : 0.f;
-          const float mk = (ignore != MEDNET_NO_IGNORE && t == (float)ignore) ? 0.f : 1.f;
-          I[k] = fmaf(p[k] * mk, t * mk, I[k]);
-          D[k] += (p[k] + t) * mk;
-        }
+      class_fwd_voxel<KIND, HL_MAXC>(sums, [&](int k) { return lg[k]; }, yl, m, sigmoid, ignore, cw);
     }
   }
-  if constexpr (CE) {
-    num = block_sum<4>(num, scratch);
-    den = block_sum<4>(den, scratch);
-    if (threadIdx.x == 0) {
-      float* o = partial + ((size_t)n * gridDim.x + blockIdx.x) * 2;
-      o[0] = num;
-      o[1] = den;
-    }
-    return;
-  }
-  if (bad) I[0] = D[0] = __builtin_nanf("");
-  float* out = partial + ((size_t)n * gridDim.x + blockIdx.x) * m * 2;
-#pragma unroll
-  for (int k = 0; k < HL_MAXC; ++k)
-    if (k < m) {
-      const float a = block_sum<4>(I[k], scratch);
-      const float b = block_sum<4>(D[k], scratch);
-      if (threadIdx.x == 0) {
-        out[2 * k] = a;
-        out[2 * k + 1] = b;
-      }
-    }
-  if constexpr (KIND == HL_DICE_CE) {
-    if (bad) num = __builtin_nanf("");
-    num = block_sum<4>(num, scratch);
-    den = block_sum<4>(den, scratch);
-    if (threadIdx.x == 0) {
-      float* o = partial + (size_t)gridDim.y * gridDim.x * m * 2 + ((size_t)n * gridDim.x + blockIdx.x) * 2;
-      o[0] = num;
-      o[1] = den;
-    }
-  }
+  class_fwd_writeout<KIND, HL_MAXC>(sums, partial, m, scratch);
 }
 
 // ---- backward: K/8 lanes per voxel, each owns 8 channels of the voxel's row; two voxels per trip --------------------------
 // wpart[n][block][wave][m * K + m]: this wave's partial of dW (row-major [class][channel]) and, behind it, of db
 // FOLD: z is the output of a fused conv -> activation layer and there are no GroupNorm sums to take (UNet3D's last block): the
 // stored gradient carries act'(z).  Its own instantiation: as a runtime branch it cost the main form its third wave per SIMD.
-// CE (head_ce): the logit gradient is loss.hip ce_bwd_kernel's closed form (dloss / saved[0]) w_y (p_k - [k == y]), 0 for an
-// ignored or out-of-range label; saved = {sum w_y} of the CE forward, `eps` and `sigmoid` unused.  Everything after it is shared.
-// Dice + CE (head_dice_ce): the sum of the two closed forms, loss.hip dice_ce_bwd_kernel's (each term in a statement of its own, added
-// by a plain add: one expression would contract the CE product into the add); saved = [m][2] {I, D}, then sum w_y.
-template <typename TO, int K, typename TL, bool FOLD = false, int KIND = HL_DICE>
+// The logit gradient of a voxel is class_logit_grad's (loss_blocks.inc), as in loss.hip class_loss_bwd_kernel.  CE (head_ce): saved =
+// {sum w_y} of the CE forward, `eps` and `sigmoid` unused.  Dice + CE (head_dice_ce): saved = [m][2] {I, D}, then sum w_y.
+template <typename TO, int K, typename TL, bool FOLD = false, int KIND = MEDNET_CLASS_DICE>
 __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_dice_bwd_kernel(const float* __restrict__ lgs, const TL* __restrict__ lab, int64_t lab_sn,
                                                             const float* __restrict__ Pb /*[m][K]*/, const float* __restrict__ weight,
                                                             const float* __restrict__ saved, const float* __restrict__ dloss,
@@ -251,7 +112,6 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
                                                             float* __restrict__ gn_partial /*nullable*/, float* __restrict__ wpart,
                                                             size_t spatial, int m) {
   constexpr int CG = K / 8, VPW = 256 / CG;
-  constexpr bool CE = KIND == HL_CE;
   const int n = blockIdx.y;
   const int cgi = threadIdx.x % CG, vi = threadIdx.x / CG;
   float wreg[HL_MAXC][8];
@@ -259,95 +119,19 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
   for (int i = 0; i < HL_MAXC; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) wreg[i][j] = i < m ? Pb[(size_t)i * K + cgi * 8 + j] : 0.f;
-  // per-class coefficients of the closed form (loss.hip dice_bwd_kernel; CE: gI[k] = w_k dloss / saved[0], ce_bwd_kernel's `w`)
-  const float go = *dloss;
-  float gI[HL_MAXC], gD[HL_MAXC];
-  // Dice + CE: gI, gD and ce_bwd_kernel's `w` per class are twelve loop-invariant values; in registers they took the 16-bit forms
+  // per-class coefficients of the closed form (loss_blocks.inc class_coef_of), in registers.  Dice + CE: gI, gD and the CE weight per class are twelve loop-invariant values; in registers they took the 16-bit forms
   // past the 168 of three waves per SIMD (2 to 8 spilled), so they live in LDS [gI | gD | w] and are read where they are used
-  // (`koff` is made opaque once per trip: left alone, the compiler hoists the reads back into registers)
-  [[maybe_unused]] float* hk = nullptr;
-  [[maybe_unused]] int koff = 0;
-  if constexpr (KIND == HL_DICE_CE) {
+  // (`off` is made opaque once per trip: left alone, the compiler hoists the reads back into registers)
+  const float go = *dloss;
+  std::conditional_t<KIND == MEDNET_CLASS_DICE_CE, ClassCoefLds<HL_MAXC>, ClassCoefRegs<HL_MAXC>> coef;
+  if constexpr (KIND == MEDNET_CLASS_DICE_CE) {
     __shared__ float hk_s[3 * HL_MAXC];
-    if (threadIdx.x < HL_MAXC) {
-      const int k = threadIdx.x;
-      float a = 0.f, b = 0.f, cw = 0.f;
-      if (k < m) {
-        const float w = weight ? weight[k] : 1.f;
-        const float I = saved[2 * k], D = saved[2 * k + 1];
-        const float Dc = fmaxf(D, eps);
-        a = -2.f * w / ((float)m * Dc) * go + ((I != I || D != D) ? __builtin_nanf("") : 0.f);
-        b = (D >= eps ? 2.f * w * I / ((float)m * Dc * Dc) : 0.f) * go;
-        cw = w * (go / saved[2 * m]);
-      }
-      hk_s[k] = a;
-      hk_s[HL_MAXC + k] = b;
-      hk_s[2 * HL_MAXC + k] = cw;
-    }
+    coef.row = hk_s;
+    if (threadIdx.x < HL_MAXC) coef.template fill<KIND>(threadIdx.x, m, weight, saved, eps, go);
     __syncthreads();
-    hk = hk_s;
+  } else {
+    coef.template fill<KIND>(m, weight, saved, eps, go);
   }
-#pragma unroll
-  for (int k = 0; k < HL_MAXC; ++k) {
-    gI[k] = gD[k] = 0.f;
-    if (KIND == HL_DICE_CE) {
-    } else if (CE && k < m) {
-      gI[k] = (weight ? weight[k] : 1.f) * (go / saved[0]);
-    } else if (k < m) {
-      const float w = weight ? weight[k] : 1.f;
-      const float I = saved[2 * k], D = saved[2 * k + 1];
-      const float Dc = fmaxf(D, eps);
-      gI[k] = -2.f * w / ((float)m * Dc) * go + ((I != I || D != D) ? __builtin_nanf("") : 0.f);
-      gD[k] = (D >= eps ? 2.f * w * I / ((float)m * Dc * Dc) : 0.f) * go;
-    }
-  }
-  auto dlogits_of = [&](const float* lg, int yl, float* dl) {  // the logit gradient of one voxel
-    if constexpr (CE) {
-      float p[HL_MAXC];
-      probs_reg(lg, m, 0, p);
-      float w = 0.f;
-#pragma unroll
-      for (int k = 0; k < HL_MAXC; ++k)
-        if (k < m && k == yl) w = gI[k];
-      w = (yl != ignore && yl >= 0 && yl < m) ? w : 0.f;
-#pragma unroll
-      for (int k = 0; k < HL_MAXC; ++k) dl[k] = k < m ? w * (p[k] - (k == yl ? 1.f : 0.f)) : 0.f;
-      return;
-    }
-    if constexpr (KIND == HL_DICE_CE) {
-      float p[HL_MAXC], g[HL_MAXC];
-      probs_reg(lg, m, 0, p);
-      float dot = 0.f, w = 0.f;
-#pragma unroll
-      for (int k = 0; k < HL_MAXC; ++k)
-        if (k < m) {
-          const float t = (k == yl) ? 1.f : 0.f;
-          g[k] = hk[koff + k] * t + hk[koff + HL_MAXC + k];  // (gI * t is exact: the Dice form's g with mask 1, fused or not)
-          dot = fmaf(p[k], g[k], dot);
-          if (k == yl) w = hk[koff + 2 * HL_MAXC + k];
-        }
-#pragma unroll
-      for (int k = 0; k < HL_MAXC; ++k) {
-        const float dl_dice = p[k] * (g[k] - dot);
-        const float dl_ce = w * (p[k] - (k == yl ? 1.f : 0.f));
-        dl[k] = k < m ? dl_dice + dl_ce : 0.f;
-      }
-      return;
-    }
-    float p[HL_MAXC], g[HL_MAXC];
-    probs_reg(lg, m, sigmoid, p);
-    float dot = 0.f;
-#pragma unroll
-    for (int k = 0; k < HL_MAXC; ++k)
-      if (k < m) {
-        const float t = (k == yl) ? 1.f : 0.f;
-        const float mk = (ignore != MEDNET_NO_IGNORE && t == (float)ignore) ? 0.f : 1.f;
-        g[k] = mk * (gI[k] * t * mk + gD[k]);
-        dot = fmaf(p[k], g[k], dot);
-      }
-#pragma unroll
-    for (int k = 0; k < HL_MAXC; ++k) dl[k] = k < m ? (sigmoid ? g[k] * p[k] * (1.f - p[k]) : p[k] * (g[k] - dot)) : 0.f;
-  };
   float ss[8], sq[8], wacc[HL_MAXC][8], bacc[HL_MAXC];
 #pragma unroll
   for (int j = 0; j < 8; ++j) ss[j] = sq[j] = 0.f;
@@ -400,10 +184,10 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
       yva = zva;
       yvb = zvb;
     }
-    float da[HL_MAXC], db[HL_MAXC];
-    if constexpr (KIND == HL_DICE_CE) asm volatile("" : "+v"(koff));
-    dlogits_of(la, ya, da);
-    dlogits_of(lb, yb, db);
+    if constexpr (KIND == MEDNET_CLASS_DICE_CE) asm volatile("" : "+v"(coef.off));
+    float (&da)[HL_MAXC] = la, (&db)[HL_MAXC] = lb;  // the logit gradient of each voxel, in place of its logits
+    class_logit_grad<KIND, HL_MAXC>(da, ya, m, sigmoid, ignore, coef);
+    class_logit_grad<KIND, HL_MAXC>(db, yb, m, sigmoid, ignore, coef);
     if (!hb) {
 #pragma unroll
       for (int i = 0; i < HL_MAXC; ++i) db[i] = 0.f;
@@ -559,14 +343,14 @@ static int head_loss_fwd(const char* what, const void* z, const void* packed, co
   MEDNET_REQUIRE(mednet_head_dice_supported(cin, cout, z_dtype, label_dtype), MEDNET_E_UNSUPPORTED,
                  "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
   MEDNET_REQUIRE(n > 0 && spatial > 0 && z && packed && labels && logits && loss && saved, MEDNET_E_SHAPE, "%s: bad arguments", what);
-  const size_t need = KIND == HL_DICE_CE ? mednet_head_dice_ce_ws_bytes(n, spatial, cin, cout) : mednet_head_dice_ws_bytes(n, spatial, cin, cout);
+  const size_t need = KIND == MEDNET_CLASS_DICE_CE ? mednet_head_dice_ce_ws_bytes(n, spatial, cin, cout) : mednet_head_dice_ws_bytes(n, spatial, cin, cout);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "%s: workspace too small", what);
   const float* Pb = head_weights_f32(packed, cin, cout);
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = hl_fwd_blocks(spatial);
   float* partial = (float*)ws;
   const dim3 grid(nb, n);
-#define HF(TI_, K_, TL_) hipLaunchKernelGGL((head_dice_fwd_kernel<TI_, K_, TL_, KIND>), grid, dim3(256), 0, s, (const TI_*)z, Pb, bias, (const TL_*)labels, label_stride_n, logits, partial, spatial, cout, sigmoid, ignore_index, KIND != HL_DICE ? weight : nullptr)
+#define HF(TI_, K_, TL_) hipLaunchKernelGGL((head_dice_fwd_kernel<TI_, K_, TL_, KIND>), grid, dim3(256), 0, s, (const TI_*)z, Pb, bias, (const TL_*)labels, label_stride_n, logits, partial, spatial, cout, sigmoid, ignore_index, KIND != MEDNET_CLASS_DICE ? weight : nullptr)
 #define HF_L(TI_, K_) do { if (label_dtype == MEDNET_U8) HF(TI_, K_, uint8_t); else HF(TI_, K_, int64_t); } while (0)
 #define HF_K(TI_) do { if (cin == 16) HF_L(TI_, 16); else if (cin == 32) HF_L(TI_, 32); else HF_L(TI_, 64); } while (0)
   if (z_dtype == MEDNET_F32) HF_K(float);
@@ -589,7 +373,7 @@ static int head_loss_bwd(const char* what, const float* logits, const void* labe
                  "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
   MEDNET_REQUIRE(n > 0 && spatial > 0 && logits && labels && packed && saved && dloss && dz && z && dw, MEDNET_E_SHAPE, "%s: bad arguments", what);
   MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "%s: gn_y and gn_partial go together", what);
-  const size_t need = KIND == HL_DICE_CE ? mednet_head_dice_ce_ws_bytes(n, spatial, cin, cout) : mednet_head_dice_ws_bytes(n, spatial, cin, cout);
+  const size_t need = KIND == MEDNET_CLASS_DICE_CE ? mednet_head_dice_ce_ws_bytes(n, spatial, cin, cout) : mednet_head_dice_ws_bytes(n, spatial, cin, cout);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "%s: workspace too small", what);
   const float* Pb = head_weights_f32(packed, cin, cout);
   hipStream_t s = (hipStream_t)stream;
@@ -621,7 +405,7 @@ extern "C" int mednet_head_dice_fwd(const void* z, const void* packed, const flo
                                     int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
                                     size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
                                     void* ws, size_t ws_bytes, mednet_stream stream) {
-  return head_loss_fwd<HL_DICE>("head_dice_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
+  return head_loss_fwd<MEDNET_CLASS_DICE>("head_dice_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
                               cin, cout, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
@@ -630,7 +414,7 @@ extern "C" int mednet_head_dice_bwd(const float* logits, const void* labels, int
                                     const void* gn_y, const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n,
                                     size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
                                     void* ws, size_t ws_bytes, mednet_stream stream) {
-  return head_loss_bwd<HL_DICE>("head_dice_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
+  return head_loss_bwd<MEDNET_CLASS_DICE>("head_dice_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
                               gn_partial, dw, dbias, n, spatial, cin, cout, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
@@ -647,7 +431,7 @@ extern "C" int mednet_head_ce_fwd(const void* z, const void* packed, const float
                                   int64_t label_stride_n, const float* weight, float* logits, float* loss, float* saved, int n,
                                   size_t spatial, int cin, int cout, int ignore_index, int z_dtype, void* ws, size_t ws_bytes,
                                   mednet_stream stream) {
-  return head_loss_fwd<HL_CE>("head_ce_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
+  return head_loss_fwd<MEDNET_CLASS_CE>("head_ce_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n, spatial,
                              cin, cout, 0.f, 0, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
@@ -655,7 +439,7 @@ extern "C" int mednet_head_ce_bwd(const float* logits, const void* labels, int l
                                   const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
                                   int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
                                   int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
-  return head_loss_bwd<HL_CE>("head_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
+  return head_loss_bwd<MEDNET_CLASS_CE>("head_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
                              gn_partial, dw, dbias, n, spatial, cin, cout, 0.f, 0, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
@@ -672,7 +456,7 @@ extern "C" int mednet_head_dice_ce_fwd(const void* z, const void* packed, const 
                                        void* ws, size_t ws_bytes, mednet_stream stream) {
   MEDNET_REQUIRE(sigmoid == 0 && ignore_index == MEDNET_NO_IGNORE, MEDNET_E_UNSUPPORTED,
                  "head_dice_ce_fwd: Dice + cross-entropy is a softmax form without ignore_index");
-  return head_loss_fwd<HL_DICE_CE>("head_dice_ce_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n,
+  return head_loss_fwd<MEDNET_CLASS_DICE_CE>("head_dice_ce_fwd", z, packed, bias, labels, label_dtype, label_stride_n, weight, logits, loss, saved, n,
                                    spatial, cin, cout, eps, 0, MEDNET_NO_IGNORE, z_dtype, ws, ws_bytes, stream);
 }
 
@@ -683,7 +467,7 @@ extern "C" int mednet_head_dice_ce_bwd(const float* logits, const void* labels, 
                                        void* ws, size_t ws_bytes, mednet_stream stream) {
   MEDNET_REQUIRE(sigmoid == 0 && ignore_index == MEDNET_NO_IGNORE, MEDNET_E_UNSUPPORTED,
                  "head_dice_ce_bwd: Dice + cross-entropy is a softmax form without ignore_index");
-  return head_loss_bwd<HL_DICE_CE>("head_dice_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z,
+  return head_loss_bwd<MEDNET_CLASS_DICE_CE>("head_dice_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z,
                                    gn_act, gn_partial, dw, dbias, n, spatial, cin, cout, eps, 0, MEDNET_NO_IGNORE, z_dtype, ws, ws_bytes,
                                    stream);
 }

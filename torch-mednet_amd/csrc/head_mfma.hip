@@ -9,7 +9,7 @@
 //   forward   head_lm_kernel<false>: logits^T = W z^T on v_mfma_f32_32x32x16 (W split hi + lo: fp32-level products), loss terms taken
 //             from the accumulator registers; nothing but per-workgroup partial sums is written (the logits only on request).
 //   backward  head_lm_kernel<true>: the same MFMAs rebuild the logits bit for bit, the logit gradient is formed in registers
-//             (closed forms of loss.hip's hm_bwd_kernel / dice_bwd_kernel) and feeds, split hi + lo,
+//             (closed forms of loss.hip's hm_bwd_kernel / class_loss_bwd_kernel<DICE>) and feeds, split hi + lo,
 //               dz^T = W^T dl^T      (stored; the first pass of the producing block's GroupNorm-3 backward is taken from the stored
 //                                     rows as head_dgrad_gn_kernel does),
 //               dW  += dl^T z        (both operands through the transposing LDS read, contraction over 32 voxels per step),
@@ -63,8 +63,8 @@ struct HlmArgs {
 };
 
 // CE: the class term is nn.CrossEntropyLoss(weight, ignore_index) (landmarks.py:49) instead of Dice: the forward accumulates
-// ce_fwd_kernel's {sum w_y nll, sum w_y} and, for dice_metric (loss.py:51-55), the unweighted, unmasked softmax sums {I, D} into
-// dice_partial; the backward's class gradient is ce_bwd_kernel's closed form (dcls / sum w) w_y (p_k - [k == y]).  Softmax only.
+// class_loss_fwd_kernel<CE>'s {sum w_y nll, sum w_y} and, for dice_metric (loss.py:51-55), the unweighted, unmasked softmax sums {I, D} into
+// dice_partial; the backward's class gradient is class_loss_bwd_kernel<CE>'s closed form (dcls / sum w) w_y (p_k - [k == y]).  Softmax only.
 // Dice + CE (HLM_DICE_CE, softmax, no ignore_index): the class term is the sum of the two.  Its forward IS the CE forward -- without a
 // mask the Dice sums are dice_metric's sums, the class weight enters in the finalize -- so only a backward is instantiated: the
 // sum of the two closed forms, with w_k dcls / sum w in the last four constants of the lane half.
@@ -106,15 +106,15 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
     else if (BWD && i < 20) {
       const int c = 8 * hh + i - 12;
       v = c < a.nh ? *a.dreg * (a.reg_weight ? a.reg_weight[c] : 1.f) * a.inv_count : 0.f;
-    } else if (BWD && i < 28) {  // loss.hip dice_bwd_kernel
+    } else if (BWD && i < 28) {  // loss.hip class_loss_bwd_kernel<DICE>
       const int k = (i - 20) & 3;
       if (CE && k < a.ncls) {
-        v = i < 24 ? (a.cls_weight ? a.cls_weight[k] : 1.f) * (*a.dcls / a.saved[0]) : 0.f;  // (ce_bwd_kernel's `w`)
+        v = i < 24 ? (a.cls_weight ? a.cls_weight[k] : 1.f) * (*a.dcls / a.saved[0]) : 0.f;  // (class_loss_bwd_kernel<CE>'s `w`)
       } else if (k < a.ncls) {
         const float w = a.cls_weight ? a.cls_weight[k] : 1.f, I = a.saved[2 * k], D = a.saved[2 * k + 1];
         v = i < 24 ? hlm_dice_gI(w, I, D, a.eps, a.ncls, *a.dcls) : hlm_dice_gD(w, I, D, a.eps, a.ncls, *a.dcls);
       }
-    } else if (BWD && KIND == HLM_DICE_CE && i - 28 < a.ncls) {  // [28..31]: ce_bwd_kernel's `w` per class
+    } else if (BWD && KIND == HLM_DICE_CE && i - 28 < a.ncls) {  // [28..31]: class_loss_bwd_kernel<CE>'s `w` per class
       v = (a.cls_weight ? a.cls_weight[i - 28] : 1.f) * (*a.dcls / a.saved[2 * a.ncls]);
     }
     cst[hh][i] = v;
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
       const int yl = (int)((lb >> (8 * j)) & 0xFFu);
       float lse = 0.f;  // (CE: max + log of the softmax's denominator)
       {
-        // softmax / sigmoid of the class logits (loss.hip probs_of on registers)
+        // softmax / sigmoid of the class logits (loss.hip cl_probs on registers)
         if (a.sigmoid) {
 #pragma unroll
           for (int k = 0; k < HLM_MAXC; ++k) p[k] = k < a.ncls ? 1.f / (1.f + expf(-lc[k])) : 0.f;
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
         }
       }
       if constexpr (!BWD) {
-        // ---- loss terms: hm_fwd_kernel / dice_fwd_kernel on registers
+        // ---- loss terms: hm_fwd_kernel / class_loss_fwd_kernel<DICE> on registers
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float d = lh[e] - (float)((tb[e] >> (8 * j)) & 0xFFu);
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
           hm_acc[e] += (live && 8 * h + e < a.nh) ? t : 0.f;
         }
         if (CE && cls_lane) {
-          // ce_fwd_kernel: w_y ((max + log sum exp) - z_y); an out-of-range label that is not ignore_index poisons the loss
+          // class_loss_fwd_kernel<CE>: w_y ((max + log sum exp) - z_y); an out-of-range label that is not ignore_index poisons the loss
           if (yl != a.ignore && (unsigned)yl >= (unsigned)a.ncls) ce_acc[0] = __builtin_nanf("");
           if (yl != a.ignore && yl < a.ncls) {
             float zy = 0.f, w = 0.f;
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
             ce_acc[0] = fmaf(w, lse - zy, ce_acc[0]);
             ce_acc[1] += w;
           }
-          // dice_metric's sums (dice_fwd_kernel without weight or mask)
+          // dice_metric's sums (class_loss_fwd_kernel<DICE> without weight or mask)
           bad |= (unsigned)yl >= (unsigned)a.ncls;
 #pragma unroll
           for (int k = 0; k < HLM_MAXC; ++k)
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void head_lm_kernel(HlmArgs a) {
             }
         }
       } else {
-        // ---- logit gradient in registers: hm_bwd_kernel / dice_bwd_kernel
+        // ---- logit gradient in registers: hm_bwd_kernel / class_loss_bwd_kernel<DICE>
         float dh[8], dc[HLM_MAXC];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(256) void head_lm_wfinal_kernel(const float* __rest
 // head_lm_kernel's heat-map rows carrying the classes in the wide-class layout of head_blocks.inc (classes 8h .. 8h+7 in lane half h;
 // the hsg_* blocks are the per-voxel loss arithmetic).  HlmArgs with nh = 0: `ncls` classes, no targets.
 //   forward   {I, D} per class (dice_finalize_kernel's rows) or {sum w_y nll, sum w_y} (ce_finalize_kernel's rows)
-//   backward  logits rebuilt, dl from dice_bwd_kernel's / ce_bwd_kernel's closed form, dz^T = W^T dl^T stored once, dW through the
+//   backward  logits rebuilt, dl from class_loss_bwd_kernel<DICE>'s / class_loss_bwd_kernel<CE>'s closed form, dz^T = W^T dl^T stored once, dW through the
 //             wave-private tiles (dl columns 0 .. 15; 16 .. 31 stay zero), db by lane sums, GroupNorm-3's first pass from the stored rows.
 // Dice + CE (HLM_DICE_CE, softmax, no ignore_index): the forward keeps the Dice accumulators in registers and the CE sums in the idle
 // LDS slot; the backward adds the two closed forms, with w_k dloss / sum w in eight more constants of the lane half.

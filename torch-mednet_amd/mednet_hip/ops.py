@@ -1255,40 +1255,15 @@ class DiceLossFn(Function):
     @staticmethod
     def forward(ctx, logits, labels, weight, eps, sigmoid, ignore_index):
         L.require_gpu(logits, "dice_loss")
-        lg, sn, sc = _planar_logits(logits)
-        n, c = lg.shape[:2]
-        spatial = lg[0, 0].numel()
-        lab, lab_sn, lab_dt = _label_view(labels, n, tuple(lg.shape[2:]))  # uint8 / int64 as they lie (no cast kernel)
-        wt = None if weight is None else weight.to(device=lg.device, dtype=torch.float32).contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=lg.device)
-        saved = torch.empty((c, 2), dtype=torch.float32, device=lg.device)
-        lib = L.lib()
-        ws = L.workspace(lib.mednet_loss_ws_bytes(n, c, spatial), lg.device)
+        opnd = _class_loss_operands(logits, labels, weight)
+        n, c, spatial = opnd[3][:3]
+        ws = L.workspace(L.lib().mednet_loss_ws_bytes(n, c, spatial), logits.device)
         ii = L.NO_IGNORE if ignore_index is None else int(ignore_index)
-        L.check(lib.mednet_dice_fwd_lt(lg.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt), loss.data_ptr(), saved.data_ptr(),
-                                       None, n, c, spatial, sn, sc, eps, int(sigmoid), ii, ws.data_ptr(), ws.numel(), L.stream()),
-                "dice_fwd")
-        ctx.save_for_backward(lg, lab, wt, saved)
-        ctx.meta = (eps, int(sigmoid), ii, sn, sc, logits.dtype, lab_sn, lab_dt)
-        ctx.split = getattr(logits, "_mednet_split", None) if lg is logits else None
-        if debug.TRACE is not None:
-            debug.trace("dice.fwd", lg, loss, saved)
-        return loss
+        return _class_loss_fwd(ctx, "dice", logits, opnd, (c, 2), (eps, int(sigmoid), ii), ws)
 
     @staticmethod
     def backward(ctx, dloss):
-        lg, lab, wt, saved = ctx.saved_tensors
-        eps, sigmoid, ii, sn, sc, in_dtype, lab_sn, lab_dt = ctx.meta
-        n, c = lg.shape[:2]
-        spatial = lg[0, 0].numel()
-        dl = dloss.to(torch.float32).contiguous()
-        dlogits = _loss_grad_like(lg, ctx.split)
-        L.check(L.lib().mednet_dice_bwd_lt(lg.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt), saved.data_ptr(), dl.data_ptr(),
-                                           dlogits.data_ptr(), n, c, spatial, sn, sc, eps, sigmoid, ii, L.stream()),
-                "dice_bwd")
-        if debug.TRACE is not None:
-            debug.trace("dice.bwd", dlogits)
-        return dlogits.to(in_dtype), None, None, None, None, None
+        return _class_loss_bwd(ctx, dloss, 6)
 
 
 def dice_loss(logits, labels, weight=None, eps=1e-5, sigmoid=False, ignore_index=None):
@@ -1343,6 +1318,56 @@ def _aligned4(t: torch.Tensor, sn: int):
 def _loss_weight(weight, device):
     """Per-class / per-channel loss weights (a tensor or a list), or None -> fp32 on the device."""
     return None if weight is None else torch.as_tensor(weight, dtype=torch.float32, device=device).contiguous()
+
+
+def _class_loss_operands(logits, labels, weight, i64=False):
+    """The operands of a stand-alone class loss (dice_loss, cross_entropy, dice_ce_loss, per_channel_dice): planar fp32 logits, the
+    labels -- uint8 / int64 as they lie, no cast kernel; `i64`: contiguous int64, what mednet_ce_* takes --, the class weights
+    -> (logits, labels, weights, (n, c, spatial, stride_n, stride_c), the label arguments behind the pointer)."""
+    lg, sn, sc = _planar_logits(logits)
+    n, c = lg.shape[:2]
+    if i64:
+        lab, lab_args = _labels_i64(labels, (n,) + tuple(lg.shape[2:])), ()
+    else:
+        lab, lab_sn, lab_dt = _label_view(labels, n, tuple(lg.shape[2:]))
+        lab_args = (lab_dt, lab_sn)
+    return lg, lab, _loss_weight(weight, lg.device), (n, c, lg[0, 0].numel(), sn, sc), lab_args
+
+
+def _class_loss_fwd(ctx, name, logits, opnd, saved_shape, scalars, ws, dice=None):
+    """What the forwards of the stand-alone class losses do alike: the outputs, the launch of mednet_<name>_fwd[_lt] and what
+    _class_loss_bwd finds on ctx (None: no gradient, no loss either -- per_channel_dice wants `dice` alone).  The workspace is the
+    caller's: the footprint tests name a request by the function that asks.  -> loss."""
+    lg, lab, wt, geom, lab_args = opnd
+    loss = None if ctx is None else torch.empty((), dtype=torch.float32, device=lg.device)
+    saved = torch.empty(saved_shape, dtype=torch.float32, device=lg.device)
+    outs = (L.ptr(loss), saved.data_ptr()) + ((L.ptr(dice),) if lab_args else ())
+    entry = getattr(L.lib(), f"mednet_{name}_fwd" + ("_lt" if lab_args else ""))
+    L.check(entry(lg.data_ptr(), lab.data_ptr(), *lab_args, L.ptr(wt), *outs, *geom, *scalars, ws.data_ptr(), ws.numel(), L.stream()),
+            name + "_fwd")
+    if ctx is None:
+        return None
+    ctx.save_for_backward(lg, lab, wt, saved)
+    ctx.meta = (name, lab_args, geom, scalars, logits.dtype)
+    ctx.split = getattr(logits, "_mednet_split", None) if lg is logits else None
+    if debug.TRACE is not None and name != "ce":
+        debug.trace(name + ".fwd", lg, loss, saved)
+    return loss
+
+
+def _class_loss_bwd(ctx, dloss, n_inputs):
+    """The matching backward: the logit gradient with the strides of the logits (a slice of a channel split's shared buffer when
+    there is one), mednet_<name>_bwd[_lt].  -> the node's gradients."""
+    lg, lab, wt, saved = ctx.saved_tensors
+    name, lab_args, geom, scalars, in_dtype = ctx.meta
+    dl = dloss.to(torch.float32).contiguous()
+    dlogits = _loss_grad_like(lg, ctx.split)
+    entry = getattr(L.lib(), f"mednet_{name}_bwd" + ("_lt" if lab_args else ""))
+    L.check(entry(lg.data_ptr(), lab.data_ptr(), *lab_args, L.ptr(wt), saved.data_ptr(), dl.data_ptr(), dlogits.data_ptr(), *geom,
+                  *scalars, L.stream()), name + "_bwd")
+    if debug.TRACE is not None and name != "ce":
+        debug.trace(name + ".bwd", dlogits)
+    return (dlogits.to(in_dtype),) + (None,) * (n_inputs - 1)
 
 
 def _head_supported(x: torch.Tensor, *targets, mfma: bool) -> bool:
@@ -1786,18 +1811,12 @@ def _landmark_fwd(x, packed, bias, hm, hm_sn, lab, lab_sn, cw, rw, nh, ncls, kin
 def per_channel_dice(logits, labels, weight=None, eps=1e-5, sigmoid=False, ignore_index=None):
     """dice_metric  -- loss.py:51-55 (no gradient)."""
     L.require_gpu(logits, "dice_metric")
-    lg, sn, sc = _planar_logits(logits.detach())
-    n, c = lg.shape[:2]
-    spatial = lg[0, 0].numel()
-    lab, lab_sn, lab_dt = _label_view(labels, n, tuple(lg.shape[2:]))
-    wt = None if weight is None else weight.to(device=lg.device, dtype=torch.float32).contiguous()
-    saved = torch.empty((c, 2), dtype=torch.float32, device=lg.device)
-    dice = torch.empty((c,), dtype=torch.float32, device=lg.device)
-    lib = L.lib()
-    ws = L.workspace(lib.mednet_loss_ws_bytes(n, c, spatial), lg.device)
+    opnd = _class_loss_operands(logits.detach(), labels, weight)
+    n, c, spatial = opnd[3][:3]
+    dice = torch.empty((c,), dtype=torch.float32, device=logits.device)
+    ws = L.workspace(L.lib().mednet_loss_ws_bytes(n, c, spatial), logits.device)
     ii = L.NO_IGNORE if ignore_index is None else int(ignore_index)
-    L.check(lib.mednet_dice_fwd_lt(lg.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt), None, saved.data_ptr(), dice.data_ptr(),
-                                   n, c, spatial, sn, sc, eps, int(sigmoid), ii, ws.data_ptr(), ws.numel(), L.stream()), "dice_fwd")
+    _class_loss_fwd(None, "dice", logits, opnd, (c, 2), (eps, int(sigmoid), ii), ws, dice)
     return dice
 
 
@@ -1807,33 +1826,14 @@ class CrossEntropyFn(Function):
     @staticmethod
     def forward(ctx, logits, labels, weight, ignore_index):
         L.require_gpu(logits, "cross_entropy")
-        lg, sn, sc = _planar_logits(logits)
-        n, c = lg.shape[:2]
-        spatial = lg[0, 0].numel()
-        lab = _labels_i64(labels, (n,) + tuple(lg.shape[2:]))
-        wt = None if weight is None else weight.to(device=lg.device, dtype=torch.float32).contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=lg.device)
-        saved = torch.empty((2,), dtype=torch.float32, device=lg.device)
-        lib = L.lib()
-        ws = L.workspace(lib.mednet_loss_ws_bytes(n, c, spatial), lg.device)
-        L.check(lib.mednet_ce_fwd(lg.data_ptr(), lab.data_ptr(), L.ptr(wt), loss.data_ptr(), saved.data_ptr(), n, c,
-                                  spatial, sn, sc, int(ignore_index), ws.data_ptr(), ws.numel(), L.stream()), "ce_fwd")
-        ctx.save_for_backward(lg, lab, wt, saved)
-        ctx.meta = (int(ignore_index), sn, sc, logits.dtype)
-        ctx.split = getattr(logits, "_mednet_split", None) if lg is logits else None
-        return loss
+        opnd = _class_loss_operands(logits, labels, weight, i64=True)
+        n, c, spatial = opnd[3][:3]
+        ws = L.workspace(L.lib().mednet_loss_ws_bytes(n, c, spatial), logits.device)
+        return _class_loss_fwd(ctx, "ce", logits, opnd, (2,), (int(ignore_index),), ws)
 
     @staticmethod
     def backward(ctx, dloss):
-        lg, lab, wt, saved = ctx.saved_tensors
-        ii, sn, sc, in_dtype = ctx.meta
-        n, c = lg.shape[:2]
-        spatial = lg[0, 0].numel()
-        dl = dloss.to(torch.float32).contiguous()
-        dlogits = _loss_grad_like(lg, ctx.split)
-        L.check(L.lib().mednet_ce_bwd(lg.data_ptr(), lab.data_ptr(), L.ptr(wt), saved.data_ptr(), dl.data_ptr(),
-                                      dlogits.data_ptr(), n, c, spatial, sn, sc, ii, L.stream()), "ce_bwd")
-        return dlogits.to(in_dtype), None, None, None
+        return _class_loss_bwd(ctx, dloss, 4)
 
 
 def cross_entropy(logits, labels, weight=None, ignore_index=-100):
@@ -1848,37 +1848,14 @@ class DiceCELossFn(Function):
     @staticmethod
     def forward(ctx, logits, labels, weight, eps):
         L.require_gpu(logits, "dice_ce_loss")
-        lg, sn, sc = _planar_logits(logits)
-        n, c = lg.shape[:2]
-        spatial = lg[0, 0].numel()
-        lab, lab_sn, lab_dt = _label_view(labels, n, tuple(lg.shape[2:]))
-        wt = None if weight is None else weight.to(device=lg.device, dtype=torch.float32).contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=lg.device)
-        saved = torch.empty((2 * c + 1,), dtype=torch.float32, device=lg.device)  # [c][2] = {I, D}, then sum w_y
-        lib = L.lib()
-        ws = L.workspace(lib.mednet_dice_ce_ws_bytes(n, c, spatial), lg.device)
-        L.check(lib.mednet_dice_ce_fwd_lt(lg.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt), loss.data_ptr(), saved.data_ptr(),
-                                          None, n, c, spatial, sn, sc, eps, ws.data_ptr(), ws.numel(), L.stream()), "dice_ce_fwd")
-        ctx.save_for_backward(lg, lab, wt, saved)
-        ctx.meta = (eps, sn, sc, logits.dtype, lab_sn, lab_dt)
-        ctx.split = getattr(logits, "_mednet_split", None) if lg is logits else None
-        if debug.TRACE is not None:
-            debug.trace("dice_ce.fwd", lg, loss, saved)
-        return loss
+        opnd = _class_loss_operands(logits, labels, weight)
+        n, c, spatial = opnd[3][:3]
+        ws = L.workspace(L.lib().mednet_dice_ce_ws_bytes(n, c, spatial), logits.device)
+        return _class_loss_fwd(ctx, "dice_ce", logits, opnd, (2 * c + 1,), (eps,), ws)  # saved: [c][2] = {I, D}, then sum w_y
 
     @staticmethod
     def backward(ctx, dloss):
-        lg, lab, wt, saved = ctx.saved_tensors
-        eps, sn, sc, in_dtype, lab_sn, lab_dt = ctx.meta
-        n, c = lg.shape[:2]
-        spatial = lg[0, 0].numel()
-        dl = dloss.to(torch.float32).contiguous()
-        dlogits = _loss_grad_like(lg, ctx.split)
-        L.check(L.lib().mednet_dice_ce_bwd_lt(lg.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, L.ptr(wt), saved.data_ptr(), dl.data_ptr(),
-                                              dlogits.data_ptr(), n, c, spatial, sn, sc, eps, L.stream()), "dice_ce_bwd")
-        if debug.TRACE is not None:
-            debug.trace("dice_ce.bwd", dlogits)
-        return dlogits.to(in_dtype), None, None, None
+        return _class_loss_bwd(ctx, dloss, 4)
 
 
 def dice_ce_loss(logits, labels, weight=None, eps=1e-5):
@@ -1899,14 +1876,8 @@ class HeatmapLossFn(Function):
             raise RuntimeError(f"heatmap_loss: target shape {tuple(target.shape)} != output {tuple(lg.shape)}")
         tgt = target if target.dtype in (torch.uint8, torch.float32) else target.float()
         # channels dense, any stride between samples: the heat-map channels of a label volume are read where they lie
-        dense, acc = [], 1
-        for sdim in reversed(tuple(tgt.shape[1:])):
-            dense.insert(0, acc)
-            acc *= sdim
-        if tuple(tgt.stride()[1:]) != tuple(dense) or (n > 1 and tgt.stride(0) < c * spatial):
-            tgt = tgt.contiguous()
-        tgt_sn = tgt.stride(0) if n > 1 else c * spatial
-        wt = None if cweight is None else torch.as_tensor(cweight, dtype=torch.float32, device=lg.device).contiguous()
+        tgt, tgt_sn = _dense_view(tgt, tuple(tgt.shape[1:]))
+        wt = _loss_weight(cweight, lg.device)
         loss = torch.empty((), dtype=torch.float32, device=lg.device)
         lib = L.lib()
         ws = L.workspace(lib.mednet_loss_ws_bytes(n, c, spatial), lg.device)
