@@ -815,6 +815,33 @@ size_t mednet_surface_stats_ws_bytes(int d, int h, int w);
 int mednet_surface_stats(const uint8_t* surf, const float* d2, int d, int h, int w, float tol_sq, int64_t* counts, float* max_d2,
                          double* sum_sqrt, void* ws, size_t ws_bytes, mednet_stream stream);
 
+/* ---- connected components of a uint8 volume (additive to ABI 3; the reference has no post-processing code) ---------------------------
+ * Volumes are dense d x h x w uint8 at any byte address, every extent in 1 .. 2048 and d * h * w < 2^31 (else MEDNET_E_SHAPE), so a
+ * linear voxel index fits an int32.  Integer atomics only: every result is a pure function of the input, bit for bit.  Every refusal
+ * -- a null pointer, the extents, a cls outside 0 .. 255 / MEDNET_CC_ALL, invert with MEDNET_CC_ALL, a misaligned labels / table /
+ * info, k < 0, fill outside 0 .. 255 (all MEDNET_E_SHAPE), a connectivity other than 6 / 18 / 26 (MEDNET_E_UNSUPPORTED), an undersized
+ * workspace (MEDNET_E_WORKSPACE) -- returns its code before anything is launched.
+ *
+ * mednet_cc_label: foreground = voxels with vol == cls (cls in 0 .. 255), with invert = 1 those with vol != cls; cls = MEDNET_CC_ALL
+ * (invert must be 0): every non-zero voxel, two voxels being connected only if their values are equal -- one labelling for all classes.
+ * connectivity 6, 18, 26: neighbours that differ in at most 1, 2, 3 coordinates by 1 (scipy's generate_binary_structure(3, 1 | 2 | 3)).
+ *   labels  int32 d x h x w (4-byte aligned): 0 on background, 1 .. K on foreground; components are numbered in raster order (z, y, x;
+ *           x fastest) of their first voxel, which is scipy.ndimage.label's numbering.  The volume holds the parents while the call runs.
+ *   info    int64 [2] (8-byte aligned): info[0] = K; info[1] = 0, or non-zero if a parent walk reached its step cap (the voxel count;
+ *           unreachable unless the kernel is wrong -- labels are then not to be used)
+ * Workspace: one uint32 per numbering row, ceil(voxels / 4096) rows up to 2048 (4-byte aligned); 0 for illegal extents. */
+#define MEDNET_CC_ALL (-1)
+size_t mednet_cc_ws_bytes(int d, int h, int w);
+int mednet_cc_label(const uint8_t* vol, int cls, int invert, int connectivity, int d, int h, int w, int32_t* labels, int64_t* info,
+                    void* ws, size_t ws_bytes, mednet_stream stream);
+/* table int64 [k][11] (8-byte aligned; may be uninitialised, NULL only with k = 0), row id - 1 for component id of `labels`:
+ *   voxel count, zmin, zmax, ymin, ymax, xmin, xmax, sum of z, sum of y, sum of x, the component's value in vol
+ * k = 0 launches nothing.  Labels above k are left out. */
+int mednet_cc_stats(const uint8_t* vol, const int32_t* labels, int d, int h, int w, int64_t k, int64_t* table, mednet_stream stream);
+/* out[v] = (labels[v] > 0 && !keep[labels[v]]) ? fill : vol[v];  keep uint8 [K + 1], entry 0 is ignored; out == vol is legal. */
+int mednet_cc_select(const uint8_t* vol, const int32_t* labels, const uint8_t* keep, int fill, uint8_t* out, int d, int h, int w,
+                     mednet_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ INTERP_LINEAR, INTERP_NEAREST = 0, 1
 BORDER_CONSTANT, BORDER_EDGE = 0, 1
 F16, U8, I64 = 2, 3, 4  # F16: fp16 storage / resident volumes; U8, I64: label types
 NO_IGNORE = -(2 ** 31)
+CC_ALL = -1  # mednet_cc_label: every non-zero voxel, connected only within one value
 
 _vp, _i, _sz, _f, _i64 = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_int64
 
@@ -180,6 +181,10 @@ SIGNATURES = {
     "mednet_edt_sq": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _vp]),
     "mednet_surface_stats_ws_bytes": (_sz, [_i] * 3),
     "mednet_surface_stats": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mednet_cc_ws_bytes": (_sz, [_i] * 3),
+    "mednet_cc_label": (_i, [_vp] + [_i] * 6 + [_vp, _vp, _vp, _sz, _vp]),
+    "mednet_cc_stats": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp]),
+    "mednet_cc_select": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
 }
 
 _lib = None

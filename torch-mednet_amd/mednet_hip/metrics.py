@@ -250,17 +250,94 @@ class CaseMetrics:
         return out
 
 
+_LESION_COUNTS = ("n_label", "n_pred", "tp_label", "fn", "fp", "tp_pred")
+_LESION_RATIOS = ("sensitivity", "precision", "f1")
+
+
+@dataclasses.dataclass
+class LesionDetection:
+    """Lesion-wise detection counts of one class, int64 scalars on the device: n_label / n_pred components of the class in label /
+    prediction; tp_label label components overlapped by some prediction component, fn = n_label - tp_label; fp prediction components
+    that overlap no label component, tp_pred = n_pred - fp.  In fp64: sensitivity tp_label / n_label, precision tp_pred / n_pred and
+    f1, their harmonic mean; a zero denominator gives NaN."""
+    n_label: torch.Tensor
+    n_pred: torch.Tensor
+    tp_label: torch.Tensor
+    fn: torch.Tensor
+    fp: torch.Tensor
+    tp_pred: torch.Tensor
+    sensitivity: torch.Tensor
+    precision: torch.Tensor
+    f1: torch.Tensor
+
+    def to_host(self) -> dict:
+        """One transfer: the nine fields in one fp64 vector (the counts are exact in it) -> counts as int, ratios as float."""
+        flat = torch.stack([getattr(self, n).double() for n in _LESION_COUNTS + _LESION_RATIOS]).cpu().numpy()
+        out = {n: int(flat[i]) for i, n in enumerate(_LESION_COUNTS)}
+        out.update({n: float(flat[len(_LESION_COUNTS) + i]) for i, n in enumerate(_LESION_RATIOS)})
+        return out
+
+
+def lesion_detection(pred: torch.Tensor, label: torch.Tensor, cls: int, connectivity: int = 26, min_overlap: int = 1) -> LesionDetection:
+    """Component-wise detection of class `cls`: the components of pred == cls and of label == cls are labelled on the device
+    (mednet_hip.components); a prediction component and a label component overlap if they share >= min_overlap voxels.  The pairs
+    are counted with torch.unique on the key pid * (K_label + 1) + gid over the voxels where both are labelled.  Synchronises with
+    the host (the two component counts and the unique); not for a captured step."""
+    from .components import label_components
+    p = _volume_u8(pred, "lesion_detection")
+    g, _ = _label_u8(label, None, "lesion_detection")
+    _same_shape(p, g, "lesion_detection")
+    if int(min_overlap) < 1:
+        raise ValueError(f"lesion_detection: min_overlap {min_overlap} must be at least 1")
+    cp, cg = label_components(p, int(cls), connectivity), label_components(g, int(cls), connectivity)
+    kp, kg, dev = cp.count, cg.count, p.device
+    both = (cp.labels > 0) & (cg.labels > 0)
+    key, shared = torch.unique(cp.labels[both].long() * (kg + 1) + cg.labels[both].long(), return_counts=True)
+    key = key[shared >= int(min_overlap)]
+    hit_p = torch.zeros((kp + 1,), dtype=torch.bool, device=dev)
+    hit_g = torch.zeros((kg + 1,), dtype=torch.bool, device=dev)
+    hit_p[torch.div(key, kg + 1, rounding_mode="floor")] = True
+    hit_g[key % (kg + 1)] = True
+    n_label, n_pred = torch.tensor(kg, dtype=torch.int64, device=dev), torch.tensor(kp, dtype=torch.int64, device=dev)
+    tp_label, tp_pred = hit_g.sum(), hit_p.sum()
+    sens, prec = tp_label.double() / n_label.double(), tp_pred.double() / n_pred.double()
+    return LesionDetection(n_label, n_pred, tp_label, n_label - tp_label, n_pred - tp_pred, tp_pred, sens, prec,
+                           2.0 * sens * prec / (sens + prec))
+
+
+@dataclasses.dataclass
+class CaseMetricsWithLesions(CaseMetrics):
+    """CaseMetrics plus `lesions`: {cls: LesionDetection} for the lesion_classes evaluate_case was asked for; to_host() adds
+    `lesion_classes` and one `lesion_<field>` array per field of LesionDetection, in the order of lesion_classes."""
+    lesions: dict = None
+
+    def to_host(self) -> dict:
+        out = super().to_host()
+        rows = [self.lesions[c].to_host() for c in self.lesions]
+        out["lesion_classes"] = tuple(self.lesions)
+        for n in _LESION_COUNTS:
+            out["lesion_" + n] = np.asarray([r[n] for r in rows], dtype=np.int64)
+        for n in _LESION_RATIOS:
+            out["lesion_" + n] = np.asarray([r[n] for r in rows], dtype=np.float64)
+        return out
+
+
 def evaluate_case(pred: torch.Tensor, label: torch.Tensor, num_classes: int, spacing=(1, 1, 1), classes=None, percentile=95.0,
-                  tolerance=1.0, ignore_index=None) -> CaseMetrics:
+                  tolerance=1.0, ignore_index=None, lesion_classes=None, lesion_connectivity=26, lesion_min_overlap=1) -> CaseMetrics:
     """Overlap for every class and surface distances for `classes` (default 1 .. C - 1) of one case.  pred, label: D x H x W on the
     device (uint8; a label of another integer type is converted).  ignore_index applies to the confusion counts.  Synchronises with
-    the host (the percentile selects the surface voxels); not for a captured step."""
+    the host (the percentile selects the surface voxels); not for a captured step.  lesion_classes: classes to count lesion-wise as
+    well (lesion_detection); the result is then a CaseMetricsWithLesions, whose to_host() has the additional `lesion_*` keys."""
     cm, oor = confusion(pred, label, num_classes, ignore_index)
     dice, iou, sens, prec, vp, vl = overlap(cm)
     classes = tuple(range(1, int(num_classes))) if classes is None else tuple(int(c) for c in classes)
     hd, hdp, assd, nsd, n_pred, n_label = surface_distances(pred, label, classes, spacing, percentile, tolerance)
-    return CaseMetrics(cm, oor, dice, iou, sens, prec, vp, vl, classes, hd, hdp, assd, nsd, n_pred, n_label,
-                       tuple(float(s) for s in spacing), float(percentile), float(tolerance))
+    fields = (cm, oor, dice, iou, sens, prec, vp, vl, classes, hd, hdp, assd, nsd, n_pred, n_label,
+              tuple(float(s) for s in spacing), float(percentile), float(tolerance))
+    if lesion_classes is None:
+        return CaseMetrics(*fields)
+    lesions = {int(c): lesion_detection(pred, label, int(c), lesion_connectivity, lesion_min_overlap) for c in lesion_classes}
+    return CaseMetricsWithLesions(*fields, lesions)
 
 
 def landmark_errors(positions: torch.Tensor, targets, spacing=(1, 1, 1)) -> torch.Tensor:

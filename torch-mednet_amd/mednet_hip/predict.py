@@ -173,9 +173,14 @@ class BlendedPrediction:
     def __init__(self, acc, wsum, num_heatmaps, blend_of):
         self.acc, self.wsum, self.num_heatmaps, self.blend_of = acc, wsum, num_heatmaps, blend_of
 
-    def result(self):
-        """uint8 (H + 1) x D x H x W: the crop-stitch predictor's layout (heat maps clipped to 0..255, then the arg-max class)."""
-        return finalize(self.acc, self.wsum, self.num_heatmaps, self.blend_of, result=True)[0]
+    def result(self, postprocess=None):
+        """uint8 (H + 1) x D x H x W: the crop-stitch predictor's layout (heat maps clipped to 0..255, then the arg-max class).
+        postprocess: a callable on the uint8 D x H x W class volume (mednet_hip.components.Postprocess) whose result replaces the
+        class channel [-1]; None runs exactly the launches of a call without it."""
+        res = finalize(self.acc, self.wsum, self.num_heatmaps, self.blend_of, result=True)[0]
+        if postprocess is not None:
+            res[-1].copy_(postprocess(res[-1]))
+        return res
 
     def probabilities(self, dtype=torch.float32):
         return finalize(self.acc, self.wsum, self.num_heatmaps, self.blend_of, probabilities=dtype)[1]
@@ -197,13 +202,14 @@ class BlendedPrediction:
 
 class GridPredictor:
     def __init__(self, model, patch_size, patch_overlap, num_heatmaps=0, pad_mode="constant", batch_size=4,
-                 channel_selection=None, blend=None, sigma_scale=0.125, mirror_axes=(), blend_of="probabilities"):
-        """blend=None: the reference's crop-stitch (the default).  blend="gaussian" / "constant" / three per-axis weight vectors:
+                 channel_selection=None, blend=None, sigma_scale=0.125, mirror_axes=(), blend_of="probabilities", postprocess=None):
+        """postprocess: a callable on the uint8 D x H x W class volume (mednet_hip.components.Postprocess), applied to the class
+        channel [-1] of what __call__ returns; `predict` is unchanged.  blend=None: the reference's crop-stitch (the default).  blend="gaussian" / "constant" / three per-axis weight vectors:
         overlapping windows are blended (`predict`); mirror_axes: patch axes averaged over their flips (2^k passes per patch);
         blend_of: what the class channels accumulate, "probabilities" (softmax per patch) or "logits" (softmax once, at the end)."""
         self.model, self.patch_size, self.patch_overlap = model, list(patch_size), list(patch_overlap)
         self.num_heatmaps, self.pad_mode, self.batch_size, self.channel_selection = num_heatmaps, pad_mode, batch_size, channel_selection
-        self.blend, self.blend_of = blend, blend_of
+        self.blend, self.blend_of, self.postprocess = blend, blend_of, postprocess
         self.mirror_bits = mirror_mask(mirror_axes)
         if blend is None:
             if self.mirror_bits:
@@ -254,7 +260,7 @@ class GridPredictor:
     @torch.no_grad()
     def __call__(self, volume):
         if self.blend is not None:
-            return self.predict(volume).result()
+            return self.predict(volume).result(self.postprocess)
         dev = next(self.model.parameters()).device
         vol = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
         if self.channel_selection is not None:
@@ -272,4 +278,6 @@ class GridPredictor:
                 assemble(logits, pos, result, self.num_heatmaps, self.patch_overlap)
         finally:
             self.model.train(was_training)
+        if self.postprocess is not None:
+            result[-1].copy_(self.postprocess(result[-1]))
         return result
