@@ -6,7 +6,7 @@
 //   heatmap_peaks     per-channel maximum of the stitched float heat maps and its flat index (landmark positions)
 // No atomics anywhere: every voxel of a launch has ONE owning thread, which adds the contributions in row order, so the same
 // patches give the same bits whatever the batch size ("Blended inference").
-#include "common.h"
+#include "volume.h"
 
 namespace mednet {
 
@@ -34,9 +34,7 @@ __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __re
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= pvox) return;
   const int b = blockIdx.y, batch = (int)gridDim.y;
-  const int x = (int)(i % pw);
-  const size_t r = i / pw;
-  const int y = (int)(r % ph), z = (int)(r / ph);
+  const auto [z, y, x] = voxel_zyx(i, ph, pw);
   const int gz = pos[b * 3] - ov0 + z, gy = pos[b * 3 + 1] - ov1 + y, gx = pos[b * 3 + 2] - ov2 + x;
   if (gz < 0 || gz >= d || gy < 0 || gy >= h || gx < 0 || gx >= w) return;  // padding in front, overhang behind
   int qz, qy, qx;
@@ -56,13 +54,10 @@ __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __re
     float* a = acc + (size_t)nh * vox + dst;
     if (class_mode == MEDNET_BLEND_LOGITS) {
       for (int k = 0; k < ncls; ++k) a[(size_t)k * vox] = fmaf(wt, cls[(size_t)k * pvox], a[(size_t)k * vox]);
-    } else {  // one softmax per voxel per patch: max-subtracted, expf, one reciprocal (the planes are re-read from cache, not held)
-      float m = cls[0];
-      for (int k = 1; k < ncls; ++k) m = fmaxf(m, cls[(size_t)k * pvox]);
-      float s = 0.f;
-      for (int k = 0; k < ncls; ++k) s += expf(cls[(size_t)k * pvox] - m);
-      const float inv = 1.f / s;
-      for (int k = 0; k < ncls; ++k) a[(size_t)k * vox] = fmaf(wt, expf(cls[(size_t)k * pvox] - m) * inv, a[(size_t)k * vox]);
+    } else {  // one softmax per voxel per patch
+      // (captures by value: by reference the compiler forms the plane addresses with four more instructions per thread)
+      plane_softmax(ncls, [=](int k) { return cls[(size_t)k * pvox]; },
+                    [=](int k, float p) { a[(size_t)k * vox] = fmaf(wt, p, a[(size_t)k * vox]); });
     }
   }
   wsum[dst] = ws;
@@ -88,31 +83,16 @@ __global__ __launch_bounds__(256) void blend_finalize_kernel(const float* __rest
   for (int k = 0; k < nh; ++k) {
     const float v = live ? acc[(size_t)k * vox + i] / ws : 0.f;
     if (heat) heat[(size_t)k * vox + i] = v;
-    if (result) result[(size_t)k * vox + i] = (uint8_t)(int)fminf(fmaxf(v, 0.f), 255.f);  // np.clip(.., 0, 255).astype(uint8)
+    if (result) result[(size_t)k * vox + i] = heat_to_u8(v);
   }
   const float* a = acc + (size_t)nh * vox + i;
-  if (result) {  // arg-max of the class accumulators (softmax and the division by ws > 0 keep the order); first maximum on ties
-    int best = 0;
-    float bv = a[0];
-    for (int k = 1; k < ncls; ++k) {
-      const float v = a[(size_t)k * vox];
-      if (v > bv) {
-        bv = v;
-        best = k;
-      }
-    }
-    result[(size_t)nh * vox + i] = (uint8_t)(live ? best : 0);
-  }
+  // arg-max of the class accumulators (softmax and the division by ws > 0 keep the order)
+  if (result) result[(size_t)nh * vox + i] = (uint8_t)(live ? argmax_first(a, vox, ncls) : 0);
   if (!prob) return;
   if (!live) {
     for (int k = 0; k < ncls; ++k) st(prob, (size_t)k * vox + i, 0.f);
   } else if (class_mode == MEDNET_BLEND_LOGITS) {  // softmax of the blended logits
-    float m = a[0] / ws;
-    for (int k = 1; k < ncls; ++k) m = fmaxf(m, a[(size_t)k * vox] / ws);
-    float s = 0.f;
-    for (int k = 0; k < ncls; ++k) s += expf(a[(size_t)k * vox] / ws - m);
-    const float inv = 1.f / s;
-    for (int k = 0; k < ncls; ++k) st_prob(prob, (size_t)k * vox + i, expf(a[(size_t)k * vox] / ws - m) * inv);
+    plane_softmax(ncls, [&](int k) { return a[(size_t)k * vox] / ws; }, [&](int k, float p) { st_prob(prob, (size_t)k * vox + i, p); });
   } else {
     for (int k = 0; k < ncls; ++k) st_prob(prob, (size_t)k * vox + i, a[(size_t)k * vox] / ws);
   }
@@ -124,7 +104,6 @@ struct Peak {
   long long i;
 };
 constexpr long long PEAK_NONE = 0x7fffffffffffffffLL;  // nothing seen yet (a channel of NaNs only ends as index -1, value -inf)
-constexpr int PEAK_BLOCK_VOX = 4096;                    // voxels per workgroup of the first stage: one partial each
 
 __device__ __forceinline__ Peak peak_better(Peak a, Peak b) { return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a; }
 __device__ __forceinline__ int peak_lo(long long i) { return (int)(unsigned)(i & 0xffffffffLL); }
@@ -174,11 +153,12 @@ __device__ __forceinline__ Peak peak_block(Peak p) {
   return p;
 }
 
-// stage 1: block (x, channel) scans PEAK_BLOCK_VOX voxels of its channel -> one partial
+// stage 1: block (x, channel) scans VOLUME_PER_ROW voxels of its channel -> one partial
 __global__ __launch_bounds__(256) void heatmap_peaks_partial_kernel(const float* __restrict__ heat, size_t vox, unsigned blocks,
                                                                     long long* __restrict__ pidx, float* __restrict__ pval) {
   const int k = blockIdx.y;
-  const size_t i0 = (size_t)blockIdx.x * PEAK_BLOCK_VOX, i1 = i0 + PEAK_BLOCK_VOX < vox ? i0 + PEAK_BLOCK_VOX : vox;
+  size_t i0, i1;
+  row_range(vox, VOLUME_PER_ROW, i0, i1);
   Peak p{-__builtin_inff(), PEAK_NONE};
   for (size_t i = i0 + threadIdx.x; i < i1; i += 256) p = peak_better(p, Peak{heat[(size_t)k * vox + i], (long long)i});
   p = peak_block(p);
@@ -202,11 +182,15 @@ __global__ __launch_bounds__(256) void heatmap_peaks_final_kernel(const long lon
   }
 }
 
-static size_t peak_blocks(size_t voxels) { return (voxels + PEAK_BLOCK_VOX - 1) / PEAK_BLOCK_VOX; }
-
 }  // namespace mednet
 
 using namespace mednet;
+
+static int class_mode_check(const char* who, int class_mode) {
+  MEDNET_REQUIRE(class_mode == MEDNET_BLEND_PROBABILITIES || class_mode == MEDNET_BLEND_LOGITS, MEDNET_E_UNSUPPORTED,
+                 "%s: class mode %d (supported: 0 probabilities, 1 logits)", who, class_mode);
+  return MEDNET_OK;
+}
 
 extern "C" int mednet_blend_accumulate(const float* logits, const int* pos, float* acc, float* wsum, const float* win0,
                                        const float* win1, const float* win2, int batch, int num_heatmaps, int num_classes, int d,
@@ -217,12 +201,9 @@ extern "C" int mednet_blend_accumulate(const float* logits, const int* pos, floa
                      pw > 0 && ov0 >= 0 && ov1 >= 0 && ov2 >= 0,
                  MEDNET_E_SHAPE, "blend_accumulate: bad shape (batch %d, channels %d + %d, volume %dx%dx%d, patch %dx%dx%d, overlap %d %d %d)",
                  batch, num_heatmaps, num_classes, d, h, w, pd, ph, pw, ov0, ov1, ov2);
-  MEDNET_REQUIRE(mirror >= 0 && mirror <= 7, MEDNET_E_UNSUPPORTED, "blend_accumulate: mirror mask %d (supported: 0..7, bit k reverses axis k)",
-                 mirror);
-  MEDNET_REQUIRE(class_mode == MEDNET_BLEND_PROBABILITIES || class_mode == MEDNET_BLEND_LOGITS, MEDNET_E_UNSUPPORTED,
-                 "blend_accumulate: class mode %d (supported: 0 probabilities, 1 logits)", class_mode);
-  const size_t pvox = (size_t)pd * ph * pw;
-  hipLaunchKernelGGL(blend_accumulate_kernel, dim3((unsigned)((pvox + 255) / 256), batch), dim3(256), 0, (hipStream_t)stream, logits, pos,
+  if (const int rc = mirror_check("blend_accumulate", mirror)) return rc;
+  if (const int rc = class_mode_check("blend_accumulate", class_mode)) return rc;
+  hipLaunchKernelGGL(blend_accumulate_kernel, dim3(grid_blocks((size_t)pd * ph * pw, 256), batch), dim3(256), 0, (hipStream_t)stream, logits, pos,
                      acc, wsum, win0, win1, win2, num_heatmaps, num_classes, d, h, w, pd, ph, pw, ov0, ov1, ov2, mirror, class_mode);
   return check_launch("blend_accumulate");
 }
@@ -235,10 +216,9 @@ extern "C" int mednet_blend_finalize(const float* acc, const float* wsum, uint8_
                  "blend_finalize: bad shape (channels %d + %d, volume %dx%dx%d)", num_heatmaps, num_classes, d, h, w);
   MEDNET_REQUIRE(!prob || prob_dtype == MEDNET_F32 || prob_dtype == MEDNET_F16, MEDNET_E_DTYPE,
                  "blend_finalize: probability type %d (supported: f32, f16)", prob_dtype);
-  MEDNET_REQUIRE(class_mode == MEDNET_BLEND_PROBABILITIES || class_mode == MEDNET_BLEND_LOGITS, MEDNET_E_UNSUPPORTED,
-                 "blend_finalize: class mode %d (supported: 0 probabilities, 1 logits)", class_mode);
+  if (const int rc = class_mode_check("blend_finalize", class_mode)) return rc;
   const size_t vox = (size_t)d * h * w;
-  const dim3 grid((unsigned)((vox + 255) / 256));
+  const dim3 grid(grid_blocks(vox, 256));
   hipStream_t s = (hipStream_t)stream;
   if (prob && prob_dtype == MEDNET_F16)
     hipLaunchKernelGGL(blend_finalize_kernel<f16>, grid, dim3(256), 0, s, acc, wsum, result_u8, (f16*)prob, heat, num_heatmaps, num_classes,
@@ -251,7 +231,7 @@ extern "C" int mednet_blend_finalize(const float* acc, const float* wsum, uint8_
 
 extern "C" size_t mednet_heatmap_peaks_ws_bytes(int num_heatmaps, size_t voxels) {
   if (num_heatmaps <= 0 || voxels == 0) return 0;
-  return (size_t)num_heatmaps * peak_blocks(voxels) * (sizeof(long long) + sizeof(float));
+  return (size_t)num_heatmaps * grid_blocks(voxels, VOLUME_PER_ROW) * (sizeof(long long) + sizeof(float));
 }
 
 extern "C" int mednet_heatmap_peaks(const float* heat, int num_heatmaps, size_t voxels, int64_t* out_index, float* out_value, void* ws,
@@ -262,7 +242,7 @@ extern "C" int mednet_heatmap_peaks(const float* heat, int num_heatmaps, size_t 
   MEDNET_REQUIRE(ws_bytes >= mednet_heatmap_peaks_ws_bytes(num_heatmaps, voxels), MEDNET_E_WORKSPACE,
                  "heatmap_peaks: workspace %zu < %zu bytes", ws_bytes, mednet_heatmap_peaks_ws_bytes(num_heatmaps, voxels));
   MEDNET_REQUIRE((uintptr_t)ws % sizeof(long long) == 0, MEDNET_E_WORKSPACE, "heatmap_peaks: workspace not 8-byte aligned");
-  const size_t blocks = peak_blocks(voxels);
+  const size_t blocks = grid_blocks(voxels, VOLUME_PER_ROW);
   long long* pidx = (long long*)ws;
   float* pval = (float*)(pidx + (size_t)num_heatmaps * blocks);
   hipStream_t s = (hipStream_t)stream;

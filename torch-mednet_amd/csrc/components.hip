@@ -12,24 +12,12 @@
 //   cc_select  one launch: out = keep[label] ? vol : fill on labelled voxels
 // Integer atomics only (order-independent), nothing waits for another workgroup inside a launch, every loop that follows parents
 // has a step cap (see unite()), every neighbour test is on coordinates.
-#include "common.h"
+#include "volume.h"
 
 namespace mednet {
 
-constexpr int CC_MAX_EXTENT = 2048;
-constexpr unsigned CC_MAX_ROWS = 2048;   // numbering rows: one workgroup each, at most 256 CUs x 8
-constexpr size_t CC_PER_BLOCK = 4096;    // voxels of a numbering row until the row limit is reached
-constexpr unsigned CC_MAX_BLOCKS = 8192; // grid of the passes that have no rows
+constexpr size_t CC_MAX_BLOCKS = 8192;   // grid of the passes that have no numbering rows (the rows are volume.h's row plan)
 constexpr int CC_CHUNK = 256;            // voxels of a wave in init: 64 lanes x one aligned 4-byte word of the volume
-
-static inline unsigned cc_rows(size_t vox) {
-  size_t b = (vox + CC_PER_BLOCK - 1) / CC_PER_BLOCK;
-  if (b > CC_MAX_ROWS) b = CC_MAX_ROWS;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-// voxels per row, a multiple of 256: row r takes [r * share, min(vox, (r + 1) * share))
-static inline size_t cc_share(size_t vox, unsigned rows) { return align_up((vox + rows - 1) / rows, 256); }
 
 // 0 on background, else what two connected voxels must agree in
 __device__ __forceinline__ int cc_key(int val, int cls, int invert) {
@@ -185,8 +173,7 @@ __global__ __launch_bounds__(256) void cc_merge_kernel(const uint8_t* __restrict
       const int key = k[j];
       if (!key) continue;
       const int64_t v = first + j;
-      const int64_t row = v / w;
-      const int x = (int)(v - row * w), y = (int)(row % h), z = (int)(row / h);
+      const auto [z, y, x] = voxel_zyx(v, h, w);
       const bool cont = x > 0 && (j ? k[j - 1] : left) == key;
       if (cont && ((v + off) & (CC_CHUNK - 1)) == 0) cc_unite(L, (int)v + 1, (int)v, cap, info);  // a run cut by a chunk border
       for (int r = 0; r < 4; ++r) {
@@ -214,10 +201,9 @@ __global__ __launch_bounds__(256) void cc_merge_kernel(const uint8_t* __restrict
 // After merge every set is a tree whose root r has P[r] = r, the smallest id of the set: its first voxel in raster order.
 __global__ __launch_bounds__(256) void cc_flatten_kernel(int* L, int64_t vox, int64_t share, unsigned* __restrict__ rows,
                                                          int64_t* info) {
-  __shared__ unsigned red[4];
-  const int64_t begin = (int64_t)blockIdx.x * share;
-  int64_t end = begin + share;
-  if (end > vox) end = vox;
+  __shared__ unsigned red[256];
+  int64_t begin, end;
+  row_range(vox, share, begin, end);
   const unsigned cap = (unsigned)vox;
   unsigned roots = 0;
   for (int64_t v = begin + threadIdx.x; v < end; v += 256) {
@@ -229,11 +215,8 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(int* L, int64_t vox, in
     if (r != p) cc_poke(L + v, r);  // a root is never rewritten here: finds of other threads through v stay valid
     roots += r == (int)v + 1 ? 1u : 0u;
   }
-  // integer sum: any order gives the same result
-  for (int s = 32; s > 0; s >>= 1) roots += __shfl_xor(roots, s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = roots;
-  __syncthreads();
-  if (threadIdx.x == 0) rows[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  roots = block_tree(roots, red, [](unsigned a, unsigned b) { return a + b; });  // integer sum: any order gives the same result
+  if (threadIdx.x == 0) rows[blockIdx.x] = roots;
 }
 
 // one workgroup: rows[r] becomes the number of roots in the rows before r, info[0] = K
@@ -267,9 +250,8 @@ __global__ __launch_bounds__(256) void cc_mark_kernel(int* __restrict__ L, int64
                                                       const unsigned* __restrict__ rows) {
   __shared__ unsigned wave_n[4];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t begin = (int64_t)blockIdx.x * share;
-  int64_t end = begin + share;
-  if (end > vox) end = vox;
+  int64_t begin, end;
+  row_range(vox, share, begin, end);
   unsigned run = rows[blockIdx.x];
   for (int64_t base = begin; base < end; base += 256) {  // uniform: the barriers are reached by every thread
     const int64_t v = base + threadIdx.x;
@@ -311,7 +293,7 @@ __global__ __launch_bounds__(256) void cc_table_init_kernel(int64_t* __restrict_
   const int64_t n = k * CC_COLS;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int col = (int)(e % CC_COLS);
-    table[e] = (col == 1 || col == 3 || col == 5) ? (int64_t)CC_MAX_EXTENT : (col == 2 || col == 4 || col == 6) ? -1 : 0;
+    table[e] = (col == 1 || col == 3 || col == 5) ? (int64_t)VOLUME_MAX_EXTENT : (col == 2 || col == 4 || col == 6) ? -1 : 0;
   }
 }
 
@@ -331,14 +313,12 @@ __global__ __launch_bounds__(256) void cc_stats_kernel(const uint8_t* __restrict
     const bool valid = v < vox;
     const int lab = valid ? labels[v] : 0;
     const int left = __shfl_up(lab, 1);
-    const int64_t row = valid ? v / w : 0;
-    const int x = (int)(v - row * w);
+    const auto [z, y, x] = valid ? voxel_zyx(v, h, w) : Zyx{0, 0, 0};
     const bool start = !valid || lane == 0 || x == 0 || lab != left;
     const unsigned long long b = __ballot(start);
     if (valid && start && lab > 0 && (int64_t)lab <= k) {
       const unsigned long long above = b & ~((2ull << lane) - 1ull);
       const int len = (above ? __ffsll((long long)above) - 1 : 64) - lane;
-      const int64_t y = row % h, z = row / h;
       int64_t* t = table + (int64_t)(lab - 1) * CC_COLS;
       cc_add(t + 0, len);
       cc_min(t + 1, z);
@@ -347,8 +327,8 @@ __global__ __launch_bounds__(256) void cc_stats_kernel(const uint8_t* __restrict
       cc_max(t + 4, y);
       cc_min(t + 5, x);
       cc_max(t + 6, x + len - 1);
-      cc_add(t + 7, z * len);
-      cc_add(t + 8, y * len);
+      cc_add(t + 7, (int64_t)z * len);
+      cc_add(t + 8, (int64_t)y * len);
       cc_add(t + 9, (int64_t)x * len + (int64_t)len * (len - 1) / 2);
       cc_max(t + 10, (int64_t)vol[v]);
     }
@@ -369,22 +349,14 @@ __global__ __launch_bounds__(256) void cc_select_kernel(const uint8_t* vol, cons
 // =================================================================================================== C ABI
 using namespace mednet;
 
-static inline bool cc_extent_ok(int e) { return e >= 1 && e <= CC_MAX_EXTENT; }
 static inline bool cc_volume_ok(int d, int h, int w) { return (size_t)d * h * w < ((size_t)1 << 31); }
-#define CC_REQUIRE_EXTENTS(who, d, h, w)                                                                                          \
-  MEDNET_REQUIRE(cc_extent_ok(d) && cc_extent_ok(h) && cc_extent_ok(w), MEDNET_E_SHAPE, who ": extents %d x %d x %d outside 1 .. %d", \
-                 d, h, w, CC_MAX_EXTENT);                                                                                          \
+#define CC_REQUIRE_EXTENTS(who, d, h, w) \
+  VOLUME_REQUIRE_EXTENTS(who, d, h, w);    \
   MEDNET_REQUIRE(cc_volume_ok(d, h, w), MEDNET_E_SHAPE, who ": %d x %d x %d voxels do not fit a 32-bit index (limit 2^31 - 1)", d, h, w)
 
-static inline unsigned cc_blocks(size_t items) {
-  size_t b = (items + 255) / 256;
-  if (b > CC_MAX_BLOCKS) b = CC_MAX_BLOCKS;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 extern "C" size_t mednet_cc_ws_bytes(int d, int h, int w) {
-  if (!cc_extent_ok(d) || !cc_extent_ok(h) || !cc_extent_ok(w) || !cc_volume_ok(d, h, w)) return 0;
-  return (size_t)cc_rows((size_t)d * h * w) * sizeof(unsigned);
+  if (!extents_ok(d, h, w) || !cc_volume_ok(d, h, w)) return 0;
+  return (size_t)row_plan((size_t)d * h * w).rows * sizeof(unsigned);
 }
 
 extern "C" int mednet_cc_label(const uint8_t* vol, int cls, int invert, int connectivity, int d, int h, int w, int32_t* labels,
@@ -402,11 +374,11 @@ extern "C" int mednet_cc_label(const uint8_t* vol, int cls, int invert, int conn
   const size_t need = mednet_cc_ws_bytes(d, h, w);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "cc_label: workspace %zu < %zu bytes", ws_bytes, need);
   const int64_t vox = (int64_t)d * h * w;
-  const unsigned rows = cc_rows((size_t)vox);
-  const int64_t share = (int64_t)cc_share((size_t)vox, rows);
+  const auto [rows, ushare] = row_plan((size_t)vox);
+  const int64_t share = (int64_t)ushare;
   const int off = (int)((uintptr_t)vol & 3);
   const uint8_t* base = vol;  // word `k` of the kernels is the aligned word at vol - off + 4 k
-  const unsigned wblocks = cc_blocks((size_t)(vox + off + 3) / 4), vblocks = cc_blocks((size_t)vox);
+  const size_t wblocks = grid_blocks((size_t)(vox + off + 3) / 4, 256, CC_MAX_BLOCKS), vblocks = grid_blocks((size_t)vox, 256, CC_MAX_BLOCKS);
   const int c = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3;
   unsigned* r = static_cast<unsigned*>(ws);
   hipStream_t s = (hipStream_t)stream;
@@ -436,10 +408,10 @@ extern "C" int mednet_cc_stats(const uint8_t* vol, const int32_t* labels, int d,
   if (k == 0) return MEDNET_OK;
   const int64_t vox = (int64_t)d * h * w;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(cc_table_init_kernel, dim3(cc_blocks((size_t)k * CC_COLS)), dim3(256), 0, s, table, k);
+  hipLaunchKernelGGL(cc_table_init_kernel, dim3(grid_blocks((size_t)k * CC_COLS, 256, CC_MAX_BLOCKS)), dim3(256), 0, s, table, k);
   const int rc = check_launch("cc_stats(init)");
   if (rc != MEDNET_OK) return rc;
-  hipLaunchKernelGGL(cc_stats_kernel, dim3(cc_blocks((size_t)vox)), dim3(256), 0, s, vol, labels, vox, h, w, k, table);
+  hipLaunchKernelGGL(cc_stats_kernel, dim3(grid_blocks((size_t)vox, 256, CC_MAX_BLOCKS)), dim3(256), 0, s, vol, labels, vox, h, w, k, table);
   return check_launch("cc_stats");
 }
 
@@ -450,7 +422,7 @@ extern "C" int mednet_cc_select(const uint8_t* vol, const int32_t* labels, const
   MEDNET_REQUIRE(fill >= 0 && fill <= 255, MEDNET_E_SHAPE, "cc_select: fill %d is no uint8 value", fill);
   MEDNET_REQUIRE(((uintptr_t)labels & 3) == 0, MEDNET_E_SHAPE, "cc_select: labels not 4-byte aligned");
   const int64_t vox = (int64_t)d * h * w;
-  hipLaunchKernelGGL(cc_select_kernel, dim3(cc_blocks((size_t)vox)), dim3(256), 0, (hipStream_t)stream, vol, labels, keep,
+  hipLaunchKernelGGL(cc_select_kernel, dim3(grid_blocks((size_t)vox, 256, CC_MAX_BLOCKS)), dim3(256), 0, (hipStream_t)stream, vol, labels, keep,
                      (uint8_t)fill, out, vox);
   return check_launch("cc_select");
 }

@@ -9,39 +9,11 @@
 // No float atomics, no loop without a bound given by an extent or a class count, nothing waits for another workgroup; every grid is a
 // function of the extents alone and every sum has a fixed order, so the same inputs give the same bits.
 #include <float.h>
-#include "common.h"
+#include "volume.h"
 
 namespace mednet {
 
-constexpr int METRIC_MAX_EXTENT = 2048;
 constexpr int METRIC_MAX_CLASSES = 32;
-constexpr unsigned METRIC_MAX_ROWS = 2048;   // memory-bound passes: at most 256 CUs x 8 workgroups
-constexpr size_t METRIC_PER_BLOCK = 4096;    // voxels of a workgroup until the row limit is reached: 256 threads x 16
-
-static inline unsigned metric_rows(size_t vox) {
-  size_t b = (vox + METRIC_PER_BLOCK - 1) / METRIC_PER_BLOCK;
-  if (b > METRIC_MAX_ROWS) b = METRIC_MAX_ROWS;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-// voxels per workgroup, a multiple of 256: workgroup r takes [r * share, min(vox, (r + 1) * share)).  At most 2^33 / 2048 = 2^22
-// voxels, so 32-bit counters per workgroup cannot overflow.
-static inline size_t metric_share(size_t vox, unsigned rows) { return align_up((vox + rows - 1) / rows, 256); }
-
-// fixed-order tree over the 256 threads of a workgroup; the result is valid in every thread
-template <typename T, typename OP>
-__device__ __forceinline__ T block_tree(T v, T* buf, OP op) {
-  buf[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) buf[threadIdx.x] = op(buf[threadIdx.x], buf[threadIdx.x + s]);
-    __syncthreads();
-  }
-  const T r = buf[0];
-  __syncthreads();
-  return r;
-}
 
 // ---------------------------------------------------------------------------------------------- confusion counts
 // Entry l * ncls + p counts label l predicted as p, entry ncls^2 the voxels with label or prediction >= ncls.  A thread keeps the
@@ -53,9 +25,8 @@ __global__ __launch_bounds__(256) void confusion_partial_kernel(const uint8_t* _
   const int entries = ncls * ncls + 1;
   for (int e = threadIdx.x; e < entries; e += 256) cnt[e] = 0u;
   __syncthreads();
-  const size_t begin = (size_t)blockIdx.x * share;
-  size_t end = begin + share;
-  if (end > vox) end = vox;
+  size_t begin, end;
+  row_range(vox, share, begin, end);
   int cur = -1;
   unsigned run = 0;
   for (size_t i = begin + threadIdx.x; i < end; i += 256) {
@@ -104,8 +75,7 @@ __global__ __launch_bounds__(256) void surface_mask_kernel(const uint8_t* __rest
                                                            int d, int h, int w) {
   const size_t vox = (size_t)d * h * w, stride = (size_t)gridDim.x * 256;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < vox; i += stride) {
-    const size_t row = i / (size_t)w;
-    const int x = (int)(i - row * w), y = (int)(row % (size_t)h), z = (int)(row / (size_t)h);
+    const auto [z, y, x] = voxel_zyx(i, h, w);
     out[i] = surface_voxel(vol, i, z, y, x, d, h, w, cls);
     if (vol2) out2[i] = surface_voxel(vol2, i, z, y, x, d, h, w, cls);
   }
@@ -130,7 +100,7 @@ static inline int edt_bundle(int n) { return edt_np(n) <= EDT_NP_64 ? 64 : edt_n
 constexpr size_t edt_lds_bytes(int np, int bx) { return ((size_t)2 * np + (size_t)np * (bx + 1)) * sizeof(float); }
 template <int BX>
 constexpr size_t edt_lds_cap() {
-  return edt_lds_bytes(BX == 64 ? EDT_NP_64 : BX == 32 ? EDT_NP_32 : METRIC_MAX_EXTENT, BX);
+  return edt_lds_bytes(BX == 64 ? EDT_NP_64 : BX == 32 ? EDT_NP_32 : VOLUME_MAX_EXTENT, BX);
 }
 
 template <int BX, bool FIRST>
@@ -263,9 +233,8 @@ __device__ __forceinline__ void stats_reduce_store(int64_t n, int64_t within, do
 __global__ __launch_bounds__(256) void surface_stats_partial_kernel(const uint8_t* __restrict__ surf, const float* __restrict__ d2,
                                                                     size_t vox, size_t share, float tol_sq, StatsRows rows) {
   __shared__ StatsShared sh;
-  const size_t begin = (size_t)blockIdx.x * share;
-  size_t end = begin + share;
-  if (end > vox) end = vox;
+  size_t begin, end;
+  row_range(vox, share, begin, end);
   int64_t n = 0, within = 0;
   double sum = 0.0;
   float mx = -__builtin_inff();
@@ -301,20 +270,15 @@ __global__ __launch_bounds__(256) void surface_stats_finalize_kernel(StatsRows r
 // =================================================================================================== C ABI
 using namespace mednet;
 
-static inline bool extent_ok(int e) { return e >= 1 && e <= METRIC_MAX_EXTENT; }
-#define METRIC_REQUIRE_EXTENTS(who, d, h, w)                                                                                  \
-  MEDNET_REQUIRE(extent_ok(d) && extent_ok(h) && extent_ok(w), MEDNET_E_SHAPE, who ": extents %d x %d x %d outside 1 .. %d", d, h, \
-                 w, METRIC_MAX_EXTENT)
-
 extern "C" size_t mednet_confusion_ws_bytes(int d, int h, int w, int ncls) {
-  if (!extent_ok(d) || !extent_ok(h) || !extent_ok(w) || ncls < 1 || ncls > METRIC_MAX_CLASSES) return 0;
-  return (size_t)metric_rows((size_t)d * h * w) * (size_t)(ncls * ncls + 1) * sizeof(unsigned);
+  if (!extents_ok(d, h, w) || ncls < 1 || ncls > METRIC_MAX_CLASSES) return 0;
+  return (size_t)row_plan((size_t)d * h * w).rows * (size_t)(ncls * ncls + 1) * sizeof(unsigned);
 }
 
 extern "C" int mednet_confusion(const uint8_t* pred, const uint8_t* label, int d, int h, int w, int ncls, int ignore_index,
                                 int64_t* counts, void* ws, size_t ws_bytes, mednet_stream stream) {
   MEDNET_REQUIRE(pred && label && counts && ws, MEDNET_E_SHAPE, "confusion: null pointer");
-  METRIC_REQUIRE_EXTENTS("confusion", d, h, w);
+  VOLUME_REQUIRE_EXTENTS("confusion", d, h, w);
   MEDNET_REQUIRE(ncls >= 1, MEDNET_E_SHAPE, "confusion: ncls %d", ncls);
   MEDNET_REQUIRE(ncls <= METRIC_MAX_CLASSES, MEDNET_E_UNSUPPORTED, "confusion: ncls %d above %d", ncls, METRIC_MAX_CLASSES);
   const size_t need = mednet_confusion_ws_bytes(d, h, w, ncls);
@@ -322,10 +286,10 @@ extern "C" int mednet_confusion(const uint8_t* pred, const uint8_t* label, int d
   MEDNET_REQUIRE(((uintptr_t)ws & 3) == 0 && ((uintptr_t)counts & 7) == 0, MEDNET_E_SHAPE,
                  "confusion: workspace not 4-byte or counts not 8-byte aligned");
   const size_t vox = (size_t)d * h * w;
-  const unsigned rows = metric_rows(vox);
+  const auto [rows, share] = row_plan(vox);
   const int entries = ncls * ncls + 1;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(confusion_partial_kernel, dim3(rows), dim3(256), 0, s, pred, label, vox, metric_share(vox, rows), ncls,
+  hipLaunchKernelGGL(confusion_partial_kernel, dim3(rows), dim3(256), 0, s, pred, label, vox, share, ncls,
                      ignore_index, (unsigned*)ws);
   const int rc = check_launch("confusion(partials)");
   if (rc != MEDNET_OK) return rc;
@@ -337,11 +301,10 @@ extern "C" int mednet_surface_mask(const uint8_t* vol, uint8_t* out, const uint8
                                    int w, mednet_stream stream) {
   MEDNET_REQUIRE(vol && out, MEDNET_E_SHAPE, "surface_mask: null pointer");
   MEDNET_REQUIRE((vol2 == nullptr) == (out2 == nullptr), MEDNET_E_SHAPE, "surface_mask: null pointer (second volume or its mask)");
-  METRIC_REQUIRE_EXTENTS("surface_mask", d, h, w);
+  VOLUME_REQUIRE_EXTENTS("surface_mask", d, h, w);
   MEDNET_REQUIRE(cls >= 0 && cls <= 255, MEDNET_E_SHAPE, "surface_mask: class %d is no uint8 value", cls);
   const size_t vox = (size_t)d * h * w;
-  size_t blocks = (vox + 1023) / 1024;  // four voxels per thread until the grid is full
-  if (blocks > 8 * METRIC_MAX_ROWS) blocks = 8 * METRIC_MAX_ROWS;
+  const size_t blocks = grid_blocks(vox, 1024, 8 * VOLUME_MAX_ROWS);  // four voxels per thread until the grid is full
   hipLaunchKernelGGL(surface_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, vol, out, vol2, out2, cls, d, h,
                      w);
   return check_launch("surface_mask");
@@ -350,7 +313,7 @@ extern "C" int mednet_surface_mask(const uint8_t* vol, uint8_t* out, const uint8
 extern "C" int mednet_edt_sq(const uint8_t* seed, float* out, int d, int h, int w, float sz, float sy, float sx,
                              mednet_stream stream) {
   MEDNET_REQUIRE(seed && out, MEDNET_E_SHAPE, "edt_sq: null pointer");
-  METRIC_REQUIRE_EXTENTS("edt_sq", d, h, w);
+  VOLUME_REQUIRE_EXTENTS("edt_sq", d, h, w);
   MEDNET_REQUIRE(sz > 0.f && sy > 0.f && sx > 0.f && sz <= FLT_MAX && sy <= FLT_MAX && sx <= FLT_MAX, MEDNET_E_SHAPE,
                  "edt_sq: spacing (%g, %g, %g) must be finite and positive", (double)sz, (double)sy, (double)sx);
   MEDNET_REQUIRE(((uintptr_t)out & 3) == 0, MEDNET_E_SHAPE, "edt_sq: output not 4-byte aligned");
@@ -365,14 +328,14 @@ extern "C" int mednet_edt_sq(const uint8_t* seed, float* out, int d, int h, int 
 }
 
 extern "C" size_t mednet_surface_stats_ws_bytes(int d, int h, int w) {
-  if (!extent_ok(d) || !extent_ok(h) || !extent_ok(w)) return 0;
-  return (size_t)metric_rows((size_t)d * h * w) * STATS_ROW_BYTES;
+  if (!extents_ok(d, h, w)) return 0;
+  return (size_t)row_plan((size_t)d * h * w).rows * STATS_ROW_BYTES;
 }
 
 extern "C" int mednet_surface_stats(const uint8_t* surf, const float* d2, int d, int h, int w, float tol_sq, int64_t* counts,
                                     float* max_d2, double* sum_sqrt, void* ws, size_t ws_bytes, mednet_stream stream) {
   MEDNET_REQUIRE(surf && d2 && counts && max_d2 && sum_sqrt && ws, MEDNET_E_SHAPE, "surface_stats: null pointer");
-  METRIC_REQUIRE_EXTENTS("surface_stats", d, h, w);
+  VOLUME_REQUIRE_EXTENTS("surface_stats", d, h, w);
   MEDNET_REQUIRE(tol_sq >= 0.f, MEDNET_E_SHAPE, "surface_stats: squared tolerance %g is negative or NaN", (double)tol_sq);
   const size_t need = mednet_surface_stats_ws_bytes(d, h, w);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "surface_stats: workspace %zu < %zu bytes", ws_bytes, need);
@@ -380,10 +343,10 @@ extern "C" int mednet_surface_stats(const uint8_t* surf, const float* d2, int d,
                      ((uintptr_t)max_d2 & 3) == 0 && ((uintptr_t)d2 & 3) == 0,
                  MEDNET_E_SHAPE, "surface_stats: pointer not aligned to its element");
   const size_t vox = (size_t)d * h * w;
-  const unsigned rows = metric_rows(vox);
+  const auto [rows, share] = row_plan(vox);
   const StatsRows r = stats_rows(ws, rows);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(surface_stats_partial_kernel, dim3(rows), dim3(256), 0, s, surf, d2, vox, metric_share(vox, rows), tol_sq, r);
+  hipLaunchKernelGGL(surface_stats_partial_kernel, dim3(rows), dim3(256), 0, s, surf, d2, vox, share, tol_sq, r);
   const int rc = check_launch("surface_stats(partials)");
   if (rc != MEDNET_OK) return rc;
   hipLaunchKernelGGL(surface_stats_finalize_kernel, dim3(1), dim3(256), 0, s, r, rows, counts, max_d2, sum_sqrt);

@@ -4,7 +4,7 @@
 //   predict_assemble examples/predict.py:88-95 (argmax of the class logits, heat maps clipped to uint8) fused with
 //                    GridPatchSampler.add_processed_batch (dataset.py:446-474): crop the overlap, clip at the volume
 //                    edge, write into the result volume -- one pass over the logits, nothing intermediate in HBM.
-#include "common.h"
+#include "volume.h"
 
 namespace mednet {
 
@@ -26,12 +26,7 @@ __global__ __launch_bounds__(256) void grid_gather_kernel(const float* __restric
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= per) return;
   const int b = blockIdx.y;
-  const int x = (int)(i % pw);
-  size_t r = i / pw;
-  const int y = (int)(r % ph);
-  r /= ph;
-  const int z = (int)(r % pd);
-  const int cc = (int)(r / pd);
+  const auto [cc, z, y, x] = voxel_czyx(i, pd, ph, pw);
   // bit k of `mirror` reverses patch axis k: voxel (z, y, x) holds what the unmirrored patch holds at (pd - 1 - z, ..)
   const int mz = (mirror & 1) ? pd - 1 - z : z, my = (mirror & 2) ? ph - 1 - y : y, mx = (mirror & 4) ? pw - 1 - x : x;
   const int sz = pad_src(pos[b * 3] + mz, ov0, d, mode), sy = pad_src(pos[b * 3 + 1] + my, ov1, h, mode),
@@ -50,10 +45,7 @@ __global__ __launch_bounds__(256) void predict_assemble_kernel(const float* __re
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= win) return;
   const int b = blockIdx.y;
-  const int x = (int)(i % cx);
-  size_t r = i / cx;
-  const int y = (int)(r % cy);
-  const int z = (int)(r / cy);
+  const auto [z, y, x] = voxel_zyx(i, cy, cx);
   const int gz = pos[b * 3] + z, gy = pos[b * 3 + 1] + y, gx = pos[b * 3 + 2] + x;
   if (gz >= d || gy >= h || gx >= w) return;  // the part of the last patches that hangs over the volume
   // The windows of one launch can overlap: the grid step on axis 0 is pd - 2 o0, the window pd - o0 - o1 long, so with o0 > o1
@@ -67,20 +59,8 @@ __global__ __launch_bounds__(256) void predict_assemble_kernel(const float* __re
   const size_t pvox = (size_t)pd * ph * pw;
   const float* src = logits + (size_t)b * (nh + ncls) * pvox + ((size_t)(z + cs0) * ph + (y + cs1)) * pw + (x + cs2);
   const size_t vox = (size_t)d * h * w, dst = ((size_t)gz * h + gy) * w + gx;
-  for (int k = 0; k < nh; ++k) {
-    const float v = fminf(fmaxf(src[(size_t)k * pvox], 0.f), 255.f);  // np.clip(.., 0, 255).astype(uint8): truncation
-    result[(size_t)k * vox + dst] = (uint8_t)(int)v;
-  }
-  int best = 0;
-  float bv = src[(size_t)nh * pvox];
-  for (int k = 1; k < ncls; ++k) {  // argmax(softmax(x)) == argmax(x); first maximum on ties like torch.argmax
-    const float v = src[(size_t)(nh + k) * pvox];
-    if (v > bv) {
-      bv = v;
-      best = k;
-    }
-  }
-  result[(size_t)nh * vox + dst] = (uint8_t)best;
+  for (int k = 0; k < nh; ++k) result[(size_t)k * vox + dst] = heat_to_u8(src[(size_t)k * pvox]);
+  result[(size_t)nh * vox + dst] = (uint8_t)argmax_first(src + (size_t)nh * pvox, pvox, ncls);  // argmax(softmax(x)) == argmax(x)
 }
 
 // ---- training-patch crop: MedDataset.__getitem__'s `vol[:, i0:i1, j0:j1, k0:k1].astype(..)`
@@ -93,12 +73,7 @@ __global__ __launch_bounds__(256) void crop_patches_kernel(const TS* __restrict_
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= per) return;
   const int b = blockIdx.y;
-  const int x = (int)(i % pw);
-  size_t r = i / pw;
-  const int y = (int)(r % ph);
-  r /= ph;
-  const int z = (int)(r % pd);
-  const int cc = (int)(r / pd);
+  const auto [cc, z, y, x] = voxel_czyx(i, pd, ph, pw);
   const TS v = src[(((size_t)cc * d + pos[b * 3] + z) * h + pos[b * 3 + 1] + y) * w + pos[b * 3 + 2] + x];
   out[(((size_t)slot[b] * c_total + c_off + cc) * pd + z) * ph * pw + (size_t)y * pw + x] = (TD)v;
 }
@@ -114,8 +89,7 @@ extern "C" int mednet_crop_patches(const void* src, int src_dtype, const int* po
                      c_off + c <= c_total,
                  MEDNET_E_SHAPE, "crop_patches: bad shape (patch %dx%dx%d in %dx%dx%d, channels %d+%d of %d)", pd, ph, pw, d, h, w,
                  c_off, c, c_total);
-  const size_t per = (size_t)c * pd * ph * pw;
-  const dim3 grid((unsigned)((per + 255) / 256), count);
+  const dim3 grid(grid_blocks((size_t)c * pd * ph * pw, 256), count);
   hipStream_t s = (hipStream_t)stream;
 #define CP_GO(TS_, TD_) hipLaunchKernelGGL((crop_patches_kernel<TS_, TD_>), grid, dim3(256), 0, s, (const TS_*)src, pos, slot, (TD_*)out, c, d, h, w, c_total, c_off, pd, ph, pw)
   if (src_dtype == MEDNET_F16 && dst_dtype == MEDNET_F32) CP_GO(_Float16, float);
@@ -132,8 +106,7 @@ static int grid_gather_go(const char* who, const float* volume, const int* pos, 
   MEDNET_REQUIRE(batch > 0 && c > 0 && d > 0 && h > 0 && w > 0 && pd > 0 && ph > 0 && pw > 0, MEDNET_E_SHAPE, "%s: bad shape", who);
   MEDNET_REQUIRE(pad_mode == MEDNET_PAD_CONSTANT || pad_mode == MEDNET_PAD_SYMMETRIC, MEDNET_E_UNSUPPORTED,
                  "%s: pad mode %d (supported: constant, symmetric)", who, pad_mode);
-  const size_t per = (size_t)c * pd * ph * pw;
-  hipLaunchKernelGGL(grid_gather_kernel, dim3((unsigned)((per + 255) / 256), batch), dim3(256), 0, (hipStream_t)stream, volume,
+  hipLaunchKernelGGL(grid_gather_kernel, dim3(grid_blocks((size_t)c * pd * ph * pw, 256), batch), dim3(256), 0, (hipStream_t)stream, volume,
                      pos, out, c, d, h, w, pd, ph, pw, ov0, ov1, ov2, pad_mode, mirror);
   return check_launch(who);
 }
@@ -147,8 +120,7 @@ extern "C" int mednet_grid_gather_mirror(const float* volume, const int* pos, fl
                                          int pd, int ph, int pw, int ov0, int ov1, int ov2, int pad_mode, int mirror,
                                          mednet_stream stream) {
   MEDNET_REQUIRE(volume && pos && out, MEDNET_E_SHAPE, "grid_gather_mirror: null pointer");
-  MEDNET_REQUIRE(mirror >= 0 && mirror <= 7, MEDNET_E_UNSUPPORTED, "grid_gather_mirror: mirror mask %d (supported: 0..7, bit k reverses axis k)",
-                 mirror);
+  if (const int rc = mirror_check("grid_gather_mirror", mirror)) return rc;
   return grid_gather_go("grid_gather_mirror", volume, pos, out, batch, c, d, h, w, pd, ph, pw, ov0, ov1, ov2, pad_mode, mirror, stream);
 }
 
@@ -162,7 +134,7 @@ extern "C" int mednet_predict_assemble(const float* logits, const int* pos, uint
                  MEDNET_E_SHAPE, "predict_assemble: crop window outside the patch");
   const size_t win = (size_t)crop_d * crop_h * crop_w;
   if (win == 0) return MEDNET_OK;  // (the reference's slicing yields an empty window when an overlap is 0)
-  hipLaunchKernelGGL(predict_assemble_kernel, dim3((unsigned)((win + 255) / 256), batch), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(predict_assemble_kernel, dim3(grid_blocks(win, 256), batch), dim3(256), 0, (hipStream_t)stream,
                      logits, pos, result, num_heatmaps, num_classes, d, h, w, pd, ph, pw, crop_start0, crop_start1,
                      crop_start2, crop_d, crop_h, crop_w);
   return check_launch("predict_assemble");

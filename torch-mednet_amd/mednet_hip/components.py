@@ -23,29 +23,11 @@ import dataclasses
 import torch
 
 from . import _lib as L
+from ._volume import like_volume, volume_u8
 
 COUNT, ZMIN, ZMAX, YMIN, YMAX, XMIN, XMAX, SUM_Z, SUM_Y, SUM_X, VALUE = range(11)
 COLUMNS = 11
-
-
-def _volume_u8(t: torch.Tensor, who: str) -> torch.Tensor:
-    """uint8 D x H x W, dense: a view such as the class channel of a uint8 C x D x H x W result is read where it lies."""
-    L.require_gpu(t, who)
-    if t.dim() != 3:
-        raise ValueError(f"{who}: a D x H x W volume expected, got shape {tuple(t.shape)}")
-    if t.dtype == torch.bool:
-        t = t.to(torch.uint8)
-    if t.dtype != torch.uint8:
-        raise ValueError(f"{who}: a uint8 volume expected, got {t.dtype}")
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _out_u8(out, vol: torch.Tensor, who: str) -> torch.Tensor:
-    if out is None:
-        return torch.empty(tuple(vol.shape), dtype=torch.uint8, device=vol.device)
-    if out.dtype != torch.uint8 or out.shape != vol.shape or not out.is_contiguous() or out.device != vol.device:
-        raise ValueError(f"{who}: out must be a contiguous uint8 volume of the input's shape on its device")
-    return out
+_OUT = "out must be a contiguous uint8 volume of the input's shape on its device"
 
 
 @dataclasses.dataclass
@@ -81,7 +63,7 @@ class Components:
         """out[v] = fill where labels[v] > 0 and keep[labels[v]] is 0, else volume[v].  keep: uint8 / bool [count + 1] on the device,
         entry 0 is ignored.  out may be the volume itself."""
         vol = self.volume
-        out = _out_u8(out, vol, "select")
+        out = like_volume(out, vol, torch.uint8, "select", _OUT)
         if keep.dtype == torch.bool:
             keep = keep.to(torch.uint8)
         if keep.dtype != torch.uint8 or keep.numel() != self.count + 1 or keep.device != vol.device:
@@ -96,7 +78,7 @@ def label_components(volume: torch.Tensor, cls=None, connectivity: int = 26, inv
     """Label the components of `volume == cls` (`!=` with invert; cls=None: of every non-zero value, each value on its own).
     Reading K is the one host synchronisation of this module: 16 bytes, which also carry the kernels' error word (non-zero raises
     RuntimeError).  Because of it this is not for a captured step."""
-    vol = _volume_u8(volume, "label_components")
+    vol = volume_u8(volume, "label_components")
     d, h, w = vol.shape
     labels = torch.empty((d, h, w), dtype=torch.int32, device=vol.device)
     info = torch.empty((2,), dtype=torch.int64, device=vol.device)
@@ -129,15 +111,22 @@ def _largest_keep(table: torch.Tensor, classes) -> torch.Tensor:
     return keep
 
 
+def _relabel(volume: torch.Tensor, who: str, cls, connectivity: int, invert: bool, keep_of, fill: int, out) -> torch.Tensor:
+    """What keep_largest, remove_small and fill_holes share: ONE labelling (cls, connectivity, invert as label_components takes
+    them), keep_of(comps) -> bool [K] of the components that stay, the others become `fill`.  A volume without a component is
+    copied (or left, where out is the volume itself)."""
+    comps = label_components(volume, cls, connectivity, invert)
+    out = like_volume(out, comps.volume, torch.uint8, who, _OUT)
+    if comps.count == 0:
+        return out if out.data_ptr() == comps.volume.data_ptr() else out.copy_(comps.volume)
+    return comps.select(_keep_vector(keep_of(comps)), fill, out)
+
+
 def keep_largest(volume: torch.Tensor, classes, connectivity: int = 26, out=None) -> torch.Tensor:
     """Per class in `classes`, every component but the one with the most voxels becomes 0 (ties go to the smaller id, i.e. the
     component that starts first in raster order); a class absent from the volume is left alone.  All classes come from ONE labelling
     of the non-zero voxels by value.  out may be `volume` (in place)."""
-    comps = label_components(volume, None, connectivity)
-    out = _out_u8(out, comps.volume, "keep_largest")
-    if comps.count == 0:
-        return out if out.data_ptr() == comps.volume.data_ptr() else out.copy_(comps.volume)
-    return comps.select(_keep_vector(_largest_keep(comps.stats(), classes)), 0, out)
+    return _relabel(volume, "keep_largest", None, connectivity, False, lambda comps: _largest_keep(comps.stats(), classes), 0, out)
 
 
 def _small_keep(table: torch.Tensor, thresholds: dict, voxel_volume=None) -> torch.Tensor:
@@ -156,31 +145,25 @@ def remove_small(volume: torch.Tensor, classes, min_voxels=None, min_volume=None
     count >= min_voxels) and min_volume (kept iff count * sz * sy * sx >= min_volume, in fp64) is given."""
     if (min_voxels is None) == (min_volume is None):
         raise ValueError("remove_small: exactly one of min_voxels and min_volume must be given")
-    comps = label_components(volume, None, connectivity)
-    out = _out_u8(out, comps.volume, "remove_small")
-    if comps.count == 0:
-        return out if out.data_ptr() == comps.volume.data_ptr() else out.copy_(comps.volume)
-    if min_voxels is not None:
-        keep = _small_keep(comps.stats(), {int(c): min_voxels for c in classes})
-    else:
-        sz, sy, sx = (float(s) for s in spacing)
-        keep = _small_keep(comps.stats(), {int(c): min_volume for c in classes}, sz * sy * sx)
-    return comps.select(_keep_vector(keep), 0, out)
+    sz, sy, sx = (float(s) for s in spacing)
+    thresholds = {int(c): min_volume if min_voxels is None else min_voxels for c in classes}
+    voxel_volume = None if min_volume is None else sz * sy * sx
+    return _relabel(volume, "remove_small", None, connectivity, False, lambda c: _small_keep(c.stats(), thresholds, voxel_volume), 0, out)
+
+
+def _border_keep(comps: Components) -> torch.Tensor:
+    """bool [K]: True for components whose bounding box touches a face of the volume."""
+    t = comps.stats()
+    d, h, w = comps.volume.shape
+    return (t[:, ZMIN] == 0) | (t[:, ZMAX] == d - 1) | (t[:, YMIN] == 0) | (t[:, YMAX] == h - 1) | (t[:, XMIN] == 0) | \
+        (t[:, XMAX] == w - 1)
 
 
 def fill_holes(volume: torch.Tensor, cls: int, out=None) -> torch.Tensor:
     """scipy.ndimage.binary_fill_holes(volume == cls) written back as `cls`: the components of `volume != cls` are labelled with
     connectivity 6 and every one whose bounding box touches no face of the volume becomes `cls`.  This OVERWRITES voxels of other
     classes that `cls` encloses."""
-    comps = label_components(volume, int(cls), 6, invert=True)
-    out = _out_u8(out, comps.volume, "fill_holes")
-    if comps.count == 0:
-        return out if out.data_ptr() == comps.volume.data_ptr() else out.copy_(comps.volume)
-    t = comps.stats()
-    d, h, w = comps.volume.shape
-    border = (t[:, ZMIN] == 0) | (t[:, ZMAX] == d - 1) | (t[:, YMIN] == 0) | (t[:, YMAX] == h - 1) | (t[:, XMIN] == 0) | \
-        (t[:, XMAX] == w - 1)
-    return comps.select(_keep_vector(border), int(cls), out)
+    return _relabel(volume, "fill_holes", int(cls), 6, True, _border_keep, int(cls), out)
 
 
 class Postprocess:
@@ -195,12 +178,9 @@ class Postprocess:
         self.connectivity = int(connectivity)
 
     def __call__(self, volume: torch.Tensor) -> torch.Tensor:
-        vol = _volume_u8(volume, "Postprocess")
-        out = vol.clone()
+        out = volume_u8(volume, "Postprocess").clone()
         if self.min_voxels:
-            comps = label_components(out, None, self.connectivity)
-            if comps.count:
-                comps.select(_keep_vector(_small_keep(comps.stats(), self.min_voxels)), 0, out)
+            _relabel(out, "Postprocess", None, self.connectivity, False, lambda c: _small_keep(c.stats(), self.min_voxels), 0, out)
         if self.keep_largest:
             keep_largest(out, self.keep_largest, self.connectivity, out=out)
         for c in self.fill_holes:

@@ -28,22 +28,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._volume import like_volume, volume_u8
 
 MAX_CLASSES = 32
 _PAD_LABEL, _PAD_IGNORE = 255, 254     # uint8 codes of a converted label outside 0 .. 255 / of an ignore_index outside 0 .. 255
-
-
-def _volume_u8(t: torch.Tensor, who: str) -> torch.Tensor:
-    """uint8 D x H x W, dense: a view such as the last channel of a uint8 C x D x H x W volume is read where it lies; another layout
-    is copied once."""
-    L.require_gpu(t, who)
-    if t.dim() != 3:
-        raise ValueError(f"{who}: a D x H x W volume expected, got shape {tuple(t.shape)}")
-    if t.dtype == torch.bool:
-        t = t.to(torch.uint8)
-    if t.dtype != torch.uint8:
-        raise ValueError(f"{who}: a uint8 volume expected, got {t.dtype}")
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def _label_u8(label: torch.Tensor, ignore_index, who: str):
@@ -52,13 +40,13 @@ def _label_u8(label: torch.Tensor, ignore_index, who: str):
     L.require_gpu(label, who)
     ign = L.NO_IGNORE if ignore_index is None else int(ignore_index)
     if label.dtype in (torch.uint8, torch.bool):
-        return _volume_u8(label, who), (ign if 0 <= ign <= 255 else L.NO_IGNORE)
+        return volume_u8(label, who), (ign if 0 <= ign <= 255 else L.NO_IGNORE)
     lab = label.long()
     out = torch.where((lab < 0) | (lab > 255), torch.full_like(lab, _PAD_LABEL), lab)
     if ignore_index is not None and not 0 <= ign <= 255:
         out = torch.where(lab == ign, torch.full_like(lab, _PAD_IGNORE), out)
         ign = _PAD_IGNORE
-    return _volume_u8(out.to(torch.uint8), who), ign
+    return volume_u8(out.to(torch.uint8), who), ign
 
 
 def _same_shape(a, b, who):
@@ -75,7 +63,7 @@ def _spacing(spacing):
 def confusion(pred: torch.Tensor, label: torch.Tensor, num_classes: int, ignore_index=None):
     """-> (int64 [C, C] with entry [l, p] = voxels of label l predicted as p, int64 scalar = voxels left out because label or
     prediction is >= C), both on the device.  Voxels whose label equals ignore_index are counted nowhere."""
-    p = _volume_u8(pred, "confusion")
+    p = volume_u8(pred, "confusion")
     lab, ign = _label_u8(label, ignore_index, "confusion")
     _same_shape(p, lab, "confusion")
     c = int(num_classes)
@@ -108,19 +96,16 @@ def _surface_masks(a: torch.Tensor, b, cls: int):
 
 def surface_mask(volume: torch.Tensor, cls: int) -> torch.Tensor:
     """uint8 D x H x W: 1 where volume == cls and a face neighbour differs or lies outside the volume."""
-    return _surface_masks(_volume_u8(volume, "surface_mask"), None, cls)[0]
+    return _surface_masks(volume_u8(volume, "surface_mask"), None, cls)[0]
 
 
 def edt_squared(seed: torch.Tensor, spacing=(1, 1, 1), out=None) -> torch.Tensor:
     """fp32 D x H x W: the squared Euclidean distance, in units of `spacing` = (z, y, x), to the nearest voxel with seed != 0; +inf
     everywhere without a seed.  Exact for unit and dyadic spacing (include/mednet_hip.h gives the arithmetic).  out: an fp32 volume
     to write into."""
-    s = _volume_u8(seed, "edt_squared")
+    s = volume_u8(seed, "edt_squared")
     d, h, w = s.shape
-    if out is None:
-        out = torch.empty((d, h, w), dtype=torch.float32, device=s.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (d, h, w) or not out.is_contiguous() or out.device != s.device:
-        raise ValueError("edt_squared: out must be a contiguous fp32 volume of the seed's shape on its device")
+    out = like_volume(out, s, torch.float32, "edt_squared", "out must be a contiguous fp32 volume of the seed's shape on its device")
     sz, sy, sx = _spacing(spacing)
     L.check(L.lib().mednet_edt_sq(s.data_ptr(), out.data_ptr(), d, h, w, sz, sy, sx, L.stream()), "edt_squared")
     return out
@@ -129,10 +114,9 @@ def edt_squared(seed: torch.Tensor, spacing=(1, 1, 1), out=None) -> torch.Tensor
 def surface_stats(surf: torch.Tensor, d2: torch.Tensor, tol_sq: float, counts=None, max_d2=None, sum_sqrt=None):
     """Over the voxels with surf != 0 -> (int64 [2] = {their number, those with d2 <= tol_sq}, fp32 scalar max d2 (-inf for none),
     fp64 scalar sum of sqrt(d2)), written into the given tensors where given."""
-    s = _volume_u8(surf, "surface_stats")
+    s = volume_u8(surf, "surface_stats")
     d, h, w = s.shape
-    if d2.dtype != torch.float32 or tuple(d2.shape) != (d, h, w) or not d2.is_contiguous():
-        raise ValueError("surface_stats: d2 must be a contiguous fp32 volume of the mask's shape")
+    like_volume(d2, s, torch.float32, "surface_stats", "d2 must be a contiguous fp32 volume of the mask's shape", same_device=False)
     counts = torch.empty((2,), dtype=torch.int64, device=s.device) if counts is None else counts
     max_d2 = torch.empty((), dtype=torch.float32, device=s.device) if max_d2 is None else max_d2
     sum_sqrt = torch.empty((), dtype=torch.float64, device=s.device) if sum_sqrt is None else sum_sqrt
@@ -168,7 +152,7 @@ def surface_distances(pred: torch.Tensor, label: torch.Tensor, classes, spacing=
     """-> hd (fp32), hd_percentile (fp32), assd (fp64), nsd (fp64), n_pred, n_label (int64), each [len(classes)] on the device; the
     module docstring gives the definitions.  tolerance is in units of `spacing`; a voxel counts as within it when its squared
     distance is <= fp32(tolerance)^2."""
-    p = _volume_u8(pred, "surface_distances")
+    p = volume_u8(pred, "surface_distances")
     g, _ = _label_u8(label, None, "surface_distances")
     _same_shape(p, g, "surface_distances")
     if not (float(tolerance) >= 0.0):
@@ -284,7 +268,7 @@ def lesion_detection(pred: torch.Tensor, label: torch.Tensor, cls: int, connecti
     are counted with torch.unique on the key pid * (K_label + 1) + gid over the voxels where both are labelled.  Synchronises with
     the host (the two component counts and the unique); not for a captured step."""
     from .components import label_components
-    p = _volume_u8(pred, "lesion_detection")
+    p = volume_u8(pred, "lesion_detection")
     g, _ = _label_u8(label, None, "lesion_detection")
     _same_shape(p, g, "lesion_detection")
     if int(min_overlap) < 1:

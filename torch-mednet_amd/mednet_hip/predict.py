@@ -15,6 +15,8 @@ overlapping windows with an importance map instead of cropping them, averages ov
 BlendedPrediction with .result() (the uint8 layout above), .probabilities(), .heatmaps() and .peaks()."""
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 
@@ -102,6 +104,13 @@ def mirror_mask(axes):
     return mask
 
 
+def _acc_check(acc: torch.Tensor, wsum: torch.Tensor, who: str, expected: str, channels=None):
+    """acc C x D x H x W and wsum D x H x W, both contiguous fp32 (C = channels where given); `expected` ends the message."""
+    if (channels is not None and acc.shape[0] != channels) or tuple(wsum.shape) != tuple(acc.shape[1:]) \
+            or acc.dtype != torch.float32 or wsum.dtype != torch.float32 or not (acc.is_contiguous() and wsum.is_contiguous()):
+        raise ValueError(f"{who}: acc {tuple(acc.shape)} {acc.dtype} / wsum {tuple(wsum.shape)} {wsum.dtype}{expected}")
+
+
 def accumulate(logits: torch.Tensor, pos: torch.Tensor, acc: torch.Tensor, wsum: torch.Tensor, windows, num_heatmaps, patch_overlap,
                mirror=0, blend_of="probabilities"):
     """logits B x (H + classes) x pD x pH x pW -> adds the window-weighted heat maps and class probabilities (or logits) of every
@@ -112,9 +121,7 @@ def accumulate(logits: torch.Tensor, pos: torch.Tensor, acc: torch.Tensor, wsum:
     lg = logits.float().contiguous()
     b, ch, pd, ph, pw = lg.shape
     _, d, h, w = acc.shape
-    if acc.shape[0] != ch or tuple(wsum.shape) != (d, h, w) or acc.dtype != torch.float32 or wsum.dtype != torch.float32 \
-            or not (acc.is_contiguous() and wsum.is_contiguous()):
-        raise ValueError(f"blend_accumulate: acc {tuple(acc.shape)} {acc.dtype} / wsum {tuple(wsum.shape)} {wsum.dtype} do not fit {ch} channels (contiguous fp32)")
+    _acc_check(acc, wsum, "blend_accumulate", f" do not fit {ch} channels (contiguous fp32)", ch)
     if [int(t.numel()) for t in windows] != [pd, ph, pw] or any(t.dtype != torch.float32 or not t.is_contiguous() for t in windows):
         raise ValueError(f"blend_accumulate: windows must be three contiguous fp32 vectors of {pd}, {ph}, {pw} entries")
     o = [int(v) for v in patch_overlap]
@@ -133,9 +140,7 @@ def finalize(acc: torch.Tensor, wsum: torch.Tensor, num_heatmaps, blend_of="prob
     L.require_gpu(acc, "blend_finalize")
     ch, d, h, w = acc.shape
     ncls = ch - num_heatmaps
-    if tuple(wsum.shape) != (d, h, w) or acc.dtype != torch.float32 or wsum.dtype != torch.float32 \
-            or not (acc.is_contiguous() and wsum.is_contiguous()):
-        raise ValueError(f"blend_finalize: acc {tuple(acc.shape)} {acc.dtype} / wsum {tuple(wsum.shape)} {wsum.dtype}: contiguous fp32 expected")
+    _acc_check(acc, wsum, "blend_finalize", ": contiguous fp32 expected")
     res = torch.empty((num_heatmaps + 1, d, h, w), dtype=torch.uint8, device=acc.device) if result else None
     prob = torch.empty((ncls, d, h, w), dtype=probabilities, device=acc.device) if probabilities is not None else None
     heat = torch.empty((num_heatmaps, d, h, w), dtype=torch.float32, device=acc.device) if heatmaps else None
@@ -226,6 +231,28 @@ class GridPredictor:
         # the passes of a patch: every subset of the mirror axes, ascending mask
         self.mirror_passes = [m for m in range(8) if m & ~self.mirror_bits == 0]
 
+    def _upload(self, volume):
+        """-> (the selected channels of the volume as fp32 on the model's device (the reference's `.float()`), uploaded once; the
+        grid of patch positions there)."""
+        dev = next(self.model.parameters()).device
+        vol = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
+        if self.channel_selection is not None:
+            vol = vol[self.channel_selection]
+        vol = vol.to(dev, non_blocking=True).float().contiguous()
+        return vol, torch.from_numpy(grid_positions(vol.shape[1:], self.patch_size, self.patch_overlap)).to(dev)
+
+    def _batches(self, vol: torch.Tensor, pos_all: torch.Tensor, mirror=0):
+        """(pos, logits) of every batch of grid positions, in order, the model in eval mode until the generator is closed: callers
+        iterate under contextlib.closing, so an exception in their loop restores the mode while it unwinds."""
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            for b0 in range(0, pos_all.shape[0], self.batch_size):
+                pos = pos_all[b0:b0 + self.batch_size].contiguous()
+                yield pos, self.model(gather_patches(vol, pos, self.patch_size, self.patch_overlap, self.pad_mode, mirror=mirror))
+        finally:
+            self.model.train(was_training)
+
     @torch.no_grad()
     def predict(self, volume) -> BlendedPrediction:
         """Blended sliding-window inference.  For every mirror pass (ascending mask) and every batch of grid positions:
@@ -233,51 +260,27 @@ class GridPredictor:
         depend on batch_size.  An overlap of 0 is legal here (nothing is cropped)."""
         if self.blend is None:
             raise ValueError("predict() needs blend (the crop-stitch path is __call__)")
-        dev = next(self.model.parameters()).device
-        vol = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
-        if self.channel_selection is not None:
-            vol = vol[self.channel_selection]
-        vol = vol.to(dev, non_blocking=True).float().contiguous()
-        pos_all = torch.from_numpy(grid_positions(vol.shape[1:], self.patch_size, self.patch_overlap)).to(dev)
-        windows = tuple(torch.from_numpy(v).to(dev) for v in self.windows)
+        vol, pos_all = self._upload(volume)
+        windows = tuple(torch.from_numpy(v).to(vol.device) for v in self.windows)
         acc = wsum = None
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            for m in self.mirror_passes:
-                for b0 in range(0, pos_all.shape[0], self.batch_size):
-                    pos = pos_all[b0:b0 + self.batch_size].contiguous()
-                    inputs = gather_patches(vol, pos, self.patch_size, self.patch_overlap, self.pad_mode, mirror=m)
-                    logits = self.model(inputs)
+        for m in self.mirror_passes:
+            with contextlib.closing(self._batches(vol, pos_all, m)) as batches:
+                for pos, logits in batches:
                     if acc is None:
-                        acc = torch.zeros((logits.shape[1],) + tuple(vol.shape[1:]), dtype=torch.float32, device=dev)
-                        wsum = torch.zeros(tuple(vol.shape[1:]), dtype=torch.float32, device=dev)
+                        acc = torch.zeros((logits.shape[1],) + tuple(vol.shape[1:]), dtype=torch.float32, device=vol.device)
+                        wsum = torch.zeros(tuple(vol.shape[1:]), dtype=torch.float32, device=vol.device)
                     accumulate(logits, pos, acc, wsum, windows, self.num_heatmaps, self.patch_overlap, m, self.blend_of)
-        finally:
-            self.model.train(was_training)
         return BlendedPrediction(acc, wsum, self.num_heatmaps, self.blend_of)
 
     @torch.no_grad()
     def __call__(self, volume):
         if self.blend is not None:
             return self.predict(volume).result(self.postprocess)
-        dev = next(self.model.parameters()).device
-        vol = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
-        if self.channel_selection is not None:
-            vol = vol[self.channel_selection]
-        vol = vol.to(dev, non_blocking=True).float().contiguous()  # predict.py:85 `.float()`
-        pos_all = torch.from_numpy(grid_positions(vol.shape[1:], self.patch_size, self.patch_overlap)).to(dev)
-        result = torch.zeros((self.num_heatmaps + 1,) + tuple(vol.shape[1:]), dtype=torch.uint8, device=dev)
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            for b0 in range(0, pos_all.shape[0], self.batch_size):
-                pos = pos_all[b0:b0 + self.batch_size].contiguous()
-                inputs = gather_patches(vol, pos, self.patch_size, self.patch_overlap, self.pad_mode)
-                logits = self.model(inputs)
+        vol, pos_all = self._upload(volume)
+        result = torch.zeros((self.num_heatmaps + 1,) + tuple(vol.shape[1:]), dtype=torch.uint8, device=vol.device)
+        with contextlib.closing(self._batches(vol, pos_all)) as batches:
+            for pos, logits in batches:
                 assemble(logits, pos, result, self.num_heatmaps, self.patch_overlap)
-        finally:
-            self.model.train(was_training)
         if self.postprocess is not None:
             result[-1].copy_(self.postprocess(result[-1]))
         return result
