@@ -587,7 +587,7 @@ int mednet_heatmap_loss_bwd_strided(const float* out, const void* target, int64_
                                     const float* dloss, float* dout, int n, int c, size_t spatial, int64_t stride_n,
                                     int64_t stride_c, int kind, int tgt_u8, mednet_stream stream);
 
-/* ---- torch.optim.Adam(lr) step  segmentation.py:119-120 (betas .9/.999, eps 1e-8, wd 0), flat fp32 buffers --- */
+/* ---- torch.optim.Adam(lr) step  segmentation.py:119-120 (betas .9/.999, eps 1e-8, wd 0), flat fp32 buffers (csrc/optim.hip) --- */
 int mednet_adam_step(float* p, const float* g, float* m, float* v, size_t count, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int step, float grad_scale,
                      mednet_stream stream);
@@ -637,7 +637,8 @@ int mednet_sgd_step(float* p, const float* g, float* buf, size_t count, float lr
  *   Adam:  gr = fma(wd, p, gr)                  AdamW:  p = p * (1 - lr * wd)                   (each when wd != 0)
  *   m   = beta1 * m + (1 - beta1) * gr;  v = beta2 * v + (1 - beta2) * gr * gr
  *   p   = p - (lr / bc1) * (m / (sqrt(v) / bc2s + eps))
- * (the lines of mednet_adam_step_scaled: with coef == 1 and decoupled == 0 the two give the same bits), then the state update as above. */
+ * (the one statement of these lines, adam_lines in csrc/optim.hip, serves mednet_adam_step and mednet_adam_step_scaled with coef == 1:
+ * with decoupled == 0 the scaled entry and this one give the same bits), then the state update as above. */
 int mednet_adamw_step(float* p, const float* g, float* m, float* v, size_t count, float lr, float beta1, float beta2, float eps,
                       float weight_decay, int decoupled, float inv_world, float* opt_state, float* scaler_state, float growth_factor,
                       float backoff_factor, int growth_interval, mednet_stream stream);

@@ -308,7 +308,7 @@ def check_gn_sums(partial, dz_stored, z, gn_y, act, what):
 
 
 # ------------------------------------------------------------------------------- the loss kernels and the Adam step
-# Inputs, fp64 references and checkers of tests/test_gpu_losses.py (csrc/loss.hip, the Adam kernels of csrc/norm_act.hip).
+# Inputs, fp64 references and checkers of tests/test_gpu_losses.py (csrc/loss.hip, the Adam kernels of csrc/optim.hip).
 # tests/test_loss_util.py runs all of them on the CPU: the exact inputs meet their premises, ATen's fp32 results pass the bounds,
 # and every checker rejects the fault it is there for.  Tensors of a case are [n, c, S] (S = the voxels of a sample).
 LOSS_BLOCK_VOX = 2048          # voxels per workgroup of loss.hip; one fp32 partial row per workgroup, the rows are added in fp64

@@ -1,5 +1,5 @@
 """The kernels at the end of every step at operator level (-m gpu): csrc/loss.hip (Dice, cross-entropy, heat-map regression: forward,
-finalize, backward) and the Adam kernels of csrc/norm_act.hip, through the C ABI with every output pre-filled with NaN and a
+finalize, backward) and the Adam kernels of csrc/optim.hip, through the C ABI with every output pre-filled with NaN and a
 workspace of exactly mednet_loss_ws_bytes (itself filled with NaN), at shapes that reach a second workgroup, a block boundary, a
 ragged last block, more than 256 partial rows (the stride of the finalize kernels) and the unrolled loop of hm_finalize_kernel.
 

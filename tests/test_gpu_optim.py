@@ -437,3 +437,37 @@ def test_a_bad_batch_is_skipped_in_bf16_storage():
         assert step.skipped_steps() == 1 and step.opt.steps_taken() == 2 and not torch.equal(step.flat.flat, p1)
         assert bool(torch.isfinite(step.flat.flat).all())
         step.flat.release()
+
+
+@pytest.mark.parametrize("kind", ["adamw", "sgd"])
+def test_a_checkpoint_behind_the_loss_scaler_resumes_bit_for_bit(kind):
+    """fp16 storage, the guarded FlatAdam / FlatSGD behind the LossScaler: two calls, state_dict, a fresh step with the parameters copied
+    and load_state_dict -- its third call leaves the bits of the uninterrupted run in parameters, buffers, optimiser and scaler state."""
+    args = dict(weight_decay=1e-2) if kind == "adamw" else dict(momentum=0.99, nesterov=True, weight_decay=3e-5)
+    kw = dict(optimizer=kind, optimizer_args=args, lr=1e-2, clip_grad_norm=0.5)
+    bits = lambda t: t.detach().view(torch.int32).cpu()
+
+    def state(step):
+        bufs = {k: bits(getattr(step.opt, k)) for k in ("buf", "m", "v") if getattr(step.opt, k, None) is not None}
+        return dict(p=bits(step.flat.flat), ost=bits(step.opt.opt_state), scaler=bits(step.scaler.state), **bufs)
+
+    with mednet_hip.precision("fp16"):
+        step, batches = _step_case("seg", "fp16", **kw)
+        assert step.scaler is not None and step.opt.guarded
+        step(batches[0])
+        step(batches[1])
+        sd, params = step.opt.state_dict(step.scaler), step.flat.flat.clone()
+        assert sd["t"] == step.opt.steps_taken(step.scaler) == 2
+        step(batches[2])
+        want = state(step)
+        step.flat.release()
+        fresh, _ = _step_case("seg", "fp16", **kw)
+        fresh.flat.flat.copy_(params)
+        fresh.opt.load_state_dict(sd, fresh.scaler)
+        fresh(batches[2])
+        got = state(fresh)
+        fresh.flat.release()
+    assert got.keys() == want.keys() and sorted(got) == sorted(["p", "ost", "scaler"] + (["m", "v"] if kind == "adamw" else ["buf"]))
+    for k in want:
+        assert torch.equal(got[k], want[k]), f"{kind}: {k} differs after the round trip"
+    assert fresh.opt.steps_taken(fresh.scaler) == 3 and not torch.equal(want["p"], bits(params))

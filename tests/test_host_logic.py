@@ -403,7 +403,7 @@ def test_fused_landmark_head_and_first_layer_entry_points_answer_without_a_devic
 
 
 def test_normalisation_entries_refuse_what_they_refused_in_the_same_order(golden_dir):
-    """tools/norm_refusals.py: every extern "C" entry of csrc/norm_act.hip with argument sets that trip each of its checks in turn
+    """tools/norm_refusals.py: every extern "C" entry of csrc/norm_act.hip (and the Adam entries of csrc/optim.hip) with argument sets that trip each of its checks in turn
     (null pointers, bad dtype, C % groups, C / vec > 256, a workspace one byte short, two violations at once, the options that
     switch a fused form off) -- all refused before any launch, no device needed.  tests/golden/norm_refusals.jsonl is the table
     the library printed BEFORE the entries were put on one host path (GnPlan, launch_gn_*, gn_bwd_coefs): return code and

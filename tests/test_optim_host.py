@@ -78,6 +78,39 @@ def _flat(n=24):
     return FlatParams(torch.nn.Linear(n, 3))
 
 
+def test_flat_adam_scaler_round_trip_and_refusals():
+    """What test_flat_sgd_state_round_trip_and_refusals does for FlatSGD, on FlatAdam: the shared state-dict code has both on it."""
+    from mednet_hip.train import FlatAdam, LossScaler
+    opt = FlatAdam(_flat(), lr=1e-2, betas=(0.8, 0.99), eps=1e-6, weight_decay=3e-5, clip_grad_norm=12.0)
+    assert opt.guarded and not opt.decoupled and opt.opt_state.tolist() == [0, 0, 1, 0, 0, 0, 0, 0]
+    opt.m.copy_(torch.arange(opt.m.numel(), dtype=torch.float32))
+    opt.v.copy_(torch.arange(opt.v.numel(), dtype=torch.float32) * 0.5)
+    opt.opt_state.copy_(torch.tensor([4.0, 2.0, 0.5, 0.0, 7.0, 2.0, 0.0, 0.0]))
+    assert opt.steps_taken() == 7
+    sd = opt.state_dict()
+    assert set(sd) == {"m", "v", "t", "lr", "betas", "eps", "weight_decay", "opt_state"}
+    sd["betas"] = list(sd["betas"])                # (as a checkpoint that went through JSON holds them)
+    opt2 = FlatAdam(_flat(), lr=1.0, skip_nonfinite=True)
+    opt2.load_state_dict(sd)
+    assert (opt2.lr, opt2.betas, opt2.eps, opt2.wd, opt2.t) == (1e-2, (0.8, 0.99), 1e-6, 3e-5, 7)
+    assert torch.equal(opt2.m, opt.m) and torch.equal(opt2.v, opt.v) and torch.equal(opt2.opt_state, opt.opt_state)
+    assert opt2.steps_taken() == 7
+    sc = LossScaler("cpu")
+    with pytest.raises(KeyError, match="scaler"):
+        opt2.load_state_dict(sd, scaler=sc)        # saved without a scaler: resuming WITH one must not restart at 65536
+    sc.state[0], sc.state[2], sc.state[4] = 1024.0, 5.0, 2.0
+    sd_s = opt.state_dict(scaler=sc)
+    assert sd_s["t"] == 5 and "scaler" in sd_s
+    sc2 = LossScaler("cpu")
+    opt2.load_state_dict(sd_s, scaler=sc2)
+    assert torch.equal(sc2.state, sc.state) and opt2.steps_taken(sc2) == 5 and sc2.skipped_steps() == 2
+    plain = FlatAdam(_flat(), lr=1e-3)             # the plain form keeps no device state: none in its state dict either
+    plain.t = 3
+    assert plain.opt_state is None and "opt_state" not in plain.state_dict() and plain.state_dict()["t"] == 3
+    plain.load_state_dict(sd)                      # a guarded run's state into the plain form: the host count takes over
+    assert plain.steps_taken() == 7 and plain.opt_state is None
+
+
 def test_flat_sgd_state_round_trip_and_refusals():
     from mednet_hip.train import FlatSGD, LossScaler
     opt = FlatSGD(_flat(), lr=1e-2, momentum=0.99, nesterov=True, weight_decay=3e-5, clip_grad_norm=12.0)

@@ -1,4 +1,4 @@
-"""Refusal table of csrc/norm_act.hip: every extern "C" entry of that file called with argument sets that trip each of its
+"""Refusal table of csrc/norm_act.hip and of the two Adam entries that lived there (now csrc/optim.hip): every extern "C" entry called with argument sets that trip each of its
 MEDNET_REQUIREs in turn -- null pointers, a bad dtype, C % groups != 0, a C with C / vec > 256, a workspace one byte short, two
 violations at once (the first check in the entry's order answers).  Every case is refused before any launch, so the tool needs
 no device; pointers that only have to be non-null are the address 4096, which nothing reads.  Prints one JSON line per case:

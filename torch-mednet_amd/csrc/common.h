@@ -62,6 +62,11 @@ static inline int launch_lds(const char* what, K kernel, dim3 grid, dim3 block, 
 inline bool dtype_ok(int dt) { return dt == MEDNET_F32 || dt == MEDNET_BF16 || dt == MEDNET_F16; }
 inline size_t dtype_size(int dt) { return dt == MEDNET_F32 ? 4 : 2; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// workgroups of a grid-strided pass: `per_block` elements per workgroup and trip, at most `cap` of them, at least one
+inline unsigned strided_grid(size_t count, size_t per_block, size_t cap) {
+  const size_t b = (count + per_block - 1) / per_block;
+  return (unsigned)(b > cap ? cap : b < 1 ? 1 : b);
+}
 
 // ---- scalar load/store with conversion ---------------------------------------------------------------------
 __device__ __forceinline__ float ld(const float* p, size_t i) { return p[i]; }

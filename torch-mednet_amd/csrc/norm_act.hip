@@ -1198,87 +1198,11 @@ __global__ __launch_bounds__(256) void upcat_bwd_x_kernel(const T* __restrict__ 
   VecIO<T, VEC>::store(dx, dst, s);
 }
 
-// ---------------------------------------------------------------------------------------------- Adam
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, size_t count, float lr,
-                                                   float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                   float gscale) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
-    float gr = g[i] * gscale;
-    if (wd != 0.f) gr = fmaf(wd, p[i], gr);
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
-  }
-}
-
-// ---- fp16 storage: dynamic loss scaling without a host synchronisation (torch.cuda.amp.GradScaler's rule) ---------------
-// state[8] (device, fp32): {scale, good steps since the last change, optimizer steps taken, found_inf, steps skipped, -, -, -}.  The loss is
-// multiplied by state[0] on the device, so every gradient arrives times `scale`; grad_check raises found_inf if any
-// gradient is not finite, adam_scaled divides by the scale and SKIPS the update when found_inf is set (bias correction
-// uses the device-side step count, which a skipped step does not advance), scaler_update then halves the scale or
-// counts a good step and doubles it every `growth_interval` of them.
-__global__ __launch_bounds__(256) void grad_check_kernel(const float* __restrict__ g, size_t count, float* __restrict__ state) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  bool bad = false;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
-    const float v = g[i];
-    bad |= !(fabsf(v) <= 3.0e38f);  // NaN or +-inf
-  }
-  if (bad) state[3] = 1.f;  // (every writer stores the same value)
-}
-__global__ __launch_bounds__(256) void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                          float* __restrict__ m, float* __restrict__ v, size_t count, float lr,
-                                                          float b1, float b2, float eps, float wd, float inv_world,
-                                                          const float* __restrict__ state) {
-  if (state[3] != 0.f) return;  // overflow somewhere in this step's gradients: no update
-  const float t = state[2] + 1.f;
-  const float bc1 = 1.f - powf(b1, t), bc2_sqrt = sqrtf(1.f - powf(b2, t));
-  const float gscale = inv_world / state[0];
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
-    float gr = g[i] * gscale;
-    if (wd != 0.f) gr = fmaf(wd, p[i], gr);
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
-  }
-}
-__global__ void scaler_update_kernel(float* __restrict__ state, float growth, float backoff, float interval) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (state[3] != 0.f) {
-    state[0] = fmaxf(state[0] * backoff, 1.f);  // never below 1: a persistent NaN (out-of-range labels) must not drive it to 0
-    state[1] = 0.f;
-    state[4] += 1.f;  // skipped steps, for the host to surface
-  } else {
-    state[2] += 1.f;
-    state[1] += 1.f;
-    if (state[1] >= interval) {
-      state[0] *= growth;
-      state[1] = 0.f;
-    }
-  }
-  state[3] = 0.f;
-}
-
 }  // namespace mednet
 
 // =================================================================================================== C ABI
 using namespace mednet;
 
-static inline unsigned flat_grid(size_t count, size_t per_block) {
-  size_t b = (count + per_block - 1) / per_block;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
 static inline int pick_vec(int c, int dtype = MEDNET_BF16) {
   if (dtype == MEDNET_F32 && c % 4 == 0 && c / 4 <= 256 && tuning_option("gn_f32_vec4", 1)) return 4;
   return (c % 8 == 0 && c / 8 <= 256) ? 8 : 1;
@@ -1787,7 +1711,7 @@ extern "C" int mednet_act_fwd(const void* x, void* z, size_t count, int act, int
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "act_fwd: bad dtype");
   by_type(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(act_fwd_kernel<T>, dim3(flat_grid(count, 2048)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)z, count, act);
+    hipLaunchKernelGGL(act_fwd_kernel<T>, dim3(strided_grid(count, 2048, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)z, count, act);
   });
   return check_launch("act_fwd");
 }
@@ -1796,7 +1720,7 @@ extern "C" int mednet_act_bwd(const void* dz, const void* z, void* dx, size_t co
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "act_bwd: bad dtype");
   by_type(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(flat_grid(count, 2048)), dim3(256), 0, (hipStream_t)stream, (const T*)dz, (const T*)z,
+    hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(strided_grid(count, 2048, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)dz, (const T*)z,
                        (T*)dx, count, act);
   });
   return check_launch("act_bwd");
@@ -1805,7 +1729,7 @@ extern "C" int mednet_add(const void* a, const void* b, void* out, size_t count,
   MEDNET_REQUIRE(dtype_ok(dtype), MEDNET_E_DTYPE, "add: bad dtype");
   by_type(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL(add_kernel<T>, dim3(flat_grid(count, 2048)), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b,
+    hipLaunchKernelGGL(add_kernel<T>, dim3(strided_grid(count, 2048, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b,
                        (T*)out, count);
   });
   return check_launch("add");
@@ -1952,28 +1876,4 @@ extern "C" int mednet_upcat_bwd(const void* dout, void* denc, void* dx, int n, i
     hipLaunchKernelGGL((upcat_bwd_x_kernel<T, V>), g2, dim3(256), 0, s, (const T*)dout, (T*)dx, n, d, h, w, c_enc, xd, xh, xw, c_x);
   });
   return check_launch("upcat_bwd");
-}
-
-extern "C" int mednet_adam_step_scaled(float* p, const float* g, float* m, float* v, size_t count, float lr, float beta1,
-                                       float beta2, float eps, float weight_decay, float inv_world, float* scaler_state,
-                                       float growth_factor, float backoff_factor, int growth_interval, mednet_stream stream) {
-  MEDNET_REQUIRE(scaler_state != nullptr && growth_interval >= 1, MEDNET_E_SHAPE, "adam_step_scaled: scaler state required");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(grad_check_kernel, dim3(flat_grid(count, 1024)), dim3(256), 0, s, g, count, scaler_state);
-  hipLaunchKernelGGL(adam_scaled_kernel, dim3(flat_grid(count, 1024)), dim3(256), 0, s, p, g, m, v, count, lr, beta1, beta2, eps,
-                     weight_decay, inv_world, scaler_state);
-  hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, s, scaler_state, growth_factor, backoff_factor,
-                     (float)growth_interval);
-  return check_launch("adam_step_scaled");
-}
-
-extern "C" int mednet_adam_step(float* p, const float* g, float* m, float* v, size_t count, float lr, float beta1,
-                                float beta2, float eps, float weight_decay, int step, float grad_scale,
-                                mednet_stream stream) {
-  MEDNET_REQUIRE(step >= 1, MEDNET_E_SHAPE, "adam_step: step must be >= 1");
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adam_kernel, dim3(flat_grid(count, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, count, lr,
-                     beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
-  return check_launch("adam_step");
 }

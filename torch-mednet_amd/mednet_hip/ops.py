@@ -1914,6 +1914,14 @@ def adam_step_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale
                                      eps, weight_decay, step, grad_scale, L.stream()), "adam_step")
 
 
+def adam_step_scaled_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, scaler, inv_world=1.0):
+    """The same update behind a train.LossScaler: overflow sweep, unscale, skip on overflow, scale update -- all on the device."""
+    L.require_gpu(p, "adam_step_scaled")
+    sc, growth, backoff, interval = _scaler_args(scaler)
+    L.check(L.lib().mednet_adam_step_scaled(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,
+                                            weight_decay, inv_world, sc, growth, backoff, interval, L.stream()), "adam_step_scaled")
+
+
 OPT_STATE_FRESH = (0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0)  # {sumsq, norm, coef, nonfinite, steps taken, steps skipped, -, -}
 
 

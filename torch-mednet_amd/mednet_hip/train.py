@@ -74,108 +74,80 @@ def _check_guard_args(who, clip_grad_norm, lr, weight_decay):
         raise ValueError(f"{who}: negative lr {lr} or weight_decay {weight_decay}")
 
 
-class FlatAdam:
-    """torch.optim.Adam(lr) semantics (betas .9/.999, eps 1e-8, weight_decay 0) as one kernel over FlatParams.
+class _FlatOptimizer:
+    """What FlatAdam and FlatSGD share: the hyper-parameters every form has, the device state of the guarded forms, the two step counts
+    (host `t` / device), the state dict and ONE step body.  A subclass states MOMENTS (its moment buffers: attributes and state-dict
+    keys), HYPER (state-dict key -> attribute of its hyper-parameters), `_norm_runs` and its one update launch `_update`."""
 
-    decoupled_weight_decay=True is torch.optim.AdamW's rule (p *= 1 - lr wd, no L2 term).  clip_grad_norm (a float: clip the mean
-    gradient to that global L2 norm, torch.nn.utils.clip_grad_norm_'s rule) and skip_nonfinite (skip the whole update when a gradient
-    is NaN / inf, in every storage mode) route the step through the norm pass and the guarded update kernel (ops.grad_norm_ +
-    ops.adamw_step_), as does the decoupled decay; the bias correction then uses the device-side count `opt_state[4]` of steps actually
-    taken.  With all three off the launches are the ones this class always made."""
+    MOMENTS, HYPER = (), {}
 
-    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
-                 clip_grad_norm=None, skip_nonfinite=False):
-        _check_guard_args("FlatAdam", clip_grad_norm, lr, weight_decay)
-        self.flat, self.lr, self.betas, self.eps, self.wd = flat, lr, betas, eps, weight_decay
-        self.decoupled, self.clip, self.skip_nonfinite = bool(decoupled_weight_decay), clip_grad_norm, bool(skip_nonfinite)
-        self.guarded = self.decoupled or self.clip is not None or self.skip_nonfinite
-        self.opt_state = ops.new_opt_state(flat.flat.device) if self.guarded else None
-        self.m = torch.zeros_like(flat.flat)
-        self.v = torch.zeros_like(flat.flat)
-        self.t = 0  # calls so far.  Plain mode: = optimizer steps taken (bias correction uses it).  Behind a LossScaler the
-        #             bias correction uses the DEVICE count scaler.state[2], which a skipped step does not advance: there
-        #             `t` only versions the parameters (_bump) and steps_taken() reads the truth.
+    def __init__(self, flat: FlatParams, lr, weight_decay, clip_grad_norm, skip_nonfinite):
+        _check_guard_args(type(self).__name__, clip_grad_norm, lr, weight_decay)
+        self.flat, self.lr, self.wd = flat, lr, weight_decay
+        self.clip, self.skip_nonfinite = clip_grad_norm, bool(skip_nonfinite)
+        self.t = 0  # calls so far; versions the parameters (_step).  The plain forms count their steps with it (FlatAdam's bias
+        #             correction uses it); the guarded forms and every form behind a LossScaler count on the DEVICE, where a skipped
+        #             step does not advance the count: steps_taken() reads the truth.
         self._scaled = None  # which of the two update forms this optimizer runs (they keep different step counts)
 
     def steps_taken(self, scaler: "LossScaler | None" = None) -> int:
-        """Optimizer steps actually applied (synchronises when a scaler holds the count)."""
+        """Optimizer steps actually applied (synchronises when the count lives on the device)."""
         if scaler is not None:
             return int(scaler.state[2].item())
         return int(self.opt_state[4].item()) if self.guarded else self.t
 
     def state_dict(self, scaler: "LossScaler | None" = None):
-        sd = {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(), "t": self.steps_taken(scaler),
-              "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd}
-        if self.guarded:
+        sd = {k: None if getattr(self, k) is None else getattr(self, k).detach().cpu().clone() for k in self.MOMENTS}
+        sd["t"] = self.steps_taken(scaler)
+        sd.update((k, getattr(self, attr)) for k, attr in self.HYPER.items())
+        if self.opt_state is not None:
             sd["opt_state"] = self.opt_state.detach().cpu().clone()
         if scaler is not None:
             sd["scaler"] = scaler.state_dict()
         return sd
 
     def load_state_dict(self, sd, scaler: "LossScaler | None" = None):
-        """Restores the moments, the step count and the hyper-parameters the state was saved with (torch.optim.Adam's
-        load_state_dict restores its param_groups too).  A run that trains behind a loss scaler must find the scaler's state
-        in `sd`: resuming fp16 training with a fresh scale of 65536 and a device step count of 0 would silently restart the
-        bias correction."""
-        self.m.copy_(sd["m"].to(self.m.device))
-        self.v.copy_(sd["v"].to(self.v.device))
+        """Restores the moments, the step count and the hyper-parameters the state was saved with (torch.optim's load_state_dict
+        restores its param_groups too).  A run that trains behind a loss scaler must find the scaler's state in `sd`: resuming fp16
+        training with a fresh scale of 65536 and a device step count of 0 would silently restart the bias correction."""
+        for k in self.MOMENTS:
+            if getattr(self, k) is not None:
+                getattr(self, k).copy_(sd[k].to(self.flat.flat.device))
         self.t = int(sd["t"])
-        self.lr = sd.get("lr", self.lr)
-        self.betas = tuple(sd.get("betas", self.betas))
-        self.eps = sd.get("eps", self.eps)
-        self.wd = sd.get("weight_decay", self.wd)
-        if self.guarded:  # (a state saved by the plain form has no device state: its host count becomes the device count)
+        for k, attr in self.HYPER.items():
+            if k in sd:
+                setattr(self, attr, tuple(sd[k]) if k == "betas" else sd[k])
+        if self.opt_state is not None:  # (a state saved by a plain form has no device state: its host count becomes the device count)
             _load_opt_state(self.opt_state, sd, self.t)
         if scaler is not None:
             if "scaler" not in sd:
-                raise KeyError("FlatAdam.load_state_dict: a LossScaler was passed but the saved state has no 'scaler' entry "
-                               "(it was saved by a run without loss scaling)")
+                raise KeyError(f"{type(self).__name__}.load_state_dict: a LossScaler was passed but the saved state has no 'scaler' "
+                               f"entry (it was saved by a run without loss scaling)")
             scaler.load_state_dict(sd["scaler"])
 
-    def _form(self, scaled: bool):
+    def _step(self, gscale, scaler):
+        scaled = scaler is not None
         if self._scaled is None:
             self._scaled = scaled
         elif self._scaled != scaled:
-            raise RuntimeError("FlatAdam: step() and step_scaled() keep different step counts (host / device) and cannot "
-                               "be mixed on one optimizer")
-
-    def _guarded_step(self, inv_world, scaler):
-        f = self.flat
-        ops.grad_norm_(f.grad, self.opt_state, self.clip, inv_world, None if scaler is None else scaler.state)
-        ops.adamw_step_(f.flat, f.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.opt_state,
-                        self.decoupled, inv_world, scaler)
-
-    def step(self, grad_scale=1.0):
-        self._form(False)
+            raise RuntimeError(f"{type(self).__name__}: step() and step_scaled() keep different step counts (host / device) and cannot "
+                               f"be mixed on one optimizer")
         self.t += 1
-        if self.guarded:
-            self._guarded_step(grad_scale, None)
-        else:
-            ops.adam_step_(self.flat.flat, self.flat.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
-                           self.wd, self.t, grad_scale)
-        self._bump()
-
-    def step_scaled(self, scaler: "LossScaler", inv_world=1.0):
-        """The same update behind the loss scaler: unscale, skip on overflow, adjust the scale -- all on the device."""
-        from . import _lib as L
-        self._form(True)
-        self.t += 1
-        if self.guarded:  # (the norm is taken of the UNSCALED gradient and its pass replaces the overflow sweep)
-            self._guarded_step(inv_world, scaler)
-            self._bump()
-            return
-        f = self.flat
-        L.check(L.lib().mednet_adam_step_scaled(f.flat.data_ptr(), f.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                f.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                                                inv_world, scaler.state.data_ptr(), scaler.growth_factor,
-                                                scaler.backoff_factor, scaler.growth_interval, L.stream()), "adam_step_scaled")
-        self._bump()
-
-    def _bump(self):
+        ost = self.opt_state if self._norm_runs(scaler) else None
+        if ost is not None:  # (behind a scaler the norm is taken of the UNSCALED gradient and its pass replaces the overflow sweep)
+            ops.grad_norm_(self.flat.grad, ost, self.clip, gscale, None if scaler is None else scaler.state)
+        self._update(gscale, ost, scaler)
         # torch's version counter only moves on torch in-place ops; a no-op in-place op on the flat buffer does not
         # reach the views' counters, so packed-weight caches are keyed on this step counter as well.
         for p in self.flat.params:
             p._mednet_step = self.t
+
+    def step(self, grad_scale=1.0):
+        self._step(grad_scale, None)
+
+    def step_scaled(self, scaler: "LossScaler", inv_world=1.0):
+        """The same update behind the loss scaler: unscale, skip on overflow, adjust the scale -- all on the device."""
+        self._step(inv_world, scaler)
 
 
 def _load_opt_state(opt_state, sd, steps):
@@ -188,90 +160,71 @@ def _load_opt_state(opt_state, sd, steps):
     opt_state[3] = 0.0
 
 
-class FlatSGD:
+class FlatAdam(_FlatOptimizer):
+    """torch.optim.Adam(lr) semantics (betas .9/.999, eps 1e-8, weight_decay 0) as one kernel over FlatParams.
+
+    decoupled_weight_decay=True is torch.optim.AdamW's rule (p *= 1 - lr wd, no L2 term).  clip_grad_norm (a float: clip the mean
+    gradient to that global L2 norm, torch.nn.utils.clip_grad_norm_'s rule) and skip_nonfinite (skip the whole update when a gradient
+    is NaN / inf, in every storage mode) route the step through the norm pass and the guarded update kernel (ops.grad_norm_ +
+    ops.adamw_step_), as does the decoupled decay; the bias correction then uses the device-side count `opt_state[4]` of steps actually
+    taken.  With all three off the launches are the ones this class always made (ops.adam_step_, or ops.adam_step_scaled_ behind a
+    LossScaler, whose state[2] is then the count of the bias correction)."""
+
+    MOMENTS, HYPER = ("m", "v"), {"lr": "lr", "betas": "betas", "eps": "eps", "weight_decay": "wd"}
+
+    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
+                 clip_grad_norm=None, skip_nonfinite=False):
+        super().__init__(flat, lr, weight_decay, clip_grad_norm, skip_nonfinite)
+        self.betas, self.eps, self.decoupled = betas, eps, bool(decoupled_weight_decay)
+        self.guarded = self.decoupled or self.clip is not None or self.skip_nonfinite
+        self.opt_state = ops.new_opt_state(flat.flat.device) if self.guarded else None
+        self.m = torch.zeros_like(flat.flat)
+        self.v = torch.zeros_like(flat.flat)
+
+    def _norm_runs(self, scaler) -> bool:
+        return self.guarded
+
+    def _update(self, gscale, ost, scaler):
+        f, hp = self.flat, (self.lr, self.betas[0], self.betas[1], self.eps, self.wd)
+        if ost is not None:
+            ops.adamw_step_(f.flat, f.grad, self.m, self.v, *hp, ost, self.decoupled, gscale, scaler)
+        elif scaler is not None:
+            ops.adam_step_scaled_(f.flat, f.grad, self.m, self.v, *hp, scaler, gscale)
+        else:
+            ops.adam_step_(f.flat, f.grad, self.m, self.v, *hp, self.t, gscale)
+
+
+class FlatSGD(_FlatOptimizer):
     """torch.optim.SGD(lr, momentum, dampening 0, weight_decay, nesterov) as one kernel over FlatParams, with FlatAdam's surface.
 
     clip_grad_norm / skip_nonfinite put the norm pass (ops.grad_norm_) in front: clip coefficient and skip rule are read by the update
     kernel on the device.  Behind a LossScaler (step_scaled) the norm pass always runs: it is what finds the overflow.  With
     momentum 0 there is no buffer and no buffer traffic.  Weight decay applies to the whole flat buffer (no parameter groups)."""
 
+    MOMENTS, HYPER = ("buf",), {"lr": "lr", "momentum": "momentum", "nesterov": "nesterov", "weight_decay": "wd"}
+
     def __init__(self, flat: FlatParams, lr, momentum=0.0, nesterov=False, weight_decay=0.0, clip_grad_norm=None, skip_nonfinite=False):
-        _check_guard_args("FlatSGD", clip_grad_norm, lr, weight_decay)
+        super().__init__(flat, lr, weight_decay, clip_grad_norm, skip_nonfinite)
         if not 0.0 <= momentum < 1.0:
             raise ValueError(f"FlatSGD: momentum {momentum} outside [0, 1)")
         if nesterov and momentum == 0.0:
             raise ValueError("FlatSGD: nesterov needs momentum > 0 (torch.optim.SGD's rule)")
-        self.flat, self.lr, self.momentum, self.nesterov, self.wd = flat, lr, momentum, bool(nesterov), weight_decay
-        self.clip, self.skip_nonfinite = clip_grad_norm, bool(skip_nonfinite)
+        self.momentum, self.nesterov = momentum, bool(nesterov)
         self.guarded = self.clip is not None or self.skip_nonfinite
         self.opt_state = ops.new_opt_state(flat.flat.device)
         self.buf = torch.zeros_like(flat.flat) if momentum != 0.0 else None
-        self.t = 0  # calls so far; versions the parameters (_bump).  Steps actually taken: steps_taken()
-        self._scaled = None
-
-    def steps_taken(self, scaler: "LossScaler | None" = None) -> int:
-        """Optimizer steps actually applied (synchronises when the count lives on the device)."""
-        if scaler is not None:
-            return int(scaler.state[2].item())
-        return int(self.opt_state[4].item()) if self.guarded else self.t
-
-    def state_dict(self, scaler: "LossScaler | None" = None):
-        sd = {"buf": None if self.buf is None else self.buf.detach().cpu().clone(), "t": self.steps_taken(scaler), "lr": self.lr,
-              "momentum": self.momentum, "nesterov": self.nesterov, "weight_decay": self.wd,
-              "opt_state": self.opt_state.detach().cpu().clone()}
-        if scaler is not None:
-            sd["scaler"] = scaler.state_dict()
-        return sd
 
     def load_state_dict(self, sd, scaler: "LossScaler | None" = None):
-        """Restores the momentum buffer, the counts and the hyper-parameters.  As FlatAdam's: a run behind a loss scaler must find the
-        scaler's state in `sd`."""
         if (self.buf is None) != (sd["buf"] is None):
             raise ValueError("FlatSGD.load_state_dict: the saved state and this optimizer disagree about a momentum buffer")
-        if self.buf is not None:
-            self.buf.copy_(sd["buf"].to(self.buf.device))
-        self.t = int(sd["t"])
-        self.lr = sd.get("lr", self.lr)
-        self.momentum, self.nesterov = sd.get("momentum", self.momentum), sd.get("nesterov", self.nesterov)
-        self.wd = sd.get("weight_decay", self.wd)
-        _load_opt_state(self.opt_state, sd, self.t)
-        if scaler is not None:
-            if "scaler" not in sd:
-                raise KeyError("FlatSGD.load_state_dict: a LossScaler was passed but the saved state has no 'scaler' entry "
-                               "(it was saved by a run without loss scaling)")
-            scaler.load_state_dict(sd["scaler"])
+        super().load_state_dict(sd, scaler)
 
-    def _form(self, scaled: bool):
-        if self._scaled is None:
-            self._scaled = scaled
-        elif self._scaled != scaled:
-            raise RuntimeError("FlatSGD: step() and step_scaled() keep different step counts and cannot be mixed on one optimizer")
+    def _norm_runs(self, scaler) -> bool:
+        return self.guarded or scaler is not None
 
-    def _update(self, inv_world, opt_state, scaler):
+    def _update(self, gscale, ost, scaler):
         f = self.flat
-        ops.sgd_step_(f.flat, f.grad, self.buf, self.lr, self.momentum, self.nesterov, self.wd, inv_world, opt_state, scaler)
-
-    def step(self, grad_scale=1.0):
-        self._form(False)
-        self.t += 1
-        if self.guarded:
-            ops.grad_norm_(self.flat.grad, self.opt_state, self.clip, grad_scale)
-            self._update(grad_scale, self.opt_state, None)
-        else:
-            self._update(grad_scale, None, None)
-        self._bump()
-
-    def step_scaled(self, scaler: "LossScaler", inv_world=1.0):
-        """The same update behind the loss scaler: the norm of the unscaled gradient, skip on overflow, scale update -- on the device."""
-        self._form(True)
-        self.t += 1
-        ops.grad_norm_(self.flat.grad, self.opt_state, self.clip, inv_world, scaler.state)
-        self._update(inv_world, self.opt_state, scaler)
-        self._bump()
-
-    def _bump(self):
-        for p in self.flat.params:
-            p._mednet_step = self.t
+        ops.sgd_step_(f.flat, f.grad, self.buf, self.lr, self.momentum, self.nesterov, self.wd, gscale, ost, scaler)
 
 
 class PolyLR:
@@ -539,9 +492,35 @@ class _GraphedStep:
 
     GRAPH_DEFAULT = os.environ.get("MEDNET_GRAPH", "0") == "1"
 
-    def _init_graph(self, graph, warm=2):
+    def _setup(self, model, world_size, graph, optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite, warm=2):
+        """What every step class is built from, after its criteria: flat parameters, optimiser, repack, world, side stream, scaler,
+        graph state and the (lazily built) gradient exchange."""
+        self.model = model
+        self.flat = FlatParams(model)
+        self.opt, self._lr_fn = make_optimizer(self.flat, optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
+        self._opt_calls = 0
+        self.repack = BatchedRepack(model)
+        self.world = world_size
+        use_side_stream()
+        self.scaler = make_scaler(self.flat.flat.device)  # fp16 storage only
         self.use_graph = self.GRAPH_DEFAULT if graph is None else bool(graph)
         self._calls, self._warm, self._graph, self._static = 0, warm, None, None
+        self._exchange = None
+
+    def __call__(self, batch):
+        """run, exchange, optimiser, repack -> the detached losses of _fwd_bwd."""
+        if self._exchange is None:  # (built lazily: bench.py sets force_allreduce after construction)
+            self._exchange = BucketedExchange(self.model, self.flat, self.world, getattr(self, "force_allreduce", False))
+        out = self._run(batch)
+        scale = self._exchange.finish()  # 1/world is folded into the optimiser (and into the gradient norm in front of it)
+        self._optimizer_step(scale)
+        self.repack.run()
+        return out
+
+    def _backward(self, loss):
+        """The tail of every _fwd_bwd: backward of the (scaled) loss, then the side-stream join."""
+        (loss if self.scaler is None else self.scaler.scale_loss(loss)).backward()
+        finish_backward()
 
     def _run(self, batch):
         """-> tuple of detached loss tensors of this step's forward/backward (gradients are in self.flat.grad)."""
@@ -565,10 +544,6 @@ class _GraphedStep:
         return self._out
 
     # ---- the optimiser of a step (outside the graph: lr and the step count are kernel arguments / device state)
-    def _init_optimizer(self, optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite):
-        self.opt, self._lr_fn = make_optimizer(self.flat, optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
-        self._opt_calls = 0
-
     def _optimizer_step(self, scale):
         if self._lr_fn is not None:
             self.opt.lr = float(self._lr_fn(self._opt_calls))  # (host arithmetic, once per call)
@@ -579,7 +554,7 @@ class _GraphedStep:
             self.opt.step_scaled(self.scaler, inv_world=scale)
 
     def _norm_runs(self) -> bool:
-        return self.opt.guarded or (isinstance(self.opt, FlatSGD) and self.scaler is not None)
+        return self.opt._norm_runs(self.scaler)
 
     @property
     def grad_norm(self):
@@ -621,6 +596,29 @@ def _class_criterion(loss, w):
     return HL.DiceLoss(weight=w) if loss == "DICE" else HL.CrossEntropyLoss(weight=w)
 
 
+def _class_spec(crit):
+    """A class criterion as the fused nodes take it: its kind ("DICE" | "CE" | "DICE_CE"; None: not one of this package's three) and
+    the keyword arguments it sets -- loss_weight, eps, sigmoid, ignore_index; what a kind does not set stays at the nodes' defaults
+    (CE: the default eps, its own ignore_index; Dice + CE: its eps, no ignore, no sigmoid)."""
+    if isinstance(crit, HL.DiceCELoss):
+        return "DICE_CE", dict(loss_weight=crit.weight, eps=crit.epsilon)
+    if isinstance(crit, HL.DiceLoss):
+        return "DICE", dict(loss_weight=crit.weight, eps=crit.epsilon, sigmoid=crit.sigmoid_normalization, ignore_index=crit.ignore_index)
+    if isinstance(crit, HL.CrossEntropyLoss):
+        return "CE", dict(loss_weight=crit.weight, ignore_index=crit.ignore_index)
+    return None, {}
+
+
+def _head_fusable(model, crit, inputs) -> bool:
+    """The conditions every fused head + loss node shares: this package's U-Net, not testing, a planar 1x1x1 head, one of the three
+    class criteria (DiceLoss without skip_last_target), CUDA, and no hook that the node would bypass (_call_is_hooked)."""
+    from .unet.model import _UNetCore
+    fc = getattr(model, "final_conv", None)
+    return (isinstance(model, _UNetCore) and not model.testing and _class_spec(crit)[0] is not None
+            and not getattr(crit, "skip_last_target", False) and fc is not None and getattr(fc, "planar_output", False)
+            and fc.kernel_size[0] == 1 and inputs.is_cuda and not _call_is_hooked(model, fc))
+
+
 def deep_supervision_weights(k, ds_weights=None):
     """The level weights w_0 .. w_k of a deep-supervision loss: 2^-s / sum_t 2^-t by default, or `ds_weights` (k + 1 non-negative
     numbers, used as given)."""
@@ -648,7 +646,6 @@ class SegmentationStep(_GraphedStep):
 
     def __init__(self, model, loss_weight=None, lr=1e-3, loss="DICE", world_size=1, graph=None, optimizer="adam", optimizer_args=None,
                  clip_grad_norm=None, skip_nonfinite=False, ds_weights=None):
-        self.model = model
         dev = next(model.parameters()).device
         w = None if loss_weight is None else torch.tensor(loss_weight, dtype=torch.float32, device=dev)
         self.loss = _class_criterion(loss, w).to(dev)
@@ -656,14 +653,7 @@ class SegmentationStep(_GraphedStep):
         # unless `ds_weights` gives them; scale_losses = the detached, unweighted L_0 .. L_k of the last step (device scalars)
         self.ds_weights = deep_supervision_weights(len(getattr(model, "ds_heads", ())), ds_weights)
         self.scale_losses = []
-        self.flat = FlatParams(model)
-        self._init_optimizer(optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
-        self.repack = BatchedRepack(model)
-        self.world = world_size
-        use_side_stream()
-        self.scaler = make_scaler(dev)  # fp16 storage only
-        self._init_graph(graph)
-        self._exchange = None
+        self._setup(model, world_size, graph, optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
 
     def _head_loss(self, inputs, label_u8):
         """`outputs = self(inputs); loss = self.loss(outputs, labels)` (segmentation.py:61-62).  When the model is this package's
@@ -672,38 +662,20 @@ class SegmentationStep(_GraphedStep):
         volume's uint8 channel consumed where it lies); with 5 to 16 classes on a 32-feature head in a 16-bit storage mode they run as the matrix-core node
         ops.head_seg, which writes no logit tensor at all: `outputs` is None in that form (as LandmarkStep has no outputs tensor).
         Anything else takes the two calls as they stand."""
-        from .unet.model import _UNetCore
         m, fc = self.model, getattr(self.model, "final_conv", None)
-        dice = isinstance(self.loss, HL.DiceLoss)
-        compound = isinstance(self.loss, HL.DiceCELoss)  # (Dice + CE: the same three forms, its one-pass loss in the two-node form)
-        if (isinstance(m, _UNetCore) and not m.testing
-                and (isinstance(self.loss, HL.CrossEntropyLoss) or compound or (dice and not self.loss.skip_last_target))
-                and fc is not None and getattr(fc, "planar_output", False) and fc.kernel_size[0] == 1 and inputs.is_cuda
-                and not _call_is_hooked(m, fc)):
+        kind, kw = _class_spec(self.loss)
+        if _head_fusable(m, self.loss, inputs):
             feats = m.forward_features(inputs)
-            if compound:
-                if ops.head_dice_ce_supported(feats, fc.in_channels, fc.out_channels, label_u8):
-                    return ops.head_dice_ce(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon)
-                if ops.head_seg_supported(feats, fc.in_channels, fc.out_channels, label_u8):
-                    return ops.head_seg(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon,
-                                        class_loss="DICE_CE")
-                outputs = fc(feats)
-                return outputs, self.loss(outputs, label_u8)  # (uint8 labels consumed where they lie)
-            if dice and ops.head_dice_supported(feats, fc.in_channels, fc.out_channels, label_u8):
-                return ops.head_dice(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon,
-                                     self.loss.sigmoid_normalization, self.loss.ignore_index)
-            if not dice and ops.head_ce_supported(feats, fc.in_channels, fc.out_channels, label_u8):
-                return ops.head_ce(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.ignore_index)
+            small = "head_" + kind.lower()  # ops.head_dice / head_ce / head_dice_ce: the fused heads of at most 4 classes
+            if getattr(ops, small + "_supported")(feats, fc.in_channels, fc.out_channels, label_u8):
+                return getattr(ops, small)(feats, fc.weight, fc.bias, fc._packed(), label_u8, **kw)
             if ops.head_seg_supported(feats, fc.in_channels, fc.out_channels, label_u8):
-                if dice:
-                    return ops.head_seg(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, self.loss.epsilon,
-                                        self.loss.sigmoid_normalization, self.loss.ignore_index, "DICE")
-                return ops.head_seg(feats, fc.weight, fc.bias, fc._packed(), label_u8, self.loss.weight, ignore_index=self.loss.ignore_index,
-                                    class_loss="CE")
+                return ops.head_seg(feats, fc.weight, fc.bias, fc._packed(), label_u8, class_loss=kind, **kw)
             outputs = fc(feats)
         else:
             outputs = m(inputs)
-        return outputs, self.loss(outputs, label_u8 if compound else label_u8.long())
+        # (Dice + CE consumes the uint8 labels where they lie)
+        return outputs, self.loss(outputs, label_u8 if kind == "DICE_CE" else label_u8.long())
 
     def _ds_level(self, s, feats, label_u8, inputs, aux):
         """Level s >= 1 of deep supervision, called from the model's decoder loop on that level's block output: L_s = the step's
@@ -711,25 +683,16 @@ class SegmentationStep(_GraphedStep):
         next decoder.  Fused (ops.ds_head: one node at the junction, the full-resolution uint8 labels read where they lie) when
         ops.ds_head_supported says yes; otherwise -- fp32 storage, other label types, the ds_head_fuse knob at 0, hooked modules -- the
         composed form: the head, then the existing loss on a contiguous strided label slice."""
-        head = self.model.ds_heads[s - 1]
-        crit = self.loss
-        dice, compound = isinstance(crit, HL.DiceLoss), isinstance(crit, HL.DiceCELoss)
-        if (inputs.is_cuda and label_u8.dtype == torch.uint8 and not _call_is_hooked(self.model, head)
-                and (compound or not dice or not crit.skip_last_target)
+        head, crit = self.model.ds_heads[s - 1], self.loss
+        kind, kw = _class_spec(crit)
+        if (inputs.is_cuda and label_u8.dtype == torch.uint8 and not _call_is_hooked(self.model, head) and kind is not None
+                and not getattr(crit, "skip_last_target", False)
                 and ops.ds_head_supported(feats, head.in_channels, head.out_channels, label_u8, s)):
-            if compound:
-                feats, aux[s] = ops.ds_head(feats, head.weight, head.bias, head._packed(), label_u8, s, crit.weight, crit.epsilon,
-                                            class_loss="DICE_CE")
-            elif dice:
-                feats, aux[s] = ops.ds_head(feats, head.weight, head.bias, head._packed(), label_u8, s, crit.weight, crit.epsilon,
-                                            crit.sigmoid_normalization, crit.ignore_index, "DICE")
-            else:
-                feats, aux[s] = ops.ds_head(feats, head.weight, head.bias, head._packed(), label_u8, s, crit.weight,
-                                            ignore_index=crit.ignore_index, class_loss="CE")
+            feats, aux[s] = ops.ds_head(feats, head.weight, head.bias, head._packed(), label_u8, s, class_loss=kind, **kw)
             return feats
         d, h, w = feats.shape[2:]
         lab = label_u8[:, :d << s:1 << s, :h << s:1 << s, :w << s:1 << s].contiguous()
-        aux[s] = crit(head(feats), lab if compound else lab.long())
+        aux[s] = crit(head(feats), lab if kind == "DICE_CE" else lab.long())
         return feats
 
     def _fwd_bwd(self, batch):
@@ -756,53 +719,38 @@ class SegmentationStep(_GraphedStep):
             for s in range(1, k + 1):
                 loss = loss + aux[s] * self.ds_weights[s]
             self.scale_losses = [aux[s].detach() for s in range(k + 1)]
-        (loss if self.scaler is None else self.scaler.scale_loss(loss)).backward()
-        finish_backward()
+        self._backward(loss)
         return (loss.detach(),)
 
     def __call__(self, batch):
-        force = getattr(self, "force_allreduce", False)
-        if self._exchange is None:  # (built lazily: bench.py sets force_allreduce after construction)
-            self._exchange = BucketedExchange(self.model, self.flat, self.world, force)
-        (loss,) = self._run(batch)
-        scale = self._exchange.finish()  # 1/world is folded into the optimiser (and into the gradient norm in front of it)
-        self._optimizer_step(scale)
-        self.repack.run()
+        (loss,) = super().__call__(batch)
         return loss
 
 
-class SegmentationValidation:
-    """SegmentationNet.validation_step / validation_epoch_end (segmentation.py:94-118; SURVEY 8f row N3) on the MI355X
-    path: forward kernels only, the configured loss and `dice_metric` each as ONE fused pass over the logits, results as
-    device scalars (no host synchronisation per batch).  Sample logging (`log_samples`, segmentation.py:67-92,100-101): with
-    log_interval set, every batch with batch_nb % log_interval == 0 hands on_samples(panels, batch_nb) the vis.SamplePanels of
-    sample 0 -- what the reference draws, computed on the device from `outputs` and the batch where they lie, still without a
-    synchronisation; drawing and the one host copy (panels.to_host()) are the callback's.  log_vis_mip: the hparams' "mean" | "max".
-    log_interval=None (the default) logs nothing; the results are the same either way."""
+class _Validation:
+    """What the two validation classes share: the evaluation-mode bracket, sample logging's arguments and rule, the `val_dice{c}`
+    naming and validation_epoch_end."""
 
-    def __init__(self, model, loss_weight=None, loss="DICE", log_interval=None, log_vis_mip="mean", on_samples=None):
+    def _setup(self, model, log_interval, log_vis_mip, on_samples):
         self.model = model
-        dev = next(model.parameters()).device
-        w = None if loss_weight is None else torch.tensor(loss_weight, dtype=torch.float32, device=dev)
-        self.loss = _class_criterion(loss, w).to(dev)
         self.log_interval, self.log_vis_mip, self.on_samples = log_interval, log_vis_mip, on_samples
 
-    @torch.no_grad()
-    def validation_step(self, batch, batch_nb=0):
-        inputs = batch["data"].float()
-        labels = batch["label"][:, -1, ...].long()
+    def _logs_samples(self, batch_nb) -> bool:
+        """`if batch_nb % self.log_interval == 0` of the reference's validation_step, off without an interval or a callback."""
+        return bool(self.log_interval) and self.on_samples is not None and batch_nb % self.log_interval == 0
+
+    def _in_eval_mode(self, fn, *args):
+        """fn(*args) with the model in evaluation mode; its training flag is put back whatever happens."""
         was_training = self.model.training
         self.model.eval()
         try:
-            outputs = self.model(inputs)
+            return fn(*args)
         finally:
             self.model.train(was_training)
-        if _logs_samples(self, batch_nb):
-            self.on_samples(vis.sample_panels(outputs, _class_map(batch["label"], labels), inputs, 0,
-                                              projection_type=self.log_vis_mip), batch_nb)
-        results = {"val_loss": self.loss(outputs, labels)}
-        per_channel_dice = HL.dice_metric(outputs, labels)
-        for c in range(outputs.shape[1]):
+
+    @staticmethod
+    def _with_dice(results, per_channel_dice):
+        for c in range(per_channel_dice.shape[0]):
             results[f"val_dice{c}"] = per_channel_dice[c]
         return results
 
@@ -812,15 +760,32 @@ class SegmentationValidation:
         return {"val_loss": logs["val_loss"], "log": logs, "progress_bar": logs}
 
 
-def _logs_samples(validation, batch_nb) -> bool:
-    """`if batch_nb % self.log_interval == 0` of the reference's validation_step, off without an interval or a callback."""
-    return bool(validation.log_interval) and validation.on_samples is not None and batch_nb % validation.log_interval == 0
+class SegmentationValidation(_Validation):
+    """SegmentationNet.validation_step / validation_epoch_end (segmentation.py:94-118; SURVEY 8f row N3) on the MI355X
+    path: forward kernels only, the configured loss and `dice_metric` each as ONE fused pass over the logits, results as
+    device scalars (no host synchronisation per batch).  Sample logging (`log_samples`, segmentation.py:67-92,100-101): with
+    log_interval set, every batch with batch_nb % log_interval == 0 hands on_samples(panels, batch_nb) the vis.SamplePanels of
+    sample 0 -- what the reference draws, computed on the device from `outputs` and the batch where they lie, still without a
+    synchronisation; drawing and the one host copy (panels.to_host()) are the callback's.  log_vis_mip: the hparams' "mean" | "max".
+    log_interval=None (the default) logs nothing; the results are the same either way."""
 
+    def __init__(self, model, loss_weight=None, loss="DICE", log_interval=None, log_vis_mip="mean", on_samples=None):
+        dev = next(model.parameters()).device
+        w = None if loss_weight is None else torch.tensor(loss_weight, dtype=torch.float32, device=dev)
+        self.loss = _class_criterion(loss, w).to(dev)
+        self._setup(model, log_interval, log_vis_mip, on_samples)
 
-def _class_map(label, labels_long):
-    """The class map for the sample panels: the last channel of the batch's label volume where it lies when the kernel reads its
-    type (uint8 / int64), else the int64 copy the loss takes anyway."""
-    return label[:, -1, ...] if label.dtype in (torch.uint8, torch.int64) else labels_long
+    @torch.no_grad()
+    def validation_step(self, batch, batch_nb=0):
+        inputs = batch["data"].float()
+        labels = batch["label"][:, -1, ...].long()
+        outputs = self._in_eval_mode(self.model, inputs)
+        if self._logs_samples(batch_nb):
+            label = batch["label"]
+            # (the class map: the label volume's last channel where it lies when the kernel reads its type, else the int64 copy)
+            class_map = label[:, -1, ...] if label.dtype in (torch.uint8, torch.int64) else labels
+            self.on_samples(vis.sample_panels(outputs, class_map, inputs, 0, projection_type=self.log_vis_mip), batch_nb)
+        return self._with_dice({"val_loss": self.loss(outputs, labels)}, HL.dice_metric(outputs, labels))
 
 
 def _landmark_losses(class_weight, regression_weight, class_loss, regression, dev):
@@ -834,35 +799,22 @@ def _landmark_losses(class_weight, regression_weight, class_loss, regression, de
 
 
 def _landmark_head_fusable(model, loss_class, loss_reg, inputs) -> bool:
-    """The fused landmark head serves this package's U-Net with a planar 1x1x1 head and L1 / L2 regression, without hooks: its node
-    bypasses model.__call__ and final_conv.__call__ and never forms `outputs`, so with a forward (pre-)hook on the model, on one of
-    its children or a global module hook the stock m(inputs) path runs and the hook sees its tensor."""
-    from .unet.model import _UNetCore
-    fc = getattr(model, "final_conv", None)
-    return (isinstance(model, _UNetCore) and not model.testing and fc is not None and getattr(fc, "planar_output", False)
-            and fc.kernel_size[0] == 1 and inputs.is_cuda and not getattr(loss_class, "skip_last_target", False)
-            and loss_reg.kind in ("L1", "L2") and not _call_is_hooked(model, fc))
+    """The fused landmark head: _head_fusable's conditions and L1 / L2 regression.  Its node never forms `outputs`: with a hook it
+    would bypass, the stock m(inputs) path runs and the hook sees its tensor."""
+    return _head_fusable(model, loss_class, inputs) and loss_reg.kind in ("L1", "L2")
 
 
 class LandmarkStep(_GraphedStep):
     """LandmarkNet.training_step (landmarks.py:66-83, loss :125-134) with the per-channel regression loop fused.  class_loss:
-    the hparams' `loss_class`, "DICE" (DiceLoss) or "CE" (nn.CrossEntropyLoss(weight=class_weight)).  optimizer, optimizer_args, lr as
-    a callable, clip_grad_norm and skip_nonfinite: as SegmentationStep's."""
+    the hparams' `loss_class`, "DICE" (DiceLoss), "CE" (nn.CrossEntropyLoss(weight=class_weight)) or "DICE_CE" (their sum).  optimizer,
+    optimizer_args, lr as a callable, clip_grad_norm and skip_nonfinite: as SegmentationStep's.  -> (loss, class loss, regression loss)."""
 
     def __init__(self, model, class_weight, regression_weight, regression="L2", lr=1e-3, world_size=1, graph=None, class_loss="DICE",
                  optimizer="adam", optimizer_args=None, clip_grad_norm=None, skip_nonfinite=False):
-        self.model = model
-        dev = next(model.parameters()).device
         self.class_loss = class_loss
-        self.loss_class, self.loss_reg = _landmark_losses(class_weight, regression_weight, class_loss, regression, dev)
-        self.flat = FlatParams(model)
-        self._init_optimizer(optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
-        self.repack = BatchedRepack(model)
-        self.world = world_size
-        use_side_stream()
-        self.scaler = make_scaler(dev)
-        self._init_graph(graph)
-        self._exchange = BucketedExchange(model, self.flat, world_size)
+        self.loss_class, self.loss_reg = _landmark_losses(class_weight, regression_weight, class_loss, regression,
+                                                          next(model.parameters()).device)
+        self._setup(model, world_size, graph, optimizer, optimizer_args, lr, clip_grad_norm, skip_nonfinite)
 
     def _head_losses(self, inputs, heatmaps, labels, nh):
         """`outputs = self(inputs)` and the two terms of LandmarkNet.loss (landmarks.py:71-75, 125-134).  In the 16-bit storage
@@ -872,17 +824,9 @@ class LandmarkStep(_GraphedStep):
         if _landmark_head_fusable(m, self.loss_class, self.loss_reg, inputs):
             feats = m.forward_features(inputs)
             if ops.head_landmark_supported(feats, fc.in_channels, nh, fc.out_channels - nh, heatmaps, labels):
-                if self.class_loss == "DICE_CE":
-                    return ops.head_landmark(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, self.loss_class.weight,
-                                             self.loss_reg.channel_weights, self.loss_reg.kind, self.loss_class.epsilon,
-                                             class_loss="DICE_CE")
-                if self.class_loss == "CE":
-                    return ops.head_landmark(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, self.loss_class.weight,
-                                             self.loss_reg.channel_weights, self.loss_reg.kind, ignore_index=self.loss_class.ignore_index,
-                                             class_loss="CE")
-                return ops.head_landmark(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, self.loss_class.weight,
-                                         self.loss_reg.channel_weights, self.loss_reg.kind, self.loss_class.epsilon,
-                                         self.loss_class.sigmoid_normalization, self.loss_class.ignore_index)
+                kind, kw = _class_spec(self.loss_class)
+                return ops.head_landmark(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, kw.pop("loss_weight"),
+                                         self.loss_reg.channel_weights, self.loss_reg.kind, class_loss=kind, **kw)
             outputs = fc(feats)
         else:
             outputs = m(inputs)
@@ -898,19 +842,11 @@ class LandmarkStep(_GraphedStep):
             labels = labels.long()
         class_loss, regression_loss = self._head_losses(inputs, heatmaps, labels, nh)
         loss = regression_loss + class_loss
-        (loss if self.scaler is None else self.scaler.scale_loss(loss)).backward()
-        finish_backward()
+        self._backward(loss)
         return loss.detach(), class_loss.detach(), regression_loss.detach()
 
-    def __call__(self, batch):
-        out = self._run(batch)
-        scale = self._exchange.finish()
-        self._optimizer_step(scale)
-        self.repack.run()
-        return out
 
-
-class LandmarkValidation:
+class LandmarkValidation(_Validation):
     """LandmarkNet.validation_step / validation_epoch_end (landmarks.py:136-174) on the MI355X path: forward kernels only, results
     as device scalars (no host synchronisation per batch).  With this package's
     U-Net and a head the fused landmark kernel serves (16-bit storage, 32 features), the head, both loss terms and dice_metric
@@ -923,11 +859,10 @@ class LandmarkValidation:
 
     def __init__(self, model, class_weight, regression_weight, class_loss="DICE", regression="L2", log_interval=None,
                  log_vis_mip="mean", on_samples=None):
-        self.model = model
-        dev = next(model.parameters()).device
         self.class_loss = class_loss
-        self.loss_class, self.loss_reg = _landmark_losses(class_weight, regression_weight, class_loss, regression, dev)
-        self.log_interval, self.log_vis_mip, self.on_samples = log_interval, log_vis_mip, on_samples
+        self.loss_class, self.loss_reg = _landmark_losses(class_weight, regression_weight, class_loss, regression,
+                                                          next(model.parameters()).device)
+        self._setup(model, log_interval, log_vis_mip, on_samples)
 
     def _log_samples(self, outputs, batch, inputs, nh, batch_nb, first=slice(None)):
         """`outputs`: the logits of the whole batch, or (first = slice(0, 1)) of its first sample alone."""
@@ -942,16 +877,17 @@ class LandmarkValidation:
     def _forward(self, inputs, heatmaps, labels, nh, batch=None, batch_nb=None):
         m, fc = self.model, getattr(self.model, "final_conv", None)
         lc = self.loss_class
+        kind, kw = _class_spec(lc)
         # (the Dice forward's sums serve dice_metric only when they are its sums: softmax, no ignore mask)
-        metric_ok = self.class_loss in ("CE", "DICE_CE") or (not lc.sigmoid_normalization and lc.ignore_index is None)
+        metric_ok = kind != "DICE" or (not lc.sigmoid_normalization and lc.ignore_index is None)
         if metric_ok and _landmark_head_fusable(m, lc, self.loss_reg, inputs):
             feats = m.forward_features(inputs)
             if ops.head_landmark_supported(feats, fc.in_channels, nh, fc.out_channels - nh, heatmaps, labels):
                 if batch is not None:
                     self._log_samples(fc(feats[0:1]), batch, inputs, nh, batch_nb, first=slice(0, 1))
-                return ops.head_landmark_eval(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, lc.weight,
-                                              self.loss_reg.channel_weights, self.loss_reg.kind, getattr(lc, "epsilon", 1e-5),
-                                              getattr(lc, "ignore_index", None), self.class_loss)
+                kw.pop("sigmoid", None)  # (False here, and the forward-only node takes none)
+                return ops.head_landmark_eval(feats, fc.weight, fc.bias, fc._packed(), heatmaps, labels, kw.pop("loss_weight"),
+                                              self.loss_reg.channel_weights, self.loss_reg.kind, class_loss=kind, **kw)
             outputs = fc(feats)
         else:
             outputs = m(inputs)
@@ -968,19 +904,7 @@ class LandmarkValidation:
         labels = batch["label"][:, -1, ...]
         if not labels.is_cuda:
             labels = labels.long()
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            class_loss, regression_loss, per_channel_dice = self._forward(inputs, heatmaps, labels, nh,
-                                                                          batch if _logs_samples(self, batch_nb) else None, batch_nb)
-        finally:
-            self.model.train(was_training)
-        results = {"val_loss": regression_loss + class_loss, "val_class_loss": class_loss, "val_regression_loss": regression_loss}
-        for c in range(per_channel_dice.shape[0]):
-            results[f"val_dice{c}"] = per_channel_dice[c]
-        return results
-
-    @staticmethod
-    def validation_epoch_end(outputs):
-        logs = {k: torch.stack([o[k] for o in outputs]).mean() for k in outputs[0]}
-        return {"val_loss": logs["val_loss"], "log": logs, "progress_bar": logs}
+        class_loss, regression_loss, per_channel_dice = self._in_eval_mode(
+            self._forward, inputs, heatmaps, labels, nh, batch if self._logs_samples(batch_nb) else None, batch_nb)
+        return self._with_dice({"val_loss": regression_loss + class_loss, "val_class_loss": class_loss,
+                                "val_regression_loss": regression_loss}, per_channel_dice)
