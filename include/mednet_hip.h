@@ -843,6 +843,41 @@ int mednet_cc_stats(const uint8_t* vol, const int32_t* labels, int d, int h, int
 int mednet_cc_select(const uint8_t* vol, const int32_t* labels, const uint8_t* keep, int fill, uint8_t* out, int d, int h, int w,
                      mednet_stream stream);
 
+/* ---- resampling between voxel grids (additive to ABI 3; the reference resamples nothing) ---------------------------------------------
+ * Separable and table-driven: the host states an axis once (mednet_hip/resample.py: axis_table) and the kernels only execute it.
+ * A table of an axis with n_out outputs is start int32[n_out], count int32[n_out], weight fp32[n_out][taps] (all 4-byte aligned):
+ * output i reads the source indices start[i] .. start[i] + count[i] - 1 with the weights weight[i * taps + k]; slots at and above
+ * count[i] are not read.  THE ARITHMETIC, pinned (fp32 throughout; tests/resample_util.py restates it).  A chain over the values
+ * v[k] of a row (f16 and u8 widened first) is
+ *   acc = w[0] * v[0];   acc = fmaf(w[k], v[k], acc)  for k = 1 .. count - 1,        in exactly this order.
+ * A voxel outside a row's count never reaches the output (a NaN next to the support does not leak).  Inside the kernels count is
+ * clamped to 1 .. taps and every index to the extent: any table is safe for memory.  No atomics, one owning thread per output
+ * voxel: the same inputs give the same bits.
+ * Refused before anything is launched, by both entries: a null pointer, an extent outside 1 .. 2048 or d * h * w >= 2^31 (a linear
+ * voxel index fits 32 bits; channel offsets are held in size_t), on the way in or out, an axis outside 0 .. 2, c < 1, taps outside
+ * 1 .. 64, ncls outside 1 .. 256, a table (or out_max) that is not 4-byte aligned (all MEDNET_E_SHAPE); an unknown dtype
+ * (MEDNET_E_DTYPE).
+ *
+ * mednet_resample_axis: one pass.  src is c x d x h x w, dst the same with extent `axis` (0, 1, 2 counting within d x h x w)
+ * replaced by n_out.  src_dtype and dst_dtype each MEDNET_F32, MEDNET_F16 or MEDNET_U8.  Stores: f32 as is, f16 one
+ * round-to-nearest-even, u8 fminf(fmaxf(acc, 0), 255) and one rintf (nearest-even). */
+int mednet_resample_axis(const void* src, int src_dtype, void* dst, int dst_dtype, int c, int d, int h, int w, int axis, int n_out,
+                         const int* start, const int* count, const float* weight, int taps, mednet_stream stream);
+/* mednet_resample_argmax: the fused way back -- one pass over the od x oh x ow output, no class volume at the output size.
+ *   src     MEDNET_F32 / MEDNET_F16: ncls planes d x h x w of scores (probabilities, logits, anything);
+ *           MEDNET_U8: ONE label volume d x h x w whose class-c score at a voxel is label == c ? 1 : 0 (one-hot linear resampling
+ *           of a segmentation without the one-hot tensor; a label >= ncls scores for nobody)
+ *   score   of (output voxel, class): the tensor product of the three tables (0: z, 1: y, 2: x) in the association of three axis
+ *           passes run x, then y, then z with fp32 between them -- the x chain for every (z-tap, y-tap), then the y chain over
+ *           those, then the z chain: bit for bit what mednet_resample_axis gives on axis 2, 1, 0 with fp32 destinations
+ *   out     uint8 od x oh x ow (any address): the first maximum over the classes, the lowest class on ties (torch.argmax); a NaN
+ *           score never wins against class 0
+ *   out_max fp32 od x oh x ow or NULL: the winning score */
+int mednet_resample_argmax(const void* src, int src_dtype, int ncls, int d, int h, int w, uint8_t* out, float* out_max, int od, int oh,
+                           int ow, const int* start0, const int* count0, const float* weight0, int taps0, const int* start1,
+                           const int* count1, const float* weight1, int taps1, const int* start2, const int* count2,
+                           const float* weight2, int taps2, mednet_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

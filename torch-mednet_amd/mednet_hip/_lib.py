@@ -185,6 +185,8 @@ SIGNATURES = {
     "mednet_cc_label": (_i, [_vp] + [_i] * 6 + [_vp, _vp, _vp, _sz, _vp]),
     "mednet_cc_stats": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp]),
     "mednet_cc_select": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "mednet_resample_axis": (_i, [_vp, _i, _vp, _i] + [_i] * 6 + [_vp, _vp, _vp, _i, _vp]),
+    "mednet_resample_argmax": (_i, [_vp, _i] + [_i] * 4 + [_vp, _vp] + [_i] * 3 + [_vp, _vp, _vp, _i] * 3 + [_vp]),
 }
 
 _lib = None

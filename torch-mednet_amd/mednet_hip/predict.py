@@ -205,16 +205,62 @@ class BlendedPrediction:
         return evaluate_case(self.result()[-1], label, num_classes, spacing=spacing, **kw)
 
 
+class ResampledPrediction(BlendedPrediction):
+    """A BlendedPrediction whose network ran on a resampled grid (GridPredictor(target_spacing=...).predict(volume, spacing=...)):
+    the accumulators lie at the network's grid, everything read from them is brought back to the native grid `native_shape`
+    (mednet_hip.resample)."""
+
+    def __init__(self, acc, wsum, num_heatmaps, blend_of, native_shape, kind="linear"):
+        super().__init__(acc, wsum, num_heatmaps, blend_of)
+        self.native_shape, self.kind = tuple(int(v) for v in native_shape), kind
+
+    def result(self, postprocess=None):
+        """uint8 (H + 1) x D x H x W at the native grid: the class channel is resample_argmax of the class probabilities (no class
+        volume at the native size), the heat maps are resampled linearly, then clipped to 0..255 and truncated as at the network's
+        grid; then `postprocess` on the class channel."""
+        from .resample import resample_argmax
+        res = torch.empty((self.num_heatmaps + 1,) + self.native_shape, dtype=torch.uint8, device=self.acc.device)
+        res[-1].copy_(resample_argmax(super().probabilities(), size=self.native_shape, kind=self.kind, antialias=True))
+        if self.num_heatmaps:
+            res[:-1].copy_(self.heatmaps().clamp_(0, 255).to(torch.uint8))
+        if postprocess is not None:
+            res[-1].copy_(postprocess(res[-1]))
+        return res
+
+    def probabilities(self, dtype=torch.float32):
+        from .resample import resample
+        return resample(super().probabilities(), size=self.native_shape, kind=self.kind, antialias=True, dtype=dtype)
+
+    def heatmaps(self):
+        from .resample import resample
+        heat = super().heatmaps()
+        if not self.num_heatmaps:
+            return torch.empty((0,) + self.native_shape, dtype=torch.float32, device=self.acc.device)
+        return resample(heat, size=self.native_shape, kind="linear", antialias=True)
+
+    def peaks(self):
+        """(positions H x 3 float64 as (z, y, x) in native voxel coordinates, values H fp32): the peaks of the blended heat maps at
+        the network's grid, mapped by p = (q + 0.5) * n_native / n_net - 0.5."""
+        zyx, value = heatmap_peaks(super().heatmaps())
+        net = torch.tensor(tuple(self.acc.shape[1:]), dtype=torch.float64, device=zyx.device)
+        native = torch.tensor(self.native_shape, dtype=torch.float64, device=zyx.device)
+        return (zyx.double() + 0.5) * native / net - 0.5, value
+
+
 class GridPredictor:
     def __init__(self, model, patch_size, patch_overlap, num_heatmaps=0, pad_mode="constant", batch_size=4,
-                 channel_selection=None, blend=None, sigma_scale=0.125, mirror_axes=(), blend_of="probabilities", postprocess=None):
-        """postprocess: a callable on the uint8 D x H x W class volume (mednet_hip.components.Postprocess), applied to the class
+                 channel_selection=None, blend=None, sigma_scale=0.125, mirror_axes=(), blend_of="probabilities", postprocess=None,
+                 target_spacing=None, resample_kind="linear"):
+        """target_spacing: the voxel spacing the network was trained at; `predict(volume, spacing=...)` then resamples the volume to
+        it (anti-aliased, resample_kind) and returns a ResampledPrediction at the native grid.  None (the default): no resampling,
+        exactly the calls of a predictor without the argument.  postprocess: a callable on the uint8 D x H x W class volume (mednet_hip.components.Postprocess), applied to the class
         channel [-1] of what __call__ returns; `predict` is unchanged.  blend=None: the reference's crop-stitch (the default).  blend="gaussian" / "constant" / three per-axis weight vectors:
         overlapping windows are blended (`predict`); mirror_axes: patch axes averaged over their flips (2^k passes per patch);
         blend_of: what the class channels accumulate, "probabilities" (softmax per patch) or "logits" (softmax once, at the end)."""
         self.model, self.patch_size, self.patch_overlap = model, list(patch_size), list(patch_overlap)
         self.num_heatmaps, self.pad_mode, self.batch_size, self.channel_selection = num_heatmaps, pad_mode, batch_size, channel_selection
         self.blend, self.blend_of, self.postprocess = blend, blend_of, postprocess
+        self.target_spacing, self.resample_kind = target_spacing, resample_kind
         self.mirror_bits = mirror_mask(mirror_axes)
         if blend is None:
             if self.mirror_bits:
@@ -254,13 +300,20 @@ class GridPredictor:
             self.model.train(was_training)
 
     @torch.no_grad()
-    def predict(self, volume) -> BlendedPrediction:
-        """Blended sliding-window inference.  For every mirror pass (ascending mask) and every batch of grid positions:
+    def predict(self, volume, spacing=None) -> BlendedPrediction:
+        """spacing (with the predictor's target_spacing): the volume's voxel spacing; the network runs at target_spacing and the
+        prediction is a ResampledPrediction at the volume's own grid.  Blended sliding-window inference.  For every mirror pass (ascending mask) and every batch of grid positions:
         gather(mirror) -> model -> accumulate(mirror).  A voxel's sums are taken pass by pass in patch order, so the result does not
         depend on batch_size.  An overlap of 0 is legal here (nothing is cropped)."""
         if self.blend is None:
             raise ValueError("predict() needs blend (the crop-stitch path is __call__)")
         vol, pos_all = self._upload(volume)
+        native_shape = None
+        if spacing is not None and self.target_spacing is not None:
+            from .resample import resample
+            native_shape = tuple(vol.shape[1:])
+            vol = resample(vol, spacing=spacing, target_spacing=self.target_spacing, kind=self.resample_kind, antialias=True)
+            pos_all = torch.from_numpy(grid_positions(vol.shape[1:], self.patch_size, self.patch_overlap)).to(vol.device)
         windows = tuple(torch.from_numpy(v).to(vol.device) for v in self.windows)
         acc = wsum = None
         for m in self.mirror_passes:
@@ -270,6 +323,8 @@ class GridPredictor:
                         acc = torch.zeros((logits.shape[1],) + tuple(vol.shape[1:]), dtype=torch.float32, device=vol.device)
                         wsum = torch.zeros(tuple(vol.shape[1:]), dtype=torch.float32, device=vol.device)
                     accumulate(logits, pos, acc, wsum, windows, self.num_heatmaps, self.patch_overlap, m, self.blend_of)
+        if native_shape is not None:
+            return ResampledPrediction(acc, wsum, self.num_heatmaps, self.blend_of, native_shape, self.resample_kind)
         return BlendedPrediction(acc, wsum, self.num_heatmaps, self.blend_of)
 
     @torch.no_grad()
