@@ -33,7 +33,8 @@ typedef void* mednet_stream; /* hipStream_t */
 enum { MEDNET_F32 = 0, MEDNET_BF16 = 1,
        MEDNET_F16 = 2, /* third activation storage type (fp16, with loss scaling: train.LossScaler); resident image volumes */
        MEDNET_U8 = 3,  /* label / heat-map volumes (mednet_crop_patches), labels of the fused head + Dice kernels */
-       MEDNET_I64 = 4  /* labels as the reference's callers pass them (`.long()`, segmentation.py:60) */ };
+       MEDNET_I64 = 4, /* labels as the reference's callers pass them (`.long()`, segmentation.py:60) */
+       MEDNET_I16 = 5  /* CT volumes as stored: a source type of the intensity entries only */ };
 enum { MEDNET_NDHWC = 0, MEDNET_NCDHW = 1 };
 enum { MEDNET_ACT_NONE = 0, MEDNET_ACT_RELU = 1, MEDNET_ACT_LEAKY = 2, MEDNET_ACT_ELU = 3 };
 enum { MEDNET_POOL_MAX = 0, MEDNET_POOL_AVG = 1 };
@@ -877,6 +878,63 @@ int mednet_resample_argmax(const void* src, int src_dtype, int ncls, int d, int 
                            int ow, const int* start0, const int* count0, const float* weight0, int taps0, const int* start1,
                            const int* count1, const float* weight1, int taps1, const int* start2, const int* count2,
                            const float* weight2, int taps2, mednet_stream stream);
+
+/* ---- intensity normalisation (additive to ABI 3; the reference normalises on the host) -------------------------------------------------
+ * Sources are c x d x h x w, dense, MEDNET_F32, MEDNET_F16, MEDNET_I16 or MEDNET_U8; every value is converted to fp32 first (exact
+ * for all four).  MEMBERSHIP: voxel (z, y, x) of channel c takes part iff mask[z, y, x] != 0 (mask: uint8 d x h x w at any address,
+ * shared by the channels, NULL: every voxel) and its value is not NaN; n_nan counts a channel's NaN voxels inside the mask; +-inf
+ * are values like any other.
+ * Refused before anything is launched: a null pointer, an extent outside 1 .. 2048, d * h * w >= 2^31, channels < 1, ranks outside
+ * 1 .. MEDNET_INTENSITY_MAX_RANKS, a level, pass or scheme that does not exist, a percentile outside 0 .. 100, a misaligned table,
+ * workspace or source (all MEDNET_E_SHAPE); an unsupported dtype (MEDNET_E_DTYPE); a workspace smaller than the _ws_bytes query
+ * answers (MEDNET_E_WORKSPACE).
+ * THE ARITHMETIC, pinned (tests/intensity_util.py restates it):
+ *   select      key(x): u = bits(x), x == 0 -> u = 0; key = u < 2^31 ? u | 2^31 : ~u.  Three levels of 11, 11, 10 key bits; integer
+ *               histograms only (LDS integer atomics, 64-bit global integer adds): the value with rank r among the members, bit-equal
+ *               to sort(members)[r]; a rank outside [0, n) gives NaN.
+ *   moments     pass A: n, n_nan, min, max, sum x in fp64 (per thread, block tree, partial rows in fixed order), mean = sum / n;
+ *               pass B: sum of d * d with d = x - mean, unfused; std = sqrt(sum / n) (population form).  n = 0: NaN.
+ *   percentile  q of n: pos = q / 100 * (n - 1); ranks floor(pos), min(floor(pos) + 1, n - 1); t = pos - floor(pos);
+ *               value = t == 0 ? a : a + (b - a) * t in fp64, each operation rounded on its own.
+ *   table       float[c][4] = (lo, hi, sub, mul), computed in fp64 and rounded to fp32 once:
+ *               zscore (-inf, +inf, mean, 1 / max(std, eps)); ct (p0, p1, mean, 1 / max(std, eps));
+ *               rescale (p0, p1, p0, 1 / max(p1 - p0, eps)), p0 / p1 the first two percentiles.
+ *   apply       y = (min(max(x, lo), hi) - sub) * mul in fp32, each operation rounded on its own; f16: one round-to-nearest-even
+ *               store; outside the mask and at a NaN: fill.
+ * The statistics table is c rows of MEDNET_INTENSITY_TABLE_BYTES: int64 n, int64 n_nan, fp32 min, fp32 max, fp64 mean, fp64 std.
+ *
+ * The accumulate form (select and moments): a level / pass is run over several volumes -- the cases of a data set -- before the
+ * next one; MEDNET_INTENSITY_FIRST on the first volume of a level clears its counters, MEDNET_INTENSITY_LAST on the last one closes it
+ * (select: the walk that refines every rank; moments: mean after pass 0, the table after either pass, std after pass 1).  The
+ * workspace carries the state between the calls: the largest of the volumes' queries, untouched in between.  level / pass
+ * MEDNET_INTENSITY_ALL: everything for one volume in one call (flags ignored).  Ranks then refer to the union of the members. */
+enum { MEDNET_INTENSITY_MAX_RANKS = 8, MEDNET_INTENSITY_TABLE_BYTES = 40 };
+enum { MEDNET_INTENSITY_ALL = -1, MEDNET_INTENSITY_FIRST = 1, MEDNET_INTENSITY_LAST = 2 };
+enum { MEDNET_INTENSITY_ZSCORE = 0, MEDNET_INTENSITY_CT = 1, MEDNET_INTENSITY_RESCALE = 2, MEDNET_INTENSITY_PERCENTILES = 3 };
+size_t mednet_intensity_select_ws_bytes(int channels, int nranks);
+/* ranks: int64 [c][nranks] in device memory, zero-based; out: fp32 [c][nranks]; counts: int64 [c][2] = (n, n_nan) or NULL, written
+ * when level 0 closes; level 0 .. 2 or MEDNET_INTENSITY_ALL. */
+int mednet_intensity_select(const void* src, int dtype, const uint8_t* mask, int c, int d, int h, int w, const int64_t* ranks,
+                            int nranks, float* out, int64_t* counts, int level, int flags, void* ws, size_t ws_bytes,
+                            mednet_stream stream);
+size_t mednet_intensity_moments_ws_bytes(int c, int d, int h, int w);
+/* pass 0 (A), 1 (B) or MEDNET_INTENSITY_ALL; table: the statistics table (written when a pass closes). */
+int mednet_intensity_moments(const void* src, int dtype, const uint8_t* mask, int c, int d, int h, int w, int pass, int flags,
+                             void* table, void* ws, size_t ws_bytes, mednet_stream stream);
+/* The ranks behind nq percentiles (q0 .. q3, the first nq count) of every channel's n in the statistics table: ranks int64
+ * [c][2 nq] as select takes them, frac fp64 [c][nq] = t.  A tiny kernel: select needs no host round trip. */
+int mednet_intensity_ranks(const void* table, int c, double q0, double q1, double q2, double q3, int nq, int64_t* ranks, double* frac,
+                           mednet_stream stream);
+/* One workgroup: statistics -> the apply table `out` of `scheme`, and / or the percentiles pct fp64 [c][nq] (NULL: not wanted;
+ * MEDNET_INTENSITY_PERCENTILES: only these).  order: select's output for mednet_intensity_ranks' ranks, fp32 [c][2 nq]. */
+int mednet_intensity_params(int scheme, const void* table, const float* order, const double* frac, int nq, int c, double eps,
+                            double* pct, float* out, mednet_stream stream);
+/* One pass, dst MEDNET_F32 or MEDNET_F16; table: float[c][4] in device memory; src == dst is legal for equal dtypes. */
+int mednet_intensity_apply(const void* src, int src_dtype, void* dst, int dst_dtype, const uint8_t* mask, int c, int d, int h, int w,
+                           const float* table, float fill, mednet_stream stream);
+/* mask[z, y, x] = any_c(src[c, z, y, x] != 0) as 0 / 1 (NaN counts as non-zero); box: int32[6] = the inclusive (z0, y0, x0, z1, y1,
+ * x1) of the mask by integer min / max; an all-zero volume gives (0, 0, 0, -1, -1, -1). */
+int mednet_nonzero_mask(const void* src, int dtype, int c, int d, int h, int w, uint8_t* mask, int32_t* box, mednet_stream stream);
 
 #ifdef __cplusplus
 }

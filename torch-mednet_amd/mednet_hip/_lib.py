@@ -31,10 +31,14 @@ BLEND_PROBABILITIES, BLEND_LOGITS = 0, 1
 INTERP_LINEAR, INTERP_NEAREST = 0, 1
 BORDER_CONSTANT, BORDER_EDGE = 0, 1
 F16, U8, I64 = 2, 3, 4  # F16: fp16 storage / resident volumes; U8, I64: label types
+I16 = 5  # CT volumes as stored: a source type of the intensity entries only
+INTENSITY_MAX_RANKS, INTENSITY_TABLE_BYTES = 8, 40
+INTENSITY_ALL, INTENSITY_FIRST, INTENSITY_LAST = -1, 1, 2
+INTENSITY_ZSCORE, INTENSITY_CT, INTENSITY_RESCALE, INTENSITY_PERCENTILES = 0, 1, 2, 3
 NO_IGNORE = -(2 ** 31)
 CC_ALL = -1  # mednet_cc_label: every non-zero voxel, connected only within one value
 
-_vp, _i, _sz, _f, _i64 = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_int64
+_vp, _i, _sz, _f, _i64, _dbl = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_int64, C.c_double
 
 # name -> (restype, argtypes); must list EVERY symbol of include/mednet_hip.h (tests/test_abi.py checks that)
 SIGNATURES = {
@@ -187,6 +191,14 @@ SIGNATURES = {
     "mednet_cc_select": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "mednet_resample_axis": (_i, [_vp, _i, _vp, _i] + [_i] * 6 + [_vp, _vp, _vp, _i, _vp]),
     "mednet_resample_argmax": (_i, [_vp, _i] + [_i] * 4 + [_vp, _vp] + [_i] * 3 + [_vp, _vp, _vp, _i] * 3 + [_vp]),
+    "mednet_intensity_select_ws_bytes": (_sz, [_i, _i]),
+    "mednet_intensity_select": (_i, [_vp, _i, _vp] + [_i] * 4 + [_vp, _i, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "mednet_intensity_moments_ws_bytes": (_sz, [_i] * 4),
+    "mednet_intensity_moments": (_i, [_vp, _i, _vp] + [_i] * 6 + [_vp, _vp, _sz, _vp]),
+    "mednet_intensity_ranks": (_i, [_vp, _i] + [_dbl] * 4 + [_i, _vp, _vp, _vp]),
+    "mednet_intensity_params": (_i, [_i, _vp, _vp, _vp, _i, _i, _dbl, _vp, _vp, _vp]),
+    "mednet_intensity_apply": (_i, [_vp, _i, _vp, _i, _vp] + [_i] * 4 + [_vp, _f, _vp]),
+    "mednet_nonzero_mask": (_i, [_vp, _i] + [_i] * 4 + [_vp, _vp, _vp]),
 }
 
 _lib = None

@@ -250,8 +250,10 @@ class ResampledPrediction(BlendedPrediction):
 class GridPredictor:
     def __init__(self, model, patch_size, patch_overlap, num_heatmaps=0, pad_mode="constant", batch_size=4,
                  channel_selection=None, blend=None, sigma_scale=0.125, mirror_axes=(), blend_of="probabilities", postprocess=None,
-                 target_spacing=None, resample_kind="linear"):
-        """target_spacing: the voxel spacing the network was trained at; `predict(volume, spacing=...)` then resamples the volume to
+                 target_spacing=None, resample_kind="linear", normalize=None):
+        """normalize: an intensity scheme (mednet_hip.intensity.ZScore / CTWindow / Rescale) applied to the uploaded volume at its
+        native grid, before any resampling (nnU-Net v2's order); int16 volumes are accepted then.  None (the default): exactly the
+        calls of a predictor without the argument.  target_spacing: the voxel spacing the network was trained at; `predict(volume, spacing=...)` then resamples the volume to
         it (anti-aliased, resample_kind) and returns a ResampledPrediction at the native grid.  None (the default): no resampling,
         exactly the calls of a predictor without the argument.  postprocess: a callable on the uint8 D x H x W class volume (mednet_hip.components.Postprocess), applied to the class
         channel [-1] of what __call__ returns; `predict` is unchanged.  blend=None: the reference's crop-stitch (the default).  blend="gaussian" / "constant" / three per-axis weight vectors:
@@ -260,7 +262,7 @@ class GridPredictor:
         self.model, self.patch_size, self.patch_overlap = model, list(patch_size), list(patch_overlap)
         self.num_heatmaps, self.pad_mode, self.batch_size, self.channel_selection = num_heatmaps, pad_mode, batch_size, channel_selection
         self.blend, self.blend_of, self.postprocess = blend, blend_of, postprocess
-        self.target_spacing, self.resample_kind = target_spacing, resample_kind
+        self.target_spacing, self.resample_kind, self.normalize = target_spacing, resample_kind, normalize
         self.mirror_bits = mirror_mask(mirror_axes)
         if blend is None:
             if self.mirror_bits:
@@ -284,7 +286,10 @@ class GridPredictor:
         vol = torch.as_tensor(np.asarray(volume) if not torch.is_tensor(volume) else volume)
         if self.channel_selection is not None:
             vol = vol[self.channel_selection]
-        vol = vol.to(dev, non_blocking=True).float().contiguous()
+        vol = vol.to(dev, non_blocking=True)
+        if self.normalize is not None:
+            vol = self.normalize(vol)
+        vol = vol.float().contiguous()
         return vol, torch.from_numpy(grid_positions(vol.shape[1:], self.patch_size, self.patch_overlap)).to(dev)
 
     def _batches(self, vol: torch.Tensor, pos_all: torch.Tensor, mirror=0):
