@@ -295,6 +295,19 @@ int mednet_gn_act_bwd_fused_res_pool(const void* dy_pool, const void* skip_grad,
                                      const float* gamma, const float* fused_partial, int rows, void* dx, void* dres, float* dgamma,
                                      float* dbeta, int n, int d, int h, int w, int c, int groups, int act, int pool_mode, int dtype,
                                      void* ws, size_t ws_bytes, mednet_stream stream);
+/* ... when dz is the feature gradient of the small fused head (mednet_head_dice_* / mednet_head_ce_* / mednet_head_dice_ce_*) and was
+ * NOT materialised: mednet_head_*_bwd_sums took the sums only, and this apply pass rebuilds each row of dz from the voxel's logits
+ * (planar fp32, cout planes), its label and the head's 4 x 32 weights (`packed`), with the loss operands of the head's backward
+ * (weight, saved, dloss, eps, sigmoid, ignore_index; class_kind = MEDNET_CLASS_*) -- the same device code as the head's backward,
+ * rounded as it would have stored the row.  dx (= dy3), dres, dgamma and dbeta are bit-identical to mednet_head_*_bwd +
+ * mednet_gn_act_bwd_fused_res.  Additive to ABI 3.  _supported: c == 32, 1 <= cout <= 4, bf16 / f16 storage, uint8 / int64 labels. */
+int mednet_gn_act_bwd_fused_res_head_supported(int c, int cout, int dtype, int label_dtype);
+int mednet_gn_act_bwd_fused_res_head(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
+                                     const void* packed, const float* weight, const float* saved, const float* dloss, float eps,
+                                     int sigmoid, int ignore_index, int class_kind, int cout, const void* x, const void* z,
+                                     const float* stats, const float* gamma, const float* fused_partial, int rows, void* dx, void* dres,
+                                     float* dgamma, float* dbeta, int n, size_t spatial, int c, int groups, int act, int dtype, void* ws,
+                                     size_t ws_bytes, mednet_stream stream);
 /* ---- nn.BatchNorm3d(C, eps, momentum) fused with the following activation and the residual add
  *      components.py:58-63 (order char 'b').  Channels-last storage: the batch is one [N * S][C] array.  stats[n][c] =
  *      {mean, rstd} and coef[n][c] = {gamma*rstd, beta - mean*gamma*rstd} are written REPLICATED per sample (all n rows equal), so
@@ -423,6 +436,14 @@ int mednet_head_dice_bwd(const float* logits, const void* labels, int label_dtyp
                          const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
                          int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
                          float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+/* mednet_head_dice_bwd (and below the CE and Dice + CE forms) WITHOUT dz: gn_partial, dw and dbias are those of the storing call, bit
+ * for bit -- the GroupNorm sums are taken from the values dz would hold -- and nothing else is written; the caller's GroupNorm-3
+ * apply pass rebuilds the rows (mednet_gn_act_bwd_fused_res_head, whose _supported says what both take).  gn_y and gn_partial are
+ * required; workspace and rows as for the storing call.  Additive to ABI 3. */
+int mednet_head_dice_bwd_sums(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const void* packed,
+                              const float* weight, const float* saved, const float* dloss, const void* gn_y, const void* z,
+                              int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
+                              float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
 
 /* The landmark head (LandmarkNet, landmarks.py:66-83: final_conv 32 -> nh heat maps + ncls classes) fused with BOTH terms of its
  * loss (landmarks.py:125-134: sum_c w_c mean f(out_c - heatmap_c), f = square | abs, plus DiceLoss of the class channels,
@@ -477,6 +498,10 @@ int mednet_head_ce_bwd(const float* logits, const void* labels, int label_dtype,
                        const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
                        int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
                        int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+int mednet_head_ce_bwd_sums(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const void* packed,
+                            const float* weight, const float* saved, const float* dloss, const void* gn_y, const void* z, int gn_act,
+                            float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout, int ignore_index,
+                            int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
 /* mednet_head_dice_ce_*: the segmentation head of mednet_head_dice_* (cin in {16, 32, 64}, cout <= 4, f32 / bf16 / f16 features) with
  * the compound class loss DiceLoss(weight, eps) + nn.CrossEntropyLoss(weight) of mednet_dice_ce_fwd_lt.  Additive to ABI 3.  Same
  * arguments, layouts, label forms, GroupNorm rows and fold rule as mednet_head_dice_*; softmax only and no ignore_index: sigmoid != 0
@@ -497,6 +522,10 @@ int mednet_head_dice_ce_bwd(const float* logits, const void* labels, int label_d
                             const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y, const void* z,
                             int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
                             float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
+int mednet_head_dice_ce_bwd_sums(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const void* packed,
+                                 const float* weight, const float* saved, const float* dloss, const void* gn_y, const void* z,
+                                 int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
+                                 float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream);
 int mednet_head_landmark_cls_fwd(const void* z, const void* packed, const float* bias, const void* heatmaps, int64_t heatmap_stride_n,
                                  const void* labels, int64_t label_stride_n, const float* class_weight, const float* reg_weight,
                                  float* logits, float* class_loss, float* reg_loss, float* saved, float* dice_metric, int n,

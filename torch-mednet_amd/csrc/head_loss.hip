@@ -103,7 +103,9 @@ __global__ __launch_bounds__(256) void head_dice_fwd_kernel(const TI* __restrict
 // stored gradient carries act'(z).  Its own instantiation: as a runtime branch it cost the main form its third wave per SIMD.
 // The logit gradient of a voxel is class_logit_grad's (loss_blocks.inc), as in loss.hip class_loss_bwd_kernel.  CE (head_ce): saved =
 // {sum w_y} of the CE forward, `eps` and `sigmoid` unused.  Dice + CE (head_dice_ce): saved = [m][2] {I, D}, then sum w_y.
-template <typename TO, int K, typename TL, bool FOLD = false, int KIND = MEDNET_CLASS_DICE>
+// STORE = false (with gy, not FOLD; 32 features in 16-bit storage): everything but the store of dz -- the sums are those of the values
+// dz WOULD hold, and the producing block's GroupNorm-3 apply pass rebuilds them (norm_act.hip gn_bwd_apply_head_kernel, head_dz_row).
+template <typename TO, int K, typename TL, bool FOLD = false, int KIND = MEDNET_CLASS_DICE, bool STORE = true>
 __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_dice_bwd_kernel(const float* __restrict__ lgs, const TL* __restrict__ lab, int64_t lab_sn,
                                                             const float* __restrict__ Pb /*[m][K]*/, const float* __restrict__ weight,
                                                             const float* __restrict__ saved, const float* __restrict__ dloss,
@@ -150,20 +152,13 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
     const size_t vbs = hb ? vb : v;
     // every load of both voxels before the first use
     float la[HL_MAXC], lb[HL_MAXC];
+    [[maybe_unused]] float oa = 0.f, ob = 0.f;
     if constexpr (CG == 4) {
       // the lanes of a voxel are one DPP quad (32 features; with 64 the extra registers spilled): lane q of the quad loads class q for both voxels and the quad hands the
       // values round -- 2 planar loads per lane and trip instead of 8 (each a whole wave instruction for 64 useful bytes)
       const int cq = threadIdx.x & 3;
-      const float oa = cq < m ? lgs[((size_t)n * m + cq) * spatial + v] : 0.f;
-      const float ob = cq < m ? lgs[((size_t)n * m + cq) * spatial + vbs] : 0.f;
-      la[0] = dpp_f32<(0) | (0 << 2) | (0 << 4) | (0 << 6)>(oa);
-      la[1] = dpp_f32<(1) | (1 << 2) | (1 << 4) | (1 << 6)>(oa);
-      la[2] = dpp_f32<(2) | (2 << 2) | (2 << 4) | (2 << 6)>(oa);
-      la[3] = dpp_f32<(3) | (3 << 2) | (3 << 4) | (3 << 6)>(oa);
-      lb[0] = dpp_f32<(0) | (0 << 2) | (0 << 4) | (0 << 6)>(ob);
-      lb[1] = dpp_f32<(1) | (1 << 2) | (1 << 4) | (1 << 6)>(ob);
-      lb[2] = dpp_f32<(2) | (2 << 2) | (2 << 4) | (2 << 6)>(ob);
-      lb[3] = dpp_f32<(3) | (3 << 2) | (3 << 4) | (3 << 6)>(ob);
+      oa = cq < m ? lgs[((size_t)n * m + cq) * spatial + v] : 0.f;
+      ob = cq < m ? lgs[((size_t)n * m + cq) * spatial + vbs] : 0.f;
       static_assert(HL_MAXC == 4, "one class per lane of a quad");
     } else {
 #pragma unroll
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
     Raw8<TO> zva, zvb, yva, yvb;
     zva.load(gz, rowa);
     zvb.load(gz, rowb);
-    if (gy) {
+    if (!STORE || gy) {
       yva.load(gy, rowa);
       yvb.load(gy, rowb);
     } else {
@@ -186,31 +181,26 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
     }
     if constexpr (KIND == MEDNET_CLASS_DICE_CE) asm volatile("" : "+v"(coef.off));
     float (&da)[HL_MAXC] = la, (&db)[HL_MAXC] = lb;  // the logit gradient of each voxel, in place of its logits
-    class_logit_grad<KIND, HL_MAXC>(da, ya, m, sigmoid, ignore, coef);
-    class_logit_grad<KIND, HL_MAXC>(db, yb, m, sigmoid, ignore, coef);
+    if constexpr (CG == 4) {  // one evaluation per voxel, shared by its quad
+      class_logit_grad_quad<KIND>(da, db, oa, ob, ya, yb, m, sigmoid, ignore, coef);
+    } else {
+      class_logit_grad<KIND, HL_MAXC>(da, ya, m, sigmoid, ignore, coef);
+      class_logit_grad<KIND, HL_MAXC>(db, yb, m, sigmoid, ignore, coef);
+    }
     if (!hb) {
 #pragma unroll
       for (int i = 0; i < HL_MAXC; ++i) db[i] = 0.f;
     }
-    F8 t, u;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t.v[j] = u.v[j] = 0.f;
+    F8 t, u;  // the stored value (rounded through TO) is what GroupNorm-3's second pass reads
+    head_dz_row<TO, HL_MAXC>(t.v, da, wreg, m);
+    head_dz_row<TO, HL_MAXC>(u.v, db, wreg, m);
 #pragma unroll
     for (int i = 0; i < HL_MAXC; ++i) {
       if (i < m) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          t.v[j] = fmaf(da[i], wreg[i][j], t.v[j]);
-          u.v[j] = fmaf(db[i], wreg[i][j], u.v[j]);
-          wacc[i][j] = fmaf(db[i], zvb.at(j), fmaf(da[i], zva.at(j), wacc[i][j]));  // dW[i][k] += dl_i * z_k
-        }
+        for (int j = 0; j < 8; ++j) wacc[i][j] = fmaf(db[i], zvb.at(j), fmaf(da[i], zva.at(j), wacc[i][j]));  // dW[i][k] += dl_i * z_k
         bacc[i] += da[i] + db[i];
       }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {  // the stored value is what GroupNorm-3's second pass reads
-      t.v[j] = (float)(TO)t.v[j];
-      u.v[j] = (float)(TO)u.v[j];
     }
     if constexpr (FOLD) {
       // x is the OUTPUT of a fused conv -> activation layer (UNet3D's last block, components.py:57-63): its derivative is folded
@@ -225,9 +215,11 @@ __global__ __launch_bounds__(256, (sizeof(TO) == 2 && !FOLD) ? 3 : 2) void head_
       act_grad_n<8>(t.v, za, act);
       act_grad_n<8>(u.v, zb, act);
     }
-    st8(dz, rowa, t);
-    if (hb) st8(dz, rowb, u);
-    if (!FOLD && gy) {
+    if constexpr (STORE) {
+      st8(dz, rowa, t);
+      if (hb) st8(dz, rowb, u);
+    }
+    if (!FOLD && (!STORE || gy)) {  // (the sums-only form always has gy)
       float za[8], zb[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -368,10 +360,14 @@ template <int KIND>
 static int head_loss_bwd(const char* what, const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
                          const void* packed, const float* weight, const float* saved, const float* dloss, void* dz, const void* gn_y,
                          const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
-                         float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+                         float eps, int sigmoid, int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream,
+                         bool store = true) {
   MEDNET_REQUIRE(mednet_head_dice_supported(cin, cout, z_dtype, label_dtype), MEDNET_E_UNSUPPORTED,
                  "%s: %d -> %d classes, dtype %d, labels %d", what, cin, cout, z_dtype, label_dtype);
-  MEDNET_REQUIRE(n > 0 && spatial > 0 && logits && labels && packed && saved && dloss && dz && z && dw, MEDNET_E_SHAPE, "%s: bad arguments", what);
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && logits && labels && packed && saved && dloss && (dz || !store) && z && dw, MEDNET_E_SHAPE, "%s: bad arguments", what);
+  // the sums-only form: what mednet_gn_act_bwd_fused_res_head rebuilds (32 features, 16-bit storage, a GroupNorm-3 in front)
+  MEDNET_REQUIRE(store || (cin == 32 && z_dtype != MEDNET_F32), MEDNET_E_UNSUPPORTED, "%s: 32 features in 16-bit storage, not %d in dtype %d", what, cin, z_dtype);
+  MEDNET_REQUIRE(store || (gn_y && gn_partial), MEDNET_E_SHAPE, "%s: gn_y and gn_partial are required", what);
   MEDNET_REQUIRE((gn_y == nullptr) == (gn_partial == nullptr), MEDNET_E_SHAPE, "%s: gn_y and gn_partial go together", what);
   const size_t need = KIND == MEDNET_CLASS_DICE_CE ? mednet_head_dice_ce_ws_bytes(n, spatial, cin, cout) : mednet_head_dice_ws_bytes(n, spatial, cin, cout);
   MEDNET_REQUIRE(ws_bytes >= need, MEDNET_E_WORKSPACE, "%s: workspace too small", what);
@@ -385,9 +381,16 @@ static int head_loss_bwd(const char* what, const float* logits, const void* labe
 #define HB(TO_, K_, TL_) do { if (fold) HB_(TO_, K_, TL_, true); else HB_(TO_, K_, TL_, false); } while (0)
 #define HB_L(TO_, K_) do { if (label_dtype == MEDNET_U8) HB(TO_, K_, uint8_t); else HB(TO_, K_, int64_t); } while (0)
 #define HB_K(TO_) do { if (cin == 16) HB_L(TO_, 16); else if (cin == 32) HB_L(TO_, 32); else HB_L(TO_, 64); } while (0)
-  if (z_dtype == MEDNET_F32) HB_K(float);
+#define HB_S(TO_, TL_) hipLaunchKernelGGL((head_dice_bwd_kernel<TO_, 32, TL_, false, KIND, false>), grid, dim3(256), 0, s, logits, (const TL_*)labels, label_stride_n, Pb, weight, saved, dloss, eps, sigmoid, ignore_index, (TO_*)nullptr, (const TO_*)gn_y, (const TO_*)z, gn_act, gn_partial, wpart, spatial, cout)
+#define HB_SL(TO_) do { if (label_dtype == MEDNET_U8) HB_S(TO_, uint8_t); else HB_S(TO_, int64_t); } while (0)
+  if (!store) {
+    if (z_dtype == MEDNET_BF16) HB_SL(bf16);
+    else HB_SL(f16);
+  } else if (z_dtype == MEDNET_F32) HB_K(float);
   else if (z_dtype == MEDNET_BF16) HB_K(bf16);
   else HB_K(f16);
+#undef HB_SL
+#undef HB_S
 #undef HB_K
 #undef HB_L
 #undef HB_
@@ -418,6 +421,17 @@ extern "C" int mednet_head_dice_bwd(const float* logits, const void* labels, int
                               gn_partial, dw, dbias, n, spatial, cin, cout, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream);
 }
 
+// ... without dz: the sums (gn_partial, dw, dbias) of mednet_head_dice_bwd, bit for bit, for a caller whose GroupNorm-3 apply pass
+// rebuilds the rows of dz (mednet_gn_act_bwd_fused_res_head, norm_act.hip)
+extern "C" int mednet_head_dice_bwd_sums(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
+                                         const void* packed, const float* weight, const float* saved, const float* dloss,
+                                         const void* gn_y, const void* z, int gn_act, float* gn_partial, float* dw, float* dbias, int n,
+                                         size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index, int z_dtype,
+                                         void* ws, size_t ws_bytes, mednet_stream stream) {
+  return head_loss_bwd<MEDNET_CLASS_DICE>("head_dice_bwd_sums", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, nullptr, gn_y, z,
+                              gn_act, gn_partial, dw, dbias, n, spatial, cin, cout, eps, sigmoid, ignore_index, z_dtype, ws, ws_bytes, stream, false);
+}
+
 // ---- the same head fused with nn.CrossEntropyLoss(weight, ignore_index) (segmentation.py:49): the CE instantiations -------------
 extern "C" int mednet_head_ce_supported(int cin, int cout, int dtype, int label_dtype) {
   return mednet_head_dice_supported(cin, cout, dtype, label_dtype);
@@ -441,6 +455,14 @@ extern "C" int mednet_head_ce_bwd(const float* logits, const void* labels, int l
                                   int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
   return head_loss_bwd<MEDNET_CLASS_CE>("head_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z, gn_act,
                              gn_partial, dw, dbias, n, spatial, cin, cout, 0.f, 0, ignore_index, z_dtype, ws, ws_bytes, stream);
+}
+
+extern "C" int mednet_head_ce_bwd_sums(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n, const void* packed,
+                                       const float* weight, const float* saved, const float* dloss, const void* gn_y, const void* z,
+                                       int gn_act, float* gn_partial, float* dw, float* dbias, int n, size_t spatial, int cin, int cout,
+                                       int ignore_index, int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  return head_loss_bwd<MEDNET_CLASS_CE>("head_ce_bwd_sums", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, nullptr, gn_y, z, gn_act,
+                             gn_partial, dw, dbias, n, spatial, cin, cout, 0.f, 0, ignore_index, z_dtype, ws, ws_bytes, stream, false);
 }
 
 // ---- the same head fused with DiceLoss + nn.CrossEntropyLoss, one class-weight vector: the Dice + CE instantiations ----------------
@@ -470,4 +492,16 @@ extern "C" int mednet_head_dice_ce_bwd(const float* logits, const void* labels, 
   return head_loss_bwd<MEDNET_CLASS_DICE_CE>("head_dice_ce_bwd", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, dz, gn_y, z,
                                    gn_act, gn_partial, dw, dbias, n, spatial, cin, cout, eps, 0, MEDNET_NO_IGNORE, z_dtype, ws, ws_bytes,
                                    stream);
+}
+
+extern "C" int mednet_head_dice_ce_bwd_sums(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
+                                            const void* packed, const float* weight, const float* saved, const float* dloss,
+                                            const void* gn_y, const void* z, int gn_act, float* gn_partial, float* dw, float* dbias,
+                                            int n, size_t spatial, int cin, int cout, float eps, int sigmoid, int ignore_index,
+                                            int z_dtype, void* ws, size_t ws_bytes, mednet_stream stream) {
+  MEDNET_REQUIRE(sigmoid == 0 && ignore_index == MEDNET_NO_IGNORE, MEDNET_E_UNSUPPORTED,
+                 "head_dice_ce_bwd_sums: Dice + cross-entropy is a softmax form without ignore_index");
+  return head_loss_bwd<MEDNET_CLASS_DICE_CE>("head_dice_ce_bwd_sums", logits, labels, label_dtype, label_stride_n, packed, weight, saved, dloss, nullptr,
+                                   gn_y, z, gn_act, gn_partial, dw, dbias, n, spatial, cin, cout, eps, 0, MEDNET_NO_IGNORE, z_dtype, ws,
+                                   ws_bytes, stream, false);
 }

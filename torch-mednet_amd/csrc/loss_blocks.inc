@@ -301,4 +301,44 @@ __device__ __forceinline__ void class_logit_grad(float* p, int y, int c, int sig
   }
 }
 
+// ---- the 32-feature head: the four lanes that own a voxel's row are one DPP quad, and a quad works on two voxels a and b per trip ----
+// Lane q of the quad has loaded the class-q logit of both voxels (oa, ob; 0 for q >= c).  The closed form runs ONCE per voxel: the
+// even lanes of the quad evaluate voxel a, the odd lanes voxel b, and the quad hands the results round -- the function and its inputs
+// are class_logit_grad's, so da / db are the values every lane used to compute for itself, bit for bit.  Every lane of the quad must be
+// active.  (head_dice_bwd_kernel and the GroupNorm-3 apply pass that rebuilds the head's feature gradient, gn_bwd_apply_head_kernel)
+template <int KIND, class Coef>
+__device__ __forceinline__ void class_logit_grad_quad(float (&da)[4], float (&db)[4], float oa, float ob, int ya, int yb, int c,
+                                                      int sigmoid, int ignore, const Coef& coef) {
+  const bool second = threadIdx.x & 1;
+  // every exchange is made by ALL lanes, in statements of its own, and the choice between the two voxels comes after it: an exchange
+  // in one arm of a conditional expression runs with the other arm's lanes switched off and reads nothing from them
+  const float a0 = dpp_f32<0x00>(oa), a1 = dpp_f32<0x55>(oa), a2 = dpp_f32<0xAA>(oa), a3 = dpp_f32<0xFF>(oa);
+  const float b0 = dpp_f32<0x00>(ob), b1 = dpp_f32<0x55>(ob), b2 = dpp_f32<0xAA>(ob), b3 = dpp_f32<0xFF>(ob);
+  float g[4] = {second ? b0 : a0, second ? b1 : a1, second ? b2 : a2, second ? b3 : a3};  // the logits of this lane's voxel
+  class_logit_grad<KIND, 4>(g, second ? yb : ya, c, sigmoid, ignore, coef);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    da[k] = dpp_f32<0x00>(g[k]);  // lane 0 of the quad: voxel a
+    db[k] = dpp_f32<0x55>(g[k]);  // lane 1: voxel b
+  }
+}
+
+// The head's feature gradient of one voxel, the 8 channels of one lane: t[j] = sum_i dl[i] * W[i][j] over the classes i < c in class
+// order from a zero start, then rounded through the storage type TO -- the value head_dice_bwd_kernel stores, whose GroupNorm sums it
+// takes, and which the apply pass of the lazy form rebuilds instead of reading it (one copy: the two must agree bit for bit).
+template <typename TO, int MAXC>
+__device__ __forceinline__ void head_dz_row(float (&t)[8], const float (&dl)[MAXC], const float (&w)[MAXC][8], int c) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) t[j] = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    if (i < c) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) t[j] = fmaf(dl[i], w[i][j], t[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) t[j] = (float)(TO)t[j];
+}
+
 }  // namespace mednet

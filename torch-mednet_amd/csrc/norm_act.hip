@@ -6,6 +6,8 @@
 // Reference call sites: components.py:57 (GroupNorm), :36-40 (activations), :177-178 (residual add + activation),
 // :208-212 (pooling), :277-280 (interpolate + cat).
 #include "common.h"
+#include "conv.h"
+#include "loss_blocks.inc"
 
 #include <type_traits>
 
@@ -1056,6 +1058,102 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_pool_kernel(const T* __restr
   }
 }
 
+// GroupNorm-3's backward apply pass of the block in front of the small fused head (head_loss.hip: 32 features, at most 4 classes,
+// 16-bit storage) WITHOUT the head's feature gradient dz in memory: head_dice_bwd_kernel<.., STORE = false> took the sums and wrote
+// no dz; here the four lanes that own a voxel's row rebuild it from the voxel's logits, its label and the 4 x 32 head weights --
+// class_logit_grad_quad (one closed form per voxel, shared by the quad) and head_dz_row, the text head_dice_bwd_kernel runs, so the
+// row is the one it would have stored, bit for bit -- and from there on this is gn_bwd_apply_kernel<T, 8> of a residual layer:
+//   du = dz * act'(out);  dy3 = k1 * du + k2 * y3 + k3;  dres = du.
+// The 537 MB gradient tensor of a 32-channel 128^3 batch is neither written (head backward) nor read (this pass).
+// Thread layout and chunking are gn_bwd_apply_kernel's at C = 32: lane % 4 = the 8-channel column, 64 voxel rows per workgroup, two
+// voxels (v, v + 64) per trip -- the quad's voxels a and b.
+template <typename T, typename TL, int KIND>
+__global__ __launch_bounds__(256, GN_WAVES) void gn_bwd_apply_head_kernel(const float* __restrict__ lgs, const TL* __restrict__ lab,
+                                                                          int64_t lab_sn, const float* __restrict__ Pb /*[m][32]*/,
+                                                                          const float* __restrict__ weight, const float* __restrict__ saved,
+                                                                          const float* __restrict__ dloss, float eps, int sigmoid, int ignore,
+                                                                          int m, const T* __restrict__ x, const T* __restrict__ z,
+                                                                          const float* __restrict__ bcoef, T* __restrict__ dx,
+                                                                          T* __restrict__ dres, size_t spatial, int act, size_t chunk_vox,
+                                                                          GnParamGrad pg) {
+  constexpr int C = 32, VEC = 8, MAXC = 4, ROWS = 256 / (C / VEC);
+  static_assert(sizeof(T) == 2, "16-bit storage");
+  if (pg.csum && blockIdx.x == 0 && blockIdx.y == 0) {  // pass 2b (gn_bwd_params_kernel) without a launch of its own
+    for (int cc = threadIdx.x; cc < C; cc += 256) {
+      double a = 0.0, b = 0.0;
+      for (int i = 0; i < pg.n; ++i) {
+        a += (double)pg.csum[((size_t)i * C + cc) * 2];
+        b += (double)pg.csum[((size_t)i * C + cc) * 2 + 1];
+      }
+      if (pg.dbeta) pg.dbeta[cc] = (float)a;
+      if (pg.dgamma) pg.dgamma[cc] = (float)b;
+    }
+  }
+  const int n = blockIdx.y, col = threadIdx.x & 3, row = threadIdx.x >> 2;
+  const size_t v0 = (size_t)blockIdx.x * chunk_vox;
+  const size_t v1 = v0 + chunk_vox < spatial ? v0 + chunk_vox : spatial;
+  float k1[VEC], k2[VEC], k3[VEC], wreg[MAXC][VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    const float* o = bcoef + ((size_t)n * C + col * VEC + k) * 3;
+    k1[k] = o[0];
+    k2[k] = o[1];
+    k3[k] = o[2];
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) wreg[i][k] = i < m ? Pb[(size_t)i * C + col * VEC + k] : 0.f;
+  }
+  // the per-class coefficients of the closed form, where head_dice_bwd_kernel keeps them (Dice + CE: twelve values, in LDS)
+  const float go = *dloss;
+  std::conditional_t<KIND == MEDNET_CLASS_DICE_CE, ClassCoefLds<MAXC>, ClassCoefRegs<MAXC>> coef;
+  if constexpr (KIND == MEDNET_CLASS_DICE_CE) {
+    __shared__ float hk_s[3 * MAXC];
+    coef.row = hk_s;
+    if (threadIdx.x < MAXC) coef.template fill<KIND>(threadIdx.x, m, weight, saved, eps, go);
+    __syncthreads();
+  } else {
+    coef.template fill<KIND>(m, weight, saved, eps, go);
+  }
+  const size_t off = (size_t)n * spatial * C + (size_t)col * VEC;
+  auto finish = [&](size_t i, F8& g1, const F8& zv, const F8& xv) {
+    act_grad_n<VEC>(g1.v, zv.v, act);
+    F8 o;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      // plain fp32 FMAs on converted operands, THEN the rounding to T, as gn_bwd_apply_kernel has them (see gn_bwd_apply_pool_kernel)
+      float xf = xv.v[k];
+      asm volatile("" : "+v"(xf));
+      o.v[k] = fmaf(k1[k], g1.v[k], fmaf(k2[k], xf, k3[k]));
+      asm volatile("" : "+v"(o.v[k]));
+    }
+    VecIO<T, VEC>::store(dx, i, o);
+    VecIO<T, VEC>::store(dres, i, g1);
+  };
+  // voxels a and b of the quad (b == a, and nothing stored for it, when the chunk has no second one left)
+  auto two = [&](size_t va, size_t vb, bool hb) {
+    const float oa = col < m ? lgs[((size_t)n * m + col) * spatial + va] : 0.f;
+    const float ob = col < m ? lgs[((size_t)n * m + col) * spatial + vb] : 0.f;
+    const int ya = label_at(lab, (size_t)n * lab_sn + va, ignore), yb = label_at(lab, (size_t)n * lab_sn + vb, ignore);
+    const size_t ia = off + va * C, ib = off + vb * C;
+    F8 zva, zvb;
+    if (act != MEDNET_ACT_NONE) {
+      zva = VecIO<T, VEC>::load(z, ia);
+      zvb = VecIO<T, VEC>::load(z, ib);
+    }
+    const F8 xva = VecIO<T, VEC>::load_last(x, ia), xvb = VecIO<T, VEC>::load_last(x, ib);
+    if constexpr (KIND == MEDNET_CLASS_DICE_CE) asm volatile("" : "+v"(coef.off));
+    float da[MAXC], db[MAXC];
+    class_logit_grad_quad<KIND>(da, db, oa, ob, ya, yb, m, sigmoid, ignore, coef);
+    F8 ga, gb;
+    head_dz_row<T, MAXC>(ga.v, da, wreg, m);
+    head_dz_row<T, MAXC>(gb.v, db, wreg, m);
+    finish(ia, ga, zva, xva);
+    if (hb) finish(ib, gb, zvb, xvb);
+  };
+  size_t v = v0 + row;
+  for (; v + (size_t)ROWS < v1; v += 2 * (size_t)ROWS) two(v, v + ROWS, true);
+  for (; v < v1; v += ROWS) two(v, v, false);
+}
+
 // ---------------------------------------------------------------------------------------------- upsample + concat
 __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
   const float scale = (float)in / (float)out;  // ATen: compute_scales_value when only `size` is given
@@ -1488,6 +1586,55 @@ extern "C" int mednet_gn_act_bwd_fused_res_pool(const void* dy_pool, const void*
                        (const T*)skip_grad, (const T*)x, (const T*)z, p.bcoef, (T*)dx, (T*)dres, n, d, h, w, c, act, pool_mode, pg);
   });
   return check_launch("gn_bwd_apply_pool");
+}
+
+// ... for the residual layer of the block in front of the small fused head (mednet_head_dice_* / _ce_* / _dice_ce_*) whose feature
+// gradient dz was not materialised (mednet_head_*_bwd_sums took the sums): the apply pass rebuilds dz per voxel from the logits,
+// the label and the head weights.  What the rebuild takes: 32 features in 16-bit storage, at most 4 classes, uint8 / int64 labels.
+extern "C" int mednet_gn_act_bwd_fused_res_head_supported(int c, int cout, int dtype, int label_dtype) {
+  return c == 32 && cout >= 1 && cout <= 4 && (dtype == MEDNET_BF16 || dtype == MEDNET_F16) &&
+         (label_dtype == MEDNET_U8 || label_dtype == MEDNET_I64);
+}
+extern "C" int mednet_gn_act_bwd_fused_res_head(const float* logits, const void* labels, int label_dtype, int64_t label_stride_n,
+                                                const void* packed, const float* weight, const float* saved, const float* dloss,
+                                                float eps, int sigmoid, int ignore_index, int class_kind, int cout, const void* x,
+                                                const void* z, const float* stats, const float* gamma, const float* fused_partial,
+                                                int rows, void* dx, void* dres, float* dgamma, float* dbeta, int n, size_t spatial,
+                                                int c, int groups, int act, int dtype, void* ws, size_t ws_bytes,
+                                                mednet_stream stream) {
+  MEDNET_REQUIRE(mednet_gn_act_bwd_fused_res_head_supported(c, cout, dtype, label_dtype), MEDNET_E_UNSUPPORTED,
+                 "gn_act_bwd_fused_res_head: %d features -> %d classes, dtype %d, labels %d", c, cout, dtype, label_dtype);
+  MEDNET_REQUIRE(class_kind == MEDNET_CLASS_DICE || class_kind == MEDNET_CLASS_CE || class_kind == MEDNET_CLASS_DICE_CE,
+                 MEDNET_E_UNSUPPORTED, "gn_act_bwd_fused_res_head: class loss %d", class_kind);
+  MEDNET_REQUIRE(class_kind != MEDNET_CLASS_DICE_CE || (sigmoid == 0 && ignore_index == MEDNET_NO_IGNORE), MEDNET_E_UNSUPPORTED,
+                 "gn_act_bwd_fused_res_head: Dice + cross-entropy is a softmax form without ignore_index");
+  MEDNET_REQUIRE(n > 0 && spatial > 0 && c % groups == 0 && rows > 0 && fused_partial && logits && labels && packed && saved && dloss &&
+                     x && z && dx && dres && stats && gamma,
+                 MEDNET_E_SHAPE, "gn_act_bwd_fused_res_head: bad arguments");
+  MEDNET_REQUIRE(ws_bytes >= mednet_gn_ws_bytes(n, c, spatial), MEDNET_E_WORKSPACE, "gn_act_bwd_fused_res_head: workspace too small");
+  const GnPlan p = gn_plan(n, spatial, c, dtype, ws);
+  hipStream_t s = (hipStream_t)stream;
+  GnParamGrad pg;
+  const int rc = gn_bwd_coefs<true>(fused_partial, rows, stats, gamma, p.csum, p.bcoef, dgamma, dbeta, n, spatial, c, groups, 0, &pg, s);
+  if (rc) return rc;
+  const float* Pb = head_weights_f32(packed, c, cout);
+  if (class_kind == MEDNET_CLASS_CE) eps = 0.f, sigmoid = 0;  // (unused by that form, as in mednet_head_ce_bwd)
+  for_class_kind(class_kind, [&](auto kind) {
+    by_type(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      if constexpr (sizeof(T) == 2) {
+        auto go = [&](auto l) {
+          using TL = typename decltype(l)::type;
+          hipLaunchKernelGGL((gn_bwd_apply_head_kernel<T, TL, decltype(kind)::value>), p.grid, dim3(256), 0, s, logits, (const TL*)labels,
+                             label_stride_n, Pb, weight, saved, dloss, eps, sigmoid, ignore_index, cout, (const T*)x, (const T*)z, p.bcoef,
+                             (T*)dx, (T*)dres, spatial, act, p.chunk_vox, pg);
+        };
+        if (label_dtype == MEDNET_U8) go(Tag<uint8_t>{});
+        else go(Tag<int64_t>{});
+      }
+    });
+  });
+  return check_launch("gn_bwd_apply_head");
 }
 
 // ---------------------------------------------------------------------------------------------- BatchNorm3d

@@ -68,6 +68,9 @@ SIGNATURES = {
     "mednet_gn_bwd_coefficients": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _sz, _i, _i, _vp, _sz, _vp]),
     "mednet_gn_act_bwd_fused_res": (_i, [_vp] * 7 + [_i, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mednet_gn_act_bwd_fused_res_pool": (_i, [_vp] * 7 + [_i, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp, _sz, _vp]),
+    "mednet_gn_act_bwd_fused_res_head_supported": (_i, [_i] * 4),
+    "mednet_gn_act_bwd_fused_res_head": (_i, [_vp, _vp, _i, _i64] + [_vp] * 4 + [_f, _i, _i, _i, _i] + [_vp] * 5 + [_i, _vp, _vp, _vp, _vp,
+                                              _i, _sz, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mednet_head_dgrad_gn_rows": (_i, [_i] * 6),
     "mednet_head_dgrad_gn": (_i, [_vp] * 5 + [_i, _vp] + [_i] * 7 + [_vp]),
     "mednet_pool2_bwd_gn_rows": (_i, [_i] * 6),
@@ -139,6 +142,9 @@ SIGNATURES = {
     "mednet_head_ce_gn_rows": (_i, [_i, _sz, _i]),
     "mednet_head_ce_fwd": (_i, [_vp] * 4 + [_i, _i64, _vp, _vp, _vp, _vp, _i, _sz, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mednet_head_ce_bwd": (_i, [_vp, _vp, _i, _i64] + [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_head_ce_bwd_sums": (_i, [_vp, _vp, _i, _i64] + [_vp] * 6 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_head_dice_bwd_sums": (_i, [_vp, _vp, _i, _i64] + [_vp] * 6 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
+    "mednet_head_dice_ce_bwd_sums": (_i, [_vp, _vp, _i, _i64] + [_vp] * 6 + [_i, _vp, _vp, _vp, _i, _sz, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
     "mednet_head_dice_supported": (_i, [_i] * 4),
     "mednet_head_dice_ws_bytes": (_sz, [_i, _sz, _i, _i]),
     "mednet_head_dice_gn_rows": (_i, [_i, _sz, _i]),

@@ -173,12 +173,16 @@ class PoolStash:
         self.mode, self.pooled, self.version = mode, None, -1  # version: the output's `_version` when the stash was attached
 
 
-def res_block(x, convs, norms, groups, eps, act, pool_mode=None):
+def res_block(x, convs, norms, groups, eps, act, pool_mode=None, head_next=False):
     """convs / norms: the three mednet_hip.nn.Conv3d / GroupNorm modules of the block.  `pool_mode`: the block's output goes into a
     2x2x2 pooling of that mode next (the next encoder level): the pooled tensor is produced in the same pass and stashed on the
-    output (`_mednet_pooled`)."""
+    output (`_mednet_pooled`).  `head_next`: the caller (the U-Net's own forward) hands the output to the network's head and to
+    nothing else: a fused head may then leave the output's gradient unwritten and let this block's backward rebuild it
+    (ops.GN3Hook.lazy_head_ok, ops._valu_head_bwd)."""
     (k1, k2, k3), (n1, n2, n3) = convs, norms
     hook = ops.GN3Hook() if (ops.FUSE_GN3 and torch.is_grad_enabled()) else None  # (training only)
+    if hook is not None:
+        hook.lazy_head_ok = bool(head_next)  # (this node's backward is the one that consumes the gradient: it holds the hook)
     stash = PoolStash(pool_mode) if (pool_mode is not None and FUSE_POOL) else None
     out = ResBlockFn.apply(x, k1.weight, n1.weight, n1.bias, k2.weight, n2.weight, n2.bias, k3.weight, n3.weight, n3.bias,
                            k1._packed(x, converts=True), k2._packed(x, converts=True), k3._packed(x, converts=True), groups, eps, act,

@@ -266,14 +266,19 @@ class GN3Hook:
     output gradient (mednet_head_dgrad_gn / mednet_pool2_bwd_gn).  The block's backward uses the sums only if the gradient it
     receives IS that tensor, untouched (same object, same version counter): any other consumer of `out` makes autograd
     accumulate into / replace it, and the block falls back to its stand-alone pass."""
-    __slots__ = ("gn_in", "act", "partial", "dx", "version", "lazy")
+    __slots__ = ("gn_in", "act", "partial", "dx", "version", "lazy", "lazy_head_ok")
 
     def __init__(self):
         self.gn_in = None  # the GroupNorm's input (y3 of an ExtResNetBlock; x of a plain GroupNorm)
         self.act = 0
         self.partial = self.dx = None
         self.version = -1
-        self.lazy = None  # (dy_pool, skip gradient, pool mode): `dx` was NOT written, the block's apply pass rebuilds it
+        # `dx` was NOT written, the block's apply pass rebuilds it: (dy_pool, skip gradient, pool mode) of SkipPool2Fn, or
+        # ("head", ...) of the small fused heads (_valu_head_bwd)
+        self.lazy = None
+        # set by the producing block (block.res_block) when its own backward will consume the gradient of its output and the caller
+        # hands that output to the head and to nothing else: the head's backward may then leave the gradient unwritten (LAZY_HEAD)
+        self.lazy_head_ok = False
 
     def offer(self, dx, partial, lazy=None):
         self.dx, self.partial, self.version, self.lazy = dx, partial, dx._version, lazy
@@ -286,10 +291,11 @@ class GN3Hook:
         self.partial = self.dx = self.lazy = None
         ok = partial is not None and dout is dx and dout._version == version
         if lazy is not None and not ok:
-            raise RuntimeError("mednet_hip: the block output handed to skip_pool2(sole_consumer=True) has another consumer (or its "
-                               "gradient was replaced by a hook): the pooling backward did not materialise its gradient (MEDNET_LAZY_POOL=0 turns "
-                               "the optimisation off)")
+            raise RuntimeError("mednet_hip: the block output handed to skip_pool2(sole_consumer=True), or to a fused head as its sole "
+                               "consumer, has another consumer (or its gradient was replaced by a hook): the pooling / head backward did "
+                               "not materialise its gradient (MEDNET_LAZY_POOL=0 / MEDNET_LAZY_HEAD=0 turn the optimisation off)")
         GN3_COUNT["taken" if ok else ("declined" if partial is not None else "absent")] += 1
+        GN3_COUNT["lazy_head"] += int(ok and lazy is not None and isinstance(lazy[0], str))
         self.lazy = lazy if ok else None  # (read and cleared by the block's backward)
         return partial if ok else None
 
@@ -340,7 +346,8 @@ def _gnb_hook_of(x, dtype):
     if h is None or h.gn_in is None or h.gn_in.shape != x.shape or h.gn_in.dtype != dtype or dtype not in config.HALF_TYPES:
         return None
     return h
-GN3_COUNT = {"taken": 0, "declined": 0, "absent": 0, "masked": 0}  # (tests: how the blocks' backward passes found their sums)
+# (tests: how the blocks' backward passes found their sums; "lazy_head": those of "taken" whose gradient the head left unwritten)
+GN3_COUNT = {"taken": 0, "declined": 0, "absent": 0, "masked": 0, "lazy_head": 0}
 
 
 def _gn3_hook_of(x, dtype):
@@ -741,7 +748,9 @@ def gn_backward(b, dz, x, z, coef, stats, gamma, act, in_act, partial, groups, d
     passes (mednet_gn_act_bwd; `dz2`: a second gradient stream, read beside dz).  `partial` = the first pass's rows, taken by the
     producer of dz (GNBHook / GN3Hook): the plain layer (mednet_gn_act_bwd_fused); with the activated output `z`, the residual layer
     of a block (_fused_res); with `lazy` = (dy_pool, skip gradient, pool mode), the residual layer of an encoder block whose dz was
-    NOT written (SkipPool2Fn, lazy): the apply pass rebuilds its rows per pooling window (_fused_res_pool)."""
+    NOT written (SkipPool2Fn, lazy): the apply pass rebuilds its rows per pooling window (_fused_res_pool); with `lazy` = ("head",
+    logits, labels, label dtype, label stride, packed, loss weight, saved, dloss, eps, sigmoid, ignore_index, class kind), the last
+    block in front of a small fused head that wrote no dz (_valu_head_bwd): the rows are rebuilt per voxel (_fused_res_head)."""
     n, c, d, h, w = x.shape
     spatial = d * h * w
     lib = L.lib()
@@ -751,7 +760,14 @@ def gn_backward(b, dz, x, z, coef, stats, gamma, act, in_act, partial, groups, d
                                       b.dx.data_ptr(), L.ptr(b.dres), *grads, n, spatial, c, groups, act, in_act, *tail), "gn_act_bwd")
         return
     assert dz2 is None and (z is None) == (b.dres is None)
-    if lazy is not None:
+    if lazy is not None and isinstance(lazy[0], str):  # ("head", ...)
+        _, lg, lab, lab_dt, lab_sn, packed, wt, saved, dl, eps, sigmoid, ii, kind = lazy
+        L.check(lib.mednet_gn_act_bwd_fused_res_head(lg.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, packed.data_ptr(), L.ptr(wt),
+                                                     saved.data_ptr(), dl.data_ptr(), eps, sigmoid, ii, kind, lg.shape[1], x.data_ptr(),
+                                                     z.data_ptr(), stats.data_ptr(), gamma.data_ptr(), partial.data_ptr(),
+                                                     partial.shape[1], b.dx.data_ptr(), b.dres.data_ptr(), *grads, n, spatial, c, groups,
+                                                     act, *tail), "gn_act_bwd_fused_res_head")
+    elif lazy is not None:
         dy_pool, dskip, pool_mode = lazy
         L.check(lib.mednet_gn_act_bwd_fused_res_pool(dy_pool.data_ptr(), L.ptr(dskip), x.data_ptr(), z.data_ptr(), stats.data_ptr(),
                                                      gamma.data_ptr(), partial.data_ptr(), partial.shape[1], b.dx.data_ptr(),
@@ -1406,14 +1422,15 @@ class _HeadBackward:
         self.act = self.hook.act if self.hook is not None else (self.inmask.act if self.inmask is not None else 0)
         self.ws = L.workspace(ws_bytes, x.device)
 
-    def finish(self, name, n_inputs):
-        """Offers dx (and the rows) to the hook or the mask -> the node's gradients, None for every input behind x, weight, bias."""
+    def finish(self, name, n_inputs, lazy=None):
+        """Offers dx (and the rows) to the hook or the mask -> the node's gradients, None for every input behind x, weight, bias.
+        `lazy`: dx is an unwritten placeholder, and these are the operands the block's apply pass rebuilds it from (GN3Hook.lazy)."""
         if self.hook is not None:
-            self.hook.offer(self.dx, self.partial)
+            self.hook.offer(self.dx, self.partial, lazy)
         elif self.inmask is not None:
             self.inmask.offer(self.dx)
         if debug.TRACE is not None:
-            debug.trace(name + ".bwd", self.dx, self.partial, self.dw, self.db)
+            debug.trace(name + ".bwd", None if lazy is not None else self.dx, self.partial, self.dw, self.db)
         return (self.dx, (None if self.direct_w else self.dw),
                 (None if (self.bias is None or self.direct_b) else self.db)) + (None,) * (n_inputs - 3)
 
@@ -1445,10 +1462,25 @@ def _valu_head_fwd(ctx, name, x, weight, bias, packed, labels, loss_weight, save
     # x is the output of a fused conv -> activation layer (UNet3D's last block): the backward folds act'(x) into the feature
     # gradient it stores and that layer skips its activation pass (ActMaskHook), as SkipPool2Fn does for the encoder levels
     ctx.inmask = getattr(x, "_mednet_actmask", None) if (ctx.gn3 is None and FUSE_GN3 and POOL_ACT_MASK) else None
+    # The producing block said that its backward consumes the gradient of x and that x goes nowhere else (GN3Hook.lazy_head_ok):
+    # the backward may then take the sums only and leave the gradient unwritten -- the block's GroupNorm-3 apply pass rebuilds its
+    # rows (mednet_gn_act_bwd_fused_res_head).  A tensor hook or retain_grad() on x would READ that gradient: then it is written as
+    # before (looked at again in the backward: both can still arrive after this forward).
+    ctx.lazy_ok = (LAZY_HEAD and ctx.gn3 is not None and ctx.gn3.lazy_head_ok and not _reads_grad(x)
+                   and bool(lib.mednet_gn_act_bwd_fused_res_head_supported(cin, cout, L.dt(x), lab_dt)))
     ctx.mark_non_differentiable(logits)
     if debug.TRACE is not None:
         debug.trace(name + ".fwd", logits, loss, saved)
     return logits, loss
+
+
+LAZY_HEAD = os.environ.get("MEDNET_LAZY_HEAD", "1") == "1"  # A/B knob
+_HEAD_KIND = {"head_dice": L.CLASS_DICE, "head_ce": L.CLASS_CE, "head_dice_ce": L.CLASS_DICE_CE}
+
+
+def _reads_grad(x) -> bool:
+    """Will autograd hand the gradient of x to anyone but the node that produced x?  (a tensor hook, retain_grad())"""
+    return bool(x._backward_hooks) or bool(getattr(x, "retains_grad", False))
 
 
 def _valu_head_bwd(ctx, name, dloss, n_inputs):
@@ -1461,6 +1493,15 @@ def _valu_head_bwd(ctx, name, dloss, n_inputs):
     dl = dloss.to(torch.float32).contiguous()
     b = _HeadBackward(ctx, x, cout, lambda: getattr(lib, f"mednet_{name}_gn_rows")(n, spatial, cin),
                       getattr(lib, f"mednet_{name}_ws_bytes")(n, spatial, cin, cout))
+    if ctx.lazy_ok and b.hook is not None and debug.TRACE is None and not _reads_grad(x):
+        # sums only: b.dx stays an unwritten placeholder (autograd needs a tensor of the right shape to hand on)
+        L.check(getattr(lib, f"mednet_{name}_bwd_sums")(logits.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, packed.data_ptr(), L.ptr(wt),
+                                                        saved.data_ptr(), dl.data_ptr(), b.gn_in, x.data_ptr(), b.act,
+                                                        b.partial.data_ptr(), b.dw.data_ptr(), L.ptr(b.db), n, spatial, cin, cout,
+                                                        *scalars, L.dt(x), b.ws.data_ptr(), b.ws.numel(), L.stream()), name + "_bwd_sums")
+        eps, sigmoid, ii = scalars if len(scalars) == 3 else (0.0, 0, scalars[0])  # (head_ce: ignore_index only)
+        return b.finish(name, n_inputs, lazy=("head", logits, lab, lab_dt, lab_sn, packed, wt, saved, dl, eps, sigmoid, ii,
+                                             _HEAD_KIND[name]))
     L.check(getattr(lib, f"mednet_{name}_bwd")(logits.data_ptr(), lab.data_ptr(), lab_dt, lab_sn, packed.data_ptr(), L.ptr(wt),
                                                saved.data_ptr(), dl.data_ptr(), b.dx.data_ptr(), b.gn_in, x.data_ptr(), b.act,
                                                L.ptr(b.partial), b.dw.data_ptr(), L.ptr(b.db), n, spatial, cin, cout, *scalars,

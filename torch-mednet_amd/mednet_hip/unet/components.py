@@ -195,18 +195,20 @@ class ExtResNetBlock(nn.Module):
             return None
         return convs, norms
 
-    def forward(self, x, pool_mode=None):
+    def forward(self, x, pool_mode=None, head_next=False):
         """`pool_mode` (not part of the reference's signature; components.py:167-180 takes x only): the caller will pool this
         block's output with a 2x2x2 pooling of that mode next -- the single-node path then writes the pooled tensor in the pass
-        that writes the output.  Purely an optimisation hint: the result is the same tensor either way."""
+        that writes the output.  `head_next`: the caller hands the output to the network's head and to nothing else
+        (block.res_block).  Purely optimisation hints: the result is the same tensor either way."""
         with config.exact_products(self._kinked):
-            return self._forward(x, pool_mode)
+            return self._forward(x, pool_mode, head_next)
 
-    def _forward(self, x, pool_mode=None):
+    def _forward(self, x, pool_mode=None, head_next=False):
         plain = self._plain() if (x.is_cuda and block.ENABLED) else None
         if plain is not None:
             convs, norms = plain
-            return block.res_block(x, convs, norms, norms[0].num_groups, norms[0].eps, self.non_linearity.code, pool_mode=pool_mode)
+            return block.res_block(x, convs, norms, norms[0].num_groups, norms[0].eps, self.non_linearity.code, pool_mode=pool_mode,
+                                   head_next=head_next)
         residual = self.conv1(x)
         out = self.conv2(residual)
         return self.conv3(out, residual=residual, final_act=self.non_linearity.code)
@@ -270,7 +272,9 @@ class Decoder(nn.Module):
         self.basic_module = basic_module(in_channels, out_channels, encoder=False, kernel_size=kernel_size,
                                          order=conv_layer_order, num_groups=num_groups)
 
-    def forward(self, encoder_features, x):
+    def forward(self, encoder_features, x, head_next=False):
+        """forward(encoder_features, x) is the reference's Decoder.forward.  `head_next`: the caller (the U-Net's own forward, on its
+        last decoder) hands the result to the network's head and to nothing else (ExtResNetBlock.forward)."""
         with config.exact_products(_module_kinked(self.basic_module)):  # (the upsampling follows its block)
             if self.upsample is None:
                 bm = self.basic_module
@@ -282,6 +286,8 @@ class Decoder(nn.Module):
                 x = ops.upsample_concat(encoder_features, x)
             else:
                 x = self.upsample(x, skip=encoder_features)
+            if head_next and isinstance(self.basic_module, ExtResNetBlock):
+                return self.basic_module(x, head_next=True)
             return self.basic_module(x)
 
 

@@ -162,6 +162,11 @@ class _UNetCore(*((_Base,) if _Base is not nn.Module else (_CheckpointCompat, nn
             skips.insert(0, x)
         top = len(self.decoders) - 1  # decoder i writes level top - i
         for i, (dec, skip) in enumerate(zip(self.decoders, skips[1:])):
+            if i == top:
+                # the last decoder's output goes to the head and nowhere else (model.py:205-207), which lets a fused head leave its
+                # gradient unwritten (ops._valu_head_bwd) ... provided nobody else SAW it: a forward hook on that decoder, as above
+                x = dec(skip, x, head_next=not _has_forward_hooks(dec))
+                continue
             x = dec(skip, x)
             if 1 <= top - i <= k:
                 x = tap(top - i, x)
