@@ -16,7 +16,12 @@ small shape only.  Forms: "gn" (every activation x residual x affine), "bn" (tra
 "double" (DoubleConv 'gcr', 'cge', 'cbe': the second convolution's data gradient takes the first backward pass of the norm in front
 of it), "block" (ExtResNetBlock alone), "encoder" (two ExtResNetBlock levels joined by max / average pooling, 1, 3 and 16 input
 channels), "net" (ResidualUNet3D and UNet3D 'gcr', 1 and 3 input channels, small shape), "upcat" (upsample_concat(want_stats=True)
-into a GroupNorm).  The last line holds ops.GN3_COUNT and block.C1GN_COUNT: that the fused forms really ran, equally on both sides.
+into a GroupNorm), "head" (ExtResNetBlock(32) -> ops.head_dice / head_ce / head_dice_ce, 2 to 4 classes, 16-bit storage, the block told
+that the head is its sole consumer: the GroupNorm-3 apply pass rebuilds the head's feature gradient; N = 2 at (8, 8, 16), whole
+trips, and (5, 7, 9), 315 voxels: rows with five voxels, a last trip with one), "pool" (ops.pool2 and ops.skip_pool2 alone, max and
+average, C in {8, 16, 24}, small shape: without and with the skip gradient, behind a 'gcr' DoubleConv whose ReLU mask the join folds
+in, with the skip gradient as the leading channels of a concatenation's gradient; max pooling also on inputs with ties and with NaNs
+inside windows).  The last line holds ops.GN3_COUNT and block.C1GN_COUNT: that the fused forms really ran, equally on both sides.
 Usage: python tools/norm_digest.py [forms, default all] > digest.jsonl"""
 import hashlib
 import json
@@ -44,7 +49,8 @@ SMALL, ODD = (3, (12, 10, 6)), (2, (24, 20, 21))
 MODES = ("fp32", "bf16", "fp16")
 CG = ((16, 8), (24, 8), (12, 4), (512, 8), (1024, 8))
 FULL = os.environ.get("DIGEST_FULL", "0") == "1"
-FORMS = (sys.argv[1] if len(sys.argv) > 1 else "gn,bn,double,block,encoder,net,upcat").split(",")
+FORMS = (sys.argv[1] if len(sys.argv) > 1 else "gn,bn,double,block,encoder,net,upcat,head,pool").split(",")
+HALF = ("bf16", "fp16")
 _CACHE = {}
 
 
@@ -206,13 +212,75 @@ def upcat(mode, n, shape, ce, cx, g):
             "dx": digest(x.grad), "dgamma": digest(gamma.grad), "dbeta": digest(beta.grad)}
 
 
+def head_cases():
+    for kind in ("head_dice", "head_ce", "head_dice_ce"):
+        for cout in (2, 3, 4):
+            yield f"head {kind} classes={cout}", ((2, (8, 8, 16)), (2, (5, 7, 9))), (kind, cout)
+
+
+def head(mode, n, shape, kind, cout):
+    blk = O.keyed_init_(HC.ExtResNetBlock(32, 32)).to(DEV)
+    conv = O.keyed_init_(hnn.Conv3d(32, cout, 1, planar_output=True)).to(DEV)
+    x = leaf("x32", n, 32, *shape)
+    lab = (rnd(f"lab{cout}", n, *shape).abs() * 1.5).floor().clamp_(0, cout - 1).to(torch.uint8).to(DEV)
+    wt = torch.tensor([0.05, 1.0, 0.7, 1.3][:cout], device=DEV)
+    out = blk(x, head_next=True)
+    logits, loss = getattr(ops, kind)(out, conv.weight, conv.bias, conv._packed(), lab, wt)
+    (loss * (1024.0 if mode == "fp16" else 1.0)).backward()
+    torch.cuda.synchronize()
+    return {"logits": digest(logits), "loss": digest(loss), "dx": digest(x.grad), **grads(blk), **{"h" + k: v for k, v in grads(conv).items()}}
+
+
+def pool_cases():
+    for pool in ("max", "avg"):
+        for c in (8, 16, 24):
+            for form in ("pool2", "noskip", "skip", "act", "slice", "act_slice"):
+                yield f"pool {form} {pool} C={c}", (SMALL,), (form, pool, c, None)
+    for special in ("tie", "nan"):
+        for c in (8, 16):
+            for form in ("pool2", "skip", "slice"):
+                yield f"pool {form} max C={c} input={special}", (SMALL,), (form, "max", c, special)
+
+
+def pool(mode, n, shape, form, how, c, special):
+    pmode = L.POOL_MAX if how == "max" else L.POOL_AVG
+    v = rnd(f"x{c}", n, c, *shape)
+    if special is not None:
+        v = (v * 2).round() / 2  # half-integers: most windows hold their maximum more than once
+    if special == "nan":
+        v = torch.where(rnd(f"nan{c}", n, c, *shape) > 1.5, torch.full_like(v, float("nan")), v)  # ~7 % of the elements
+    x = ops.to_cl(v.to(DEV).to(mednet_hip.config.act_dtype())).requires_grad_(True)
+    res, front, src = {}, None, x
+    if form.startswith("act"):
+        front = O.keyed_init_(HC.DoubleConv(c, c, encoder=False, order="gcr", num_groups=4 if c == 8 else 8)).to(DEV)
+        src = front(x)
+        res["masked"] = getattr(src, "_mednet_actmask", None) is not None
+    if form == "pool2":
+        outs = [ops.pool2(src, pmode)]
+    else:
+        skip, y = ops.skip_pool2(src, pmode)
+        outs = [y] if form == "noskip" else [skip, y]
+        if form.endswith("slice"):  # the skip gradient arrives as the leading channels of the concatenation's gradient
+            up = leaf("u8", n, 8, *[s // 2 for s in shape])
+            outs = [ops.upsample_concat(skip, up), y]
+    backward(outs, mode)
+    res.update({f"out{i}": digest(o) for i, o in enumerate(outs)})
+    res["dx"] = digest(x.grad)
+    if front is not None:
+        res.update(grads(front))
+    if form.endswith("slice"):
+        res["dup"] = digest(up.grad)
+    return res
+
+
 RUN = {"gn": (gn_cases, gn), "bn": (bn_cases, bn), "double": (double_cases, double), "block": (block_cases, resblock),
-       "encoder": (encoder_cases, encoder), "net": (net_cases, net), "upcat": (upcat_cases, upcat)}
+       "encoder": (encoder_cases, encoder), "net": (net_cases, net), "upcat": (upcat_cases, upcat), "head": (head_cases, head),
+       "pool": (pool_cases, pool)}
 for form in FORMS:
     cases, fn = RUN[form]
     for name, shapes, axes in cases():
         res = {}
-        for mode in MODES:
+        for mode in (HALF if form == "head" else MODES):
             for n, shape in shapes:
                 with mednet_hip.precision(mode):
                     try:

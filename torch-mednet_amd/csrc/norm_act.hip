@@ -150,6 +150,203 @@ __device__ __forceinline__ void column_reduce_lds_free(float* vals, int cols, in
   }
 }
 
+// ---------------------------------------------------------------------------------------------- shared pieces
+// ONE statement of each per-element rule that several kernels below must agree on bit for bit: a fused or lazy kernel equals the
+// launches it replaces because it calls the same function, not because its text was copied.  Everything is inlined.
+
+// a workgroup's voxels [v0, v1) of its sample: chunk blockIdx.x of chunk_vox voxels, the last one ragged
+struct Chunk {
+  size_t v0, v1;
+  __device__ __forceinline__ Chunk(size_t chunk_vox, size_t spatial) {
+    v0 = (size_t)blockIdx.x * chunk_vox;
+    v1 = v0 + chunk_vox < spatial ? v0 + chunk_vox : spatial;
+  }
+};
+
+// the forward affine of VEC channels from coef[n][c] = {a, b}, ch0 = n * c + first channel: z = act(a * x + b (+ res))
+template <int VEC>
+struct PreCoef {
+  float a[VEC], b[VEC];
+  __device__ __forceinline__ void load(const float* coef, size_t ch0) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      a[k] = coef[(ch0 + k) * 2];
+      b[k] = coef[(ch0 + k) * 2 + 1];
+    }
+  }
+};
+// GroupNorm apply row: fmaf(a, x, b) (+ res), activation
+template <int VEC>
+__device__ __forceinline__ void gn_apply_row(const PreCoef<VEC>& k, const F8& xin, const F8& rin, bool res, int act, F8& out) {
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    out.v[j] = fmaf(k.a[j], xin.v[j], k.b[j]);
+    if (res) out.v[j] += rin.v[j];
+  }
+  act_apply_n<VEC>(out.v, act);
+}
+// what a tensor of T holds after a store of v
+template <typename T, int VEC>
+__device__ __forceinline__ void round_to(F8& v) {
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) v.v[k] = (float)(T)v.v[k];
+}
+
+// the backward coefficients of VEC channels from bcoef[n][c] = {k1, k2, k3}
+template <int VEC>
+struct BwdCoef {
+  float k1[VEC], k2[VEC], k3[VEC];
+  __device__ __forceinline__ void load(const float* bcoef, size_t ch0, int k) {
+    const float* o = bcoef + (ch0 + k) * 3;
+    k1[k] = o[0];
+    k2[k] = o[1];
+    k3[k] = o[2];
+  }
+  __device__ __forceinline__ void load(const float* bcoef, size_t ch0) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) load(bcoef, ch0, k);
+  }
+};
+// the closed form dx = k1 * du + k2 * x + k3 of the apply kernels that rebuild their dz: plain fp32 FMAs on converted operands,
+// THEN the store's rounding to T.  Left alone the compiler folds the conversions of the fp16 form into v_fma_mix_f32 /
+// v_fma_mixlo_f16, whose results are not those of v_fma_f32 + v_cvt (measured: about 4 % of the exact fp16 ties of dx then round
+// the other way, a handful of elements per 10^6).  gn_bwd_apply_kernel does NOT call this: it keeps its own unpinned line (with
+// the pins its 16-bit code is other code, and on shared functions it ran slower, profiles/norm_blocks.md).  That the two forms give
+// the same bits is held by tests only -- test_gpu_exact_norm.py, test_gpu_head_lazy.py, tools/norm_digest.py -- not by shared text.
+template <typename T, int VEC>
+__device__ __forceinline__ F8 gn_dx(const BwdCoef<VEC>& c, const F8& du, const F8& xv) {
+  F8 o;
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    float xf = xv.v[k];
+    if (sizeof(T) == 2) asm volatile("" : "+v"(xf));
+    o.v[k] = fmaf(c.k1[k], du.v[k], fmaf(c.k2[k], xf, c.k3[k]));
+    if (sizeof(T) == 2) asm volatile("" : "+v"(o.v[k]));
+  }
+  return o;
+}
+
+// pass 2b: dgamma_c = sum_n sum(du*xhat), dbeta_c = sum_n sum du of channel cc from csum[n][c][2] (fp64 over n)
+__device__ __forceinline__ void gn_param_grad(const float* csum, int n, int c, int cc, float* dgamma, float* dbeta) {
+  double a = 0.0, b = 0.0;
+  for (int i = 0; i < n; ++i) {
+    a += (double)csum[((size_t)i * c + cc) * 2];
+    b += (double)csum[((size_t)i * c + cc) * 2 + 1];
+  }
+  if (dbeta) dbeta[cc] = (float)a;
+  if (dgamma) dgamma[cc] = (float)b;
+}
+// ... of every channel by one workgroup: the first workgroup of an apply kernel when the one-launch form ran (no launch of its own)
+struct GnParamGrad {
+  const float* csum = nullptr;
+  float* dgamma = nullptr;
+  float* dbeta = nullptr;
+  int n = 0;
+};
+__device__ __forceinline__ void gn_param_grads(const GnParamGrad& pg, int c) {
+  for (int cc = threadIdx.x; cc < c; cc += 256) gn_param_grad(pg.csum, pg.n, c, cc, pg.dgamma, pg.dbeta);
+}
+
+// 2x2x2 pooling over a channels-last [n][d][h][w][c] tensor (even extents are the caller's business): a thread owns one pooled
+// voxel (nn, oz, oy, ox) and the VEC channels of piece cc; element i of the pooled tensor's pieces decodes to them.
+template <int VEC>
+struct PoolVoxel {
+  int d, h, w, c, cv;
+  int nn, oz, oy, ox, cc;
+  __device__ __forceinline__ PoolVoxel(int d_, int h_, int w_, int c_) : d(d_), h(h_), w(w_), c(c_), cv(c_ / VEC) {}
+  __device__ __forceinline__ size_t pieces(int n) const { return (size_t)n * (d / 2) * (h / 2) * (w / 2) * cv; }
+  __device__ __forceinline__ size_t row_of(size_t v) {  // pooled voxel -> ox, oy; what is left (nn * od + oz) is returned
+    ox = (int)(v % (w / 2));
+    v /= w / 2;
+    oy = (int)(v % (h / 2));
+    return v / (h / 2);
+  }
+  __device__ __forceinline__ void decode(size_t i) {  // i over all samples
+    cc = (int)(i % cv);
+    const size_t v = row_of(i / cv);
+    oz = (int)(v % (d / 2));
+    nn = (int)(v / (d / 2));
+  }
+  __device__ __forceinline__ bool own(int n, size_t& i) {  // the thread's element of a one-thread-per-piece grid; false: none
+    const size_t total = pieces(n);
+    i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return false;
+    decode(i);
+    return true;
+  }
+  __device__ __forceinline__ void decode_in_sample(size_t i, int n, int piece) {  // i within sample n, piece == i % cv known
+    cc = piece;
+    oz = (int)row_of(i / cv);
+    nn = n;
+  }
+  // channels-last element offset of the thread's piece at window tap t (scan order: z, y, x)
+  __device__ __forceinline__ size_t tap_offset(int t) const {
+    const int iz = 2 * oz + (t >> 2), iy = 2 * oy + ((t >> 1) & 1), ix = 2 * ox + (t & 1);
+    return ((((size_t)nn * d + iz) * h + iy) * w + ix) * c + (size_t)cc * VEC;
+  }
+};
+// window arg-max: first maximum in scan order, NaN propagates (ATen)
+template <int VEC>
+struct WindowArgmax {
+  float best[VEC];
+  int arg[VEC];
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      best[k] = -INFINITY;
+      arg[k] = 0;
+    }
+  }
+  __device__ __forceinline__ void take(const F8& xv, int t) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      if (xv.v[k] > best[k] || xv.v[k] != xv.v[k]) {
+        best[k] = xv.v[k];
+        arg[k] = t;
+      }
+    }
+  }
+};
+// window maximum (the same rule) or mean
+template <int VEC>
+struct WindowReduce {
+  F8 best;
+  __device__ __forceinline__ WindowReduce(int mode) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) best.v[k] = mode == MEDNET_POOL_MAX ? -INFINITY : 0.f;
+  }
+  __device__ __forceinline__ void take(const F8& xv, int mode) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      if (mode == MEDNET_POOL_MAX) best.v[k] = (xv.v[k] > best.v[k] || xv.v[k] != xv.v[k]) ? xv.v[k] : best.v[k];
+      else best.v[k] += xv.v[k];
+    }
+  }
+  __device__ __forceinline__ const F8& finish(int mode) {
+    if (mode == MEDNET_POOL_AVG) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) best.v[k] *= 0.125f;
+    }
+    return best;
+  }
+};
+// pooling gradient at tap t of the window: the pooled gradient g where the arg-max sits (max) or an eighth of it (mean), plus the
+// other consumer's gradient of the same element (add != nullptr: the decoder's skip join), rounded to T: the value a store leaves,
+// for the kernel that goes on computing with it and for the one that rebuilds the row without the store
+template <typename T, int VEC>
+__device__ __forceinline__ F8 pool_grad_row(const F8& g, const int* arg, int t, int mode, const T* add, size_t ai) {
+  F8 o;
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) o.v[k] = mode == MEDNET_POOL_MAX ? (arg[k] == t ? g.v[k] : 0.f) : 0.125f * g.v[k];
+  if (add) {
+    const F8 a = VecIO<T, VEC>::load(add, ai);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] += a.v[k];
+  }
+  round_to<T, VEC>(o);
+  return o;
+}
+
 // ---------------------------------------------------------------------------------------------- GN statistics
 // The stand-alone statistics pass is PIVOTED: a variance taken as sum x^2 / N - mean^2 from fp32 sums loses (mean / std)^2 ulps
 // (an image at -1000 +- 5: everything).  The pivot of a statistics unit -- a GroupNorm group of a sample (cg channels), a
@@ -169,8 +366,8 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
   __shared__ float lds[256 * 2 * VEC];
   const Cols<VEC> L(c);
   const int n = blockIdx.y;
-  const size_t v0 = (size_t)blockIdx.x * chunk_vox;
-  const size_t v1 = v0 + chunk_vox < spatial ? v0 + chunk_vox : spatial;
+  const Chunk ch(chunk_vox, spatial);
+  const size_t v1 = ch.v1;
   float acc[2 * VEC];
 #pragma unroll
   for (int k = 0; k < 2 * VEC; ++k) acc[k] = 0.f;
@@ -180,7 +377,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
     float piv[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) piv[k] = ld(first, (size_t)((L.col * VEC + k) / cg * cg));
-    size_t v = v0 + L.row;
+    size_t v = ch.v0 + L.row;
     for (; v + 3 * (size_t)L.rows < v1; v += 4 * (size_t)L.rows) {  // 4 independent 16-byte loads in flight per lane
       F8 xv[4];
 #pragma unroll
@@ -350,24 +547,12 @@ __global__ __launch_bounds__(256) void gn_act_fwd_kernel(const TX* __restrict__ 
   const Cols<VEC> L(c);
   if (!L.active) return;
   const int n = blockIdx.y;
-  const size_t v0 = (size_t)blockIdx.x * chunk_vox;
-  const size_t v1 = v0 + chunk_vox < spatial ? v0 + chunk_vox : spatial;
-  float a[VEC], b[VEC];
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    a[k] = coef[((size_t)n * c + L.col * VEC + k) * 2];
-    b[k] = coef[((size_t)n * c + L.col * VEC + k) * 2 + 1];
-  }
+  const Chunk ch(chunk_vox, spatial);
+  const size_t v1 = ch.v1;
+  PreCoef<VEC> k;
+  k.load(coef, (size_t)n * c + L.col * VEC);
   const size_t off = (size_t)n * spatial * c + (size_t)L.col * VEC;
-  auto one = [&](const F8& xin, const F8& rin, F8& out) {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      out.v[k] = fmaf(a[k], xin.v[k], b[k]);
-      if (res) out.v[k] += rin.v[k];
-    }
-    act_apply_n<VEC>(out.v, act);
-  };
-  size_t v = v0 + L.row;
+  size_t v = ch.v0 + L.row;
   const size_t R = (size_t)L.rows;
   for (; v + 3 * R < v1; v += 4 * R) {  // four voxels per trip: 4-8 loads in flight per lane
     size_t i[4];
@@ -381,7 +566,7 @@ __global__ __launch_bounds__(256) void gn_act_fwd_kernel(const TX* __restrict__ 
       for (int u = 0; u < 4; ++u) ri[u] = VecIO<TZ, VEC>::load(res, i[u]);
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) one(xi[u], ri[u], zo[u]);
+    for (int u = 0; u < 4; ++u) gn_apply_row<VEC>(k, xi[u], ri[u], res != nullptr, act, zo[u]);
 #pragma unroll
     for (int u = 0; u < 4; ++u) VecIO<TZ, VEC>::store(z, i[u], zo[u]);
   }
@@ -390,7 +575,7 @@ __global__ __launch_bounds__(256) void gn_act_fwd_kernel(const TX* __restrict__ 
     const F8 xv = VecIO<TX, VEC>::load(x, i);
     F8 rv, zv;
     if (res) rv = VecIO<TZ, VEC>::load(res, i);
-    one(xv, rv, zv);
+    gn_apply_row<VEC>(k, xv, rv, res != nullptr, act, zv);
     VecIO<TZ, VEC>::store(z, i, zv);
   }
 }
@@ -407,8 +592,8 @@ __global__ __launch_bounds__(256, GN_WAVES) void gn_bwd_partial_kernel(const T* 
   __shared__ float lds[256 * 2 * VEC];
   const Cols<VEC> L(c);
   const int n = blockIdx.y;
-  const size_t v0 = (size_t)blockIdx.x * chunk_vox;
-  const size_t v1 = v0 + chunk_vox < spatial ? v0 + chunk_vox : spatial;
+  const Chunk ch(chunk_vox, spatial);
+  const size_t v0 = ch.v0, v1 = ch.v1;
   float acc[2 * VEC];
 #pragma unroll
   for (int k = 0; k < 2 * VEC; ++k) acc[k] = 0.f;
@@ -575,25 +760,11 @@ static bool gn_bwd_one_launch(int c, int groups) {
   const int cg = c / groups;
   return cg >= 1 && cg <= 256 && 256 % cg == 0 && tuning_option("gn_bwd_one_launch", 1);
 }
-// the parameter gradients of pass 2b, computed by the first workgroup of the apply kernel when the one-launch form ran
-struct GnParamGrad {
-  const float* csum = nullptr;
-  float* dgamma = nullptr;
-  float* dbeta = nullptr;
-  int n = 0;
-};
-// pass 2b: dgamma_c = sum_n sum(du*xhat), dbeta_c = sum_n sum du
+// pass 2b in a launch of its own
 __global__ __launch_bounds__(256) void gn_bwd_params_kernel(const float* __restrict__ csum, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta, int n, int c) {
   const int cc = blockIdx.x * 256 + threadIdx.x;
-  if (cc >= c) return;
-  double a = 0.0, b = 0.0;
-  for (int i = 0; i < n; ++i) {
-    a += (double)csum[((size_t)i * c + cc) * 2];
-    b += (double)csum[((size_t)i * c + cc) * 2 + 1];
-  }
-  if (dbeta) dbeta[cc] = (float)a;
-  if (dgamma) dgamma[cc] = (float)b;
+  if (cc < c) gn_param_grad(csum, n, c, cc, dgamma, dbeta);
 }
 // pass 3: apply
 template <typename T, int VEC>
@@ -603,22 +774,12 @@ __global__ __launch_bounds__(256, GN_WAVES) void gn_bwd_apply_kernel(const T* __
                                                            const float* __restrict__ bcoef, T* __restrict__ dx,
                                                            T* __restrict__ dres, size_t spatial, int c, int act,
                                                            size_t chunk_vox, int in_act, GnParamGrad pg) {
-  if (pg.csum && blockIdx.x == 0 && blockIdx.y == 0) {  // pass 2b (gn_bwd_params_kernel) without a launch of its own
-    for (int cc = threadIdx.x; cc < c; cc += 256) {
-      double a = 0.0, b = 0.0;
-      for (int i = 0; i < pg.n; ++i) {
-        a += (double)pg.csum[((size_t)i * c + cc) * 2];
-        b += (double)pg.csum[((size_t)i * c + cc) * 2 + 1];
-      }
-      if (pg.dbeta) pg.dbeta[cc] = (float)a;
-      if (pg.dgamma) pg.dgamma[cc] = (float)b;
-    }
-  }
+  if (pg.csum && blockIdx.x == 0 && blockIdx.y == 0) gn_param_grads(pg, c);
   const Cols<VEC> L(c);
   if (!L.active) return;
   const int n = blockIdx.y;
-  const size_t v0 = (size_t)blockIdx.x * chunk_vox;
-  const size_t v1 = v0 + chunk_vox < spatial ? v0 + chunk_vox : spatial;
+  const Chunk ch(chunk_vox, spatial);
+  const size_t v0 = ch.v0, v1 = ch.v1;
   float k1[VEC], k2[VEC], k3[VEC], ca[VEC], cb[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
@@ -716,168 +877,87 @@ __global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void pool2_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int n, int d, int h,
                                                         int w, int c, int mode) {
-  const int od = d / 2, oh = h / 2, ow = w / 2, cv = c / VEC;
-  const size_t total = (size_t)n * od * oh * ow * cv;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int cc = (int)(i % cv);
-  size_t v = i / cv;
-  const int ox = (int)(v % ow);
-  v /= ow;
-  const int oy = (int)(v % oh);
-  v /= oh;
-  const int oz = (int)(v % od);
-  const int nn = (int)(v / od);
-  F8 best;
+  PoolVoxel<VEC> P(d, h, w, c);
+  size_t i;
+  if (!P.own(n, i)) return;
+  WindowReduce<VEC> red(mode);
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) best.v[k] = mode == MEDNET_POOL_MAX ? -INFINITY : 0.f;
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int iz = 2 * oz + (t >> 2), iy = 2 * oy + ((t >> 1) & 1), ix = 2 * ox + (t & 1);
-    const size_t src = ((((size_t)nn * d + iz) * h + iy) * w + ix) * c + (size_t)cc * VEC;
-    const F8 xv = VecIO<T, VEC>::load(x, src);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      if (mode == MEDNET_POOL_MAX) best.v[k] = (xv.v[k] > best.v[k] || xv.v[k] != xv.v[k]) ? xv.v[k] : best.v[k];
-      else best.v[k] += xv.v[k];
-    }
-  }
-  if (mode == MEDNET_POOL_AVG) {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) best.v[k] *= 0.125f;
-  }
-  VecIO<T, VEC>::store(y, i * VEC, best);
+  for (int t = 0; t < 8; ++t) red.take(VecIO<T, VEC>::load(x, P.tap_offset(t)), mode);
+  VecIO<T, VEC>::store(y, i * VEC, red.finish(mode));
 }
 
 // GroupNorm apply (+ residual, + activation) of an encoder block's last layer AND the 2x2x2 pooling that consumes the block's
 // output (components.py:177-178 -> :222-224), in one pass: a thread owns one POOLED voxel and 8 channels, normalises the 8 voxels of
 // its window (reads y and the residual, writes the block output z) and writes their maximum / mean to the pooled tensor -- the
-// stand-alone pooling pass and its re-read of z are gone.  z is computed and rounded exactly as gn_act_fwd_kernel
-// does, the pooling runs on the ROUNDED values in pool2_fwd_kernel's scan order: both outputs are bit-identical to the two
-// launches.  Even d, h, w.
+// stand-alone pooling pass and its re-read of z are gone.  z is gn_apply_row's, as in gn_act_fwd_kernel, and the pooling
+// is pool2_fwd_kernel's WindowReduce on the ROUNDED values: both outputs are bit-identical to the two launches.  Even d, h, w.
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void gn_act_pool_fwd_kernel(const T* __restrict__ x, const float* __restrict__ coef,
                                                               const T* __restrict__ res, T* __restrict__ z, T* __restrict__ pooled,
                                                               int n, int d, int h, int w, int c, int act, int mode) {
-  const int od = d / 2, oh = h / 2, ow = w / 2, cv = c / VEC;
-  const size_t total = (size_t)n * od * oh * ow * cv;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int cc = (int)(i % cv);
-  size_t v = i / cv;
-  const int ox = (int)(v % ow);
-  v /= ow;
-  const int oy = (int)(v % oh);
-  v /= oh;
-  const int oz = (int)(v % od);
-  const int nn = (int)(v / od);
-  float a[VEC], b[VEC];
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    a[k] = coef[((size_t)nn * c + cc * VEC + k) * 2];
-    b[k] = coef[((size_t)nn * c + cc * VEC + k) * 2 + 1];
-  }
+  PoolVoxel<VEC> P(d, h, w, c);
+  size_t i;
+  if (!P.own(n, i)) return;
+  PreCoef<VEC> k;
+  k.load(coef, (size_t)P.nn * c + P.cc * VEC);
   size_t src[8];
   F8 xv[8], rv[8];
 #pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int iz = 2 * oz + (t >> 2), iy = 2 * oy + ((t >> 1) & 1), ix = 2 * ox + (t & 1);
-    src[t] = ((((size_t)nn * d + iz) * h + iy) * w + ix) * c + (size_t)cc * VEC;
-  }
+  for (int t = 0; t < 8; ++t) src[t] = P.tap_offset(t);
 #pragma unroll
   for (int t = 0; t < 8; ++t) xv[t] = VecIO<T, VEC>::load(x, src[t]);
   if (res) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) rv[t] = VecIO<T, VEC>::load(res, src[t]);
   }
-  F8 best;
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) best.v[k] = mode == MEDNET_POOL_MAX ? -INFINITY : 0.f;
+  WindowReduce<VEC> red(mode);
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
     F8 o;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      o.v[k] = fmaf(a[k], xv[t].v[k], b[k]);
-      if (res) o.v[k] += rv[t].v[k];
-    }
-    act_apply_n<VEC>(o.v, act);
+    gn_apply_row<VEC>(k, xv[t], rv[t], res != nullptr, act, o);
     VecIO<T, VEC>::store(z, src[t], o);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      const float s = (float)(T)o.v[k];  // what the pooling pass would read back
-      if (mode == MEDNET_POOL_MAX) best.v[k] = (s > best.v[k] || s != s) ? s : best.v[k];
-      else best.v[k] += s;
-    }
+    round_to<T, VEC>(o);  // what the pooling pass would read back
+    red.take(o, mode);
   }
-  if (mode == MEDNET_POOL_AVG) {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) best.v[k] *= 0.125f;
-  }
-  VecIO<T, VEC>::store(pooled, i * VEC, best);
+  VecIO<T, VEC>::store(pooled, i * VEC, red.finish(mode));
 }
 
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void pool2_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                         const T* __restrict__ add, T* __restrict__ dx, int n, int d,
                                                         int h, int w, int c, int mode, int in_act, int add_c) {
-  const int od = d / 2, oh = h / 2, ow = w / 2, cv = c / VEC;
-  const size_t total = (size_t)n * od * oh * ow * cv;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int cc = (int)(i % cv);
-  size_t v = i / cv;
-  const int ox = (int)(v % ow);
-  v /= ow;
-  const int oy = (int)(v % oh);
-  v /= oh;
-  const int oz = (int)(v % od);
-  const int nn = (int)(v / od);
+  PoolVoxel<VEC> P(d, h, w, c);
+  size_t i;
+  if (!P.own(n, i)) return;
   const F8 g = VecIO<T, VEC>::load(dy, i * VEC);
-  int arg[VEC];
+  WindowArgmax<VEC> am;
   if (mode == MEDNET_POOL_MAX) {
-    float best[VEC];
+    am.init();
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      best[k] = -INFINITY;
-      arg[k] = 0;
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int iz = 2 * oz + (t >> 2), iy = 2 * oy + ((t >> 1) & 1), ix = 2 * ox + (t & 1);
-      const size_t src = ((((size_t)nn * d + iz) * h + iy) * w + ix) * c + (size_t)cc * VEC;
-      const F8 xv = VecIO<T, VEC>::load(x, src);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        if (xv.v[k] > best[k] || xv.v[k] != xv.v[k]) {  // first maximum in scan order, NaN propagates (ATen)
-          best[k] = xv.v[k];
-          arg[k] = t;
-        }
-      }
-    }
+    for (int t = 0; t < 8; ++t) am.take(VecIO<T, VEC>::load(x, P.tap_offset(t)), t);
   }
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
-    const int iz = 2 * oz + (t >> 2), iy = 2 * oy + ((t >> 1) & 1), ix = 2 * ox + (t & 1);
-    const size_t dst = ((((size_t)nn * d + iz) * h + iy) * w + ix) * c + (size_t)cc * VEC;
+    const size_t dst = P.tap_offset(t);
+    // the row of pool_grad_row, written out: through that function this kernel's <float, 8> instance took 73 registers instead of
+    // 70 and lost a wave of occupancy; its skip gradient is indexed differently and it rounds only under in_act anyway
+    // (add_c: channels per voxel of the tensor `add` is a channel slice of -- the gradient of UNet3D's concatenation, read where it
+    //  lies instead of being copied out first)
+    // in_act: x is the OUTPUT of a fused conv -> activation layer (UNet3D's 'gcr' blocks, components.py:57-63): its derivative is
+    // folded in here, on the ROUNDED value a stand-alone join would have stored, and the conv layer's backward skips its activation
+    // pass (ops.ActMaskHook) -- 3 passes over the level's output less
     F8 o;
 #pragma unroll
     for (int k = 0; k < VEC; ++k)
-      o.v[k] = mode == MEDNET_POOL_MAX ? (arg[k] == t ? g.v[k] : 0.f) : 0.125f * g.v[k];
-    if (add) {  // the other consumer's gradient of the same tensor (the decoder's skip join): one pass instead of an add kernel
-      // (add_c: channels per voxel of the tensor `add` is a channel slice of -- the gradient of UNet3D's concatenation, read where
-      //  it lies instead of being copied out first)
+      o.v[k] = mode == MEDNET_POOL_MAX ? (am.arg[k] == t ? g.v[k] : 0.f) : 0.125f * g.v[k];
+    if (add) {
       const F8 a = VecIO<T, VEC>::load(add, (dst / c) * add_c + dst % c);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) o.v[k] += a.v[k];
     }
-    // x is the OUTPUT of a fused conv -> activation layer (UNet3D's 'gcr' blocks, components.py:57-63): its derivative is folded in
-    // here, on the value a stand-alone join would have stored, and the conv layer's backward skips its activation pass
-    // (ops.ActMaskHook) -- 3 passes over the level's output less
     if (in_act != MEDNET_ACT_NONE) {
       const F8 xv = VecIO<T, VEC>::load(x, dst);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) o.v[k] = (float)(T)o.v[k];
+      round_to<T, VEC>(o);
       act_grad_n<VEC>(o.v, xv.v, in_act);
     }
     VecIO<T, VEC>::store(dx, dst, o);
@@ -896,9 +976,9 @@ __global__ __launch_bounds__(256) void pool2_bwd_gn_kernel(const T* __restrict__
                                                            const T* __restrict__ gy, float* __restrict__ partial, int d,
                                                            int h, int w, int c, int mode, int act) {
   constexpr int VEC = 8;
-  const int od = d / 2, oh = h / 2, ow = w / 2, cv = c / VEC;
-  const size_t per = (size_t)od * oh * ow * cv;
-  const int nn = blockIdx.y;
+  PoolVoxel<VEC> P(d, h, w, c);
+  const size_t per = P.pieces(1);
+  const int nn = blockIdx.y, cv = P.cv;
   const int cc = (int)(threadIdx.x % cv);  // (256 % cv == 0: a thread keeps its channels)
   float acc[2 * VEC];
 #pragma unroll
@@ -906,47 +986,20 @@ __global__ __launch_bounds__(256) void pool2_bwd_gn_kernel(const T* __restrict__
   for (int it = 0; it < POOL_GN_PV; ++it) {
     const size_t i = ((size_t)blockIdx.x * POOL_GN_PV + it) * 256 + threadIdx.x;
     if (i >= per) break;
-    size_t v = i / cv;
-    const int ox = (int)(v % ow);
-    v /= ow;
-    const int oy = (int)(v % oh);
-    const int oz = (int)(v / oh);
+    P.decode_in_sample(i, nn, cc);
     const F8 g = VecIO<T, VEC>::load(dy, ((size_t)nn * per + i) * VEC);
     F8 xv[8];
-    int arg[VEC];
-    float best[VEC];
+    WindowArgmax<VEC> am;
+    am.init();
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      best[k] = -INFINITY;
-      arg[k] = 0;
+    for (int t = 0; t < 8; ++t) {
+      xv[t] = VecIO<T, VEC>::load(x, P.tap_offset(t));
+      am.take(xv[t], t);
     }
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      const int iz = 2 * oz + (t >> 2), iy = 2 * oy + ((t >> 1) & 1), ix = 2 * ox + (t & 1);
-      const size_t src = ((((size_t)nn * d + iz) * h + iy) * w + ix) * c + (size_t)cc * VEC;
-      xv[t] = VecIO<T, VEC>::load(x, src);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        if (xv[t].v[k] > best[k] || xv[t].v[k] != xv[t].v[k]) {  // first maximum in scan order, NaN propagates (ATen)
-          best[k] = xv[t].v[k];
-          arg[k] = t;
-        }
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int iz = 2 * oz + (t >> 2), iy = 2 * oy + ((t >> 1) & 1), ix = 2 * ox + (t & 1);
-      const size_t dst = ((((size_t)nn * d + iz) * h + iy) * w + ix) * c + (size_t)cc * VEC;
-      F8 o;
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) o.v[k] = mode == MEDNET_POOL_MAX ? (arg[k] == t ? g.v[k] : 0.f) : 0.125f * g.v[k];
-      if (add) {
-        const F8 a = VecIO<T, VEC>::load(add, dst);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) o.v[k] += a.v[k];
-      }
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) o.v[k] = (float)(T)o.v[k];  // the stored value is what GroupNorm-3's second pass reads
+      const size_t dst = P.tap_offset(t);
+      F8 o = pool_grad_row<T, VEC>(g, am.arg, t, mode, add, dst);  // (rounded: GroupNorm-3's second pass reads the stored value)
       if (dx) VecIO<T, VEC>::store(dx, dst, o);  // (dx == nullptr: statistics only, gn_bwd_apply_pool_kernel rebuilds the rows)
       const F8 yv = VecIO<T, VEC>::load(gy, dst);
       act_grad_n<VEC>(o.v, xv[t].v, act);
@@ -963,8 +1016,8 @@ __global__ __launch_bounds__(256) void pool2_bwd_gn_kernel(const T* __restrict__
 
 // GroupNorm-3's backward apply pass of an encoder block whose output gradient is the pooling backward + skip join above, WITHOUT
 // that gradient in memory: a thread owns one pooled voxel x VEC channels, rebuilds the 8 gradient rows of its window from the
-// pooled gradient, the arg-max of the block output (which it reads anyway for act') and the skip gradient -- rounded to T exactly
-// as pool2_bwd_gn_kernel rounds what it would have stored -- and applies gn_bwd_apply_kernel's closed form:
+// pooled gradient, the arg-max of the block output (which it reads anyway for act') and the skip gradient -- pool_grad_row, the
+// rows pool2_bwd_gn_kernel stores and sums -- and applies the closed form of the apply pass (gn_dx):
 //   du = dz * act'(out);  dy3 = k1 * du + k2 * y3 + k3;  dres = du.
 // The 537 MB gradient tensor of a 32-channel 128^3 batch is neither written (pooling backward) nor read (this pass).
 template <typename T, int VEC>
@@ -973,87 +1026,30 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_pool_kernel(const T* __restr
                                                                 const float* __restrict__ bcoef, T* __restrict__ dx,
                                                                 T* __restrict__ dres, int n, int d, int h, int w, int c, int act,
                                                                 int mode, GnParamGrad pg) {
-  if (pg.csum && blockIdx.x == 0) {  // pass 2b (gn_bwd_params_kernel) without a launch of its own
-    for (int cc = threadIdx.x; cc < c; cc += 256) {
-      double a = 0.0, b = 0.0;
-      for (int i = 0; i < pg.n; ++i) {
-        a += (double)pg.csum[((size_t)i * c + cc) * 2];
-        b += (double)pg.csum[((size_t)i * c + cc) * 2 + 1];
-      }
-      if (pg.dbeta) pg.dbeta[cc] = (float)a;
-      if (pg.dgamma) pg.dgamma[cc] = (float)b;
-    }
-  }
-  const int od = d / 2, oh = h / 2, ow = w / 2, cv = c / VEC;
-  const size_t total = (size_t)n * od * oh * ow * cv;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int cc = (int)(i % cv);
-  size_t v = i / cv;
-  const int ox = (int)(v % ow);
-  v /= ow;
-  const int oy = (int)(v % oh);
-  v /= oh;
-  const int oz = (int)(v % od);
-  const int nn = (int)(v / od);
-  float k1[VEC], k2[VEC], k3[VEC];
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    const float* o = bcoef + ((size_t)nn * c + cc * VEC + k) * 3;
-    k1[k] = o[0];
-    k2[k] = o[1];
-    k3[k] = o[2];
-  }
+  if (pg.csum && blockIdx.x == 0) gn_param_grads(pg, c);
+  PoolVoxel<VEC> P(d, h, w, c);
+  size_t i;
+  if (!P.own(n, i)) return;
+  BwdCoef<VEC> k;
+  k.load(bcoef, (size_t)P.nn * c + P.cc * VEC);
   const F8 g = VecIO<T, VEC>::load(dyp, i * VEC);
   size_t src[8];
   F8 zv[8];
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
-    const int iz = 2 * oz + (t >> 2), iy = 2 * oy + ((t >> 1) & 1), ix = 2 * ox + (t & 1);
-    src[t] = ((((size_t)nn * d + iz) * h + iy) * w + ix) * c + (size_t)cc * VEC;
+    src[t] = P.tap_offset(t);
     zv[t] = VecIO<T, VEC>::load(z, src[t]);
   }
-  int arg[VEC];
-  float best[VEC];
+  WindowArgmax<VEC> am;
+  am.init();
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    best[k] = -INFINITY;
-    arg[k] = 0;
-  }
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-#pragma unroll
-    for (int k = 0; k < VEC; ++k)
-      if (zv[t].v[k] > best[k] || zv[t].v[k] != zv[t].v[k]) {  // first maximum in scan order, NaN propagates (ATen)
-        best[k] = zv[t].v[k];
-        arg[k] = t;
-      }
+  for (int t = 0; t < 8; ++t) am.take(zv[t], t);
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
     const F8 xv = VecIO<T, VEC>::load(x, src[t]);
-    F8 g1;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) g1.v[k] = mode == MEDNET_POOL_MAX ? (arg[k] == t ? g.v[k] : 0.f) : 0.125f * g.v[k];
-    if (add) {
-      const F8 a = VecIO<T, VEC>::load(add, src[t]);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) g1.v[k] += a.v[k];
-    }
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) g1.v[k] = (float)(T)g1.v[k];  // the value pool2_bwd_gn_kernel would have stored (and summed)
+    F8 g1 = pool_grad_row<T, VEC>(g, am.arg, t, mode, add, src[t]);  // rounded: the row the pooling backward would have stored
     act_grad_n<VEC>(g1.v, zv[t].v, act);
-    F8 o;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      // plain fp32 FMAs on converted operands, THEN the rounding to T, as gn_bwd_apply_kernel has them: left alone the compiler
-      // folds the conversions of the fp16 form into v_fma_mix_f32 / v_fma_mixlo_f16, whose results are not those of v_fma_f32 +
-      // v_cvt (measured: about 4 % of the exact fp16 ties of dy3 then round the other way, a handful of elements per 10^6)
-      float xf = xv.v[k];
-      if (sizeof(T) == 2) asm volatile("" : "+v"(xf));
-      o.v[k] = fmaf(k1[k], g1.v[k], fmaf(k2[k], xf, k3[k]));
-      if (sizeof(T) == 2) asm volatile("" : "+v"(o.v[k]));
-    }
-    VecIO<T, VEC>::store(dx, src[t], o);
+    VecIO<T, VEC>::store(dx, src[t], gn_dx<T, VEC>(k, g1, xv));
     VecIO<T, VEC>::store(dres, src[t], g1);
   }
 }
@@ -1062,7 +1058,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_pool_kernel(const T* __restr
 // 16-bit storage) WITHOUT the head's feature gradient dz in memory: head_dice_bwd_kernel<.., STORE = false> took the sums and wrote
 // no dz; here the four lanes that own a voxel's row rebuild it from the voxel's logits, its label and the 4 x 32 head weights --
 // class_logit_grad_quad (one closed form per voxel, shared by the quad) and head_dz_row, the text head_dice_bwd_kernel runs, so the
-// row is the one it would have stored, bit for bit -- and from there on this is gn_bwd_apply_kernel<T, 8> of a residual layer:
+// row is the one it would have stored, bit for bit -- and from there on this is the apply pass of a residual layer (gn_dx):
 //   du = dz * act'(out);  dy3 = k1 * du + k2 * y3 + k3;  dres = du.
 // The 537 MB gradient tensor of a 32-channel 128^3 batch is neither written (head backward) nor read (this pass).
 // Thread layout and chunking are gn_bwd_apply_kernel's at C = 32: lane % 4 = the 8-channel column, 64 voxel rows per workgroup, two
@@ -1078,27 +1074,15 @@ __global__ __launch_bounds__(256, GN_WAVES) void gn_bwd_apply_head_kernel(const 
                                                                           GnParamGrad pg) {
   constexpr int C = 32, VEC = 8, MAXC = 4, ROWS = 256 / (C / VEC);
   static_assert(sizeof(T) == 2, "16-bit storage");
-  if (pg.csum && blockIdx.x == 0 && blockIdx.y == 0) {  // pass 2b (gn_bwd_params_kernel) without a launch of its own
-    for (int cc = threadIdx.x; cc < C; cc += 256) {
-      double a = 0.0, b = 0.0;
-      for (int i = 0; i < pg.n; ++i) {
-        a += (double)pg.csum[((size_t)i * C + cc) * 2];
-        b += (double)pg.csum[((size_t)i * C + cc) * 2 + 1];
-      }
-      if (pg.dbeta) pg.dbeta[cc] = (float)a;
-      if (pg.dgamma) pg.dgamma[cc] = (float)b;
-    }
-  }
+  if (pg.csum && blockIdx.x == 0 && blockIdx.y == 0) gn_param_grads(pg, C);
   const int n = blockIdx.y, col = threadIdx.x & 3, row = threadIdx.x >> 2;
-  const size_t v0 = (size_t)blockIdx.x * chunk_vox;
-  const size_t v1 = v0 + chunk_vox < spatial ? v0 + chunk_vox : spatial;
-  float k1[VEC], k2[VEC], k3[VEC], wreg[MAXC][VEC];
+  const Chunk ch(chunk_vox, spatial);
+  const size_t v1 = ch.v1;
+  BwdCoef<VEC> kc;
+  float wreg[MAXC][VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
-    const float* o = bcoef + ((size_t)n * C + col * VEC + k) * 3;
-    k1[k] = o[0];
-    k2[k] = o[1];
-    k3[k] = o[2];
+    kc.load(bcoef, (size_t)n * C + col * VEC, k);
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) wreg[i][k] = i < m ? Pb[(size_t)i * C + col * VEC + k] : 0.f;
   }
@@ -1116,16 +1100,7 @@ __global__ __launch_bounds__(256, GN_WAVES) void gn_bwd_apply_head_kernel(const 
   const size_t off = (size_t)n * spatial * C + (size_t)col * VEC;
   auto finish = [&](size_t i, F8& g1, const F8& zv, const F8& xv) {
     act_grad_n<VEC>(g1.v, zv.v, act);
-    F8 o;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      // plain fp32 FMAs on converted operands, THEN the rounding to T, as gn_bwd_apply_kernel has them (see gn_bwd_apply_pool_kernel)
-      float xf = xv.v[k];
-      asm volatile("" : "+v"(xf));
-      o.v[k] = fmaf(k1[k], g1.v[k], fmaf(k2[k], xf, k3[k]));
-      asm volatile("" : "+v"(o.v[k]));
-    }
-    VecIO<T, VEC>::store(dx, i, o);
+    VecIO<T, VEC>::store(dx, i, gn_dx<T, VEC>(kc, g1, xv));
     VecIO<T, VEC>::store(dres, i, g1);
   };
   // voxels a and b of the quad (b == a, and nothing stored for it, when the chunk has no second one left)
@@ -1149,7 +1124,7 @@ __global__ __launch_bounds__(256, GN_WAVES) void gn_bwd_apply_head_kernel(const 
     finish(ia, ga, zva, xva);
     if (hb) finish(ib, gb, zvb, xvb);
   };
-  size_t v = v0 + row;
+  size_t v = ch.v0 + row;
   for (; v + (size_t)ROWS < v1; v += 2 * (size_t)ROWS) two(v, v + ROWS, true);
   for (; v < v1; v += ROWS) two(v, v, false);
 }
@@ -1199,8 +1174,8 @@ __global__ __launch_bounds__(256) void upcat_stats_fwd_kernel(const T* __restric
   const Cols<VEC> L(ct);
   const int n = blockIdx.y;
   const size_t spatial = (size_t)d * h * w;
-  const size_t v0 = (size_t)blockIdx.x * chunk_vox;
-  const size_t v1 = v0 + chunk_vox < spatial ? v0 + chunk_vox : spatial;
+  const Chunk ch(chunk_vox, spatial);
+  const size_t v1 = ch.v1;
   float acc[2 * VEC];
 #pragma unroll
   for (int k = 0; k < 2 * VEC; ++k) acc[k] = 0.f;
@@ -1216,7 +1191,7 @@ __global__ __launch_bounds__(256) void upcat_stats_fwd_kernel(const T* __restric
       const int oy = (int)(r % h), oz = (int)(r / h);
       return ((size_t)(nearest_src(oz, xd, d) * xh + nearest_src(oy, xh, h)) * xw + nearest_src(ox, xw, w)) * cx;
     };
-    size_t v = v0 + L.row;
+    size_t v = ch.v0 + L.row;
     for (; v + 3 * (size_t)L.rows < v1; v += 4 * (size_t)L.rows) {
       F8 xv[4];
 #pragma unroll
