@@ -965,6 +965,41 @@ int mednet_intensity_apply(const void* src, int src_dtype, void* dst, int dst_dt
  * x1) of the mask by integer min / max; an all-zero volume gives (0, 0, 0, -1, -1, -1). */
 int mednet_nonzero_mask(const void* src, int dtype, int c, int d, int h, int w, uint8_t* mask, int32_t* box, mednet_stream stream);
 
+/* ---- image degradation of a training batch (additive to ABI 3; the reference degrades nothing) -------------------------------------------
+ * Gaussian noise, Gaussian blur and simulated low resolution (mednet_hip/sampler.py: ImageDegradation).  Both entries work on
+ * rows x spatial dense fp32, rows = B * C of the batch tensor; both refuse bad arguments before anything is launched; no atomics,
+ * one owning thread per element: the same inputs give the same bits.
+ *
+ * mednet_noise_patches: in place, data[r][v] = fmaf(std[r], z(seed, r, v), data[r][v]).  std: fp32 [rows] in device memory (4-byte
+ * aligned); a row with std[r] == 0 is neither read nor written.  z is a pure function of (seed, r, v) -- not of the grid, of other
+ * rows' std or of the batch size.  THE ARITHMETIC, pinned (tests/degrade_util.py restates it):
+ *   block j = v >> 2, lane v & 3;
+ *   (r0, r1, r2, r3) = philox4x32-10(counter = (j, r, 0, 0), key = (seed & 0xffffffff, seed >> 32)) -- multipliers 0xD2511F53 and
+ *   0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten rounds;
+ *   lanes 0 and 1 come from the pair (r0, r1), lanes 2 and 3 from (r2, r3); for a pair (a, b):
+ *   u1 = ((a >> 8) + 1) * 2^-24 (in (0, 1]: the logarithm is finite), u2 = (b >> 8) * 2^-24, rad = sqrtf(-2 * logf(u1)),
+ *   z_even = rad * cospif(2 * u2), z_odd = rad * sinpif(2 * u2).
+ * One thread owns one block of four voxels: a 16-byte load and store where the address allows, scalar accesses otherwise (the
+ * tail of a row when spatial % 4 != 0).
+ * Refused (MEDNET_E_SHAPE): a null pointer, rows < 1, spatial < 1, spatial >= 2^32 (the counter's word 0 never wraps: "32-bit
+ * index"), a std (or data) pointer that is not 4-byte aligned. */
+int mednet_noise_patches(float* data, const float* std, uint64_t seed, int rows, size_t spatial, mednet_stream stream);
+/* mednet_filter_rows: one extent-preserving axis pass over the whole batch, out of place (src != dst).  Every row is a d x h x w
+ * volume; n is the extent of `axis` (0: d, 1: h, 2: w).
+ *   row_table int32 [rows]: the table of row r, -1 .. n_tables - 1.  A row with -1 (or any entry outside that range) is COPIED bit
+ *             for bit, NaN payloads and -0.0 included.
+ *   count     int32 [n_tables][n], index int32 [n_tables][n][taps], weight fp32 [n_tables][n][taps] (all 4-byte aligned).
+ * THE ARITHMETIC, pinned: output i of a row with table t is the chain over the row's values v along the axis
+ *   acc = weight[(t n + i) taps] * v[index[(t n + i) taps]];
+ *   acc = fmaf(weight[.. + k], v[index[.. + k]], acc)  for k = 1 .. count[t n + i] - 1,          in exactly this order,
+ * fp32 throughout: the chain of mednet_resample_axis with an explicit index per tap in place of start + k.  Slots at and above
+ * count are never read (a NaN next to the support does not leak).  Inside the kernels count is clamped to 1 .. taps and every index
+ * to 0 .. n - 1 (csrc/degrade_index.h): any table is safe for memory.
+ * Refused (MEDNET_E_SHAPE): a null pointer, an extent outside 1 .. 2048, d * h * w >= 2^31, axis outside 0 .. 2, rows < 1,
+ * n_tables < 1, taps outside 1 .. 64, src == dst, a table (or volume) that is not 4-byte aligned. */
+int mednet_filter_rows(const float* src, float* dst, int rows, int d, int h, int w, int axis, const int* row_table, int n_tables,
+                       const int* count, const int* index, const float* weight, int taps, mednet_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

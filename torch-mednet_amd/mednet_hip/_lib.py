@@ -205,6 +205,8 @@ SIGNATURES = {
     "mednet_intensity_params": (_i, [_i, _vp, _vp, _vp, _i, _i, _dbl, _vp, _vp, _vp]),
     "mednet_intensity_apply": (_i, [_vp, _i, _vp, _i, _vp] + [_i] * 4 + [_vp, _f, _vp]),
     "mednet_nonzero_mask": (_i, [_vp, _i] + [_i] * 4 + [_vp, _vp, _vp]),
+    "mednet_noise_patches": (_i, [_vp, _vp, C.c_uint64, _i, _sz, _vp]),
+    "mednet_filter_rows": (_i, [_vp, _vp] + [_i] * 5 + [_vp, _i, _vp, _vp, _vp, _i, _vp]),
 }
 
 _lib = None

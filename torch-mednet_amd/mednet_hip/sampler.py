@@ -20,7 +20,13 @@ mednet_crop_patches (images trilinear, heat maps trilinear and rounded once, lab
 unpinned here as well, and the elastic model is NOT batchgenerators' (Gaussian-filtered full-resolution noise) but this library's
 own: normal displacements on a coarse control lattice, interpolated trilinearly.  As with batchgenerators, a rotated or deformed
 patch may lose the labelled voxel the class-balanced position was drawn for.  `spatial=None` is the path without any of this: the
-same launches and the same generator calls as before."""
+same launches and the same generator calls as before.
+
+Gaussian noise, Gaussian blur and simulated low resolution -- the transforms nnU-Net's pipeline runs between the spatial transform
+and the brightness / contrast / gamma group -- are `degrade=ImageDegradation(...)`: drawn per sample after the spatial draws and
+before the intensity ones, run on the device (csrc/degrade.hip) between the crop or warp and `augment_`.  The noise is the library's
+own counter-based generator (philox4x32-10, a pure function of the batch's seed, the row and the voxel); blur and low resolution
+are separable table passes over the whole batch with one table per (sample, channel) row.  `degrade=None` changes nothing."""
 from __future__ import annotations
 
 import numpy as np
@@ -204,15 +210,233 @@ def warp_patches(volume, affine, slot, out, c_off=0, interp="linear", border="ed
     return out
 
 
+# ---------------------------------------------------------------------------------------------- noise, blur, low resolution
+# csrc/degrade.hip, DESIGN.md section 32.  Blur and simulated low resolution are separable table passes like resample.py's, per
+# (sample, channel) row of the batch: a table states, per output index, `count` taps with an explicit source index and a weight.
+FILTER_MAX_TAPS = 64
+
+
+def _reflect(j, n):
+    """scipy's mode="reflect" (d c b a | a b c d | d c b a) by the periodic formula, so any j and n >= 1 are legal."""
+    j = np.mod(j, 2 * n)
+    return np.where(j >= n, 2 * n - 1 - j, j)
+
+
+def blur_table(n, sigma):
+    """(count int32 [n], index int32 [n][taps], weight fp32 [n][taps], taps) of scipy.ndimage.gaussian_filter1d(sigma,
+    mode="reflect", truncate=4.0) on an axis of extent n: radius r = int(4 sigma + 0.5), weights exp(-k^2 / 2 sigma^2) normalised in
+    fp64 and rounded once to fp32, index reflect(i - r + k).  None for sigma == 0 (no table: the row is copied)."""
+    n, sigma = int(n), float(sigma)
+    if not (np.isfinite(sigma) and sigma >= 0):
+        raise ValueError(f"blur_table: sigma {sigma!r} is not finite and non-negative")
+    if sigma == 0:
+        return None
+    r = int(4.0 * sigma + 0.5)
+    taps = 2 * r + 1
+    if taps > FILTER_MAX_TAPS:
+        raise ValueError(f"blur_table: sigma {sigma} needs {taps} taps (at most {FILTER_MAX_TAPS})")
+    k = np.arange(-r, r + 1, dtype=np.float64)
+    wt = np.exp(-0.5 * k * k / (sigma * sigma))
+    wt = (wt / wt.sum()).astype(np.float32)
+    index = _reflect(np.arange(n)[:, None] + np.arange(-r, r + 1)[None, :], n).astype(np.int32)
+    return np.full(n, taps, dtype=np.int32), index, np.broadcast_to(wt, (n, taps)).copy(), taps
+
+
+_low_resolution_tables = {}
+
+
+def low_resolution_table(n, zoom):
+    """The composite of nearest-neighbour down-sampling to m = max(1, round(n zoom)) and cubic up-sampling back to n, as one table:
+    count and weight are those of U = axis_table(m, n, "cubic"), index[i][k] is the source index that row U.start[i] + k of
+    S = axis_table(n, m, "nearest") reads.  None for zoom >= 1 or m == n.  The table depends on (n, m) alone and is kept per pair
+    (read-only arrays): a training run meets at most n of them per extent."""
+    from .resample import axis_table
+    n, zoom = int(n), float(zoom)
+    if not (np.isfinite(zoom) and zoom > 0):
+        raise ValueError(f"low_resolution_table: zoom {zoom!r} is not finite and positive")
+    m = max(1, int(round(n * zoom)))
+    if zoom >= 1 or m == n:
+        return None
+    hit = _low_resolution_tables.get((n, m))
+    if hit is None:
+        s_start = axis_table(n, m, "nearest")[0]
+        u_start, u_count, u_weight, taps = axis_table(m, n, "cubic")
+        low = np.minimum(u_start[:, None].astype(np.int64) + np.arange(taps)[None, :], m - 1)   # (slots past count are never read)
+        hit = (u_count.copy(), s_start[low].astype(np.int32), u_weight.copy(), taps)
+        for a in hit[:3]:
+            a.setflags(write=False)
+        _low_resolution_tables[(n, m)] = hit
+    return hit
+
+
+def filter_rows(src, dst, axis, row_table, tables):
+    """One axis pass over a batch (mednet_filter_rows, include/mednet_hip.h): src, dst B x C x D x H x W fp32, contiguous, distinct;
+    row_table int32 [B * C]; tables = (count int32 [T][n], index int32 [T][n][taps], weight fp32 [T][n][taps]) -- device tensors."""
+    L.require_gpu(src, "filter_rows")
+    count, index, weight = tables
+    assert src.dtype == dst.dtype == torch.float32 and src.is_contiguous() and dst.is_contiguous() and src.shape == dst.shape
+    assert src.dim() == 5 and row_table.dtype == torch.int32 and row_table.numel() == src.shape[0] * src.shape[1]
+    assert count.dtype == index.dtype == torch.int32 and weight.dtype == torch.float32
+    assert all(t.is_contiguous() for t in (row_table, count, index, weight))
+    n = src.shape[2 + axis]
+    n_tables, taps = int(index.shape[0]), int(index.shape[2])
+    assert tuple(count.shape) == (n_tables, n) and tuple(index.shape) == tuple(weight.shape) == (n_tables, n, taps)
+    d, h, w = src.shape[2:]
+    L.check(L.lib().mednet_filter_rows(src.data_ptr(), dst.data_ptr(), row_table.numel(), d, h, w, int(axis), row_table.data_ptr(),
+                                       n_tables, count.data_ptr(), index.data_ptr(), weight.data_ptr(), taps, L.stream()), "filter_rows")
+    return dst
+
+
+def stack_tables(n, params, table_of):
+    """The distinct tables of a pass: params is one value per row; -> (row_table int32 [rows], count [T][n], index [T][n][taps],
+    weight [T][n][taps]) as numpy, each distinct (n, parameter) built once, padded to the longest table's taps; None if no row has
+    a table."""
+    built, row_table = {}, []
+    for p in params:
+        p = float(p)
+        if p not in built:
+            built[p] = table_of(n, p)
+        row_table.append(p)
+    keys = [p for p in built if built[p] is not None]
+    if not keys:
+        return None
+    taps = max(built[p][3] for p in keys)
+    count = np.stack([built[p][0] for p in keys]).astype(np.int32)
+    index = np.zeros((len(keys), n, taps), dtype=np.int32)
+    weight = np.zeros((len(keys), n, taps), dtype=np.float32)
+    for t, p in enumerate(keys):
+        index[t, :, :built[p][3]], weight[t, :, :built[p][3]] = built[p][1], built[p][2]
+    slot = {p: t for t, p in enumerate(keys)}
+    return np.array([slot.get(p, -1) for p in row_table], dtype=np.int32), count, index, weight
+
+
+def _row_params(data, value):
+    b, c = data.shape[:2]
+    v = np.asarray(value, dtype=np.float64)
+    return np.ascontiguousarray(np.broadcast_to(v if v.ndim else v.reshape(1, 1), (b, c))).reshape(b * c)
+
+
+def _filter_passes(data, params, table_of, scratch, who):
+    """Axis 2, then 1, then 0, ping-pong between data and ONE scratch tensor; an axis on which no row has a table launches nothing.
+    -> the tensor that holds the result (data or the scratch)."""
+    L.require_gpu(data, who)
+    if data.dtype != torch.float32 or data.dim() != 5 or not data.is_contiguous():
+        raise ValueError(f"{who}: a contiguous float32 B x C x D x H x W batch expected, got {tuple(data.shape)} {data.dtype}")
+    cur, other = data, scratch
+    for axis in (2, 1, 0):
+        st = stack_tables(int(data.shape[2 + axis]), params, table_of)
+        if st is None:
+            continue
+        if other is None:
+            other = torch.empty_like(data)
+        assert other.shape == data.shape and other.dtype == data.dtype and other.is_contiguous() and other.data_ptr() != cur.data_ptr()
+        row_table, count, index, weight = (torch.from_numpy(a).to(data.device) for a in st)     # one copy per array
+        filter_rows(cur, other, axis, row_table, (count, index, weight))
+        cur, other = other, cur
+    return cur
+
+
+def gaussian_noise_(data, std, seed):
+    """In place on a B x C x ... fp32 device tensor: data += std * z(seed, row, voxel) (mednet_noise_patches: philox4x32-10 and
+    Box-Muller, a pure function of the seed, the row b * C + c and the voxel).  std: a scalar or a (B, C) array; rows with std 0 are
+    not touched, and nothing is launched when every row's is 0."""
+    L.require_gpu(data, "gaussian_noise_")
+    if data.dtype != torch.float32 or data.dim() < 3 or not data.is_contiguous():
+        raise ValueError(f"gaussian_noise_: a contiguous float32 B x C x ... batch expected, got {tuple(data.shape)} {data.dtype}")
+    sd = _row_params(data, std).astype(np.float32)
+    if not sd.any():
+        return data
+    rows = sd.size
+    L.check(L.lib().mednet_noise_patches(data.data_ptr(), torch.from_numpy(sd).to(data.device).data_ptr(), int(seed) & (2 ** 64 - 1), rows,
+                                         data.numel() // rows, L.stream()), "noise_patches")
+    return data
+
+
+def gaussian_blur(data, sigma, scratch=None):
+    """scipy.ndimage.gaussian_filter(mode="reflect", truncate=4.0) of every (sample, channel) volume of a B x C x D x H x W fp32 device
+    batch, one sigma (a scalar or a (B, C) array, 0: untouched) for all three axes.  -> the tensor that holds the result: `data`
+    itself or the scratch tensor (`scratch`, or one allocated here), whichever the last pass wrote."""
+    return _filter_passes(data, _row_params(data, sigma), blur_table, scratch, "gaussian_blur")
+
+
+def simulate_low_resolution(data, zoom, scratch=None):
+    """Every (sample, channel) volume down-sampled by `zoom` (a scalar or a (B, C) array; >= 1: untouched) with nearest neighbour and
+    back up with this library's cubic kernel: bit for bit resample(resample(x, size=m, kind="nearest"), size=n, kind="cubic"),
+    in three composite passes -- the low-resolution volume never exists.  -> the tensor that holds the result, as gaussian_blur."""
+    return _filter_passes(data, _row_params(data, zoom), low_resolution_table, scratch, "simulate_low_resolution")
+
+
+class ImageDegradation:
+    """Gaussian noise, Gaussian blur and simulated low resolution with nnU-Net's default ranges and probabilities; a range that is
+    None switches its transform off.
+
+    noise           (lo, hi) of the STANDARD DEVIATION, one per sample (batchgenerators passes the number it calls a variance to
+                    np.random.normal as the scale, so the two agree)
+    blur            (lo, hi) of sigma in voxels, one per channel
+    low_resolution  (lo, hi) of the zoom factor, one per channel
+    p_*             probability that a sample takes the transform;  p_*_channel: that a channel of such a sample does
+
+    draw(channels) makes these calls into numpy's global generator, in this order, whatever the outcome of a probability test --
+    a sample always consumes calls_per_sample(channels) of them, each one uniform double:
+      noise:           uniform() [p_noise], uniform(lo, hi)                                            2 calls
+      blur:            uniform() [p_blur], then per channel uniform() [p_blur_channel], uniform(lo, hi)  1 + 2 C calls
+      low resolution:  the same with its own probabilities                                              1 + 2 C calls
+    The noise seed of a batch is drawn by the sampler, not here (DevicePatchSampler.batch)."""
+
+    def __init__(self, noise=(0.0, 0.1), blur=(0.5, 1.0), low_resolution=(0.5, 1.0), p_noise=0.1, p_blur=0.2, p_blur_channel=0.5,
+                 p_low_resolution=0.25, p_low_resolution_channel=0.5):
+        pair = lambda r: None if r is None else (float(r[0]), float(r[1]))
+        self.noise, self.blur, self.low_resolution = pair(noise), pair(blur), pair(low_resolution)
+        assert self.noise is None or 0 <= self.noise[0] <= self.noise[1]
+        assert self.blur is None or 0 <= self.blur[0] <= self.blur[1]
+        assert self.low_resolution is None or 0 < self.low_resolution[0] <= self.low_resolution[1]
+        if self.blur is not None:
+            blur_table(1, self.blur[1])      # a sigma that needs more than 64 taps is refused here, not in the middle of an epoch
+        self.p_noise, self.p_blur, self.p_blur_channel = float(p_noise), float(p_blur), float(p_blur_channel)
+        self.p_low_resolution, self.p_low_resolution_channel = float(p_low_resolution), float(p_low_resolution_channel)
+
+    def calls_per_sample(self, channels):
+        return 2 * (self.noise is not None) + (1 + 2 * channels) * ((self.blur is not None) + (self.low_resolution is not None))
+
+    def draw(self, channels):
+        """One sample: (channels, 3) float64 = (std, sigma, zoom) per channel, (0, 0, 1) where a transform is off."""
+        out = np.zeros((channels, 3))
+        out[:, 2] = 1.0
+        if self.noise is not None:
+            take = np.random.uniform() < self.p_noise
+            std = np.random.uniform(*self.noise)
+            if take:
+                out[:, 0] = std
+        for col, rng, p, p_channel in ((1, self.blur, self.p_blur, self.p_blur_channel),
+                                       (2, self.low_resolution, self.p_low_resolution, self.p_low_resolution_channel)):
+            if rng is None:
+                continue
+            take = np.random.uniform() < p
+            for c in range(channels):
+                take_c = np.random.uniform() < p_channel
+                v = np.random.uniform(*rng)
+                if take and take_c:
+                    out[c, col] = v
+        return out
+
+
 class DevicePatchSampler:
     """images[i]: C x D x H x W float16/float32, labels[i]: L x D x H x W uint8 (class map last), heatmaps[i] optional uint8
-    (numpy arrays or tensors).  `batch(indices)` -> the collated batch dict on the device."""
+    (numpy arrays or tensors).  `batch(indices)` -> the collated batch dict on the device.
+
+    degrade: an ImageDegradation.  Per sample the draws run position -> spatial -> degradation -> intensity; after the last sample,
+    and only if some row of the batch drew noise, ONE further call np.random.randint(0, 2^64, dtype=uint64) draws the batch's noise
+    seed.  Per batch the kernels run crop or warp -> noise -> blur -> low resolution -> augment_.  `last_degradation` holds what was
+    drawn ({"params": (B, C, 3) = (std, sigma, zoom), "seed": int or None}); the batch dict is unchanged.  degrade=None makes no
+    call into numpy's generator and no launch of its own."""
 
     def __init__(self, images, labels, patch_size, samples_per_subject=1, heatmaps=None, class_probabilities=None,
-                 subject_keys=None, device="cuda:0", augment=False, spatial=None):
+                 subject_keys=None, device="cuda:0", augment=False, spatial=None, degrade=None):
         self.device = torch.device(device)
         self.spatial = spatial  # a SpatialAugmentation: mednet_warp_patches takes the place of mednet_crop_patches
         self.last_spatial = None
+        self.degrade = degrade  # an ImageDegradation: noise, blur, low resolution on 'data' between the crop / warp and augment_
+        self.last_degradation = None
         self.augment = augment  # the reference's `transform` (train_seg.py:82-86) on 'data'
         self.last_augmentation = None
         self.patch_size = np.array(patch_size, dtype=int)
@@ -247,13 +471,19 @@ class DevicePatchSampler:
 
     def batch(self, indices):
         L.require_gpu(self.images[0], "patch sampler")
-        plan, aug, warp = [], [], []
+        plan, aug, warp, deg = [], [], [], []
         for i in indices:  # per sample: position draws, then (optionally) the transform's draws -- the reference's order
             plan.append(self.position(i))
             if self.spatial is not None:  # spatial transforms first, then the intensity ones
                 warp.append(self.spatial.draw(plan[-1][1], self.patch_size))
+            if self.degrade is not None:
+                deg.append(self.degrade.draw(self.images[0].shape[0]))
             if self.augment:
                 aug.append(draw_augmentation(self.images[0].shape[0]))
+        if self.degrade is not None:
+            deg = np.stack(deg)
+            seed = int(np.random.randint(0, 2 ** 64, dtype=np.uint64)) if deg[:, :, 0].any() else None
+            self.last_degradation = {"params": deg, "seed": seed}
         b = len(plan)
         pd, ph, pw = (int(v) for v in self.patch_size)
         c_img = self.images[0].shape[0]
@@ -265,6 +495,8 @@ class DevicePatchSampler:
             self._warp_batch(plan, warp, data, label, n_hm)
         else:
             self._crop_batch(plan, data, label, n_hm, n_lab)
+        if self.degrade is not None:
+            data = self._degrade_batch(data)
         if self.augment:
             self.last_augmentation = np.stack(aug)
             augment_(data, self.last_augmentation)
@@ -274,6 +506,18 @@ class DevicePatchSampler:
         if self.spatial is not None:
             out["spatial"] = self.last_spatial["affine"]
         return out
+
+    def _degrade_batch(self, data):
+        """noise -> blur -> low resolution with last_degradation; a transform that no row drew launches nothing."""
+        prm, seed = self.last_degradation["params"], self.last_degradation["seed"]
+        if seed is not None:
+            gaussian_noise_(data, prm[:, :, 0], seed)
+        scratch = torch.empty_like(data) if (prm[:, :, 1] != 0).any() or (prm[:, :, 2] < 1).any() else None
+        for run, values in ((gaussian_blur, prm[:, :, 1]), (simulate_low_resolution, prm[:, :, 2])):
+            out = run(data, values, scratch)
+            if out is not data:
+                data, scratch = out, data
+        return data
 
     def _crop_batch(self, plan, data, label, n_hm, n_lab):
         lib = L.lib()
